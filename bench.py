@@ -29,6 +29,7 @@ replicated, samples are sharded.  Default: one sample per GPU per step (weak sca
 B samples split over the ranks (BASELINE config 4: B=64 over 8 GPUs; strong scaling in the batch).
 """
 import argparse
+import collections
 import json
 import os
 import sys
@@ -44,7 +45,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps of the forward workload (default 2); --workload ntt times "
+                    "--ntt-steps steps and --workload ops a fixed count, so both reject --steps")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", choices=["forward", "ntt", "ops"], default="forward")
     ap.add_argument("--batch", type=int, default=0, help="samples per step over ALL ranks (0: one per rank per step); a rank's share of a "
@@ -86,7 +88,38 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL, one GPU per rank) or gloo (rehearsal: ranks may share GPU 0)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="forward workload: after the timed steps, write what the last "
+                    "step handed its caller (rank 0's samples) as DIR/logits.npy [samples, 20] and DIR/slots.npy [samples, 16384], the "
+                    "decrypted output slots, both float64 (over 64 MB: a fixed-seed sample of the samples, listed in DIR/rows.npy); "
+                    "every input is seeded, so two builds compare output for output")
+    args = ap.parse_args()
+    if args.steps is not None and (args.workload != "forward" or args.micro):
+        ap.error("--steps sets the timed steps of the forward workload only (--workload ntt: --ntt-steps)")
+    if args.steps is None:
+        args.steps = 2
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "forward" or args.micro):
+        ap.error("--dump-outputs needs the forward workload")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, np, **arrays):
+    """--dump-outputs: one float64 .npy per array, one row per sample of the step, 64 MB at most in all.  A step whose
+    rows take more keeps the same fixed-seed sample of rows in every array, and rows.npy lists which (in order)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n_rows = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n_rows
+    if row_bytes * n_rows > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n_rows, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_cpus():
@@ -566,6 +599,7 @@ def main():
             dist.barrier()
         t0 = time.perf_counter()
         logits = []
+        last_slots = collections.deque(maxlen=per_rank)           # decrypted outputs of the last step (--dump-outputs)
         timed_inputs = []
         host_enqueue = 0.0
         if batched:
@@ -575,14 +609,16 @@ def main():
                 outs_b = server_pass_batched([e for _, e in cur])
                 host_enqueue += time.perf_counter() - th
                 for x in range(per_rank):
-                    logits.append(lf.logits_from_slots(eng.decrypt(outs_b[x])))
+                    last_slots.append(eng.decrypt(outs_b[x]))
+                    logits.append(lf.logits_from_slots(last_slots[-1]))
                     timed_inputs.append(cur[x][0])
         else:
             for i in range(args.warmup * per_rank, n_samples):
                 th = time.perf_counter()
                 out = server_pass(samples[i][1])
                 host_enqueue += time.perf_counter() - th           # host time to ISSUE the pass (the GPU runs behind asynchronously)
-                logits.append(lf.logits_from_slots(eng.decrypt(out)))
+                last_slots.append(eng.decrypt(out))
+                logits.append(lf.logits_from_slots(last_slots[-1]))
                 timed_inputs.append(samples[i][0])
         eng.sync()
         torch.cuda.synchronize()
@@ -603,6 +639,8 @@ def main():
                     "held_peak_GB": round(stats.pop("pool_reserved_peak_bytes") / 1e9, 1), "out_of_memory_trims_in_the_timed_region": stats.pop("pool_trims")}
         for k in stats:
             stats[k] = stats[k] // max(1, n_timed)          # per sample
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, np, logits=logits[-per_rank:], slots=list(last_slots))
         # parity of the timed path: EVERY timed sample vs the same op sequence in the clear (oracle/circuit_sim.py),
         # after the timed region
         err, err_sum = 0.0, 0.0
@@ -665,7 +703,7 @@ def main():
             if rank == 0:
                 print(json.dumps({"metric": "encrypted Linformer-d128 forward ms/sample (profiling run)",
                                   "value": round(elapsed * 1e3 / (n_timed * world), 2), "unit": "ms/sample", "n_gpus": world,
-                                  "steps": args.steps, "warmup": args.warmup, "log_n": args.log_n, "n_q": eng.n_q, "n_p": eng.n_p, "special_bits": args.special_bits, "variant": args.variant,
+                                  "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 2), "log_n": args.log_n, "n_q": eng.n_q, "n_p": eng.n_p, "special_bits": args.special_bits, "variant": args.variant,
                                   "host_issue_ms_per_sample": round(host_enqueue * 1e3 / n_timed, 2), "ops_per_sample": stats, "device_pool": pool_now,
                                   "samples_per_pass": width, "passes_per_step": n_pass if batched else per_rank, "lanes": args.lanes if (batched and laned) else 1, "distinct_input_sets": n_sets,
                                   "logit_err_vs_circuit_oracle": round(err, 5), "level_plan": bool(plan)}))
