@@ -323,6 +323,7 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
         pool.have_streams = true;
         if (const char* e = std::getenv("FHELIN_ASYNC")) async_lanes = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_MODDOWN")) fuse_moddown = std::atoi(e) != 0;
+        if (const char* e = std::getenv("FHELIN_FUSE_FINISH")) fuse_finish = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_HOST_ENCODE")) host_encode = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_GATHER")) fuse_gather = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_LIFT")) fuse_lift = std::atoi(e) != 0;

@@ -236,9 +236,12 @@ struct Context {
     const u32* automorph_map(u64 galois);          // device map for the NTT-domain permutation
     const u32* automorph_inverse_of(const u32* map);  // the map of the inverse automorphism (built together with `map`)
     std::map<const u32*, const u32*> automorph_inverse;
-    // FHELIN_FUSE_MODDOWN=1: K8b as an epilogue of NTT(conv)'s row pass instead of its own kernel.  Bit-identical, one
-    // memory pass fewer — and measured SLOWER end to end (1615 vs 1574 ms/sample): the epilogue's ~25 instructions per
-    // residue land in the VALU-bound NTT, while the separate kernel is bandwidth-bound and overlaps with it.  Off.
+    // Row-pass epilogues (kernels.h NttEpilogue): the forward NTT that feeds a rescale, a merged ModDown + rescale or a ModDown
+    // finishes it in registers instead of storing the transform for a separate streaming kernel.  Bit-identical either way.
+    // FHELIN_FUSE_FINISH=0: the separate kernels (rescale_finish, moddown_rescale_finish, moddown_finish) everywhere (A/B).
+    bool fuse_finish = true;
+    // FHELIN_FUSE_MODDOWN=1: also the ModDown of a ROTATION (output through the inverse automorphism map: scattered stores)
+    // rides in the row pass.  Off: measured slower.
     bool fuse_moddown = false;
     // FHELIN_HOST_ENCODE=1 / fhelin_ctx_set_host_encode: the special FFT of CKKS encoding on the host (the original path, kept
     // as the reference the device encoder is compared with bit for bit); default: on the GPU (kernels_client.hip)
@@ -273,9 +276,10 @@ struct Context {
     int trace_small_ntt = 0;
     std::map<std::string, std::pair<u64, u64>> small_ntt_sites;   // call stack -> (launches, limb vectors)
     void note_small_ntt(int nvec);
-    void ntt_moddown(const LimbBatch& b, const NttModDown& md) {
+    void ntt_epilogue(const LimbBatch& b, const NttEpilogue& ep) {
         stats.limb_ntt += (u64)b.nvec;
-        launch_ntt_moddown(dt, b, md, stream);
+        if (trace_small_ntt && b.nvec <= trace_small_ntt) note_small_ntt(b.nvec);
+        launch_ntt_epilogue(dt, b, ep, stream);
     }
 };
 

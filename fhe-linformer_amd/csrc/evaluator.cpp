@@ -183,27 +183,30 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, L1, K}, true);
     u64* conv = c_.dalloc<u64>((size_t)B * 2 * ell * N);
     launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, s);
-    if (c_.fuse_moddown) {
-        // K8b rides in the row pass of NTT(conv): (accQ - NTT(conv)) * P^-1 + add (+ post) is formed in registers and
-        // written through the inverse automorphism map — NTT(conv) never goes to memory
-        NttModDown md;
-        md.accQ = accQ;
-        md.out = out;
-        md.add0 = add0;
-        md.add1 = add1;
-        md.post = post;
-        md.pinv = c_.d_pinv;
-        md.ell = ell;
-        md.out_stride = out_stride;
-        md.add_stride = add_stride;
-        md.post_stride = post_stride;
+    // K8b rides in the row pass of NTT(conv): (accQ - NTT(conv)) * P^-1 + add (+ post) is formed in registers — NTT(conv) never
+    // goes to memory.  Always for an identity output map (relinearisation); for a rotation (written through the inverse
+    // automorphism map) only with FHELIN_FUSE_MODDOWN=1.
+    const bool identity = !map && !rows;
+    if (c_.fuse_moddown || (c_.fuse_finish && identity)) {
+        NttEpilogue ep;
+        ep.acc = accQ;
+        ep.acc_poly_stride = (size_t)ell * N;
+        ep.out = out;
+        ep.out_stride = out_stride;
+        ep.w = c_.d_pinv;
+        ep.ell = ell;
+        ep.add0 = add0;
+        ep.add1 = add1;
+        ep.add_stride = add_stride;
+        ep.post = post;
+        ep.post_stride = post_stride;
         if (rows) {
-            md.per_row = 1;
-            for (int b = 0; b < B; ++b) md.invmap_row[b] = c_.automorph_inverse_of(rows->maps[b]);
-        } else {
-            md.invmap = c_.automorph_inverse_of(map);
+            ep.per_row = 1;
+            for (int b = 0; b < B; ++b) ep.invmap_row[b] = c_.automorph_inverse_of(rows->maps[b]);
+        } else if (map) {
+            ep.invmap = c_.automorph_inverse_of(map);
         }
-        c_.ntt_moddown(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, md);
+        c_.ntt_epilogue(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, ep);
     } else {
         c_.ntt(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, false);
         launch_moddown_finish(c_.dt, sh, out, accQ, conv, c_.d_pinv, add0, add1, map, post, s);
@@ -214,6 +217,25 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     c_.pool.free(accQ);
     c_.pool.free(accP);
     c_.pool.free(conv);
+}
+
+// the row pass of NTT(conv) finishes (accQ - NTT(conv)) * minv into out (FHELIN_FUSE_FINISH=0: moddown_rescale_finish_kernel)
+void Evaluator::moddown_rescale_finish(const KsShape& sh, u64* out, const u64* accQ, u64* conv, const u64* minv) {
+    const int e1 = sh.ell - 1;
+    const LimbBatch cb{conv, sh.batch * 2 * e1, nullptr, 0, e1};
+    if (c_.fuse_finish) {
+        NttEpilogue ep;
+        ep.acc = accQ;
+        ep.acc_poly_stride = (size_t)sh.ell * c_.N;
+        ep.out = out;
+        ep.out_stride = sh.out_stride;
+        ep.w = minv;
+        ep.ell = e1;
+        c_.ntt_epilogue(cb, ep);
+        return;
+    }
+    c_.ntt(cb, false);
+    launch_moddown_rescale_finish(c_.dt, sh, out, accQ, conv, minv, c_.stream);
 }
 
 bool Evaluator::have_rotation_keys(const std::vector<int>& indices, int slots) const {
@@ -501,8 +523,7 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
             }
             conv = c_.dalloc<u64>((size_t)B * 2 * (ell - 1) * N);
             launch_moddown_rescale_conv(c_.dt, sh, conv, accP, top, lt.md_hatinv, lt.md_hatmod, lt.md_mmod, s);
-            c_.ntt(LimbBatch{conv, B * 2 * (ell - 1), nullptr, 0, ell - 1}, false);
-            launch_moddown_rescale_finish(c_.dt, sh, o[0]->d, accQ, conv, lt.md_minv, s);
+            moddown_rescale_finish(sh, o[0]->d, accQ, conv, lt.md_minv);
         }
         launch_ok("hoisted_dot_rows");
         c_.pool.free(cc);
@@ -829,7 +850,13 @@ std::vector<CtPtr> Evaluator::rotate_each(const std::vector<CtPtr>& vin, const s
 // each polynomial -> lifted [P][ell-1][N].  The lift rides in the load of the transform's first pass (LimbBatch::lift_qlm)
 // when the dropped modulus is below twice every remaining one (x mod q_j is then one conditional subtraction); otherwise,
 // or with FHELIN_FUSE_LIFT=0, the separate lift kernel runs first.  Same residues either way.
-void Evaluator::lift_and_ntt(u64* lifted, const u64* last, int P, int ell) {
+void Evaluator::lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const NttEpilogue* ep) {
+    auto ntt = [&](const LimbBatch& b) {
+        if (ep)
+            c_.ntt_epilogue(b, *ep);
+        else
+            c_.ntt(b, false);
+    };
     const u64* qlm = c_.d_qlmod + (size_t)(ell - 1) * (c_.L + 1);
     bool fuse = c_.fuse_lift;
     for (int j = 0; j + 1 < ell && fuse; ++j) fuse = c_.chain.q[ell - 1] < 2 * c_.chain.q[j];
@@ -837,18 +864,38 @@ void Evaluator::lift_and_ntt(u64* lifted, const u64* last, int P, int ell) {
         LimbBatch fb{lifted, P * (ell - 1), nullptr, 0, ell - 1, last};
         fb.lift_qlm = qlm;
         fb.lift_limb = ell - 1;
-        c_.ntt(fb, false);
+        ntt(fb);
         return;
     }
     launch_rescale_lift(c_.dt, lifted, last, P, ell, qlm, c_.stream);
-    c_.ntt(LimbBatch{lifted, P * (ell - 1), nullptr, 0, ell - 1}, false);
+    ntt(LimbBatch{lifted, P * (ell - 1), nullptr, 0, ell - 1});
+}
+
+// K5 step 4 rides in the row pass of the lift's NTT (FHELIN_FUSE_FINISH=0: rescale_finish_kernel reads the stored transform)
+void Evaluator::rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell) {
+    const size_t N = c_.N;
+    const u64* qlinv = c_.d_qlinv + (size_t)(ell - 1) * (c_.L + 1) * 2;
+    u64* lifted = c_.dalloc<u64>((size_t)P * (ell - 1) * N);
+    if (c_.fuse_finish) {
+        NttEpilogue ep;
+        ep.acc = c;
+        ep.acc_poly_stride = (size_t)ell * N;
+        ep.out = out;
+        ep.out_stride = (size_t)2 * (ell - 1) * N;
+        ep.w = qlinv;
+        ep.ell = ell - 1;
+        lift_and_ntt(lifted, last, P, ell, &ep);
+    } else {
+        lift_and_ntt(lifted, last, P, ell);
+        launch_rescale_finish(c_.dt, out, c, lifted, P, ell, qlinv, c_.stream);
+    }
+    c_.pool.free(lifted);
 }
 
 CtPtr Evaluator::raw_rescale(const CtPtr& a) {
     const int ell = a->ell, P = a->npoly;
     if (ell < 2) throw Error(FHELIN_ERR_STATE, "rescale: no limb left to drop");
     const size_t N = c_.N;
-    hipStream_t s = c_.stream;
     u64* last = c_.dalloc<u64>((size_t)P * N);
     c_.stats.rescale += 1;
     c_.stats.rescale_limbs += (u64)ell;
@@ -859,13 +906,10 @@ CtPtr Evaluator::raw_rescale(const CtPtr& a) {
         lb.src_group_stride = (size_t)ell * N;
         c_.ntt(lb, true);
     }
-    u64* lifted = c_.dalloc<u64>((size_t)P * (ell - 1) * N);
-    lift_and_ntt(lifted, last, P, ell);
     CtPtr o = new_ct(P, ell - 1, a->deg, a->scale, a->slots);
-    launch_rescale_finish(c_.dt, o->d, a->d, lifted, P, ell, c_.d_qlinv + (size_t)(ell - 1) * (c_.L + 1) * 2, s);
+    rescale_finish(o->d, a->d, last, P, ell);
     launch_ok("rescale");
     c_.pool.free(last);
-    c_.pool.free(lifted);
     return o;
 }
 
@@ -1097,7 +1141,6 @@ std::vector<CtPtr> Evaluator::rescale_batch(const std::vector<CtPtr>& vin) {
         const int B = (int)chunk.size(), ell = chunk[0]->ell, P = 2 * B;
         if (ell < 2) throw Error(FHELIN_ERR_STATE, "rescale: no limb left to drop");
         const size_t N = c_.N;
-        hipStream_t s = c_.stream;
         const u64* base = chunk[0]->d;
         u64* last = c_.dalloc<u64>((size_t)P * N);
         c_.stats.rescale += (u64)B;
@@ -1106,13 +1149,10 @@ std::vector<CtPtr> Evaluator::rescale_batch(const std::vector<CtPtr>& vin) {
         lb.src_group = 1;
         lb.src_group_stride = (size_t)ell * N;
         c_.ntt(lb, true);
-        u64* lifted = c_.dalloc<u64>((size_t)P * (ell - 1) * N);
-        lift_and_ntt(lifted, last, P, ell);
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell - 1, 1, 0, chunk[0]->slots);
-        launch_rescale_finish(c_.dt, o[0]->d, base, lifted, P, ell, c_.d_qlinv + (size_t)(ell - 1) * (c_.L + 1) * 2, s);
+        rescale_finish(o[0]->d, base, last, P, ell);
         launch_ok("rescale_batch");
         c_.pool.free(last);
-        c_.pool.free(lifted);
         for (int b = 0; b < B; ++b) {
             const CtPtr& a = vin[idx[b]];
             o[b]->scale = a->scale / (long double)c_.chain.q[ell - 1];
@@ -1659,9 +1699,8 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
         }
         u64* conv = c_.dalloc<u64>((size_t)B * 2 * (ell - 1) * N);
         launch_moddown_rescale_conv(c_.dt, sh, conv, accP, top, lt.md_hatinv, lt.md_hatmod, lt.md_mmod, s);
-        c_.ntt(LimbBatch{conv, B * 2 * (ell - 1), nullptr, 0, ell - 1}, false);
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell - 1, 1, 0, x[first]->slots);
-        launch_moddown_rescale_finish(c_.dt, sh, o[0]->d, accQ, conv, lt.md_minv, s);
+        moddown_rescale_finish(sh, o[0]->d, accQ, conv, lt.md_minv);
         launch_ok("mult_affine_rescale_batch");
         c_.pool.free(cc);
         c_.pool.free(ext);

@@ -259,7 +259,9 @@ public:
 
     // raw, no bookkeeping (parity tests): exactly the residue functions of the oracle
     CtPtr raw_rescale(const CtPtr& a);
-    void lift_and_ntt(u64* lifted, const u64* last, int P, int ell);
+    void lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const NttEpilogue* ep = nullptr);
+    // K5 steps 2-4: out [P][ell-1][N] = (c - NTT(centred lift of last)) * q_{ell-1}^-1, c [P][ell][N]
+    void rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell);
     CtPtr raw_rotate(const CtPtr& a, u64 galois, const EvalKey& key, bool accumulate = false);
     CtPtr rotate_add(const CtPtr& a, int index);            // a + rot(a, index), one fused key switch (rotsum step :833)
     CtPtr raw_mult_relin(const CtPtr& a, const CtPtr& b, const EvalKey& key);
@@ -272,6 +274,8 @@ private:
     void keyswitch_impl(int batch, const KsRows* rows, const u64* c_ntt, size_t c_stride, int ell, const EvalKey* key, u64* out,
                         size_t out_stride, const u64* add0, const u64* add1, size_t add_stride, const u32* map, const u64* post,
                         size_t post_stride);
+    // NTT(conv) [batch][2][ell-1][N] and the merged ModDown + rescale finish into out (launch_moddown_rescale_finish)
+    void moddown_rescale_finish(const KsShape& sh, u64* out, const u64* accQ, u64* conv, const u64* minv);
     typedef std::vector<CtPtr> CtRow;  // one value per input ciphertext
     CtRow cheb_recurse(const std::vector<double>& c, const std::vector<CtRow>& T, const std::map<int, CtRow>& G, int baby);
     std::vector<CtPtr> add_sub_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, int op);

@@ -55,22 +55,29 @@ struct DeviceTables {
     const u64* ninv;       // [n_limbs][8]   N^{-1}, shoup, ipsi_br[1]*N^{-1}, shoup, lazy shift, lazy ratio, 0, 0
 };
 
-// Optional epilogue of the FORWARD transform's row pass: instead of storing NTT(conv), finish the ModDown of hybrid key
-// switching in registers (K8b, see kernels_elem.h launch_moddown_finish):
-//   out[bi][c][t][j] = (accQ[v][m] - NTT(conv)[v][m]) * P^-1 + add_c[bi][t][m] (+ post[bi][c][t][j]),   j = invmap[m]
-// for vector v = (bi*2 + c)*ell + t.  invmap is the INVERSE automorphism map (position m lands at j), so a wave still
-// writes whole 128-byte lines: the map permutes lines and the 16 residues inside a line.
-struct NttModDown {
+// Optional epilogue of the FORWARD transform's row pass: instead of storing x = NTT(batch vector v), finish the operation
+// that reads it in registers and store only the result.  The transformed batch is [poly][ell][N] (vector v = poly*ell + t,
+// limb t, poly = bi*2 + c):
+//   out[bi][c][t][j] = (acc[poly][t][m] - x[m]) * w_t (+ add_c[bi][t][m]) (+ post[bi][c][t][j]),   j = invmap ? invmap[m] : m
+// which covers, bit for bit, the kernels it replaces:
+//   rescale (K5, launch_rescale_finish):           acc = c (ell+1 limbs per poly), w = q_ell^-1, no add / post / map
+//   ModDown + rescale (launch_moddown_rescale_finish): acc = accQ (ell+1 limbs per poly), w = minv, no add / post / map
+//   ModDown (K8b, launch_moddown_finish):          acc = accQ (ell limbs per poly), w = P^-1, optional add / post / map
+// invmap is the INVERSE automorphism map (position m lands at j), so a wave still writes whole 128-byte lines: the map
+// permutes lines and the 16 residues inside a line.  Without a map every load and store is a contiguous 512-byte wave access.
+struct NttEpilogue {
     static constexpr int MAX_ROWS = 16;
-    const u64* accQ = nullptr;
+    const u64* acc = nullptr;
+    size_t acc_poly_stride = 0;  // words between the polys of acc
     u64* out = nullptr;
+    size_t out_stride = 0;       // words between the batch rows bi of out / add / post
+    const u64* w = nullptr;      // [ell][2] multiplier and Shoup companion per limb
+    int ell = 0;                 // limbs per poly of the transformed batch (and of out)
     const u64* add0 = nullptr;
     const u64* add1 = nullptr;
     const u64* post = nullptr;
+    size_t add_stride = 0, post_stride = 0;
     const u32* invmap = nullptr;
-    const u64* pinv = nullptr;   // [L+1][2] P^-1 mod q_t, shoup
-    int ell = 0;
-    size_t out_stride = 0, add_stride = 0, post_stride = 0;
     int per_row = 0;
     const u32* invmap_row[MAX_ROWS] = {};
 };
@@ -78,8 +85,8 @@ struct NttModDown {
 // K1: negacyclic NTT (natural -> bit-reversed) / INTT (bit-reversed -> natural, scaled by N^{-1}).
 // In place, canonical [0,q) in and out.
 void launch_ntt(const DeviceTables& t, const LimbBatch& b, bool inverse, hipStream_t s);
-// forward NTT of b (conv, [batch][2][ell][N]) whose row pass ends in the ModDown epilogue; b.data is scratch afterwards
-void launch_ntt_moddown(const DeviceTables& t, const LimbBatch& b, const NttModDown& md, hipStream_t s);
+// forward NTT of b whose row pass ends in the epilogue ep instead of storing the transform; b.data is scratch afterwards
+void launch_ntt_epilogue(const DeviceTables& t, const LimbBatch& b, const NttEpilogue& ep, hipStream_t s);
 
 
 }  // namespace fhelin

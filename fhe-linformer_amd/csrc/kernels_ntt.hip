@@ -341,9 +341,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIFT ? 3 : 
 // pass B: row transforms over the low 8 bits of the index.  Tile = 16 consecutive rows of 256
 // (4096 contiguous residues); tile-local index e == global index - tile*4096.
 // ------------------------------------------------------------------------------------------------
-template <bool INVERSE, bool LAZY, bool MODDOWN>
+template <bool INVERSE, bool LAZY, bool EPI>
 __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, int tile, int limb, const LimbConst& c,
-                                          const NttModDown* md) {
+                                          const NttEpilogue* ep) {
     const int log_n = a.log_n;
     const u64x2* tw = reinterpret_cast<const u64x2*>(a.tw) + ((size_t)limb << log_n);
     const u64x2* trows = reinterpret_cast<const u64x2*>(a.tw_rows) + (((size_t)limb << (log_n - 12)) + tile) * (15 * 256);
@@ -361,13 +361,29 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
         load_round_tw_rows(rn, trows, tau);                          // per-thread twiddles of the last four stages
         exchange(x, lds, tau, 4, 0, false);
         fwd_round<0, 4, LAZY>(x, rn, c);
-        if (!(LAZY && !MODDOWN && a.lazy_out && c.q < (1ull << 53))) {
+        // epilogue operand, read at the store offsets (bit-8 window) now so that its latency hides behind the reduction and
+        // the exchange below
+        [[maybe_unused]] u64 av[16];
+        [[maybe_unused]] int ell = 0, t = 0, poly = 0;
+        if constexpr (EPI) {
+            ell = ep->ell;
+            t = vec % ell;
+            poly = vec / ell;
+            const u64* acc = ep->acc + (size_t)poly * ep->acc_poly_stride + ((size_t)t << log_n) + ((size_t)tile << 12);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) av[k] = acc[tile_index(tau, k, 8)];
+        }
+        if constexpr (EPI) {
+            // [0, 2q) is enough: the epilogue's Shoup product takes any 64-bit input and ends canonical
+#pragma unroll
+            for (int k = 0; k < 16; ++k) x[k] = reduce_lazy_2q(x[k], c.q, c.sh, c.rr);
+        } else if (!(LAZY && a.lazy_out && c.q < (1ull << 53))) {
 #pragma unroll
             for (int k = 0; k < 16; ++k)
                 x[k] = csub_mask(reduce_lazy_2q(x[k], c.q, c.sh, c.rr), c.q);   // from < 86q (lazy) or < 10q (semi-lazy)
         }
 #if defined(FHELIN_ROWS_DIRECT_STORE)   // A/B builds only: 16-byte stores straight from the bit-0 window (128-byte lane stride), no exchange
-        if constexpr (!MODDOWN) {
+        if constexpr (!EPI) {
 #pragma unroll
             for (int k = 0; k < 16; k += 2) {
                 u64x2 v;
@@ -381,26 +397,40 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
         // window at bit 0 leaves 16 consecutive residues per thread (128-byte lane stride); one more LDS exchange
         // to the bit-8 window makes every store instruction a contiguous 512-byte wave access
         exchange(x, lds, tau, 0, 8, true);
-        if constexpr (MODDOWN) {
-            const int ell = md->ell;
-            const int bi = vec / (2 * ell), comp = (vec / ell) & 1, t = vec % ell;
+        if constexpr (EPI) {
+            const int bi = poly >> 1, comp = poly & 1;
             const size_t n = (size_t)1 << log_n;
-            const u64 pw = md->pinv[2 * t], pws = md->pinv[2 * t + 1];
-            const u64* aq = md->accQ + ((size_t)vec << log_n) + ((size_t)tile << 12);
-            const u64* add = comp == 0 ? md->add0 : md->add1;
-            if (add) add += (size_t)bi * md->add_stride + (size_t)t * n + ((size_t)tile << 12);
-            const u32* im = md->per_row ? md->invmap_row[bi] : md->invmap;
-            const u64* post = md->post ? md->post + (size_t)bi * md->post_stride + (size_t)(comp * ell + t) * n : nullptr;
-            u64* out = md->out + (size_t)bi * md->out_stride + (size_t)(comp * ell + t) * n;
+            const u64 w = ep->w[2 * t], ws = ep->w[2 * t + 1];
+            const u64 q2 = 2 * c.q;   // av + 2q - x in (0, 3q): the same residue as av - x, and mul_shoup returns it canonical
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int e = tile_index(tau, k, 8);
-                u64 r = mul_shoup(sub_mod(aq[e], x[k], c.q), pw, pws, c.q);
-                if (add) r = add_mod(r, add[e], c.q);
-                const size_t m = ((size_t)tile << 12) + e;
-                const size_t j = im ? (size_t)im[m] : m;
-                if (post) r = add_mod(r, post[j], c.q);
-                out[j] = r;
+            for (int k = 0; k < 16; ++k) x[k] = mul_shoup(av[k] + q2 - x[k], w, ws, c.q);
+            const u64* add = comp == 0 ? ep->add0 : ep->add1;
+            if (add) {
+                add += (size_t)bi * ep->add_stride + (size_t)t * n + ((size_t)tile << 12);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], add[tile_index(tau, k, 8)], c.q);
+            }
+            const size_t row_off = (size_t)(comp * ell + t) * n;
+            const u64* post = ep->post ? ep->post + (size_t)bi * ep->post_stride + row_off : nullptr;
+            u64* out = ep->out + (size_t)bi * ep->out_stride + row_off;
+            const u32* im = ep->per_row ? ep->invmap_row[bi] : ep->invmap;
+            if (im) {   // rotation: through the inverse automorphism map
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const size_t j = im[((size_t)tile << 12) + tile_index(tau, k, 8)];
+                    u64 r = x[k];
+                    if (post) r = add_mod(r, post[j], c.q);
+                    out[j] = r;
+                }
+            } else {
+                out += (size_t)tile << 12;
+                if (post) {
+                    post += (size_t)tile << 12;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], post[tile_index(tau, k, 8)], c.q);
+                }
+#pragma unroll
+                for (int k = 0; k < 16; ++k) out[tile_index(tau, k, 8)] = x[k];
             }
         } else {
 #pragma unroll
@@ -426,8 +456,8 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
     }
 }
 
-template <bool INVERSE, bool MODDOWN = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ntt_rows_kernel(NttArgs a, NttModDown md) {
+template <bool INVERSE, bool EPI = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ntt_rows_kernel(NttArgs a, NttEpilogue ep) {
     __shared__ u64 lds[LDS_WORDS];
     const int logtiles = a.log_n - 12;
     // Block -> (vector, tile) map.  A row tile needs its own 4 KiB twiddle slice per (limb, tile); vectors of the same
@@ -451,9 +481,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
     if (limb < 0) return;
     const LimbConst c = limb_const(a, limb);
     if (lazy_prime<INVERSE>(c.q))
-        rows_body<INVERSE, true, MODDOWN>(a, lds, vec, tile, limb, c, &md);
+        rows_body<INVERSE, true, EPI>(a, lds, vec, tile, limb, c, &ep);
     else
-        rows_body<INVERSE, false, MODDOWN>(a, lds, vec, tile, limb, c, &md);
+        rows_body<INVERSE, false, EPI>(a, lds, vec, tile, limb, c, &ep);
 }
 
 template <int A>
@@ -468,14 +498,14 @@ void launch_cols(const NttArgs& a, bool inverse, int blocks, hipStream_t s) {
 
 }  // namespace
 
-static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttModDown* md, hipStream_t s);
+static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s);
 
 void launch_ntt(const DeviceTables& t, const LimbBatch& b, bool inverse, hipStream_t s) { launch_ntt_impl(t, b, inverse, nullptr, s); }
-void launch_ntt_moddown(const DeviceTables& t, const LimbBatch& b, const NttModDown& md, hipStream_t s) {
-    launch_ntt_impl(t, b, false, &md, s);
+void launch_ntt_epilogue(const DeviceTables& t, const LimbBatch& b, const NttEpilogue& ep, hipStream_t s) {
+    launch_ntt_impl(t, b, false, &ep, s);
 }
 
-static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttModDown* md, hipStream_t s) {
+static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s) {
     if (b.nvec <= 0) return;
     NttArgs a;
     a.data = b.data;
@@ -512,7 +542,7 @@ static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inve
         return e ? std::atoi(e) : 0;
     }();
     int chunk = b.nvec;
-    if (chunk_mb > 0 && !md) {
+    if (chunk_mb > 0 && !ep) {
         const size_t vec_bytes = (size_t)8 << t.log_n;
         const int want = (int)std::max<size_t>(1, ((size_t)chunk_mb << 20) / vec_bytes);
         if (b.nvec > want + want / 2) {
@@ -548,12 +578,12 @@ static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inve
             a.src = a.data;
             a.src_group = 0;
             a.src_group2 = 0;
-            if (md)
-                hipLaunchKernelGGL((ntt_rows_kernel<false, true>), dim3(blocks), dim3(256), 0, s, a, *md);
+            if (ep)
+                hipLaunchKernelGGL((ntt_rows_kernel<false, true>), dim3(blocks), dim3(256), 0, s, a, *ep);
             else
-                hipLaunchKernelGGL((ntt_rows_kernel<false, false>), dim3(blocks), dim3(256), 0, s, a, NttModDown());
+                hipLaunchKernelGGL((ntt_rows_kernel<false, false>), dim3(blocks), dim3(256), 0, s, a, NttEpilogue());
         } else {
-            hipLaunchKernelGGL((ntt_rows_kernel<true, false>), dim3(blocks), dim3(256), 0, s, a, NttModDown());
+            hipLaunchKernelGGL((ntt_rows_kernel<true, false>), dim3(blocks), dim3(256), 0, s, a, NttEpilogue());
             a.src = a.data;
             a.src_group = 0;
             a.src_group2 = 0;
