@@ -185,6 +185,9 @@ def load_library():
         "fhelin_bootstrap_partial": (i32, [vp, vp, i32, C.POINTER(vp)]),
         "fhelin_bootstrap_drop": (i32, [vp, vp, i32, C.POINTER(vp)]),
         "fhelin_bootstrap_batch": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp)]),
+        "fhelin_bootstrap_iter": (i32, [vp, vp, i32, C.POINTER(vp)]),
+        "fhelin_bootstrap_iter_batch": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp)]),
+        "fhelin_bootstrap_iter_drop": (i32, [vp, vp, i32, i32, C.POINTER(vp)]),
         "fhelin_bootstrap_describe": (i32, [vp, C.POINTER(i32), i32, C.POINTER(i32)]),
         "fhelin_bootstrap_diag": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
         "fhelin_bootstrap_cheb": (i32, [vp, C.POINTER(C.c_double), i32, C.POINTER(i32)]),
@@ -687,6 +690,21 @@ class Engine:
     def bootstrap_drop(self, a, drop):
         """bootstrap raising to L+1-drop limbs only (what a level plan asks of a bootstrap)"""
         return self._un(self.lib.fhelin_bootstrap_drop, a, int(drop))
+
+    def bootstrap_iter(self, a, precision):
+        """iterative (two-pass) bootstrap, EvalBootstrap(a, 2, precision): about twice the bits of bootstrap(), one limb fewer
+        (include/fhelin.h fhelin_bootstrap_iter; 1 <= precision <= 30, useful up to one bootstrap's precision)"""
+        return self._un(self.lib.fhelin_bootstrap_iter, a, int(precision))
+
+    def bootstrap_iter_batch(self, v, precision):
+        """bootstrap_iter on independent ciphertexts, both bootstraps batched (same residues as bootstrap_iter() one by one)"""
+        outs = self._outs(len(v))
+        self._ck(self.lib.fhelin_bootstrap_iter_batch(self.h, self._harr(v), len(v), int(precision), outs))
+        return self._cts(outs, len(v))
+
+    def bootstrap_iter_drop(self, a, precision, drop):
+        """bootstrap_iter with both bootstraps raising to L+1-drop limbs only"""
+        return self._un(self.lib.fhelin_bootstrap_iter_drop, a, int(precision), int(drop))
 
     def bootstrap_describe(self):
         """the bootstrapping set-up as the residue-level oracle needs it: parameters + per linear stage the stage's slot count

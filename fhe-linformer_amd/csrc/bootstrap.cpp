@@ -556,6 +556,67 @@ std::vector<CtPtr> Bootstrapper::bootstrap_batch(const std::vector<CtPtr>& cts, 
     return run_batch(cts, drop);
 }
 
+// ---- iterative bootstrapping ------------------------------------------------------------------------------------------------
+std::vector<CtPtr> Bootstrapper::bootstrap_iter_batch(const std::vector<CtPtr>& cts, int p, int drop) {
+    if (p < 1 || p > MAX_ITER_PRECISION) throw Error(FHELIN_ERR_ARG, "bootstrap_iter: precision must be in [1, 30]");
+    if (!ready()) throw Error(FHELIN_ERR_STATE, "EvalBootstrapSetup has not been called");
+    Context& c = ev_.ctx();
+    if (drop < 0) throw Error(FHELIN_ERR_ARG, "bootstrap: level plan leaves no limb for the result");
+    const int ell_y = c.L + 1 - drop - depth_;
+    if (ell_y < 3) throw Error(FHELIN_ERR_STATE, "bootstrap_iter: the first bootstrap must leave at least three limbs (one for the final scaling)");
+    const size_t B = cts.size();
+    if (B == 0) return {};
+    // x2: exactly what ModRaise reads (rescaled if degree 2, two limbs); bootstrapping it gives the residues of bootstrapping x
+    std::vector<CtPtr> x2(B);
+    {
+        std::vector<CtPtr> need;
+        std::vector<size_t> pos;
+        for (size_t i = 0; i < B; ++i) {
+            if (cts[i]->npoly != 2) throw Error(FHELIN_ERR_STATE, "bootstrap: ciphertext must be relinearised");
+            if (cts[i]->deg >= 2) {
+                need.push_back(cts[i]);
+                pos.push_back(i);
+            } else {
+                x2[i] = cts[i];
+            }
+        }
+        if (!need.empty()) {
+            std::vector<CtPtr> r = ev_.rescale_batch(need);
+            for (size_t k = 0; k < pos.size(); ++k) x2[pos[k]] = r[k];
+        }
+        for (CtPtr& x : x2) {
+            if (x->ell < 2) throw Error(FHELIN_ERR_STATE, "bootstrap: need at least two limbs to set the message scale (bootstrap one level earlier)");
+            x = ev_.level_reduce(x, 2);
+        }
+    }
+    const std::vector<CtPtr> y = bootstrap_batch(x2, drop);
+    // e' = 2^p (y - x2): y brought to x2's two limbs and exact scale (FLEXIBLEAUTO, Evaluator::adjust), then one scaled difference
+    std::vector<long double> xs_scale(B);
+    for (size_t i = 0; i < B; ++i) xs_scale[i] = x2[i]->scale;
+    const std::vector<CtPtr> ya = ev_.adjust_deg1_batch(y, 2, xs_scale);
+    const u128 two_p = (u128)1 << p;
+    const std::vector<CtPtr> e = ev_.scaled_diff_batch(ya, x2, std::vector<u128>(B, two_p), std::vector<u128>(B, two_p), false, xs_scale);
+    const std::vector<CtPtr> z = bootstrap_batch(e, drop);
+    // out = rescale(k (2^p y - z)): the scaled difference at 2^p s_y k, rescaled to the next level's standard scale
+    std::vector<u128> ka(B), kc(B);
+    std::vector<long double> w_scale(B);
+    for (size_t i = 0; i < B; ++i) {
+        if (z[i]->ell != y[i]->ell || z[i]->scale != y[i]->scale || z[i]->deg != y[i]->deg)
+            throw Error(FHELIN_ERR_INTERNAL, "bootstrap_iter: the two bootstraps ended at different levels or scales");
+        const long double s_w = y[i]->scale * (long double)two_p;
+        const u64 k = (u64)llroundl(c.sf_real[y[i]->level() + 1] * (long double)c.chain.q[y[i]->ell - 1] / s_w);
+        if (k < 1) throw Error(FHELIN_ERR_STATE, "bootstrap_iter: precision too large for the ciphertext scale");
+        ka[i] = (u128)k << p;
+        kc[i] = k;
+        w_scale[i] = s_w * (long double)k;
+    }
+    std::vector<CtPtr> out = ev_.rescale_batch(ev_.scaled_diff_batch(y, z, ka, kc, true, w_scale));
+    for (size_t i = 0; i < B; ++i) out[i]->slots = y[i]->slots;
+    return out;
+}
+
+CtPtr Bootstrapper::bootstrap_iter(const CtPtr& ct, int p, int drop) { return bootstrap_iter_batch({ct}, p, drop)[0]; }
+
 CtPtr Bootstrapper::bootstrap(const CtPtr& ct, int drop) { return run(ct, 0, drop); }
 CtPtr Bootstrapper::partial(const CtPtr& ct, int stage) { return run(ct, stage); }
 

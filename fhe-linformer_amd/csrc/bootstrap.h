@@ -39,6 +39,15 @@ public:
     // affine-1, :319-320): every launch of the pipeline carries all of them, the switching keys and plaintext diagonals are
     // read once per batch.  out[i] holds exactly the residues of bootstrap(cts[i], drop).
     std::vector<CtPtr> bootstrap_batch(const std::vector<CtPtr>& cts, int drop = 0);
+    // Iterative (two-pass) bootstrapping, OpenFHE's EvalBootstrap(ct, 2, p) as this engine defines it: y = BTS(x),
+    // z = BTS(2^p (y - x)) at x's two limbs and scale, out = rescale(k (2^p y - z)) with k = round(Delta_next q_top / (2^p s_y)).
+    // The result keeps about twice the bits of one bootstrap and has one limb fewer than it.  1 <= p <= 30 (FHELIN_ERR_ARG
+    // otherwise); 2^p |y - x| must stay inside the bootstrap's input range, so p at or below one bootstrap's precision is useful.
+    // drop as for bootstrap(); one bootstrap's output must keep >= 3 limbs (FHELIN_ERR_STATE otherwise).
+    CtPtr bootstrap_iter(const CtPtr& ct, int p, int drop = 0);
+    // both bootstraps as bootstrap_batch over all inputs; out[i] holds exactly the residues of bootstrap_iter(cts[i], p, drop)
+    std::vector<CtPtr> bootstrap_iter_batch(const std::vector<CtPtr>& cts, int p, int drop = 0);
+    static constexpr int MAX_ITER_PRECISION = 30;
     // debug / test hook: stop after stage 1 (ModRaise+SubSum), 2 (CoeffsToSlots, real part), 3 (EvalMod, real part)
     CtPtr partial(const CtPtr& ct, int stage);
     int depth() const { return depth_; }

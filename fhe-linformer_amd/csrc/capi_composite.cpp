@@ -211,7 +211,7 @@ void flush_heavy(fhelin_ctx* c, bool report) {
                 LazyHeavy& g = *ready[k];
                 const bool same = !taken[k] && g.kind == f.kind && g.in->ell == f.in->ell && g.in->deg == f.in->deg &&
                                   g.in->npoly == f.in->npoly &&
-                                  (f.kind == LazyHeavy::Boot ? g.drop == f.drop : (g.a == f.a && g.b == f.b && g.coeffs == f.coeffs));
+                                  (f.kind == LazyHeavy::Boot ? g.drop == f.drop && g.precision == f.precision : (g.a == f.a && g.b == f.b && g.coeffs == f.coeffs));
                 if (same) {
                     grp.push_back(&g);
                     taken[k] = 1;
@@ -220,7 +220,9 @@ void flush_heavy(fhelin_ctx* c, bool report) {
             guarded(grp, [&] {
                 CtVec in;
                 for (LazyHeavy* g : grp) in.push_back(g->in);
-                CtVec out = f.kind == LazyHeavy::Boot ? c->boot.bootstrap_batch(in, f.drop) : c->ev.eval_chebyshev_many(in, f.coeffs, f.a, f.b);
+                CtVec out = f.kind != LazyHeavy::Boot ? c->ev.eval_chebyshev_many(in, f.coeffs, f.a, f.b)
+                            : f.precision > 0         ? c->boot.bootstrap_iter_batch(in, f.precision, f.drop)
+                                                      : c->boot.bootstrap_batch(in, f.drop);
                 for (size_t k = 0; k < grp.size(); ++k) {
                     grp[k]->result = out[k];
                     grp[k]->done = true;
@@ -842,6 +844,81 @@ int fhelin_bootstrap_drop(fhelin_ctx* c, const fhelin_ct* a, int32_t drop, fheli
     NEED(c && a && out);
     FHELIN_TRY
     *out = wrap(c, c->boot.bootstrap(ct_in(c, a), drop));
+    FHELIN_CATCH
+}
+static void check_precision(int32_t precision) {
+    if (precision < 1 || precision > Bootstrapper::MAX_ITER_PRECISION)
+        throw Error(FHELIN_ERR_ARG, "bootstrap_iter: precision must be in [1, 30]");
+}
+// the planned drop of the next iterative bootstrap: its full output has out_ell() - 1 limbs, and one bootstrap must keep three
+static int iter_drop(fhelin_ctx* c) {
+    return std::min(c->plan.next_drop(c->boot.out_ell() - 1), std::max(0, c->boot.out_ell() - 3));
+}
+int fhelin_bootstrap_iter(fhelin_ctx* c, const fhelin_ct* a, int32_t precision, fhelin_ct** out) {
+    NEED(c && a && out);
+    FHELIN_TRY
+    check_precision(precision);
+    // like fhelin_bootstrap: a terminal reading two limbs of its input and a source of the level plan, whose full output has one
+    // limb fewer than a single bootstrap's
+    const int drop = iter_drop(c);
+    if (c->plan.live(a->node, a->node_epoch)) c->plan.terminal(a->node, 2);
+    if (defer_ok(c)) {
+        if (!c->boot.ready()) throw Error(FHELIN_ERR_STATE, "EvalBootstrapSetup has not been called");
+        auto op = std::make_shared<LazyHeavy>();
+        op->kind = LazyHeavy::Boot;
+        op->drop = drop;
+        op->precision = precision;
+        if (c->boot.out_ell() - drop < 3)
+            throw Error(FHELIN_ERR_STATE, "bootstrap_iter: the first bootstrap must leave at least three limbs (one for the final scaling)");
+        *out = defer_heavy(c, a, op);
+        return FHELIN_OK;
+    }
+    *out = wrap(c, run_heavy(c, a, [&](const CtPtr& in) { return c->boot.bootstrap_iter(in, precision, drop); }));
+    if (c->plan.live((*out)->node, (*out)->node_epoch)) {
+        LevelPlan::Node& nd = c->plan.nodes[(*out)->node];
+        nd.in.clear();
+        nd.ordinal = c->plan.next_ordinal - 1;
+    }
+    FHELIN_CATCH
+}
+int fhelin_bootstrap_iter_batch(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, int32_t precision, fhelin_ct** outs) {
+    NEED(c && v && outs && n >= 0);
+    FHELIN_TRY
+    check_precision(precision);
+    CtVec in = vec_of(c, v, n);
+    std::vector<int> drop(n);
+    for (int i = 0; i < n; ++i) {
+        drop[i] = iter_drop(c);
+        if (c->plan.live(v[i]->node, v[i]->node_epoch)) c->plan.terminal(v[i]->node, 2);
+    }
+    const int first_ordinal = c->plan.next_ordinal - n;
+    CtVec r(n);
+    std::vector<char> done(n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (done[i]) continue;
+        std::vector<int> pick;
+        CtVec sub;
+        for (int k = i; k < n; ++k)
+            if (!done[k] && drop[k] == drop[i]) {
+                pick.push_back(k);
+                sub.push_back(in[k]);
+                done[k] = 1;
+            }
+        CtVec o = c->boot.bootstrap_iter_batch(sub, precision, drop[i]);
+        for (size_t k = 0; k < pick.size(); ++k) r[pick[k]] = o[k];
+    }
+    plan_inputs().clear();
+    for (int i = 0; i < n; ++i) {
+        outs[i] = wrap(c, r[i]);
+        if (c->plan.live(outs[i]->node, outs[i]->node_epoch)) c->plan.nodes[outs[i]->node].ordinal = first_ordinal + i;
+    }
+    FHELIN_CATCH
+}
+int fhelin_bootstrap_iter_drop(fhelin_ctx* c, const fhelin_ct* a, int32_t precision, int32_t drop, fhelin_ct** out) {
+    NEED(c && a && out);
+    FHELIN_TRY
+    check_precision(precision);
+    *out = wrap(c, c->boot.bootstrap_iter(ct_in(c, a), precision, drop));
     FHELIN_CATCH
 }
 int fhelin_bootstrap_describe(fhelin_ctx* c, int32_t* out, int32_t cap, int32_t* n) {

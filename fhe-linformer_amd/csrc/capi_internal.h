@@ -82,6 +82,7 @@ struct LazyHeavy {
     std::vector<double> coeffs;             // Cheb
     double a = 0, b = 0;
     int drop = 0;                           // Boot: limbs left out under a level plan
+    int precision = 0;                      // Boot: > 0 = iterative bootstrap with this precision (Bootstrapper::bootstrap_iter)
     CtPtr result;
     bool done = false, failed = false;
     int err_code = 0;                       // failed: what the batched call that evaluated it threw (reported when the handle is read)

@@ -1849,6 +1849,11 @@ CtPtr Evaluator::mult_int(const CtPtr& a, u64 k, bool raise_deg, long double new
 // FLEXIBLEAUTO level adjustment of several degree-1 ciphertexts to ONE (limb count, scale): integer scalar x, the limbs above
 // ell + 1 left out, and ONE batched rescale for all of them.  Same residues as adjust() one by one.
 std::vector<CtPtr> Evaluator::adjust_deg1_batch(const std::vector<CtPtr>& v, int ell, long double scale) {
+    return adjust_deg1_batch(v, ell, std::vector<long double>(v.size(), scale));
+}
+
+std::vector<CtPtr> Evaluator::adjust_deg1_batch(const std::vector<CtPtr>& v, int ell, const std::vector<long double>& scales) {
+    if (scales.size() != v.size()) throw Error(FHELIN_ERR_ARG, "adjust_deg1_batch: one target scale per ciphertext");
     std::vector<CtPtr> out(v.size()), pending, src;
     std::vector<size_t> pos;
     for (size_t i = 0; i < v.size(); ++i) {
@@ -1871,7 +1876,7 @@ std::vector<CtPtr> Evaluator::adjust_deg1_batch(const std::vector<CtPtr>& v, int
         for (size_t j = 0; j < src.size(); ++j) {
             const CtPtr& cur = src[j];
             const long double qdrop = (long double)c_.chain.q[ell];
-            const u64 k = (u64)llroundl(scale * qdrop / cur->scale);
+            const u64 k = (u64)llroundl(scales[pos[j]] * qdrop / cur->scale);
             if (!same) {
                 pending.push_back(mult_int(cur, k, true, cur->scale * (long double)k, ell + 1));
                 continue;
@@ -1894,9 +1899,55 @@ std::vector<CtPtr> Evaluator::adjust_deg1_batch(const std::vector<CtPtr>& v, int
     if (!pending.empty()) {
         std::vector<CtPtr> r = rescale_batch(pending);
         for (size_t k = 0; k < pos.size(); ++k) {
-            r[k]->scale = scale;
+            r[k]->scale = scales[pos[k]];
             out[pos[k]] = r[k];
         }
+    }
+    return out;
+}
+
+std::vector<CtPtr> Evaluator::scaled_diff_batch(const std::vector<CtPtr>& u, const std::vector<CtPtr>& w, const std::vector<u128>& a,
+                                                const std::vector<u128>& c, bool raise_deg, const std::vector<long double>& scales) {
+    const size_t B = u.size();
+    if (w.size() != B || a.size() != B || c.size() != B || scales.size() != B)
+        throw Error(FHELIN_ERR_ARG, "scaled_diff_batch: one operand pair, two constants and one scale per result");
+    if (B == 0) return {};
+    const int npoly = u[0]->npoly, ell = u[0]->ell;
+    for (size_t i = 0; i < B; ++i)
+        if (u[i]->npoly != npoly || w[i]->npoly != npoly || u[i]->ell != ell || w[i]->ell != ell)
+            throw Error(FHELIN_ERR_STATE, "scaled_diff_batch: operands of different shapes");
+    std::vector<u64> consts(B * ell * 4);
+    for (size_t i = 0; i < B; ++i)
+        for (int l = 0; l < ell; ++l) {
+            const u64 q = c_.chain.q[l], ra = (u64)(a[i] % q), rc = (u64)(c[i] % q);
+            u64* k = &consts[(i * ell + l) * 4];
+            k[0] = ra;
+            k[1] = h_shoup(ra, q);
+            k[2] = rc;
+            k[3] = h_shoup(rc, q);
+        }
+    u64* dk = c_.dalloc<u64>(consts.size());
+    for (size_t off = 0; off < consts.size(); off += 2 * c_.N)   // upload_async takes <= 2N words per call
+        c_.upload_async(dk + off, consts.data() + off, std::min(consts.size() - off, (size_t)2 * c_.N));
+    std::vector<CtPtr> out = new_ct_batch((int)B, npoly, ell, 1, 0, u[0]->slots);
+    for (size_t lo = 0; lo < B; lo += EwScaledDiff::MAX_ITEMS) {
+        EwScaledDiff d;
+        d.n = (int)std::min(B - lo, (size_t)EwScaledDiff::MAX_ITEMS);
+        d.vecs = npoly * ell;
+        d.ell = ell;
+        for (int k = 0; k < d.n; ++k) {
+            d.out[k] = out[lo + k]->d;
+            d.u[k] = u[lo + k]->d;
+            d.w[k] = w[lo + k]->d;
+        }
+        launch_ew_scaled_diff(c_.dt, d, dk + lo * ell * 4, c_.stream);
+    }
+    launch_ok("scaled_diff_batch");
+    c_.pool.free(dk);
+    for (size_t i = 0; i < B; ++i) {
+        out[i]->deg = raise_deg ? u[i]->deg + 1 : u[i]->deg;
+        out[i]->scale = scales[i];
+        out[i]->slots = u[i]->slots;
     }
     return out;
 }

@@ -236,6 +236,12 @@ public:
     CtPtr relinearize(const CtPtr& a);
     CtPtr mult_int(const CtPtr& a, u64 k, bool raise_deg, long double new_scale, int keep_ell = 0);
     std::vector<CtPtr> adjust_deg1_batch(const std::vector<CtPtr>& v, int ell, long double scale);  // by an integer constant
+    std::vector<CtPtr> adjust_deg1_batch(const std::vector<CtPtr>& v, int ell, const std::vector<long double>& scales);  // one target scale each
+    // out[i] = a[i] * u[i] - c[i] * w[i] (integers a, c reduced per limb; kernels_elem.h launch_ew_scaled_diff) for pairs of identical
+    // shape, one launch per 32 pairs, the results in ONE block (a batched rescale takes them as they stand).  Degree u's (+1 if
+    // raise_deg), scale scales[i].  The residues of sub(mult_int(u, a), mult_int(w, c)) at equal (limbs, degree).
+    std::vector<CtPtr> scaled_diff_batch(const std::vector<CtPtr>& u, const std::vector<CtPtr>& w, const std::vector<u128>& a,
+                                         const std::vector<u128>& c, bool raise_deg, const std::vector<long double>& scales);
     CtPtr mult_real(const CtPtr& a, double c);              // by a real constant: per-limb scalar round(c * Delta_level)
     CtPtr add_real(const CtPtr& a, double c);               // add a real constant to every slot
     // sum_k coef[k] * terms[k] + c0 for ciphertexts of identical (level, degree 1, scale): the residues of the chain

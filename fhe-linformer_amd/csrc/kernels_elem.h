@@ -58,6 +58,20 @@ struct EwItems {
     const u64* b[MAX_ITEMS];
 };
 void launch_ew_items(const DeviceTables& t, const EwItems& it, int op, int limb_count, hipStream_t s);
+// Scaled difference of up to MAX_ITEMS pairs of ciphertexts of identical shape in ONE launch:
+//     out_i[v] = (a_{i,l} * u_i[v] - c_{i,l} * w_i[v]) mod q_l,   l = v % ell
+// consts: device array [n][ell][4] = (a, shoup(a), c, shoup(c)) per item and limb (the constants depend on each ciphertext's scale).
+// Canonical output.  The glue of an iterative bootstrap (Bootstrapper::bootstrap_iter_batch): 2^p (y - x) and k 2^p y - k z.
+struct EwScaledDiff {
+    static constexpr int MAX_ITEMS = 32;
+    int n = 0;
+    int vecs = 0;   // limb vectors per operand (npoly * ell)
+    int ell = 0;
+    u64* out[MAX_ITEMS];
+    const u64* u[MAX_ITEMS];
+    const u64* w[MAX_ITEMS];
+};
+void launch_ew_scaled_diff(const DeviceTables& t, const EwScaledDiff& d, const u64* consts, hipStream_t s);
 // out[v] = sum_i a_i[v] * b_i[v % b_vecs] over the n items (n <= MAX_ITEMS): an inner product of ciphertexts with plaintexts in
 // one pass (the diagonal sums of the bootstrapping linear transforms, wrapUpRepeated, matmulCRlarge) instead of n product
 // launches and a tree of additions.  128-bit accumulation, one reduction: the canonical residue of the sum.

@@ -463,6 +463,25 @@ __global__ __launch_bounds__(256) void ew_scalar_kernel(DeviceTables t, u64* out
     reinterpret_cast<u64x2*>(out)[(size_t)v * row + n2] = r;
 }
 
+// out_i[v] = a_{i,l} * u_i[v] - c_{i,l} * w_i[v]  (l = v % ell); grid (N/512, n * vecs).  The four constants of (item, limb) are
+// wave-uniform (scalar loads); u and w stream through 16-byte accesses.
+__global__ __launch_bounds__(256) void ew_scaled_diff_kernel(DeviceTables t, EwScaledDiff d, const u64* __restrict__ consts) {
+    const int item = blockIdx.y / d.vecs, v = blockIdx.y % d.vecs;
+    const int limb = v % d.ell;
+    const u64 q = t.moduli[limb];
+    const u64* k = consts + ((size_t)item * d.ell + limb) * 4;
+    const u64 a = k[0], as = k[1], c = k[2], cs = k[3];
+    const size_t n2 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t row = ((size_t)1 << t.log_n) >> 1;
+    const size_t at = (size_t)v * row + n2;
+    const u64x2 x = reinterpret_cast<const u64x2*>(d.u[item])[at];
+    const u64x2 y = reinterpret_cast<const u64x2*>(d.w[item])[at];
+    u64x2 r;
+    r.x = sub_mod(mul_shoup(x.x, a, as, q), mul_shoup(y.x, c, cs, q), q);
+    r.y = sub_mod(mul_shoup(x.y, a, as, q), mul_shoup(y.y, c, cs, q), q);
+    reinterpret_cast<u64x2*>(d.out[item])[at] = r;
+}
+
 // out[v] = a[v] + s[limb]   (adds a constant to every NTT slot == adds the constant polynomial)
 // add_vecs: only the first add_vecs vectors (component 0 of a ciphertext) get the constant, the others are copied through
 __global__ __launch_bounds__(256) void ew_addscalar_kernel(DeviceTables t, u64* out, const u64* a, ScalarSet sc, int limb_first,
@@ -749,6 +768,10 @@ void launch_ew_scalar(const DeviceTables& t, u64* out, const u64* a, const Scala
                       int in_limbs) {
     if (nvec <= 0) return;
     hipLaunchKernelGGL(ew_scalar_kernel, grid2(t.log_n, nvec), dim3(256), 0, s, t, out, a, sc, limb_first, limb_count, in_limbs);
+}
+void launch_ew_scaled_diff(const DeviceTables& t, const EwScaledDiff& d, const u64* consts, hipStream_t s) {
+    if (d.n <= 0 || d.vecs <= 0 || d.ell <= 0) return;
+    hipLaunchKernelGGL(ew_scaled_diff_kernel, grid2(t.log_n, d.n * d.vecs), dim3(256), 0, s, t, d, consts);
 }
 void launch_ew_addscalar(const DeviceTables& t, u64* out, const u64* a, const ScalarSet& sc, int nvec, int limb_first, int limb_count, hipStream_t s,
                          int add_vecs) {

@@ -101,8 +101,11 @@ class GpuController:
     def rotate(self, a, i):
         return self.e.rotate(a, i)
 
-    def bootstrap(self, a):
+    def bootstrap(self, a, precision=None):
+        """precision: None = one bootstrap; p = the iterative bootstrap EvalBootstrap(a, 2, p) (Engine.bootstrap_iter)"""
         self.n_boot += 1
+        if precision is not None:
+            return self.e.bootstrap_iter(a, precision)
         return self.e.bootstrap(a)
 
     # composites: same names as the reference
@@ -350,11 +353,16 @@ class BatchedController:
     def rotate(self, a, i):
         return Batch(self.e.rotate_batch(list(a), i))
 
-    def bootstrap(self, a):
+    def bootstrap(self, a, precision=None):
         # one call per handle, as the single pass makes them: the C ABI defers bootstraps / Chebyshev evaluations and runs everything
         # pending as ONE batch when a result is first read (fhelin_bootstrap_batch) - here the driver's loop over containers
         # (src/main.cpp:354-358) times B samples: 5B wide.  With deferral off (FHELIN_LAZY_HEAVY=0) the B samples still share a batch.
+        # precision: the iterative bootstrap (Engine.bootstrap_iter), deferred and batched the same way
         self.n_boot += 1
+        if precision is not None:
+            if self.e.lazy_heavy:
+                return Batch(self.e.bootstrap_iter(h, precision) for h in a)
+            return Batch(self.e.bootstrap_iter_batch(list(a), precision))
         if self.e.lazy_heavy:
             return Batch(self.e.bootstrap(h) for h in a)
         return Batch(self.e.bootstrap_batch(list(a)))

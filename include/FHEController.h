@@ -422,11 +422,15 @@ public:
         if (timing) print_duration(start, "Bootstrapping " + to_string(c->GetSlots()) + " slots");
         return wrap(o);
     }
+    // EvalBootstrap(c, 2, precision): the iterative bootstrap (include/fhelin.h fhelin_bootstrap_iter), one limb fewer than bootstrap(c)
     Ctxt bootstrap(const Ctxt& c, int precision, bool timing = false) {
-        (void)precision;
         if (static_cast<int>(c->GetLevel()) + 2 < circuit_depth)
             cout << "You are bootstrapping with remaining levels! You are at " << to_string(c->GetLevel()) << "/" << circuit_depth - 2 << endl;
-        return bootstrap(c, timing);
+        auto start = start_time();
+        fhelin_ct* o = nullptr;
+        fhelin_shim::check(fhelin_bootstrap_iter(context, c->h, precision, &o), "EvalBootstrap");
+        if (timing) print_duration(start, "Double Bootstrapping " + to_string(c->GetSlots()) + " slots");
+        return wrap(o);
     }
     Ctxt relu(const Ctxt& c, double scale, bool timing = false) {
         auto start = start_time();

@@ -106,6 +106,12 @@ public:
         for (auto& h : a->v) v.push_back(c_.bootstrap(h, timing));
         return make(v);
     }
+    CtxtBatch bootstrap(const CtxtBatch& a, int precision, bool timing = false) {
+        // the iterative bootstrap, per handle: deferred and batched like bootstrap(a)
+        vector<Ctxt> v;
+        for (auto& h : a->v) v.push_back(c_.bootstrap(h, precision, timing));
+        return make(v);
+    }
 
     /* matmuls (reference :869-1058) */
     vector<CtxtBatch> matmulRE(const vector<CtxtBatch>& rows, const Ptxt& weight, const Ptxt& bias) { return mm_pt(rows, weight, bias, 128, 128); }

@@ -369,6 +369,21 @@ int fhelin_bootstrap_partial(fhelin_ctx* c, const fhelin_ct* a, int32_t stage, f
 /* fhelin_bootstrap raising to L+1-drop limbs only: what a level plan (fhelin_level_plan_*) asks of the k-th bootstrap of a
  * recorded program, here with the number given by the caller */
 int fhelin_bootstrap_drop(fhelin_ctx* c, const fhelin_ct* a, int32_t drop, fhelin_ct** out);
+/* Iterative (two-pass) bootstrapping, the reference's EvalBootstrap(c, 2, precision) (src/FHEController.cpp:454-469): a second
+ * bootstrap of 2^p (y - x) removes most of the first one's error y - x, so the result keeps about twice the bits of one bootstrap.
+ * The engine's definition, residue-exact: y = BTS(x); e = 2^p (y - x) at x's two limbs and exact scale; z = BTS(e);
+ * out = rescale(k (2^p y - z)), k = round(Delta_next q_top / (2^p s_y)).  The result has one limb fewer than a single bootstrap's.
+ * precision p: 1 <= p <= 30, else FHELIN_ERR_ARG (checked before any device work).  2^p |y - x| must stay inside the bootstrap's
+ * input range: useful values are at or below the precision of ONE bootstrap (about 14 bits at the headline ring); larger ones
+ * make the second bootstrap fail silently.  Two iterations only, as the reference.  Deferred and batched like fhelin_bootstrap
+ * (calls with equal precision and planned drop share a batch); each call is a source of the level plan of its own. */
+int fhelin_bootstrap_iter(fhelin_ctx* c, const fhelin_ct* a, int32_t precision, fhelin_ct** out);
+/* fhelin_bootstrap_iter on n independent ciphertexts, both bootstraps batched over all of them; outs[i] holds exactly the residues
+ * of fhelin_bootstrap_iter(v[i], precision) */
+int fhelin_bootstrap_iter_batch(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, int32_t precision, fhelin_ct** outs);
+/* test hook: fhelin_bootstrap_iter with both bootstraps raising to L+1-drop limbs (fhelin_bootstrap_drop); a drop that leaves a
+ * single bootstrap fewer than 3 limbs is FHELIN_ERR_STATE */
+int fhelin_bootstrap_iter_drop(fhelin_ctx* c, const fhelin_ct* a, int32_t precision, int32_t drop, fhelin_ct** out);
 /* ---- read-only views of the bootstrapping set-up: the residue-level oracle (oracle/residue_boot.py, tests only) composes
  * EvalBootstrap (:445) from the same linear stages, Chebyshev coefficients and keys and must reach the same residues.
  * describe: out = {packed, slots, K, R, cheb_degree, correction, depth, n_c2s, n_s2c, then per stage (CoeffsToSlots stages

@@ -54,3 +54,31 @@ if os.environ.get("BOOT_BATCH"):
             e.bootstrap_drop(c, drop)
         e.sync(); ts.append((time.time() - t0) * 1e3)
     print(f"one by one (drop {drop}): {min(ts):.1f} ms = {min(ts)/B:.2f} ms per bootstrap")
+
+# iterative bootstrapping, EvalBootstrap(c, 2, p) (BOOT_PRECISION=p): alone on the input above next to the single form, then in a batch
+# of five next to bootstrap_batch; the maximum error of each
+if os.environ.get("BOOT_PRECISION"):
+    p = int(os.environ["BOOT_PRECISION"])
+
+    def best(f, reps=4):
+        ts, out = [], None
+        for _ in range(reps):
+            e.sync(); t0 = time.time()
+            out = f()
+            e.sync(); ts.append((time.time() - t0) * 1e3)
+        return min(ts), out
+
+    t1, one = best(lambda: e.bootstrap_drop(ct, 0))
+    t2, two = best(lambda: e.bootstrap_iter_drop(ct, p, 0))
+    e1, e2 = np.max(np.abs(e.decrypt(one) - m)), np.max(np.abs(e.decrypt(two) - m))
+    print(f"single: {t1:.1f} ms, out ell {one.info()['ell']}, max err {e1:.3e}")
+    print(f"iterative p={p}: {t2:.1f} ms ({t2 / t1:.2f} x single), out ell {two.info()['ell']}, max err {e2:.3e} ({e1 / e2:.0f} x smaller)")
+    B = 5
+    ms = [np.random.default_rng(30 + i).uniform(-1, 1, n) for i in range(B)]
+    cts = [e.encrypt(v, level=e.n_q - 3) for v in ms]
+    tb1, outs1 = best(lambda: e.bootstrap_batch(cts))
+    tb2, outs2 = best(lambda: e.bootstrap_iter_batch(cts, p))
+    eb1 = max(np.max(np.abs(e.decrypt(o) - v)) for o, v in zip(outs1, ms))
+    eb2 = max(np.max(np.abs(e.decrypt(o) - v)) for o, v in zip(outs2, ms))
+    print(f"batch of {B}, single: {tb1:.1f} ms = {tb1 / B:.2f} ms each, max err {eb1:.3e}")
+    print(f"batch of {B}, iterative p={p}: {tb2:.1f} ms = {tb2 / B:.2f} ms each ({tb2 / tb1:.2f} x single), max err {eb2:.3e}")
