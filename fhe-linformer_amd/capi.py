@@ -202,6 +202,11 @@ def load_library():
         "fhelin_add_plain_batch": (i32, [vp, C.POINTER(vp), i32, vp, C.POINTER(vp)]),
         "fhelin_eval_poly_batch": (i32, [vp, C.POINTER(vp), i32, C.POINTER(C.c_double), i32, C.POINTER(vp)]),
         "fhelin_mult_many_batch": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp)]),
+        "fhelin_evalkeys_save": (i32, [vp, C.c_char_p]),
+        "fhelin_evalkeys_params": (i32, [C.c_char_p, C.POINTER(Params)]),
+        "fhelin_evalkeys_info": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]),
+        "fhelin_evalkeys_load": (i32, [vp, C.c_char_p]),
+        "fhelin_debug_key_digest": (i32, [vp, vp, i32, i32, C.POINTER(C.c_uint64), C.POINTER(i32)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -418,6 +423,9 @@ class Engine:
         arr = (C.c_int32 * len(indices))(*indices)
         self._ck(self.lib.fhelin_gen_rotation_keys(self.h, arr, len(indices)))
 
+    def gen_conj_key(self):
+        self._ck(self.lib.fhelin_gen_conj_key(self.h))
+
     @property
     def n_limbs(self):
         return self.n_q + self.n_p
@@ -444,6 +452,55 @@ class Engine:
         arr = np.ascontiguousarray(arr, dtype=np.uint64)
         assert arr.shape == (self.dnum_digits, 2, self.n_limbs, self.N)
         self._ck(self.lib.fhelin_key_import(self.h, kind, index, arr.ctypes.data_as(C.c_void_p), arr.size))
+
+    # ---- evaluation-key sets (include/fhelin.h "Evaluation-key sets")
+    def save_eval_keys(self, path):
+        """write the public parameters and every public key this context holds (never the secret) to `path`"""
+        self._ck(self.lib.fhelin_evalkeys_save(self.h, os.fsencode(path)))
+
+    @staticmethod
+    def eval_keys_params(path):
+        """(parameter dict, bootstrap dict or None, key count) of a set's header; host-only"""
+        lib = load_library()
+        prm, boot, n = Params(), (C.c_int32 * 7)(), C.c_int32()
+        for rc in (lib.fhelin_evalkeys_params(os.fsencode(path), C.byref(prm)),
+                   lib.fhelin_evalkeys_info(os.fsencode(path), boot, C.byref(n))):
+            if rc != 0:
+                raise FhelinError(rc, lib.fhelin_last_error().decode())
+        cfg = {k: getattr(prm, k) for k in ("log_n", "n_q", "first_bits", "scale_bits", "n_p", "special_bits", "dnum", "log_slots", "hamming")}
+        b = list(boot)
+        bt = dict(zip(("budget_enc", "budget_dec", "slots", "K", "R", "cheb_degree", "correction"), b)) if b[2] > 0 else None
+        return cfg, bt, n.value
+
+    @classmethod
+    def from_eval_keys(cls, path, device=0, seed=0):
+        """an EVALUATION context (no secret) from a set written by save_eval_keys: the header's parameters, its keys, and the
+        client's bootstrapping set up again from them when the client had set it up.  seed: this context's own generator
+        (public-key encryption randomness), 0 = OS entropy."""
+        cfg, boot, _ = cls.eval_keys_params(path)
+        eng = cls(cfg, device=device, seed=seed)
+        try:
+            eng._ck(eng.lib.fhelin_evalkeys_load(eng.h, os.fsencode(path)))
+            if boot is not None:
+                eng.bootstrap_setup(boot["budget_enc"], boot["budget_dec"], boot["slots"])
+        except Exception:
+            eng.close()
+            raise
+        return eng
+
+    def load_eval_keys(self, path):
+        """load a set into this (fresh) context; it becomes an evaluation context"""
+        self._ck(self.lib.fhelin_evalkeys_load(self.h, os.fsencode(path)))
+
+    def debug_key_digest(self, words, limb_first=0):
+        """the device digest kernel on limb vectors words[n][N]: (digests[n] uint64, ok[n] bool)"""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        n = w.shape[0]
+        assert w.shape == (n, self.N)
+        d, ok = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32)
+        self._ck(self.lib.fhelin_debug_key_digest(self.h, w.ctypes.data_as(C.c_void_p), n, int(limb_first),
+                                                  d.ctypes.data_as(C.POINTER(C.c_uint64)), ok.ctypes.data_as(C.POINTER(C.c_int32))))
+        return d, ok.astype(bool)
 
     # ---- plaintexts / ciphertexts
     def encode(self, vals, level=0, slots=0):

@@ -157,11 +157,14 @@ LinStage Bootstrapper::prepare(const DiagMap& m, int n) {
 void Bootstrapper::setup(int budget_enc, int budget_dec, int slots) {
     Context& c = ev_.ctx();
     c.require_device();
-    if (!cl_.has_keys()) throw Error(FHELIN_ERR_KEY, "bootstrap setup needs the secret key (keygen first)");
+    // an evaluation context (no secret) builds its stages from the imported keys: a missing one is named below (FHELIN_ERR_KEY)
+    if (!cl_.has_keys() && !cl_.eval_only()) throw Error(FHELIN_ERR_KEY, "bootstrap setup needs the secret key (keygen first)");
     if (slots <= 0) slots = 1 << c.prm.log_slots;
     if (slots & (slots - 1) || slots > c.N / 2 || slots < 4) throw Error(FHELIN_ERR_ARG, "bootstrap: slots must be a power of two in [4, N/2]");
     if (budget_enc < 1 || budget_dec < 1) throw Error(FHELIN_ERR_ARG, "bootstrap: level budget must be >= 1");
     slots_ = slots;
+    budget_enc_ = budget_enc;
+    budget_dec_ = budget_dec;
     const int n = slots;
     int logn = 0;
     while ((1 << logn) < n) ++logn;

@@ -58,6 +58,8 @@ public:
     const std::vector<double>& cheb() const { return cheb_; }
     bool packed() const { return packed_; }
     int slots() const { return slots_; }
+    int budget_enc() const { return budget_enc_; }   // as setup() was called (evaluation-key sets record them)
+    int budget_dec() const { return budget_dec_; }
 
     // parameters (DESIGN.md "Bootstrapping")
     int K = 28;            // bound on |I|: t = Delta m + q0 I
@@ -69,6 +71,7 @@ private:
     Evaluator& ev_;
     Client& cl_;
     int slots_ = 0;
+    int budget_enc_ = 0, budget_dec_ = 0;
     bool stage_order_legacy_ = false;   // FHELIN_BOOT_STAGES_LEGACY=1: larger stages first (round-1 split 5+5+4)
     bool packed_ = false;   // sparse packing: real and imaginary halves share one ciphertext through EvalMod (bootstrap.cpp)
     int depth_ = 0;

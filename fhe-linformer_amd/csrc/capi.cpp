@@ -93,6 +93,8 @@ int fhelin_ctx_create_seeded(const fhelin_params* p, const uint8_t* seed32, fhel
 }
 int fhelin_ctx_secret_seed(const fhelin_ctx* c, uint8_t* out32) {
     if (!c || !out32) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    // an evaluation context's generator seed only drives its own encryption randomness: no secret derives from it
+    if (c->cl.eval_only()) return capi_fail(FHELIN_ERR_KEY, "secret_seed: an evaluation context holds no secret");
     std::memcpy(out32, c->ctx.prm.seed_bytes, 32);
     return FHELIN_OK;
 }

@@ -184,6 +184,7 @@ int fhelin_debug_sample(fhelin_ctx* c, int32_t kind, int32_t n_poly, int64_t* ou
 int fhelin_decrypt(fhelin_ctx* c, const fhelin_ct* ct, double* out, int32_t slots) {
     NEED(c && ct && out);
     FHELIN_TRY
+    if (c->cl.eval_only()) throw Error(FHELIN_ERR_KEY, "decrypt: an evaluation context holds no secret key");
     if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
     c->plan.check_terminal(*ct_in(c, ct), 2);
     auto v = c->cl.decrypt(ct_in(c, ct), slots);

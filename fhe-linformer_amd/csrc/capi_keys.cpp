@@ -1,0 +1,482 @@
+// extern "C" boundary, part 4: evaluation-key sets (include/fhelin.h "Evaluation-key sets": the file format is documented there).
+// A client context writes its public key and every switching key it holds; a context that never held a secret loads them and
+// evaluates with them alone.  Every key is range-checked and digested on the device (kernels_keys.hip) on the way out and on
+// the way in; the file is streamed through two pinned staging buffers, so host memory stays bounded by them.
+#include "../../include/fhelin.h"
+#include <hip/hip_runtime.h>
+#include <sys/stat.h>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include "capi_internal.h"
+#include "kernels_keys.h"
+
+using namespace fhelin;
+
+#if !defined(__BYTE_ORDER__) || __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
+#error "the evaluation-key set is written in host byte order, which must be little-endian"
+#endif
+
+namespace {
+
+constexpr char EK_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'K'};
+constexpr uint32_t EK_VERSION = 1;
+constexpr size_t EK_HEADER = 96, EK_ENTRY = 40, EK_ALIGN = 4096;
+constexpr uint32_t EK_MAX_KEYS = 1u << 16;
+constexpr size_t EK_STAGE_BYTES = size_t(4) << 20;   // per staging buffer (two of them)
+enum : uint32_t { EK_PUBLIC = 0, EK_RELIN = 1, EK_ROTATION = 2, EK_CONJ = 3 };
+
+struct EkEntry {
+    uint32_t kind = 0, digits = 0;
+    uint64_t galois = 0, offset = 0, words = 0, digest = 0;
+};
+struct EkFile {
+    int32_t prm[9] = {};    // log_n, n_q, first_bits, scale_bits, n_p, special_bits, dnum, log_slots, hamming
+    int32_t boot[7] = {};   // budget_enc, budget_dec, slots (0: no bootstrapping set up), K, R, cheb_degree, correction
+    std::vector<uint64_t> moduli;
+    std::vector<EkEntry> keys;
+    uint64_t data_offset = 0;
+};
+
+struct File {
+    FILE* f = nullptr;
+    File(const char* path, const char* mode) : f(std::fopen(path, mode)) {}
+    ~File() {
+        if (f) std::fclose(f);
+    }
+};
+
+const char* kind_name(uint32_t k) {
+    static const char* n[] = {"public key", "relinearisation key", "rotation key", "conjugation key"};
+    return k < 4 ? n[k] : "?";
+}
+
+Params to_params(const int32_t* p, int device, uint64_t seed) {
+    Params q;
+    q.log_n = p[0];
+    q.n_q = p[1];
+    q.first_bits = p[2];
+    q.scale_bits = p[3];
+    q.n_p = p[4];
+    q.special_bits = p[5];
+    q.dnum = p[6];
+    q.log_slots = p[7];
+    q.hamming = p[8];
+    q.device = device;
+    q.seed = seed;
+    return q;
+}
+void from_params(const Params& q, int32_t* p) {
+    const int32_t v[9] = {q.log_n, q.n_q, q.first_bits, q.scale_bits, q.n_p, q.special_bits, q.dnum, q.log_slots, q.hamming};
+    std::memcpy(p, v, sizeof(v));
+}
+
+template <class T> T get(const uint8_t* b, size_t off) {
+    T v;
+    std::memcpy(&v, b + off, sizeof(T));
+    return v;
+}
+template <class T> void put(std::vector<uint8_t>& b, size_t off, T v) { std::memcpy(b.data() + off, &v, sizeof(T)); }
+
+// header + moduli + key table, every field validated against the others and against the file's size: a malformed set is
+// FHELIN_ERR_ARG before anything is allocated
+EkFile read_header(const char* path) {
+    File fh(path, "rb");
+    if (!fh.f) throw Error(FHELIN_ERR_ARG, std::string("evaluation-key set: cannot open ") + path);
+    struct stat st;
+    if (fstat(fileno(fh.f), &st) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: cannot stat the file");
+    const uint64_t fsize = (uint64_t)st.st_size;
+    uint8_t h[EK_HEADER];
+    if (fsize < EK_HEADER || std::fread(h, 1, EK_HEADER, fh.f) != EK_HEADER) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
+    if (std::memcmp(h, EK_MAGIC, 8) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad magic");
+    if (get<uint32_t>(h, 8) != EK_VERSION) throw Error(FHELIN_ERR_ARG, "evaluation-key set: unsupported version");
+    EkFile e;
+    const uint32_t n_keys = get<uint32_t>(h, 12);
+    for (int i = 0; i < 9; ++i) e.prm[i] = get<int32_t>(h, 16 + 4 * i);
+    for (int i = 0; i < 7; ++i) e.boot[i] = get<int32_t>(h, 52 + 4 * i);
+    e.data_offset = get<uint64_t>(h, 80);
+    const int log_n = e.prm[0], n_q = e.prm[1], n_p = e.prm[4];
+    if (log_n < 12 || log_n > 17 || n_q < 1 || n_q > 64 || n_p < 0 || n_p > 64 || e.prm[6] < 1 || get<uint64_t>(h, 88) != 0)
+        throw Error(FHELIN_ERR_ARG, "evaluation-key set: parameters out of range");
+    const int32_t* b = e.boot;
+    const bool boot_ok = b[2] == 0 ? (b[0] | b[1] | b[3] | b[4] | b[5] | b[6]) == 0
+                                   : b[0] >= 1 && b[1] >= 1 && b[2] >= 4 && !(b[2] & (b[2] - 1)) && b[3] >= 1 && b[4] >= 0 && b[4] <= 8 &&
+                                         b[5] >= 3 && b[5] <= 255 && b[6] >= 0 && b[6] <= 20;
+    if (!boot_ok) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad bootstrap configuration");
+    if (n_keys > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evaluation-key set: too many keys");
+    const uint64_t N = 1ull << log_n, nm = (uint64_t)n_q + n_p;
+    const uint64_t table_end = EK_HEADER + 8 * nm + EK_ENTRY * (uint64_t)n_keys;
+    if (fsize < table_end) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated key table");
+    e.moduli.resize(nm);
+    if (std::fread(e.moduli.data(), 8, nm, fh.f) != nm) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated moduli");
+    std::vector<uint8_t> t((size_t)EK_ENTRY * n_keys);
+    if (n_keys && std::fread(t.data(), 1, t.size(), fh.f) != t.size()) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated key table");
+    if (e.data_offset != (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN)
+        throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad payload offset");
+    uint64_t at = e.data_offset;
+    int seen[4] = {};
+    uint64_t last_g = 0;
+    for (uint32_t k = 0; k < n_keys; ++k) {
+        const uint8_t* r = t.data() + (size_t)EK_ENTRY * k;
+        EkEntry x;
+        x.kind = get<uint32_t>(r, 0);
+        x.digits = get<uint32_t>(r, 4);
+        x.galois = get<uint64_t>(r, 8);
+        x.offset = get<uint64_t>(r, 16);
+        x.words = get<uint64_t>(r, 24);
+        x.digest = get<uint64_t>(r, 32);
+        if (x.kind > EK_CONJ) throw Error(FHELIN_ERR_ARG, "evaluation-key set: unknown key kind");
+        if (x.kind != EK_ROTATION && ++seen[x.kind] > 1) throw Error(FHELIN_ERR_ARG, "evaluation-key set: duplicate key");
+        const uint64_t want = x.kind == EK_PUBLIC ? 2 * (uint64_t)n_q * N : (uint64_t)x.digits * 2 * nm * N;
+        if ((x.kind == EK_PUBLIC) != (x.digits == 0) || x.digits > (uint32_t)n_q || x.words != want)
+            throw Error(FHELIN_ERR_ARG, "evaluation-key set: key size does not match the parameters");
+        const uint64_t g_want = x.kind == EK_CONJ ? 2 * N - 1 : 0;
+        if (x.kind == EK_ROTATION) {
+            if (!(x.galois & 1) || x.galois >= 2 * N - 1 || x.galois <= last_g)
+                throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad or unordered Galois element");
+            last_g = x.galois;
+        } else if (x.galois != g_want) {
+            throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad Galois element");
+        }
+        if (x.offset != at || x.digest >= KEY_DIGEST_P) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad key table entry");
+        at += 8 * x.words;
+        e.keys.push_back(x);
+    }
+    if (fsize != at) throw Error(FHELIN_ERR_ARG, "evaluation-key set: file size does not match the key table (truncated?)");
+    return e;
+}
+
+// the host-only parameter context of the header: its prime chain must be the file's
+void check_moduli(const EkFile& e, const std::vector<u64>& moduli) {
+    if (moduli.size() != e.moduli.size() || std::memcmp(moduli.data(), e.moduli.data(), 8 * moduli.size()) != 0)
+        throw Error(FHELIN_ERR_ARG, "evaluation-key set: moduli do not match the parameters");
+}
+
+struct Pinned {
+    void* p[2] = {};
+    hipEvent_t ev[2] = {};
+    bool used[2] = {};
+    hipStream_t s;
+    explicit Pinned(hipStream_t st) : s(st) {
+        for (int i = 0; i < 2; ++i) {
+            hip_check(hipHostMalloc(&p[i], EK_STAGE_BYTES, hipHostMallocDefault), "hipHostMalloc(key staging)");
+            hip_check(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming), "hipEventCreate(key staging)");
+        }
+    }
+    void wait(int i) {
+        if (used[i]) hip_check(hipEventSynchronize(ev[i]), "hipEventSynchronize(key staging)");
+        used[i] = false;
+    }
+    ~Pinned() {
+        (void)hipStreamSynchronize(s);
+        for (int i = 0; i < 2; ++i) {
+            if (p[i]) (void)hipHostFree(p[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    }
+};
+
+struct Seg {
+    u64* d;
+    size_t words;
+};
+
+// per-vector digests / range flags of every key on the device, folded into one digest per key on the host.  ok[k] = every
+// residue of key k below its limb's modulus.
+void key_digests(Context& x, const std::vector<Seg>& segs, const std::vector<uint32_t>& kinds, std::vector<uint64_t>& digest,
+                 std::vector<char>& ok) {
+    const size_t N = x.N;
+    size_t total = 0, max_vec = 0;
+    for (const Seg& s : segs) {
+        total += s.words / N;
+        max_vec = std::max(max_vec, s.words / N);
+    }
+    digest.assign(segs.size(), 0);
+    ok.assign(segs.size(), 1);
+    if (!total) return;
+    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, (int)max_vec));
+    u64* out = x.dalloc<u64>(2 * total);
+    size_t v0 = 0;
+    for (size_t k = 0; k < segs.size(); ++k) {
+        const int n_vec = (int)(segs[k].words / N);
+        const int limb_count = kinds[k] == EK_PUBLIC ? x.L + 1 : x.L + 1 + x.K;
+        launch_key_digest(x.dt, segs[k].d, n_vec, 0, limb_count, part, out + 2 * v0, x.stream);
+        v0 += n_vec;
+    }
+    hip_check(hipGetLastError(), "key digest kernels");
+    std::vector<u64> h(2 * total);
+    hip_check(hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "key digest download");
+    hip_check(hipStreamSynchronize(x.stream), "key digest sync");
+    x.pool.free(part);
+    x.pool.free(out);
+    v0 = 0;
+    for (size_t k = 0; k < segs.size(); ++k) {
+        const size_t n_vec = segs[k].words / N;
+        u128 acc = 0;
+        for (size_t j = 0; j < n_vec; ++j) {
+            acc += (u128)h[2 * (v0 + j)] * key_weight_vec((u32)j);
+            if (!h[2 * (v0 + j) + 1]) ok[k] = 0;
+        }
+        digest[k] = (u64)(acc % KEY_DIGEST_P);
+        v0 += n_vec;
+    }
+}
+
+bool fresh(const fhelin_ctx* c) {
+    if (c->cl.keygen_run() || c->cl.eval_only() || c->cl.has_public_key() || c->ev.relin_key || c->ev.conj_key || c->boot.ready())
+        return false;
+    for (const auto& kv : c->ev.rot_keys)
+        if (kv.second) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhelin_evalkeys_params(const char* path, fhelin_params* out) {
+    if (!path || !out) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    EkFile e = read_header(path);
+    Context host(to_params(e.prm, -1, 1));   // host-only: the prime chain the parameters give
+    check_moduli(e, host.moduli);
+    Params q = to_params(e.prm, 0, 0);
+    fhelin_params r{q.log_n, q.n_q, q.first_bits, q.scale_bits, q.n_p, q.special_bits, q.dnum, q.log_slots, q.hamming, 0, 0};
+    *out = r;
+    FHELIN_CATCH
+}
+
+int fhelin_evalkeys_info(const char* path, int32_t* boot7, int32_t* n_keys) {
+    if (!path) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    EkFile e = read_header(path);
+    if (boot7) std::memcpy(boot7, e.boot, sizeof(e.boot));
+    if (n_keys) *n_keys = (int32_t)e.keys.size();
+    FHELIN_CATCH
+}
+
+int fhelin_evalkeys_save(fhelin_ctx* c, const char* path) {
+    if (!c || !path) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    x.sync();
+    const u64 g_conj = 2ull * x.N - 1;
+    std::vector<Seg> segs;
+    std::vector<EkEntry> ents;
+    auto add = [&](uint32_t kind, uint32_t digits, uint64_t g, u64* d, size_t words) {
+        EkEntry e;
+        e.kind = kind;
+        e.digits = digits;
+        e.galois = g;
+        e.words = words;
+        ents.push_back(e);
+        segs.push_back({d, words});
+    };
+    if (c->cl.has_public_key()) add(EK_PUBLIC, 0, 0, const_cast<u64*>(c->cl.public_key()), (size_t)2 * (x.L + 1) * x.N);
+    if (c->ev.relin_key) add(EK_RELIN, c->ev.relin_key->digits, 0, c->ev.relin_key->d, c->ev.relin_key->words());
+    if (c->ev.conj_key) add(EK_CONJ, c->ev.conj_key->digits, g_conj, c->ev.conj_key->d, c->ev.conj_key->words());
+    for (const auto& kv : c->ev.rot_keys)   // ordered by Galois element; the conjugation key is stored once, above
+        if (kv.second && kv.first != g_conj) add(EK_ROTATION, kv.second->digits, kv.first, kv.second->d, kv.second->words());
+    if (ents.empty()) throw Error(FHELIN_ERR_KEY, "evalkeys_save: the context holds no keys");
+    if (ents.size() > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evalkeys_save: too many keys");
+    if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "evalkeys_save: ring dimension below 2^12");
+
+    std::vector<uint32_t> kinds;
+    for (const auto& e : ents) kinds.push_back(e.kind);
+    std::vector<uint64_t> digest;
+    std::vector<char> ok;
+    key_digests(x, segs, kinds, digest, ok);
+    for (size_t k = 0; k < ents.size(); ++k) {
+        if (!ok[k]) throw Error(FHELIN_ERR_INTERNAL, std::string("evalkeys_save: ") + kind_name(ents[k].kind) + " holds a residue out of range");
+        ents[k].digest = digest[k];
+    }
+
+    const size_t nm = x.moduli.size();
+    const uint64_t table_end = EK_HEADER + 8 * nm + EK_ENTRY * ents.size();
+    const uint64_t data_offset = (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN;
+    std::vector<uint8_t> h(data_offset, 0);
+    std::memcpy(h.data(), EK_MAGIC, 8);
+    put<uint32_t>(h, 8, EK_VERSION);
+    put<uint32_t>(h, 12, (uint32_t)ents.size());
+    int32_t prm[9];
+    from_params(x.prm, prm);
+    std::memcpy(h.data() + 16, prm, sizeof(prm));
+    if (c->boot.ready()) {
+        const int32_t b[7] = {c->boot.budget_enc(), c->boot.budget_dec(), c->boot.slots(), c->boot.K, c->boot.R, c->boot.cheb_degree,
+                              c->boot.correction};
+        std::memcpy(h.data() + 52, b, sizeof(b));
+    }
+    put<uint64_t>(h, 80, data_offset);
+    std::memcpy(h.data() + EK_HEADER, x.moduli.data(), 8 * nm);
+    uint64_t at = data_offset;
+    for (size_t k = 0; k < ents.size(); ++k) {
+        ents[k].offset = at;
+        at += 8 * ents[k].words;
+        const size_t o = EK_HEADER + 8 * nm + EK_ENTRY * k;
+        put<uint32_t>(h, o, ents[k].kind);
+        put<uint32_t>(h, o + 4, ents[k].digits);
+        put<uint64_t>(h, o + 8, ents[k].galois);
+        put<uint64_t>(h, o + 16, ents[k].offset);
+        put<uint64_t>(h, o + 24, ents[k].words);
+        put<uint64_t>(h, o + 32, ents[k].digest);
+    }
+
+    bool written = false;
+    {
+        File fh(path, "wb");
+        if (!fh.f) throw Error(FHELIN_ERR_ARG, std::string("evalkeys_save: cannot create ") + path);
+        bool io_ok = std::fwrite(h.data(), 1, h.size(), fh.f) == h.size();
+        // payloads: device -> pinned buffer b while the host writes the other buffer's previous chunk
+        Pinned stg(x.stream);
+        int cur = 0;
+        size_t pend_bytes[2] = {};
+        for (const Seg& s : segs) {
+            const size_t bytes = s.words * 8;
+            for (size_t off = 0; off < bytes && io_ok; off += EK_STAGE_BYTES) {
+                const size_t n = std::min(EK_STAGE_BYTES, bytes - off);
+                hip_check(hipMemcpyAsync(stg.p[cur], reinterpret_cast<const char*>(s.d) + off, n, hipMemcpyDeviceToHost, x.stream),
+                          "key download");
+                hip_check(hipEventRecord(stg.ev[cur], x.stream), "hipEventRecord(key staging)");
+                stg.used[cur] = true;
+                pend_bytes[cur] = n;
+                const int prev = cur ^ 1;
+                if (stg.used[prev]) {
+                    stg.wait(prev);
+                    io_ok = std::fwrite(stg.p[prev], 1, pend_bytes[prev], fh.f) == pend_bytes[prev];
+                }
+                cur = prev;
+            }
+        }
+        const int last = cur ^ 1;
+        if (io_ok && stg.used[last]) {
+            stg.wait(last);
+            io_ok = std::fwrite(stg.p[last], 1, pend_bytes[last], fh.f) == pend_bytes[last];
+        }
+        written = io_ok && std::fflush(fh.f) == 0;
+    }
+    if (!written) {
+        std::remove(path);
+        throw Error(FHELIN_ERR_ARG, std::string("evalkeys_save: write to ") + path + " failed");
+    }
+    FHELIN_CATCH
+}
+
+int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
+    if (!c || !path) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    EkFile e = read_header(path);
+    if (!fresh(c)) throw Error(FHELIN_ERR_STATE, "evalkeys_load: the context must be fresh (no keygen, no keys, no bootstrap set-up)");
+    int32_t prm[9];
+    from_params(x.prm, prm);
+    if (std::memcmp(prm, e.prm, sizeof(prm)) != 0) throw Error(FHELIN_ERR_STATE, "evalkeys_load: the set was made for other parameters");
+    check_moduli(e, x.moduli);
+    const int digits = x.digits_at(x.L + 1);
+    for (const auto& k : e.keys)
+        if (k.kind != EK_PUBLIC && (int)k.digits != digits)
+            throw Error(FHELIN_ERR_ARG, "evalkeys_load: switching key digit count does not match the context");
+
+    // destinations: nothing is installed until every key has passed (the guards free the blocks on any failure)
+    struct PkGuard {
+        Context& x;
+        u64* d = nullptr;
+        ~PkGuard() {
+            if (d) x.pool.free(d);
+        }
+    } pk{x};
+    std::vector<KeyPtr> sw(e.keys.size());
+    std::vector<Seg> segs;
+    std::vector<uint32_t> kinds;
+    for (size_t k = 0; k < e.keys.size(); ++k) {
+        if (e.keys[k].kind == EK_PUBLIC) {
+            pk.d = x.dalloc<u64>(e.keys[k].words);
+            segs.push_back({pk.d, e.keys[k].words});
+        } else {
+            sw[k] = c->ev.new_key();
+            segs.push_back({sw[k]->d, sw[k]->words()});
+        }
+        kinds.push_back(e.keys[k].kind);
+    }
+    {
+        File fh(path, "rb");
+        if (!fh.f || std::fseek(fh.f, (long)e.data_offset, SEEK_SET) != 0) throw Error(FHELIN_ERR_ARG, "evalkeys_load: cannot read the payloads");
+        // file -> pinned buffer b while buffer b^1's previous chunk is on its way to the device
+        Pinned stg(x.stream);
+        int cur = 0;
+        for (const Seg& s : segs) {
+            const size_t bytes = s.words * 8;
+            for (size_t off = 0; off < bytes; off += EK_STAGE_BYTES) {
+                const size_t n = std::min(EK_STAGE_BYTES, bytes - off);
+                stg.wait(cur);
+                if (std::fread(stg.p[cur], 1, n, fh.f) != n) throw Error(FHELIN_ERR_ARG, "evalkeys_load: truncated payload");
+                hip_check(hipMemcpyAsync(reinterpret_cast<char*>(s.d) + off, stg.p[cur], n, hipMemcpyHostToDevice, x.stream), "key upload");
+                hip_check(hipEventRecord(stg.ev[cur], x.stream), "hipEventRecord(key staging)");
+                stg.used[cur] = true;
+                cur ^= 1;
+            }
+        }
+    }
+    std::vector<uint64_t> digest;
+    std::vector<char> ok;
+    key_digests(x, segs, kinds, digest, ok);
+    for (size_t k = 0; k < e.keys.size(); ++k) {
+        const auto& ek = e.keys[k];
+        std::string what = std::string(kind_name(ek.kind)) + (ek.kind == EK_ROTATION ? " (Galois element " + std::to_string(ek.galois) + ")" : "");
+        if (!ok[k]) throw Error(FHELIN_ERR_ARG, "evalkeys_load: " + what + " holds a residue not below its modulus");
+        if (digest[k] != ek.digest) throw Error(FHELIN_ERR_ARG, "evalkeys_load: " + what + " does not match its digest");
+    }
+
+    // install
+    for (size_t k = 0; k < e.keys.size(); ++k) {
+        switch (e.keys[k].kind) {
+            case EK_RELIN: c->ev.relin_key = sw[k]; break;
+            case EK_CONJ:
+                c->ev.conj_key = sw[k];
+                c->ev.rot_keys[2ull * x.N - 1] = sw[k];
+                break;
+            case EK_ROTATION: c->ev.rot_keys[e.keys[k].galois] = sw[k]; break;
+            default: break;
+        }
+    }
+    c->cl.install_public_key(pk.d);
+    pk.d = nullptr;
+    if (e.boot[2] > 0) {   // the client's approximation parameters; fhelin_bootstrap_setup is the caller's (fhelin_evalkeys_info)
+        c->boot.K = e.boot[3];
+        c->boot.R = e.boot[4];
+        c->boot.cheb_degree = e.boot[5];
+        c->boot.correction = e.boot[6];
+    }
+    FHELIN_CATCH
+}
+
+int fhelin_debug_key_digest(fhelin_ctx* c, const uint64_t* words, int32_t n_limbs, int32_t limb_first, uint64_t* out_digests,
+                            int32_t* out_ok) {
+    if (!c || !words || !out_digests || !out_ok) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    if (n_limbs < 1 || limb_first < 0 || limb_first + n_limbs > x.L + 1 + x.K) throw Error(FHELIN_ERR_ARG, "debug_key_digest: limbs out of range");
+    if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "debug_key_digest: ring dimension below 2^12");
+    const size_t n = (size_t)n_limbs * x.N;
+    u64* d = x.dalloc<u64>(n);
+    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, n_limbs));
+    u64* out = x.dalloc<u64>(2 * (size_t)n_limbs);
+    hip_check(hipMemcpyAsync(d, words, n * 8, hipMemcpyHostToDevice, x.stream), "debug digest upload");
+    launch_key_digest(x.dt, d, n_limbs, limb_first, n_limbs, part, out, x.stream);
+    hip_check(hipGetLastError(), "key digest kernels");
+    std::vector<u64> h(2 * (size_t)n_limbs);
+    hip_check(hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "debug digest download");
+    hip_check(hipStreamSynchronize(x.stream), "debug digest sync");
+    x.pool.free(d);
+    x.pool.free(part);
+    x.pool.free(out);
+    for (int i = 0; i < n_limbs; ++i) {
+        out_digests[i] = h[2 * i];
+        out_ok[i] = (int32_t)h[2 * i + 1];
+    }
+    FHELIN_CATCH
+}
+
+}  // extern "C"

@@ -366,8 +366,16 @@ void Client::sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind) 
     c_.pool.free(dco);
 }
 
+void Client::install_public_key(u64* d_pk) {
+    if (pk) c_.pool.free(pk);
+    pk = d_pk;
+    eval_only_ = true;
+}
+
 void Client::keygen() {
+    if (eval_only_) throw Error(FHELIN_ERR_KEY, "keygen: an evaluation context holds no secret and cannot make one");
     c_.require_device();
+    keygen_run_ = true;
     const size_t N = c_.N;
     const int L1 = c_.L + 1, nl = L1 + c_.K;
     // sparse ternary secret of Hamming weight h (reference SetSecretKeyDist(SPARSE_TERNARY), :8)
@@ -449,7 +457,10 @@ KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all) {
 }
 
 void Client::gen_relin_key() {
-    if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+    if (!s_all) {
+        if (ev_.relin_key) return;   // without the secret: a key that is present is all this call can confirm
+        throw Error(FHELIN_ERR_KEY, eval_only_ ? "relinearisation key not in the evaluation-key set" : "keygen() has not been called");
+    }
     const int nl = c_.L + 1 + c_.K;
     u64* s2 = c_.dalloc<u64>((size_t)nl * c_.N);
     launch_ew_mul(c_.dt, s2, s_all, s_all, nl, nl, 0, nl, c_.stream);
@@ -458,8 +469,13 @@ void Client::gen_relin_key() {
 }
 
 void Client::gen_rotation_key(int index) {
-    if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     const u64 g = c_.galois_element(index);
+    if (!s_all) {
+        auto it = ev_.rot_keys.find(g);
+        if (it != ev_.rot_keys.end() && it->second) return;
+        throw Error(FHELIN_ERR_KEY, eval_only_ ? "rotation key for index " + std::to_string(index) + " not in the evaluation-key set"
+                                              : "keygen() has not been called");
+    }
     if (ev_.rot_keys.count(g)) return;
     const int nl = c_.L + 1 + c_.K;
     // key switches from s to sigma_{g^-1}(s); applying sigma_g afterwards restores s (oracle orc_rotate)
@@ -471,7 +487,10 @@ void Client::gen_rotation_key(int index) {
 }
 
 void Client::gen_conj_key() {
-    if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+    if (!s_all) {
+        if (ev_.conj_key) return;
+        throw Error(FHELIN_ERR_KEY, eval_only_ ? "conjugation key not in the evaluation-key set" : "keygen() has not been called");
+    }
     const u64 g = 2ull * c_.N - 1;  // X -> X^{-1}; its own inverse
     const int nl = c_.L + 1 + c_.K;
     u64* sp = c_.dalloc<u64>((size_t)nl * c_.N);
@@ -730,7 +749,9 @@ void Client::export_secret(u64* out) {
 }
 
 void Client::import_secret(const u64* in) {
+    if (eval_only_) throw Error(FHELIN_ERR_KEY, "import_secret: an evaluation context holds no secret");
     c_.require_device();
+    keygen_run_ = true;
     const size_t n = (size_t)(c_.L + 1 + c_.K) * c_.N;
     if (!s_all) s_all = c_.dalloc<u64>(n);
     hip_check(hipMemcpyAsync(s_all, in, n * 8, hipMemcpyHostToDevice, c_.stream), "import secret");

@@ -36,6 +36,13 @@ public:
     ~Client();
     void keygen();                       // secret (sparse ternary) + public key
     bool has_keys() const { return s_all != nullptr; }
+    // Evaluation context (include/fhelin.h fhelin_evalkeys_load): public key and switching keys imported from a set, no secret.
+    // Key generation then only confirms keys that are present; decryption and everything else that needs s fails (FHELIN_ERR_KEY).
+    bool eval_only() const { return eval_only_; }
+    bool keygen_run() const { return keygen_run_; }   // keygen() or import_secret() ever ran on this context
+    bool has_public_key() const { return pk != nullptr; }
+    const u64* public_key() const { return pk; }      // device [2][L+1][N]
+    void install_public_key(u64* d_pk);               // takes ownership (a pool block); makes this an evaluation context
     void gen_relin_key();                // EvalMultKeyGen
     void gen_rotation_key(int index);    // EvalRotateKeyGen for one index
     void gen_conj_key();
@@ -70,6 +77,7 @@ private:
     // c0 = b u + e0 + m, c1 = a u + e1 for n_vec encodings enc [n_vec][ell][N] (enc_stride words apart; 0 = one shared encoding)
     void encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out);
     u64 sample_calls_ = 0;
+    bool eval_only_ = false, keygen_run_ = false;
 };
 
 // special FFT helpers (shared by encode/decode); slots must be a power of two

@@ -18,8 +18,10 @@
  * secret-key.txt (:80-86) — the client's 256-bit SECRET seed to ../<parameters_folder>/secret-key.txt.  All key material
  * derives from that seed through a ChaCha20 stream, so `load_context` (which, like the reference :208-214, reads the
  * secret key file) + `load_bootstrapping_and_rotation_keys` regenerate bit-identical keys.  Whoever holds secret-key.txt
- * can decrypt: ship it to an evaluation server only where the reference would ship its own secret-key.txt (it does, for
- * its debug prints).  Ciphertexts are saved in the engine's own little-endian limb format.
+ * can decrypt, so it never goes to an evaluation server: the client writes an evaluation-key set instead
+ * (`save_evaluation_keys`: the public key and every switching key, no secret) and the server opens it with
+ * `load_evaluation_context`, which never reads secret-key.txt ("Client / server split").  On such a server
+ * decrypt and the debug prints throw.  Ciphertexts are saved in the engine's own little-endian limb format.
  */
 #ifndef FHELIN_FHECONTROLLER_SHIM_H
 #define FHELIN_FHECONTROLLER_SHIM_H
@@ -239,20 +241,7 @@ public:
         fhelin_shim::check(fhelin_gen_relin_key(context), "EvalMultKeyGen");
     }
     void load_context(bool verbose = true) {
-        ifstream f("../" + parameters_folder + "/crypto-context.txt", ios::in | ios::binary);
-        if (!f.is_open()) {
-            cerr << "I cannot find ../" << parameters_folder << "/crypto-context.txt" << endl;
-            exit(1);
-        }
-        string magic;
-        int ver = 0;
-        fhelin_params p = default_params();
-        f >> magic >> ver >> p.log_n >> p.n_q >> p.first_bits >> p.scale_bits >> p.n_p >> p.special_bits >> p.dnum >> p.log_slots >>
-            p.hamming;
-        if (!f || magic != "fhelin-context" || ver != 2) {
-            cerr << "Error reading serialization of the crypto context from crypto-context.txt" << endl;
-            exit(1);
-        }
+        fhelin_params p = read_crypto_context();
         ifstream sk("../" + parameters_folder + "/secret-key.txt", ios::in | ios::binary);
         if (!sk.is_open()) {
             cerr << "I cannot read serialization from ../" << parameters_folder << "/secret-key.txt" << endl;
@@ -276,6 +265,26 @@ public:
         fhelin_shim::check(fhelin_keygen(context), "KeyGen");
         fhelin_shim::check(fhelin_gen_relin_key(context), "EvalMultKeyGen");
         if (verbose) cout << "CtoS: " << level_budget[0] << ", StoC: " << level_budget[1] << endl;
+    }
+
+    /* Client / server split (include/fhelin.h "Evaluation-key sets").  The client, after generate_context and
+     * generate_bootstrapping_and_rotation_keys, writes its public key and every switching key to ../<parameters_folder>/<filename>;
+     * the server reads crypto-context.txt and that set and never opens secret-key.txt.  load_bootstrapping_and_rotation_keys then
+     * works unchanged on the server (the keys it asks for are present); decrypt and the print* helpers throw, as OpenFHE does
+     * without a secret key. */
+    void save_evaluation_keys(const string& filename) {
+        const string path = "../" + parameters_folder + "/" + filename;
+        fhelin_shim::check(fhelin_evalkeys_save(context, path.c_str()), "Serialize(evaluation keys)");
+    }
+    void load_evaluation_context(const string& filename, bool verbose = true) {
+        fhelin_params p = read_crypto_context();
+        num_slots = 1 << 14;
+        level_budget = {3, 3};
+        circuit_depth = 12 + 14;  // as load_context
+        create(p);                // this context's own generator (public-key encryption randomness): OS entropy
+        const string path = "../" + parameters_folder + "/" + filename;
+        fhelin_shim::check(fhelin_evalkeys_load(context, path.c_str()), "Deserialize(evaluation keys)");
+        if (verbose) cout << "Evaluation keys loaded from " << path << "; CtoS: " << level_budget[0] << ", StoC: " << level_budget[1] << endl;
     }
 
     /* rotation / bootstrapping keys (reference :237-343) */
@@ -737,6 +746,23 @@ public:
 private:
     vector<uint32_t> level_budget = {4, 4};
 
+    fhelin_params read_crypto_context() {
+        ifstream f("../" + parameters_folder + "/crypto-context.txt", ios::in | ios::binary);
+        if (!f.is_open()) {
+            cerr << "I cannot find ../" << parameters_folder << "/crypto-context.txt" << endl;
+            exit(1);
+        }
+        string magic;
+        int ver = 0;
+        fhelin_params p = default_params();
+        f >> magic >> ver >> p.log_n >> p.n_q >> p.first_bits >> p.scale_bits >> p.n_p >> p.special_bits >> p.dnum >> p.log_slots >>
+            p.hamming;
+        if (!f || magic != "fhelin-context" || ver != 2) {
+            cerr << "Error reading serialization of the crypto context from crypto-context.txt" << endl;
+            exit(1);
+        }
+        return p;
+    }
     static fhelin_params default_params() {
         fhelin_params p;
         const char* preset = std::getenv("FHELIN_PRESET");

@@ -394,6 +394,63 @@ int fhelin_bootstrap_describe(fhelin_ctx* c, int32_t* out, int32_t cap, int32_t*
 int fhelin_bootstrap_diag(fhelin_ctx* c, int32_t which, int32_t stage, int32_t term, fhelin_pt** out);
 int fhelin_bootstrap_cheb(fhelin_ctx* c, double* out, int32_t cap, int32_t* n);
 
+/* ---- evaluation-key sets: the server side without the secret key --------------------------------
+ * A client context writes its public parameters and all of its PUBLIC key material to one file; a context that never held a
+ * secret loads it and then evaluates bit-identically to the client's context ("Client / server split").
+ *
+ * File format, version 1 (all integers little-endian):
+ *   offset  0  char[8]  magic "FHELINEK"
+ *           8  u32      version = 1
+ *          12  u32      n_keys
+ *          16  i32[9]   log_n, n_q, first_bits, scale_bits, n_p (resolved, >= 0), special_bits, dnum, log_slots, hamming
+ *                       (fhelin_params without seed and device)
+ *          52  i32[7]   bootstrapping as the client set it up: budget_enc, budget_dec, slots, K, R, cheb_degree, correction
+ *                       (fhelin_bootstrap_setup / _config); all zero when it was not set up
+ *          80  u64      data_offset: first payload byte = (end of the key table) rounded up to a multiple of 4096
+ *          88  u64      0 (reserved)
+ *          96  u64[n_q + n_p]  the moduli, Q then P: a set whose moduli differ from the chain its parameters give is refused
+ *   then the key table, n_keys entries of 40 bytes:
+ *           0  u32 kind     0 public key, 1 relinearisation key, 2 rotation key, 3 conjugation key (at most one each of 0, 1, 3)
+ *           4  u32 digits   0 for the public key, else the switching key's digit count dnum' = ceil(n_q / alpha)
+ *           8  u64 galois   rotation: the Galois element 5^r mod 2N (entries of kind 2 in increasing order); conjugation: 2N - 1;
+ *                           else 0.  The conjugation key is stored once (the engine also files it as the rotation key of 2N - 1).
+ *          16  u64 offset   byte offset of the payload: payloads follow each other in table order from data_offset, no gaps,
+ *                           and the last one ends the file
+ *          24  u64 words    payload length in u64 words
+ *          32  u64 digest   the key's digest (below)
+ *   then the payloads: u64 residues in NTT form, the engine's at-rest layout.  Public key [2][n_q][N] (b = -a s + e, then a);
+ *   switching keys [digits][2][n_q + n_p][N] (fhelin_key_export).  Derived copies (permuted / pre-scaled key copies, the
+ *   bootstrap's diagonals and Chebyshev coefficients) are not stored: the loading context rebuilds them.  Never stored: the
+ *   secret, its 32-byte seed or any generator state.
+ * Digest, P = 2^61 - 1, mix(x) = lowbias32 on u32 (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16):
+ *   limb digest of a vector v[0..N) of the payload:  d(v) = sum_i (v_i mod P) * mix(i ^ 0x9E3779B9) mod P
+ *   key digest over its n_vec = words / N limb vectors in storage order:  D = sum_j d(v_j) * mix(j | 0x80000000) mod P
+ * Every residue must also be below its limb's modulus (vector j of a payload belongs to limb j mod n_q for the public key and
+ * j mod (n_q + n_p) for a switching key).  Both are checked on the device (one streaming kernel) before a save writes and after
+ * a load uploads, before anything is installed. */
+/* write every key the context holds (any context that holds at least one key; FHELIN_ERR_KEY when it holds none) */
+int fhelin_evalkeys_save(fhelin_ctx* c, const char* path);
+/* the header's parameters (seed and device 0); host-only, no device needed.  A malformed header or key table, or moduli that
+ * differ from the chain the parameters give: FHELIN_ERR_ARG */
+int fhelin_evalkeys_params(const char* path, fhelin_params* out);
+/* the header's bootstrapping configuration (boot7: budget_enc, budget_dec, slots, K, R, cheb_degree, correction; slots 0 = none)
+ * and key count; host-only */
+int fhelin_evalkeys_info(const char* path, int32_t* boot7, int32_t* n_keys);
+/* load a set into a FRESH context with the same parameters (no keygen, no key, no bootstrap set-up: FHELIN_ERR_STATE otherwise;
+ * other parameters: FHELIN_ERR_STATE; other moduli, a malformed file, a residue out of range or a digest mismatch:
+ * FHELIN_ERR_ARG).  All or nothing: on failure the context holds none of the file's keys.  Afterwards the context is an
+ * EVALUATION CONTEXT: decryption, fhelin_secret_export / _import, fhelin_ctx_secret_seed and fhelin_keygen return FHELIN_ERR_KEY;
+ * fhelin_gen_relin_key / _rotation_keys / _conj_key succeed when every requested key is present and otherwise return
+ * FHELIN_ERR_KEY naming the missing one; fhelin_bootstrap_setup builds its stages from the loaded keys (FHELIN_ERR_KEY naming a
+ * missing key); the bootstrap's approximation parameters are taken from the header (call fhelin_bootstrap_setup with its budgets
+ * and slots, fhelin_evalkeys_info).  Public-key encryption draws its randomness from this context's own generator (params.seed:
+ * 0 = OS entropy). */
+int fhelin_evalkeys_load(fhelin_ctx* c, const char* path);
+/* test hook: the digest kernel on n_limbs limb vectors words[n_limbs][N] (vector i belongs to limb limb_first + i):
+ * out_digests[i] = d(words[i]), out_ok[i] = 1 if every residue is below the limb's modulus */
+int fhelin_debug_key_digest(fhelin_ctx* c, const uint64_t* words, int32_t n_limbs, int32_t limb_first, uint64_t* out_digests,
+                            int32_t* out_ok);
+
 #ifdef __cplusplus
 }
 #endif
