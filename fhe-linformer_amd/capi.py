@@ -207,6 +207,12 @@ def load_library():
         "fhelin_evalkeys_info": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]),
         "fhelin_evalkeys_load": (i32, [vp, C.c_char_p]),
         "fhelin_debug_key_digest": (i32, [vp, vp, i32, i32, C.POINTER(C.c_uint64), C.POINTER(i32)]),
+        "fhelin_ctx_set_seeded_encryption": (i32, [vp, i32]),
+        "fhelin_ct_compact_bytes": (i32, [vp, C.POINTER(C.c_size_t)]),
+        "fhelin_ct_export_compact": (i32, [vp, vp, vp, C.c_size_t]),
+        "fhelin_compact_info": (i32, [vp, C.c_size_t, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "fhelin_ct_import_compact": (i32, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), i32, C.POINTER(vp)]),
+        "fhelin_debug_seeded_expand": (i32, [vp, vp, C.c_uint64, i32, i32, i32, vp, f32p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -214,6 +220,18 @@ def load_library():
         fn.argtypes = args
     _LIB = lib
     return lib
+
+
+def compact_info(blob):
+    """header of a compact ciphertext (include/fhelin.h "Compact ciphertexts"), validated against itself and its size:
+    dict(log_n, ell, deg, slots); host-only"""
+    lib = load_library()
+    b = bytes(blob)
+    v = [C.c_int32() for _ in range(4)]
+    rc = lib.fhelin_compact_info(C.c_char_p(b), len(b), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise FhelinError(rc, lib.fhelin_last_error().decode())
+    return dict(zip(("log_n", "ell", "deg", "slots"), (x.value for x in v)))
 
 
 def _np_u64(a):
@@ -501,6 +519,30 @@ class Engine:
         self._ck(self.lib.fhelin_debug_key_digest(self.h, w.ctypes.data_as(C.c_void_p), n, int(limb_first),
                                                   d.ctypes.data_as(C.POINTER(C.c_uint64)), ok.ctypes.data_as(C.POINTER(C.c_int32))))
         return d, ok.astype(bool)
+
+    # ---- seeded encryption / compact ciphertexts (include/fhelin.h "Compact ciphertexts")
+    def set_seeded_encryption(self, on):
+        """on: encrypt / encrypt_batch / client_ingest encrypt with the secret key, c1 expanded from a per-call public seed"""
+        self._ck(self.lib.fhelin_ctx_set_seeded_encryption(self.h, 1 if on else 0))
+
+    def import_compact(self, blobs):
+        """compact blobs (Ct.export_compact) -> handles, all in one call; all or nothing"""
+        bs = [bytes(b) for b in blobs]
+        n = len(bs)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.cast(C.c_char_p(b), C.c_void_p) for b in bs])
+        sizes = (C.c_size_t * max(n, 1))(*[len(b) for b in bs])
+        outs = self._outs(n)
+        self._ck(self.lib.fhelin_ct_import_compact(self.h, ptrs, sizes, n, outs))
+        return self._cts(outs, n)
+
+    def debug_seeded_expand(self, seed, nonce0, ell, n_ct=1, reps=0, download=True):
+        """the expansion kernel alone: (c1 [n_ct][ell][N] or None, mean ms per launch over `reps` timed launches)"""
+        sb = (C.c_uint8 * 32)(*bytes(seed))
+        out = np.empty((n_ct, ell, self.N), dtype=np.uint64) if download else None
+        ms = C.c_float()
+        self._ck(self.lib.fhelin_debug_seeded_expand(self.h, sb, nonce0, ell, n_ct, reps,
+                                                     out.ctypes.data_as(C.c_void_p) if download else None, C.byref(ms)))
+        return out, ms.value
 
     # ---- plaintexts / ciphertexts
     def encode(self, vals, level=0, slots=0):
@@ -1017,6 +1059,18 @@ class Ct:
         hi, lo = C.c_double(), C.c_double()
         self.eng._ck(self.eng.lib.fhelin_ct_scale(self.h, C.byref(hi), C.byref(lo)))
         return hi.value, lo.value
+
+    def compact_bytes(self):
+        n = C.c_size_t()
+        self.eng._ck(self.eng.lib.fhelin_ct_compact_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def export_compact(self):
+        """the compact form (c0, seed, nonce) of an unmodified seeded encryption, as bytes"""
+        n = self.compact_bytes()
+        out = C.create_string_buffer(n)
+        self.eng._ck(self.eng.lib.fhelin_ct_export_compact(self.eng.h, self.h, out, n))
+        return out.raw
 
     def export_device(self, dptr, cap_words):
         self.eng._ck(self.eng.lib.fhelin_ct_export_device(self.eng.h, self.h, C.c_void_p(dptr), cap_words))

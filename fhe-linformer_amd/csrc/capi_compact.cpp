@@ -1,0 +1,273 @@
+// extern "C" boundary, part 5: seeded secret-key encryption and compact ciphertexts (include/fhelin.h "Compact ciphertexts": the
+// expansion and the blob format are documented there).  A seeded encryption's c1 is the expansion of a public (seed, nonce), so a
+// compact blob carries c0 alone; import uploads every c0, range-checks and digests them on the device (kernels_keys.hip) and
+// expands every c1 in one launch (kernels_seeded.hip), with one host synchronisation per call.
+#include "../../include/fhelin.h"
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include "capi_internal.h"
+#include "kernels_keys.h"
+#include "kernels_seeded.h"
+
+using namespace fhelin;
+
+#if !defined(__BYTE_ORDER__) || __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
+#error "compact ciphertexts are written in host byte order, which must be little-endian"
+#endif
+
+namespace {
+
+constexpr char CC_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'C', 'C'};
+constexpr uint32_t CC_VERSION = 1;
+constexpr size_t CC_FIXED = 96;   // header bytes before the moduli
+
+struct CcHeader {
+    int32_t log_n = 0, ell = 0, deg = 0, slots = 0;
+    double scale_hi = 0, scale_lo = 0;
+    uint64_t nonce = 0, digest = 0;
+    uint8_t seed[32] = {};
+    const uint64_t* moduli = nullptr;   // [ell], inside the blob (may be unaligned: read with memcpy)
+    const uint8_t* c0 = nullptr;        // [ell][N] u64, inside the blob
+};
+
+template <class T> T get(const uint8_t* b, size_t off) {
+    T v;
+    std::memcpy(&v, b + off, sizeof(T));
+    return v;
+}
+template <class T> void put(uint8_t* b, size_t off, T v) { std::memcpy(b + off, &v, sizeof(T)); }
+
+size_t cc_bytes(int log_n, int ell) { return CC_FIXED + 8 * (size_t)ell + 8 * (size_t)ell * ((size_t)1 << log_n); }
+
+// every field validated against the others and against the blob's size; nothing about a context (host-only)
+CcHeader read_header(const uint8_t* b, size_t bytes) {
+    if (!b) throw Error(FHELIN_ERR_ARG, "compact ciphertext: null blob");
+    if (bytes < CC_FIXED) throw Error(FHELIN_ERR_ARG, "compact ciphertext: truncated header");
+    if (std::memcmp(b, CC_MAGIC, 8) != 0) throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad magic");
+    if (get<uint32_t>(b, 8) != CC_VERSION) throw Error(FHELIN_ERR_ARG, "compact ciphertext: unsupported version");
+    CcHeader h;
+    h.log_n = get<int32_t>(b, 16);
+    h.ell = get<int32_t>(b, 20);
+    h.deg = get<int32_t>(b, 24);
+    h.slots = get<int32_t>(b, 28);
+    h.scale_hi = get<double>(b, 32);
+    h.scale_lo = get<double>(b, 40);
+    h.nonce = get<uint64_t>(b, 48);
+    std::memcpy(h.seed, b + 56, 32);
+    h.digest = get<uint64_t>(b, 88);
+    if (h.log_n < 12 || h.log_n > 17 || h.ell < 1 || h.ell > 64) throw Error(FHELIN_ERR_ARG, "compact ciphertext: ring dimension or limb count out of range");
+    if (get<uint32_t>(b, 12) != CC_FIXED + 8 * (uint32_t)h.ell) throw Error(FHELIN_ERR_ARG, "compact ciphertext: header size does not match the limb count");
+    if (bytes != cc_bytes(h.log_n, h.ell)) throw Error(FHELIN_ERR_ARG, "compact ciphertext: size does not match the header (truncated?)");
+    if (h.deg < 1 || h.deg > 2 || h.slots < 1 || (h.slots & (h.slots - 1)) || h.slots > (1 << (h.log_n - 1)))
+        throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad degree or slot count");
+    if (!(std::isfinite(h.scale_hi) && h.scale_hi > 0 && std::isfinite(h.scale_lo) && std::fabs(h.scale_lo) <= std::ldexp(h.scale_hi, -52)))
+        throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad scale");
+    if (h.digest >= KEY_DIGEST_P) throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad digest field");
+    h.moduli = reinterpret_cast<const uint64_t*>(b + CC_FIXED);
+    h.c0 = b + CC_FIXED + 8 * (size_t)h.ell;
+    return h;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhelin_ctx_set_seeded_encryption(fhelin_ctx* c, int32_t on) {
+    if (!c) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    c->cl.set_seeded(on != 0);
+    FHELIN_CATCH
+}
+
+int fhelin_ct_compact_bytes(const fhelin_ct* ct, size_t* bytes) {
+    if (!ct || !bytes) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    // a deferred handle is an operation's result: never a seeded encryption
+    if (!ct->p || !ct->p->seeded) return capi_fail(FHELIN_ERR_STATE, "compact form: only an unmodified seeded (secret-key) encryption has one");
+    *bytes = cc_bytes(ct->p->ctx->prm.log_n, ct->p->ell);
+    return FHELIN_OK;
+}
+
+int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, size_t cap) {
+    if (!c || !ct || !out) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    if (!ct->p || !ct->p->seeded) throw Error(FHELIN_ERR_STATE, "compact form: only an unmodified seeded (secret-key) encryption has one");
+    if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
+    const CtPtr& p = ct_in(c, ct);
+    c->plan.check_terminal(*p, 2);
+    Context& x = c->ctx;
+    const int ell = p->ell;
+    const size_t N = x.N, bytes = cc_bytes(x.prm.log_n, ell);
+    if (cap < bytes) throw Error(FHELIN_ERR_ARG, "export_compact: buffer too small");
+    if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "export_compact: ring dimension below 2^12");
+    // c0's digest on the device, c0 itself straight into the blob; one synchronisation
+    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, ell));
+    u64* dg = x.dalloc<u64>(2 * (size_t)ell);
+    launch_key_digest(x.dt, p->d, ell, 0, ell, part, dg, x.stream);
+    hip_check(hipGetLastError(), "compact digest kernels");
+    std::vector<u64> h(2 * (size_t)ell);
+    hip_check(hipMemcpyAsync(h.data(), dg, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "compact digest download");
+    hip_check(hipMemcpyAsync(out + CC_FIXED + 8 * (size_t)ell, p->d, (size_t)ell * N * 8, hipMemcpyDeviceToHost, x.stream), "compact export");
+    hip_check(hipStreamSynchronize(x.stream), "compact export sync");
+    x.pool.free(part);
+    x.pool.free(dg);
+    u128 acc = 0;
+    for (int j = 0; j < ell; ++j) {
+        if (!h[2 * j + 1]) throw Error(FHELIN_ERR_INTERNAL, "export_compact: c0 holds a residue out of range");
+        acc += (u128)h[2 * j] * key_weight_vec((u32)j);
+    }
+    std::memcpy(out, CC_MAGIC, 8);
+    put<uint32_t>(out, 8, CC_VERSION);
+    put<uint32_t>(out, 12, (uint32_t)(CC_FIXED + 8 * ell));
+    const int32_t shape[4] = {x.prm.log_n, ell, p->deg, p->slots};
+    std::memcpy(out + 16, shape, sizeof(shape));
+    const double hi = (double)p->scale, lo = (double)(p->scale - (long double)hi);   // as fhelin_ct_scale
+    put<double>(out, 32, hi);
+    put<double>(out, 40, lo);
+    put<uint64_t>(out, 48, p->nonce);
+    std::memcpy(out + 56, p->seed, 32);
+    put<uint64_t>(out, 88, (uint64_t)(acc % KEY_DIGEST_P));
+    std::memcpy(out + CC_FIXED, x.chain.q.data(), 8 * (size_t)ell);
+    FHELIN_CATCH
+}
+
+int fhelin_compact_info(const uint8_t* blob, size_t bytes, int32_t* log_n, int32_t* ell, int32_t* deg, int32_t* slots) {
+    FHELIN_TRY
+    const CcHeader h = read_header(blob, bytes);
+    if (log_n) *log_n = h.log_n;
+    if (ell) *ell = h.ell;
+    if (deg) *deg = h.deg;
+    if (slots) *slots = h.slots;
+    FHELIN_CATCH
+}
+
+int fhelin_ct_import_compact(fhelin_ctx* c, const uint8_t* const* blobs, const size_t* sizes, int32_t n, fhelin_ct** outs) {
+    if (!c || (n > 0 && (!blobs || !sizes || !outs)) || n < 0) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    if (n == 0) return FHELIN_OK;
+    if (n > 65535) throw Error(FHELIN_ERR_ARG, "import_compact: at most 65535 blobs per call");
+    if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "import_compact: ring dimension below 2^12");
+    const size_t N = x.N;
+    // 1. every header, against the blob and against this context, before anything is allocated
+    std::vector<CcHeader> hs(n);
+    for (int i = 0; i < n; ++i) {
+        hs[i] = read_header(blobs[i], sizes[i]);
+        const CcHeader& h = hs[i];
+        const std::string at = "import_compact: blob " + std::to_string(i) + ": ";
+        if (h.log_n != x.prm.log_n) throw Error(FHELIN_ERR_ARG, at + "made for another ring dimension");
+        if (h.ell > x.L + 1) throw Error(FHELIN_ERR_ARG, at + "more limbs than the context's chain");
+        if (std::memcmp(h.moduli, x.chain.q.data(), 8 * (size_t)h.ell) != 0) throw Error(FHELIN_ERR_ARG, at + "moduli do not match the context");
+    }
+    // 2. one batch allocation per limb count; c0 of every blob uploaded into its ciphertext
+    std::map<int, std::vector<int>> groups;
+    for (int i = 0; i < n; ++i) groups[hs[i].ell].push_back(i);
+    std::vector<CtPtr> cts(n);
+    int max_ell = 0, max_vec = 0;
+    for (auto& g : groups) {
+        const int ell = g.first;
+        std::vector<CtPtr> b = c->ev.new_ct_batch((int)g.second.size(), 2, ell, 1, 1.0L, 1);
+        for (size_t k = 0; k < g.second.size(); ++k) cts[g.second[k]] = b[k];
+        max_ell = std::max(max_ell, ell);
+        max_vec = std::max(max_vec, (int)g.second.size() * ell);
+    }
+    if (max_vec > 65535) throw Error(FHELIN_ERR_ARG, "import_compact: too many limbs of one level in one call");
+    std::vector<SeededEntry> tab(n);
+    for (int i = 0; i < n; ++i) {
+        const CcHeader& h = hs[i];
+        Ciphertext& ct = *cts[i];
+        ct.deg = h.deg;
+        ct.slots = h.slots;
+        ct.scale = (long double)h.scale_hi + (long double)h.scale_lo;
+        hip_check(hipMemcpyAsync(ct.d, h.c0, (size_t)h.ell * N * 8, hipMemcpyHostToDevice, x.stream), "compact upload");
+        for (int w = 0; w < 8; ++w) tab[i].key.w[w] = get<uint32_t>(h.seed, 4 * w);
+        tab[i].nonce = h.nonce;
+        tab[i].dst = ct.d + (size_t)h.ell * N;
+        tab[i].ell = h.ell;
+    }
+    // 3. range check + digest of every c0 (one launch pair per limb count: c0 vectors ell apart in groups of 2 ell), then every c1
+    // in one launch; one synchronisation for the call
+    struct Scratch {
+        Context& x;
+        std::vector<void*> d;
+        ~Scratch() {
+            for (void* p : d) x.pool.free(p);
+        }
+    } sc{x, {}};
+    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, max_vec));
+    sc.d.push_back(part);
+    u64* dg = x.dalloc<u64>(2 * (size_t)n * max_ell);
+    sc.d.push_back(dg);
+    SeededEntry* d_tab = x.dalloc<SeededEntry>((size_t)n);
+    sc.d.push_back(d_tab);
+    hip_check(hipMemcpyAsync(d_tab, tab.data(), (size_t)n * sizeof(SeededEntry), hipMemcpyHostToDevice, x.stream), "seed table upload");
+    std::vector<size_t> dg_at(n);   // first digest vector of blob i
+    size_t v0 = 0;
+    for (auto& g : groups) {
+        const int ell = g.first, cnt = (int)g.second.size();
+        launch_key_digest_strided(x.dt, cts[g.second[0]]->d, cnt * ell, 0, ell, 2 * ell, part, dg + 2 * v0, x.stream);
+        for (int k = 0; k < cnt; ++k) dg_at[g.second[k]] = v0 + (size_t)k * ell;
+        v0 += (size_t)cnt * ell;
+    }
+    launch_seeded_expand(x.dt, d_tab, n, max_ell, x.stream);
+    hip_check(hipGetLastError(), "compact import kernels");
+    std::vector<u64> h(2 * v0);
+    hip_check(hipMemcpyAsync(h.data(), dg, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "compact digest download");
+    hip_check(hipStreamSynchronize(x.stream), "compact import sync");
+    // 4. all or nothing: a handle only when every blob passed
+    for (int i = 0; i < n; ++i) {
+        u128 acc = 0;
+        for (int j = 0; j < hs[i].ell; ++j) {
+            const size_t v = dg_at[i] + j;
+            if (!h[2 * v + 1]) throw Error(FHELIN_ERR_ARG, "import_compact: blob " + std::to_string(i) + " holds a residue not below its modulus");
+            acc += (u128)h[2 * v] * key_weight_vec((u32)j);
+        }
+        if ((uint64_t)(acc % KEY_DIGEST_P) != hs[i].digest) throw Error(FHELIN_ERR_ARG, "import_compact: blob " + std::to_string(i) + " does not match its digest");
+    }
+    for (int i = 0; i < n; ++i) outs[i] = wrap(c, cts[i]);   // imported: not a level-plan source, never lowered
+    FHELIN_CATCH
+}
+
+int fhelin_debug_seeded_expand(fhelin_ctx* c, const uint8_t* seed32, uint64_t nonce0, int32_t ell, int32_t n_ct, int32_t reps,
+                               uint64_t* out, float* ms) {
+    if (!c || !seed32) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    if (ell < 1 || ell > x.L + 1 || n_ct < 1 || n_ct > 65535 || reps < 0) throw Error(FHELIN_ERR_ARG, "debug_seeded_expand: bad shape");
+    const size_t words = (size_t)ell * x.N;
+    u64* d = x.dalloc<u64>(words * n_ct);
+    SeededEntry* d_tab = x.dalloc<SeededEntry>((size_t)n_ct);
+    std::vector<SeededEntry> tab(n_ct);
+    for (int i = 0; i < n_ct; ++i) {
+        for (int w = 0; w < 8; ++w) tab[i].key.w[w] = get<uint32_t>(seed32, 4 * w);
+        tab[i].nonce = nonce0 + (uint64_t)i;
+        tab[i].dst = d + words * i;
+        tab[i].ell = ell;
+    }
+    hip_check(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(SeededEntry), hipMemcpyHostToDevice, x.stream), "seed table upload");
+    launch_seeded_expand(x.dt, d_tab, n_ct, ell, x.stream);
+    hipEvent_t ev[2] = {};
+    float t = 0;
+    if (reps > 0) {
+        for (auto& e : ev) hip_check(hipEventCreate(&e), "hipEventCreate");
+        hip_check(hipEventRecord(ev[0], x.stream), "hipEventRecord");
+        for (int r = 0; r < reps; ++r) launch_seeded_expand(x.dt, d_tab, n_ct, ell, x.stream);
+        hip_check(hipEventRecord(ev[1], x.stream), "hipEventRecord");
+    }
+    hip_check(hipGetLastError(), "seeded expand kernel");
+    if (out) hip_check(hipMemcpyAsync(out, d, words * n_ct * 8, hipMemcpyDeviceToHost, x.stream), "expansion download");
+    hip_check(hipStreamSynchronize(x.stream), "debug_seeded_expand sync");
+    if (reps > 0) {
+        (void)hipEventElapsedTime(&t, ev[0], ev[1]);
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    }
+    if (ms) *ms = reps > 0 ? t / (float)reps : 0.0f;
+    x.pool.free(d);
+    x.pool.free(d_tab);
+    FHELIN_CATCH
+}
+
+}  // extern "C"

@@ -123,6 +123,7 @@ int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32
     const int first_ordinal = c->plan.next_ordinal - n_vec;
     std::vector<CtPtr> r(n_vec);
     std::vector<char> seen(n_vec, 0);
+    c->cl.begin_call();   // seeded mode: one seed for the whole call, every vector's nonce its output index (pick)
     for (int i = 0; i < n_vec; ++i) {
         if (seen[i]) continue;
         std::vector<int> pick;
@@ -132,13 +133,13 @@ int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32
                 seen[j] = 1;
             }
         if ((int)pick.size() == n_vec) {
-            r = c->cl.encrypt_batch(vals, n_vec, n_per, level + drop[i], slots);
+            r = c->cl.encrypt_batch(vals, n_vec, n_per, level + drop[i], slots, pick.data());
             break;
         }
         std::vector<double> sub((size_t)pick.size() * n_per);
         for (size_t k = 0; k < pick.size(); ++k)
             std::memcpy(sub.data() + k * n_per, vals + (size_t)pick[k] * n_per, (size_t)n_per * sizeof(double));
-        std::vector<CtPtr> part = c->cl.encrypt_batch(sub.data(), (int)pick.size(), n_per, level + drop[i], slots);
+        std::vector<CtPtr> part = c->cl.encrypt_batch(sub.data(), (int)pick.size(), n_per, level + drop[i], slots, pick.data());
         for (size_t k = 0; k < pick.size(); ++k) r[pick[k]] = part[k];
     }
     for (int i = 0; i < n_vec; ++i) {

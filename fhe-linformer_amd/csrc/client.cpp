@@ -1,9 +1,11 @@
 #include "client.h"
+#include "kernels_seeded.h"
 #include <time.h>
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <complex>
+#include <cstring>
 #include <map>
 #include <mutex>
 
@@ -538,12 +540,49 @@ std::vector<long> Client::debug_sample(int kind, int n_poly) {
     return out;
 }
 
-// c0 = b u + e0 + m, c1 = a u + e1 for n_vec encodings enc [n_vec][ell][N] (stride enc_stride words; 0 = one shared encoding)
-void Client::encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out) {
+void Client::set_seeded(bool on) {
+    if (on && eval_only_) throw Error(FHELIN_ERR_KEY, "seeded encryption needs the secret key: an evaluation context holds none");
+    seeded_ = on;
+}
+
+void Client::begin_call() {
+    if (!seeded_) return;
+    for (int i = 0; i < 4; ++i) {   // a fresh public seed per call, drawn from the client's own stream
+        const u64 w = rng_.next();
+        for (int b = 0; b < 8; ++b) call_seed_[8 * i + b] = (uint8_t)(w >> (8 * b));
+    }
+}
+
+// c0 = b u + e0 + m, c1 = a u + e1 for n_vec encodings enc [n_vec][ell][N] (stride enc_stride words; 0 = one shared encoding);
+// seeded mode: c0 = m - a s + e, c1 = a with a the expansion of (call seed, nonces[b])
+void Client::encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out,
+                             const u64* nonces) {
     Context& c = c_;
     const size_t N = c.N, pn = (size_t)ell * N;
     const int L1 = c.L + 1;
     std::vector<CtPtr> cts = ev_.new_ct_batch(n_vec, 2, ell, 1, scale, slots);
+    if (seeded_) {
+        if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+        SamplerKey key;
+        for (int i = 0; i < 8; ++i)
+            key.w[i] = (u32)call_seed_[4 * i] | ((u32)call_seed_[4 * i + 1] << 8) | ((u32)call_seed_[4 * i + 2] << 16) |
+                       ((u32)call_seed_[4 * i + 3] << 24);
+        u64* e = c.dalloc<u64>((size_t)n_vec * pn);              // e [n_vec][ell][N]
+        sample_small_device(e, n_vec, ell, 0);
+        c.ntt(LimbBatch{e, n_vec * ell, nullptr, 0, ell}, false);
+        launch_sk_encrypt_combine(c.dt, cts[0]->d, s_all, e, enc, enc_stride, ell, key, nonces, n_vec, c.stream);
+        hip_check(hipGetLastError(), "secret-key encrypt kernels");
+        // the encryption noise does not stay behind in a recycled pool block
+        hip_check(hipMemsetAsync(e, 0, (size_t)n_vec * pn * sizeof(u64), c.stream), "hipMemsetAsync(encryption noise)");
+        c.pool.free(e);
+        for (int b = 0; b < n_vec; ++b) {
+            cts[b]->seeded = true;
+            cts[b]->nonce = nonces[b];
+            std::memcpy(cts[b]->seed, call_seed_, 32);
+        }
+        for (auto& ct : cts) out.push_back(ct);
+        return;
+    }
     u64* rnd = c.dalloc<u64>((size_t)3 * n_vec * pn);       // u | e0 | e1, each [n_vec][ell][N]
     sample_small_device(rnd, n_vec, ell, 1);
     sample_small_device(rnd + (size_t)n_vec * pn, 2 * n_vec, ell, 0);
@@ -558,17 +597,19 @@ void Client::encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int e
 }
 
 CtPtr Client::encrypt(const PtPtr& p, int drop) {
-    if (!pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+    if (seeded_ ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     const int level = std::min(c_.L, p->level + std::max(0, drop));   // level plan: start `drop` limbs lower
     const int ell = c_.L + 1 - level;
     auto enc = p->at(ell, c_.sf_real[level]);
     std::vector<CtPtr> out;
-    encrypt_encoded(enc->d, 0, 1, ell, enc->scale, p->slots, out);
+    begin_call();
+    const u64 nonce = 0;
+    encrypt_encoded(enc->d, 0, 1, ell, enc->scale, p->slots, out, &nonce);
     return out[0];
 }
 
-std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots) {
-    if (!pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots, const int* nonce_of) {
+    if (seeded_ ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     if (slots <= 0) slots = 1 << c_.prm.log_slots;
     if (level < 0 || level > c_.L) throw Error(FHELIN_ERR_ARG, "encrypt: level out of range");
     if (n_vec < 0 || n_per < 0) throw Error(FHELIN_ERR_ARG, "encrypt_batch: negative count");
@@ -576,12 +617,15 @@ std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_pe
     const size_t pn = (size_t)ell * c_.N;
     const long double scale = c_.sf_real[level];
     std::vector<CtPtr> out;
+    if (!nonce_of) begin_call();
     const int CHUNK = 32;                                    // bounds the temporaries (4 polynomials per vector in flight)
     for (int lo = 0; lo < n_vec; lo += CHUNK) {
         const int n = std::min(CHUNK, n_vec - lo);
         u64* enc = c_.dalloc<u64>((size_t)n * pn);
         encode_batch_device(c_, enc, vals + (size_t)lo * n_per, nullptr, n, n_per, slots, ell, scale);
-        encrypt_encoded(enc, pn, n, ell, scale, slots, out);
+        u64 nonces[CHUNK];
+        for (int k = 0; k < n; ++k) nonces[k] = nonce_of ? (u64)nonce_of[lo + k] : (u64)(lo + k);
+        encrypt_encoded(enc, pn, n, ell, scale, slots, out, nonces);
         c_.pool.free(enc);
     }
     return out;
@@ -593,7 +637,7 @@ std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_pe
 std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, const double* table, int vocab, int S, const double* cls,
                                          const double* pos, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
                                          int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out) {
-    if (!pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+    if (seeded_ ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     const int slots = 1 << c_.prm.log_slots, S1 = S + 1, n_vec = 64 + S1;
     if (slots != 16384) throw Error(FHELIN_ERR_ARG, "ingest: the expanded layout needs 16384 slots (128 x 128)");
     if (S < 1 || S1 > w_cols || (!emb && !(tokens && table && vocab > 0))) throw Error(FHELIN_ERR_ARG, "ingest: bad token count / inputs");
@@ -647,6 +691,7 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
         hip_check(hipMemcpyAsync(proj_out->data() + (size_t)S1 * 128, proj, (size_t)64 * 128 * 8, hipMemcpyDeviceToHost, s), "ingest download");
     }
     hip_check(hipStreamSynchronize(s), "ingest sync");   // the host buffers are the caller's: done with them
+    begin_call();
     std::vector<CtPtr> out(n_vec);
     std::vector<char> seen(n_vec, 0);
     for (int i = 0; i < n_vec; ++i) {
@@ -668,7 +713,9 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
             u64* enc = (u64*)tmp.get((size_t)n * pn * sizeof(u64));   // the encoded plaintext: wiped and freed with the other temporaries
             encode_complex_on_device(c_, enc, dv + (size_t)j * slots * 2, n, slots, ell, scale);
             std::vector<CtPtr> part;
-            encrypt_encoded(enc, pn, n, ell, scale, slots, part);
+            u64 nonces[32];
+            for (int k = 0; k < n; ++k) nonces[k] = (u64)(j + k);
+            encrypt_encoded(enc, pn, n, ell, scale, slots, part, nonces);
             for (int k = 0; k < n; ++k) {
                 out[j + k] = part[k];
                 seen[j + k] = 1;

@@ -52,7 +52,9 @@ public:
     CtPtr encrypt(const PtPtr& p, int drop = 0);   // drop: limbs left out below the plaintext's level (level plan)
     // n_vec real vectors of n_per values each (row-major) -> n_vec fresh ciphertexts at `level`: encoding (special FFT, scaling,
     // rounding), sampling of (u, e0, e1) and the dyadic combination all on the GPU, in batched launches
-    std::vector<CtPtr> encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots);
+    // nonce_of (seeded mode): null = a call of its own (a fresh seed, nonce = vector index); else the output index of every vector
+    // within a call whose seed the caller drew with begin_call()
+    std::vector<CtPtr> encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots, const int* nonce_of = nullptr);
     std::vector<CtPtr> ingest_sample(const double* emb, const int* tokens, const double* table, int vocab, int S, const double* cls,
                                      const double* pos, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
                                      int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out = nullptr);
@@ -62,6 +64,12 @@ public:
     CtPtr phase(const CtPtr& c, int nlimbs);   // c0 + c1 s (+ c2 s^2) on the first nlimbs limbs, NTT form, 1 component
 
     // raw import/export of key material (parity tests feed identical arrays to the oracle)
+    // Seeded mode (include/fhelin.h fhelin_ctx_set_seeded_encryption): encrypt / encrypt_batch / ingest_sample encrypt with the
+    // secret key, c0 = m - a s + e, c1 = a with a expanded from a fresh 32-byte seed per call and nonce = output index in the call
+    void set_seeded(bool on);
+    bool seeded() const { return seeded_; }
+    void begin_call();                   // seeded mode: draw the next call's seed from the generator (no-op otherwise)
+
     void export_secret(u64* out);        // [L+1+k][N]
     void import_secret(const u64* in);   // replaces the secret (NTT form) — tests only
 
@@ -75,9 +83,13 @@ private:
     // device sampler (encryption randomness): dst [n_poly][ell][N] coefficient form; a fresh ChaCha20 key per call
     void sample_small_device(u64* dst, int n_poly, int ell, int kind);
     // c0 = b u + e0 + m, c1 = a u + e1 for n_vec encodings enc [n_vec][ell][N] (enc_stride words apart; 0 = one shared encoding)
-    void encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out);
+    // seeded mode: c0 = m - a s + e, c1 = a instead; nonces [n_vec] are the vectors' output indices within the current call
+    void encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out,
+                         const u64* nonces);
     u64 sample_calls_ = 0;
     bool eval_only_ = false, keygen_run_ = false;
+    bool seeded_ = false;
+    uint8_t call_seed_[32] = {};
 };
 
 // special FFT helpers (shared by encode/decode); slots must be a power of two

@@ -33,6 +33,12 @@ struct Ciphertext {
     int async_lane = 0;
     u64 async_seq = 0;
     hipEvent_t async_ev = nullptr;
+    // set only by the client's seeded (secret-key) encryptor: c1 is the expansion of (seed, nonce) (include/fhelin.h "Compact
+    // ciphertexts") and the ciphertext can be exported compact.  Every operation makes a new Ciphertext and nothing writes into an
+    // existing one, so no operation's result carries it.
+    bool seeded = false;
+    u64 nonce = 0;
+    uint8_t seed[32] = {};
     ~Ciphertext();
     int level() const { return ctx->L + 1 - ell; }
     size_t words() const { return (size_t)npoly * ell * ctx->N; }

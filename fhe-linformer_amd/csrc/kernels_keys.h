@@ -28,5 +28,10 @@ FHE_HD u64 key_red61(u64 a) {
 size_t key_digest_scratch_words(int N, int n_vec);
 void launch_key_digest(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, u64* d_part, u64* d_out,
                        hipStream_t s);
+// the same over vectors that come in groups of limb_count, group_stride vectors apart: vector v is read from
+// data + ((v / limb_count) * group_stride + v % limb_count) * N (the c0 limbs of a batch of ciphertexts [n][2][ell][N]:
+// limb_count = ell, group_stride = 2 ell)
+void launch_key_digest_strided(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, int group_stride,
+                               u64* d_part, u64* d_out, hipStream_t s);
 
 }  // namespace fhelin

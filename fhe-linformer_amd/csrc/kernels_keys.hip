@@ -32,12 +32,13 @@ __device__ __forceinline__ u64 dg_mul(u64 x, u64 k) {
 
 __global__ __launch_bounds__(DG_THREADS) void key_digest_partial_kernel(const u64* __restrict__ data, int log_n,
                                                                           const u64* __restrict__ moduli, int limb_first,
-                                                                          int limb_count, u64* __restrict__ part) {
+                                                                          int limb_count, int group_stride, u64* __restrict__ part) {
     const int v = blockIdx.y;
     const size_t N = (size_t)1 << log_n;
     const u64 q = moduli[limb_first + v % limb_count];
     const u32 base = blockIdx.x * DG_CHUNK;
-    const u64x2* src = reinterpret_cast<const u64x2*>(data + (size_t)v * N + base);
+    const size_t row = (size_t)(v / limb_count) * group_stride + v % limb_count;   // = v when the vectors are contiguous
+    const u64x2* src = reinterpret_cast<const u64x2*>(data + row * N + base);
     u64x2 w[DG_ITER];
 #pragma unroll
     for (int it = 0; it < DG_ITER; ++it) w[it] = __builtin_nontemporal_load(src + it * DG_THREADS + threadIdx.x);
@@ -82,11 +83,18 @@ size_t key_digest_scratch_words(int N, int n_vec) { return (size_t)n_vec * (size
 
 void launch_key_digest(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, u64* d_part, u64* d_out,
                        hipStream_t s) {
+    launch_key_digest_strided(dt, data, n_vec, limb_first, limb_count, limb_count, d_part, d_out, s);
+}
+
+void launch_key_digest_strided(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, int group_stride,
+                               u64* d_part, u64* d_out, hipStream_t s) {
     const int N = 1 << dt.log_n;
-    if (N % DG_CHUNK || n_vec < 1 || n_vec > 65535 || limb_count < 1 || limb_first < 0 || limb_first + limb_count > dt.n_limbs)
-        return;   // callers check (evalkeys.cpp): N >= 4096, limbs inside the context
+    if (N % DG_CHUNK || n_vec < 1 || n_vec > 65535 || limb_count < 1 || limb_first < 0 || limb_first + limb_count > dt.n_limbs ||
+        group_stride < limb_count)
+        return;   // callers check (capi_keys.cpp, capi_compact.cpp): N >= 4096, limbs inside the context
     const int nb = N / DG_CHUNK;
-    key_digest_partial_kernel<<<dim3(nb, n_vec), DG_THREADS, 0, s>>>(data, dt.log_n, dt.moduli, limb_first, limb_count, d_part);
+    key_digest_partial_kernel<<<dim3(nb, n_vec), DG_THREADS, 0, s>>>(data, dt.log_n, dt.moduli, limb_first, limb_count, group_stride,
+                                                                     d_part);
     key_digest_final_kernel<<<(n_vec + 63) / 64, 64, 0, s>>>(d_part, nb, n_vec, d_out);
 }
 

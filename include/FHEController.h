@@ -690,6 +690,29 @@ public:
             f.write((const char*)limbs.data(), (streamsize)(limbs.size() * 8));
         }
     }
+    /* Compact inputs (include/fhelin.h "Compact ciphertexts"): with seeded encryption on, encrypt / read_expanded_input encrypt with
+     * the secret key and c1 expanded from a public seed, and save_compact writes c0, the seed and the nonce of each, half the bytes
+     * of save().  File: magic, count, then per ciphertext a u64 byte length and the blob.  load_vector / load_ciphertext read both
+     * formats; a compact file is imported in one batched call (all or nothing).  The server needs no secret to load one. */
+    void set_seeded_encryption(bool on) { fhelin_shim::check(fhelin_ctx_set_seeded_encryption(context, on ? 1 : 0), "SetSeededEncryption"); }
+    void save_compact(vector<Ctxt> v, string filename) {
+        ofstream f(filename, ios::out | ios::binary);
+        if (!f.is_open()) throw std::runtime_error("save_compact: cannot create " + filename);
+        uint64_t magic = COMPACT_FILE_MAGIC, n = v.size();
+        f.write((const char*)&magic, 8);
+        f.write((const char*)&n, 8);
+        vector<uint8_t> blob;
+        for (auto& c : v) {
+            size_t bytes = 0;
+            fhelin_shim::check(fhelin_ct_compact_bytes(c->h, &bytes), "Serialize(compact)");
+            blob.resize(bytes);
+            fhelin_shim::check(fhelin_ct_export_compact(context, c->h, blob.data(), bytes), "Serialize(compact)");
+            const uint64_t len = bytes;
+            f.write((const char*)&len, 8);
+            f.write((const char*)blob.data(), (streamsize)bytes);
+        }
+        if (!f) throw std::runtime_error("save_compact: write to " + filename + " failed");
+    }
     vector<Ctxt> load_vector(string filename) {
         vector<Ctxt> result;
         ifstream f(filename, ios::in | ios::binary);
@@ -697,6 +720,28 @@ public:
         if (f.is_open()) {
             f.read((char*)&magic, 8);
             f.read((char*)&n, 8);
+        }
+        if (f && magic == COMPACT_FILE_MAGIC) {
+            vector<vector<uint8_t>> blobs;
+            for (uint64_t i = 0; i < n; i++) {
+                uint64_t len = 0;
+                f.read((char*)&len, 8);
+                if (!f || len > ((uint64_t)1 << 36)) throw std::runtime_error("Deserialize(compact): truncated " + filename);
+                blobs.emplace_back(len);
+                f.read((char*)blobs.back().data(), (streamsize)len);
+                if (!f) throw std::runtime_error("Deserialize(compact): truncated " + filename);
+            }
+            vector<const uint8_t*> ptrs;
+            vector<size_t> sizes;
+            for (auto& b : blobs) {
+                ptrs.push_back(b.data());
+                sizes.push_back(b.size());
+            }
+            vector<fhelin_ct*> outs(blobs.size(), nullptr);
+            fhelin_shim::check(fhelin_ct_import_compact(context, ptrs.data(), sizes.data(), (int32_t)blobs.size(), outs.data()),
+                               "Deserialize(compact)");
+            for (fhelin_ct* o : outs) result.push_back(wrap(o));
+            return result;
         }
         if (!f || magic != 0x46484C4E43543031ull) {
             cerr << "Could not find \"" << filename << "\"" << endl;
@@ -720,6 +765,8 @@ public:
         vector<Ctxt> v = load_vector(filename);
         return v.empty() ? Ctxt() : v[0];
     }
+
+    static constexpr uint64_t COMPACT_FILE_MAGIC = 0x46484C4E43433031ull;
 
     int relu_degree = 119;
     string parameters_folder = "keys";

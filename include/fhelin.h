@@ -451,6 +451,56 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path);
 int fhelin_debug_key_digest(fhelin_ctx* c, const uint64_t* words, int32_t n_limbs, int32_t limb_first, uint64_t* out_digests,
                             int32_t* out_ok);
 
+/* ---- seeded secret-key encryption and compact ciphertexts -------------------------------------------
+ * The party that encrypts is the client, which holds the secret, so it may encrypt with the secret key: c0 = -a s + e + m, c1 = a
+ * with a uniform and e one rounded Gaussian (sigma 3.19).  Here a is not random data but the EXPANSION of a public 32-byte seed and a
+ * u64 nonce, so c1 never needs to travel: a compact ciphertext carries c0, the seed and the nonce, half the bytes of the full form.
+ *
+ * Expansion.  c1 of a seeded ciphertext on Q-limb l (ABSOLUTE limb index 0 .. ell-1) at storage position j (the order
+ * fhelin_ct_export writes, NTT form): with b = j / 4 and k = j % 4, let W[0..7] be the ChaCha20 block (RFC 8439 block function) for
+ * key `seed`, 64-bit block counter (l << 32) | b and 64-bit stream `nonce` - the state layout of fhelin_prng_block: counter in words
+ * 12-13, stream in words 14-15 - read as 8 little-endian u64.  Then
+ *     c1[l][j] = (W[2k+1] * 2^64 + W[2k]) mod q_l.
+ * Every position is independent; the distance from uniform is below 2^-67 per residue.  Since l is the absolute limb index, a
+ * ciphertext at a lower level expands to a prefix of the same limbs.
+ *
+ * Compact format, version 1 (all integers little-endian; exactly 96 + 8 ell + 8 ell N bytes):
+ *   offset  0  char[8]  magic "FHELINCC"
+ *           8  u32      version = 1
+ *          12  u32      header bytes = 96 + 8 ell
+ *          16  i32[4]   log_n, ell, deg, slots
+ *          32  f64[2]   scale hi, lo (the 80-bit scale as hi + lo, as fhelin_ct_scale gives it)
+ *          48  u64      nonce
+ *          56  u8[32]   seed
+ *          88  u64      digest of c0: the key digest of the evaluation-key format ("Evaluation-key sets" above) over c0's ell limb
+ *                       vectors, D = sum_j d(c0[j]) * mix(j | 0x80000000) mod 2^61 - 1
+ *          96  u64[ell] q_0 .. q_{ell-1}
+ *   then   u64[ell][N]  c0, NTT form */
+/* 1: fhelin_encrypt, fhelin_encrypt_batch and fhelin_client_ingest encrypt with the secret key and an expanded c1; 0 (default):
+ * public-key encryption.  Each call draws a fresh 32-byte seed from the client's generator; a ciphertext's nonce is its output
+ * index within the call.  The calls stay level-plan sources in the same order and count as in public-key mode (a plan recorded in
+ * one mode applies in the other).  An evaluation context (no secret): FHELIN_ERR_KEY. */
+int fhelin_ctx_set_seeded_encryption(fhelin_ctx* c, int32_t on);
+/* size of the compact form; FHELIN_ERR_STATE unless ct is an unmodified seeded encryption (any operation's result, a public-key
+ * encryption or an imported value has none) */
+int fhelin_ct_compact_bytes(const fhelin_ct* ct, size_t* bytes);
+/* write the compact form (fhelin_ct_compact_bytes bytes) to out; an export is a level-plan terminal, as fhelin_ct_export */
+int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, size_t cap_bytes);
+/* validate a blob's header against itself and its size (magic, version, header size, log_n in [12, 17], 1 <= ell <= 64, exact
+ * size, 1 <= deg <= 2, slots a power of two <= N/2, scale): FHELIN_ERR_ARG otherwise.  Host-only, no context. */
+int fhelin_compact_info(const uint8_t* blob, size_t bytes, int32_t* log_n, int32_t* ell, int32_t* deg, int32_t* slots);
+/* n blobs -> n handles with the full ciphertexts (c0 as stored, c1 expanded; scale, deg and slots exact).  Every c0 is uploaded,
+ * range-checked and digested on the device, every c1 expanded in one launch, and the host synchronises once per call.  All or
+ * nothing: another log_n or other moduli, a malformed header, a residue >= q or a digest mismatch in ANY blob is FHELIN_ERR_ARG
+ * and no handle is created.  Imported values are not level-plan sources and are never lowered (as fhelin_ct_import); works on an
+ * evaluation context. */
+int fhelin_ct_import_compact(fhelin_ctx* c, const uint8_t* const* blobs, const size_t* sizes, int32_t n, fhelin_ct** outs);
+/* test / measurement hook: the expansion kernel alone for n_ct ciphertexts of ell limbs (seed, nonces nonce0 .. nonce0 + n_ct - 1) into
+ * scratch, then `reps` more launches timed with device events (ms: mean per launch, 0 when reps = 0); out (optional,
+ * [n_ct][ell][N]): the expanded c1 */
+int fhelin_debug_seeded_expand(fhelin_ctx* c, const uint8_t* seed32, uint64_t nonce0, int32_t ell, int32_t n_ct, int32_t reps,
+                               uint64_t* out, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
