@@ -308,8 +308,11 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
             e->lanes_ordered |= 1u << lane;
         }
     };
+    // the encodings over the full key basis (ell = L + 1 + k, fhelin_hoisted_dot's folded keys) are asked for at a level's exact scale:
+    // matched exactly, since neighbouring levels' scales can lie within 1e-12 of each other (~60-bit scaling primes)
+    const bool full = ell > ctx->L + 1;
     for (size_t i = 0; i < cache.size(); ++i)
-        if (cache[i]->ell == ell && fabsl(cache[i]->scale / scale - 1.0L) < 1e-12L) {
+        if (cache[i]->ell == ell && (full ? cache[i]->scale == scale : fabsl(cache[i]->scale / scale - 1.0L) < 1e-12L)) {
             if (i) std::rotate(cache.begin(), cache.begin() + i, cache.begin() + i + 1);   // most recently used first
             order(cache[0]);
             return cache[0];

@@ -291,6 +291,11 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
     }
     moduli = chain.q;
     moduli.insert(moduli.end(), chain.p.begin(), chain.p.end());
+    // the bit-size check above bounds the arguments, not the primes: the scaling primes alternate around 2^scale_bits, so
+    // scale_bits = 60 yields 61-bit primes.  The 30-bit split accumulators (Acc30) and the Montgomery-finished sums of 16
+    // products need every residue below 2^60.
+    for (u64 q : moduli)
+        if (q >> 60) throw Error(FHELIN_ERR_ARG, "prime chain: a modulus is >= 2^60 (lower scale_bits or first_bits)");
     for (u64 q : moduli) {
         barrett.push_back(h_barrett(q));
         tw.push_back(make_twiddles(q, p.log_n));

@@ -360,12 +360,14 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
 }
 
 Evaluator::FoldedKey Evaluator::folded_key(const PtPtr& p, int index, long double scale) {
+    // the scale must match exactly: the scaling factors of neighbouring levels can lie within 1e-12 of each other (always for
+    // ~60-bit scaling primes, whose spacing is 2N / 2^60), and a key folded at another level's scale is a different encoding
     const u64 g = c_.galois_element(index);
     auto kit = rot_keys.find(g);
     if (kit == rot_keys.end()) throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
     for (size_t i = 0; i < folded_keys.size(); ++i) {
         const FoldedKey& f = folded_keys[i];
-        if (f.pt.get() == p.get() && f.key.get() == kit->second.get() && f.index == index && fabsl(f.scale / scale - 1.0L) < 1e-12L) {
+        if (f.pt.get() == p.get() && f.key.get() == kit->second.get() && f.index == index && f.scale == scale) {
             FoldedKey hit = f;
             if (i + 1 != folded_keys.size()) {   // least recently used goes first when the cache is full
                 folded_keys.erase(folded_keys.begin() + i);
@@ -409,6 +411,8 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
     const int ns = xin[0]->slots > 0 ? xin[0]->slots : (1 << c_.prm.log_slots);
     for (int r : indices)
         if (r % ns == 0) throw Error(FHELIN_ERR_ARG, "hoisted_dot_rows: a rotation by 0 is the unrotated term (pts[0])");
+    if (rescale_out && c_.K + 1 > 16)   // the merged ModDown + rescale takes at most 16 sources: ModDown, then a separate rescale
+        return rescale_batch(hoisted_dot_rows(xin, pts, indices, false));
     std::vector<CtPtr> x = xin;
     {   // degree-2 operands are rescaled first (as before any product with a plaintext)
         std::vector<CtPtr> need;

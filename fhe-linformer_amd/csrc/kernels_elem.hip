@@ -500,7 +500,7 @@ __global__ __launch_bounds__(256) void ew_addscalar_kernel(DeviceTables t, u64* 
 }
 
 // out[v] = sum_k a_k[v] * s_k[limb] + s_n[limb]; grid (N/512, vecs).  The products are summed in 128 bits and reduced once:
-// the canonical residue of the sum, whatever the order (32 q^2 < q 2^64 for the Q limbs, q < 2^59).
+// the canonical residue of the sum, whatever the order (32 q^2 < 2^128 for q < 2^60; barrett_reduce128 takes any 128-bit value).
 __global__ __launch_bounds__(256) void ew_lincomb_kernel(DeviceTables t, u64* out, LinComb lc, const u64* __restrict__ scal, int ell,
                                                          int in_limbs) {
     const int v = blockIdx.y;

@@ -308,9 +308,10 @@ __global__ __launch_bounds__(256) void ks_inner_multi_kernel(DeviceTables t, KsS
             }
             if (++pending == 8) {  // at most 8 products of 60-bit halves fit the 64-bit columns
                 pending = 0;
-                // barrett_reduce128 needs a sum below q * 2^64: 16 products of operands below 2^60 (special limbs:
-                // canonical digits and keys, 16 p^2 < p * 2^64; scaling limbs: digits below 86q, 16 * 86 q^2 < q * 2^64
-                // for q < 2^53) plus one carried residue.  R * beta can reach 28 (giant steps): fold every 16.
+                // the final redc128 needs a sum below q * 2^64.  Keys are canonical; digits are canonical for q >= 2^53 and
+                // below 86q from the lazy forward NTT (lazy_out) for q < 2^53.  16 products plus one carried residue: below
+                // 16 q^2 + q < q * 2^64 for q < 2^60, and 16 * 86 q^2 + q < q * 2^64 for q < 2^53.  R * beta reaches 28 and
+                // more (giant steps; 56 at alpha = 1, beta = 8), and 32 products on a 60-bit chain can pass the bound: fold every 16.
                 const bool fold = ++folded == 2;
                 if (fold) folded = 0;
 #pragma unroll

@@ -57,6 +57,11 @@ typedef struct fhelin_params {
     uint64_t seed;         /* 0: the client-side generator (ChaCha20) is keyed with 256 bits of OS entropy — the default and the
                               only secure choice; != 0: deterministic 64-bit TEST seed (reproducible tests / benchmarks) */
 } fhelin_params;
+/* Accepted parameters (fhelin_ctx_create returns FHELIN_ERR_ARG otherwise): 12 <= log_n <= 17; 1 <= n_q <= 64; 0 <= n_p <= 16
+ * after resolution; first_bits, scale_bits and special_bits (the last only when n_p > 0) in [20, 60]; digit size
+ * ceil(n_q / dnum) <= 16 limbs and at most 16 digits.  Every prime of the resulting chain must lie below 2^60, and a chain that holds
+ * one at or above 2^60 is refused.  The scaling primes alternate around 2^scale_bits, so scale_bits = 60 is refused as soon as the
+ * chain needs a scaling prime above 2^scale_bits (n_q >= 3); first_bits = 60 and scale_bits = 59 are accepted.  n_p = 0 is a chain without key switching: rotations and relinearisation return FHELIN_ERR_STATE. */
 
 const char* fhelin_last_error(void);
 const char* fhelin_version(void);
@@ -245,7 +250,8 @@ int fhelin_rotate_sum(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, const
  * §7) is the call {128, 256, 384} over all rows.  Result: noise degree + 1, scale x the level's plaintext scale.  The plaintext
  * encodings over the full key basis are fhelin_pt_export(p, L + 1 + k, scale).
  * rescale != 0: the result rescaled, with ModDown and rescale as ONE basis conversion (P and the top limb dropped together: one rounding
- * instead of two, 2 ell fewer transforms per row): one limb fewer, the input's noise degree, scale / q_top. */
+ * instead of two, 2 ell fewer transforms per row): one limb fewer, the input's noise degree, scale / q_top.  That conversion takes at
+ * most 16 sources: with k = 16 the ModDown and the rescale run one after the other (two roundings). */
 int fhelin_hoisted_dot(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, const fhelin_pt* const* pts, const int32_t* indices,
                        int32_t n_rot, int32_t rescale, fhelin_ct** outs);
 /* out = sum_i EvalRotate(v[i], indices[i]) (index 0 = plain addend): the giant steps of EvalBootstrap's linear

@@ -139,6 +139,56 @@ def test_rescale_divides_by_last_prime(orc):
         assert abs(g * qs[-1] - c) <= qs[-1] // 2 + 1
 
 
+
+def _chain_bits(orc, log_n, n_q, n_p, first, scale, special):
+    q, p = orc.prime_chain(log_n, n_q, first, scale, n_p, special)
+    psi_q = np.array([orc.min_root(x, 2 << log_n) for x in q], dtype=np.uint64)
+    psi_p = np.array([orc.min_root(x, 2 << log_n) for x in p], dtype=np.uint64)
+    return q, p, psi_q, psi_p
+
+
+# prime classes of tests/test_param_corners_gpu.py: (n_q, first_bits, scale_bits, special_bits)
+CORNER_CHAINS = {
+    "p60": (8, 60, 59, 60),      # 60-bit q0, scaling primes on both sides of 2^59
+    "p57": (12, 55, 57, 60),     # 57/58-bit scaling primes, q_last >= 2 q0
+    "p53": (12, 55, 53, 60),
+    "lift": (8, 40, 50, 30),     # q_last >= 2 q0: the unfused lift
+    "p24": (4, 24, 24, 24),
+}
+
+
+@pytest.mark.parametrize("corner", sorted(CORNER_CHAINS))
+@pytest.mark.parametrize("ell", [3, 2])
+def test_rescale_divides_by_last_prime_at_corner_chains(orc, corner, ell):
+    """the rescale KAT on the corner chains: exact division by q_last, rounded, for coefficients up to Q / 8 (both signs), the
+    centring boundaries of the last limb included"""
+    n_q, fb, sb, pb = CORNER_CHAINS[corner]
+    log_n = 12
+    q, _, psi, _ = _chain_bits(orc, log_n, n_q, 1, fb, sb, pb)
+    q, psi = q[:ell], psi[:ell]
+    qs = [int(x) for x in q]
+    Q = 1
+    for m in qs:
+        Q *= m
+    rng = np.random.default_rng(50 + ell)
+    n = 1 << log_n
+    lim = Q // 8
+    coeffs = [int.from_bytes(rng.bytes(32), "little") % (2 * lim) - lim for _ in range(n)]
+    ql = qs[-1]
+    for i, r in enumerate([0, ql // 2, ql // 2 + 1, ql - 1]):           # c mod q_last at the centring threshold
+        coeffs[i] = (coeffs[i] // ql) * ql + r
+    limbs = np.array([[c % m for c in coeffs] for m in qs], dtype=np.uint64)
+    out = orc.rescale(orc.ntt_batch(limbs, q, psi)[None], q, psi)[0]
+    back = orc.ntt_batch(out, q[:-1], psi[:-1], inverse=True)
+    if ell == 2:
+        got = [int(v) if int(v) <= qs[0] // 2 else int(v) - qs[0] for v in back[0]]
+    else:
+        got = _crt2(back[0], back[1], qs[0], qs[1])
+    for c, g in zip(coeffs, got):
+        r = c % ql
+        r = r - ql if r > ql // 2 else r
+        assert g * ql == c - r, (corner, c)          # (c - [c]_ql centred) / ql, exactly
+
 def _toy_keys(orc, log_n, q, p, psi_q, psi_p, alpha, s_from, s_to, rng):
     """Hybrid key-switching key from secret s_from to s_to (both small ternary coefficient vectors)."""
     n = 1 << log_n
@@ -195,6 +245,33 @@ def test_keyswitch_correct_by_decryption(orc, ell):
     err = _crt2(diff[0], diff[1], int(ql[0]), int(ql[1]))
     assert max(abs(e) for e in err) < 2 ** 40   # noise << q (2^52): ~ N * dnum * q_digit * e / P + rounding
 
+
+
+@pytest.mark.parametrize("L1,k,alpha,fb,sb,ells", [
+    (16, 2, 1, 55, 52, [16, 9, 2]),         # alpha = 1, beta = 16
+    (16, 16, 16, 55, 52, [16, 9]),          # alpha = 16, beta = 1, k = 16
+    (8, 3, 2, 60, 59, [8, 5, 3]),           # 60-bit q0, 59/60-bit scaling primes
+])
+def test_keyswitch_correct_by_decryption_at_corners(orc, L1, k, alpha, fb, sb, ells):
+    """the key-switching KAT at the digit-shape and prime-size corners of tests/test_param_corners_gpu.py"""
+    log_n = 12
+    q, p, psi_q, psi_p = _chain_bits(orc, log_n, L1, k, fb, sb, 60)
+    rng = np.random.default_rng(16 + L1 + k)
+    n = 1 << log_n
+    s = [int(v) for v in rng.integers(-1, 2, size=n)]
+    s2 = [int(v) for v in rng.integers(-1, 2, size=n)]
+    evk, _ = _toy_keys(orc, log_n, q, p, psi_q, psi_p, alpha, s2, s, rng)
+    for ell in ells:
+        ql = q[:ell]
+        c = np.array([rng.integers(0, int(m), size=n, dtype=np.uint64) for m in ql])
+        c[:, :2] = (ql - 1)[:, None]                              # maximal residues in two slots
+        ks = orc.keyswitch(c, evk, alpha, q, p, psi_q, psi_p)
+        s_ntt = orc.ntt_batch(np.array([[v % int(m) for v in s] for m in ql], dtype=np.uint64), ql, psi_q[:ell])
+        s2_ntt = orc.ntt_batch(np.array([[v % int(m) for v in s2] for m in ql], dtype=np.uint64), ql, psi_q[:ell])
+        lhs = orc.add(ks[0], orc.mul(ks[1], s_ntt, ql), ql)
+        diff = orc.ntt_batch(orc.sub(lhs, orc.mul(c, s2_ntt, ql), ql), ql, psi_q[:ell], inverse=True)
+        err = _crt2(diff[0], diff[1], int(ql[0]), int(ql[1]))
+        assert max(abs(e) for e in err) < 2 ** 40, (L1, k, alpha, ell)
 
 def test_rotate_matches_definition(orc):
     """orc_rotate == automorphism of (c0 + ks0, ks1) and decrypts to the rotated message polynomial."""
@@ -413,6 +490,26 @@ def test_modraise_is_the_centred_lift(orc):
             want = np.array([(int(v) - q0 if int(v) > q0 // 2 else int(v)) % qt for v in co[pidx]], dtype=np.uint64)
             assert np.array_equal(back[t], want), t
 
+
+
+@pytest.mark.parametrize("corner", ["p60", "lift", "p24"])
+def test_modraise_is_the_centred_lift_at_corner_chains(orc, corner):
+    """the ModRaise KAT with a 60-bit, a 40-bit and a 24-bit source prime (targets larger and smaller than the source)"""
+    n_q, fb, sb, pb = CORNER_CHAINS[corner]
+    log_n = 12
+    q, _, psi, _ = _chain_bits(orc, log_n, n_q, 1, fb, sb, pb)
+    n = 1 << log_n
+    q0 = int(q[0])
+    co = np.random.default_rng(14).integers(0, q0, size=(2, n), dtype=np.uint64)
+    co[0, :4] = [0, q0 - 1, q0 // 2, q0 // 2 + 1]
+    src = np.stack([orc.ntt_forward(c, q0, psi[0]) for c in co])
+    out = orc.modraise(src, n_q, q, psi)
+    for pidx in range(2):
+        back = orc.ntt_batch(out[pidx], q, psi, inverse=True)
+        for t in range(n_q):
+            qt = int(q[t])
+            want = np.array([(int(v) - q0 if int(v) > q0 // 2 else int(v)) % qt for v in co[pidx]], dtype=np.uint64)
+            assert np.array_equal(back[t], want), (corner, t)
 
 def test_fast_build_equals_definition_build(orc):
     """libfhe_oracle_fast.so (Barrett reductions; the timed cpu_baseline leg) returns the residues of the
