@@ -206,6 +206,9 @@ def load_library():
         "fhelin_evalkeys_params": (i32, [C.c_char_p, C.POINTER(Params)]),
         "fhelin_evalkeys_info": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]),
         "fhelin_evalkeys_load": (i32, [vp, C.c_char_p]),
+        "fhelin_evalkeys_save_compact": (i32, [vp, C.c_char_p]),
+        "fhelin_ctx_set_seeded_keys": (i32, [vp, i32]),
+        "fhelin_ctx_key_set_seed": (i32, [vp, vp]),
         "fhelin_debug_key_digest": (i32, [vp, vp, i32, i32, C.POINTER(C.c_uint64), C.POINTER(i32)]),
         "fhelin_ctx_set_seeded_encryption": (i32, [vp, i32]),
         "fhelin_ct_compact_bytes": (i32, [vp, C.POINTER(C.c_size_t)]),
@@ -472,9 +475,22 @@ class Engine:
         self._ck(self.lib.fhelin_key_import(self.h, kind, index, arr.ctypes.data_as(C.c_void_p), arr.size))
 
     # ---- evaluation-key sets (include/fhelin.h "Evaluation-key sets")
-    def save_eval_keys(self, path):
-        """write the public parameters and every public key this context holds (never the secret) to `path`"""
-        self._ck(self.lib.fhelin_evalkeys_save(self.h, os.fsencode(path)))
+    def save_eval_keys(self, path, compact=False):
+        """write the public parameters and every public key this context holds (never the secret) to `path`.  compact: the b
+        halves and the key-set seed only (every key must be seeded: set_seeded_keys before keygen)"""
+        fn = self.lib.fhelin_evalkeys_save_compact if compact else self.lib.fhelin_evalkeys_save
+        self._ck(fn(self.h, os.fsencode(path)))
+
+    # ---- seeded evaluation keys (include/fhelin.h "Seeded evaluation keys")
+    def set_seeded_keys(self, on):
+        """on: keygen draws a public key-set seed and every key's a half is its expansion (call before keygen)"""
+        self._ck(self.lib.fhelin_ctx_set_seeded_keys(self.h, 1 if on else 0))
+
+    def key_set_seed(self):
+        """the public 32-byte key-set seed of a seeded-key context (or one loaded from a compact set)"""
+        out = (C.c_uint8 * 32)()
+        self._ck(self.lib.fhelin_ctx_key_set_seed(self.h, out))
+        return bytes(out)
 
     @staticmethod
     def eval_keys_params(path):
@@ -492,7 +508,7 @@ class Engine:
 
     @classmethod
     def from_eval_keys(cls, path, device=0, seed=0):
-        """an EVALUATION context (no secret) from a set written by save_eval_keys: the header's parameters, its keys, and the
+        """an EVALUATION context (no secret) from a set written by save_eval_keys (full or compact): the header's parameters, its keys, and the
         client's bootstrapping set up again from them when the client had set it up.  seed: this context's own generator
         (public-key encryption randomness), 0 = OS entropy."""
         cfg, boot, _ = cls.eval_keys_params(path)

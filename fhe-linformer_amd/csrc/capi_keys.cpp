@@ -1,7 +1,9 @@
-// extern "C" boundary, part 4: evaluation-key sets (include/fhelin.h "Evaluation-key sets": the file format is documented there).
-// A client context writes its public key and every switching key it holds; a context that never held a secret loads them and
-// evaluates with them alone.  Every key is range-checked and digested on the device (kernels_keys.hip) on the way out and on
-// the way in; the file is streamed through two pinned staging buffers, so host memory stays bounded by them.
+// extern "C" boundary, part 4: evaluation-key sets (include/fhelin.h "Evaluation-key sets" and "Seeded evaluation keys": both file
+// formats are documented there).  A client context writes its public key and every switching key it holds; a context that never
+// held a secret loads them and evaluates with them alone.  Every key is range-checked and digested on the device (kernels_keys.hip)
+// on the way out and on the way in; the file is streamed through two pinned staging buffers, so host memory stays bounded by them.
+// A compact set ("FHELINEC") stores the b halves and the key-set seed; the loader expands every a half in one launch
+// (kernels_seeded.hip) before it digests.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -10,6 +12,7 @@
 #include <memory>
 #include "capi_internal.h"
 #include "kernels_keys.h"
+#include "kernels_seeded.h"
 
 using namespace fhelin;
 
@@ -20,8 +23,9 @@ using namespace fhelin;
 namespace {
 
 constexpr char EK_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'K'};
-constexpr uint32_t EK_VERSION = 1;
-constexpr size_t EK_HEADER = 96, EK_ENTRY = 40, EK_ALIGN = 4096;
+constexpr char EC_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'C'};   // compact (seeded) set
+constexpr uint32_t EK_VERSION = 1, EC_VERSION = 1;
+constexpr size_t EK_HEADER = 96, EC_HEADER = 128, EK_ENTRY = 40, EK_ALIGN = 4096;
 constexpr uint32_t EK_MAX_KEYS = 1u << 16;
 constexpr size_t EK_STAGE_BYTES = size_t(4) << 20;   // per staging buffer (two of them)
 enum : uint32_t { EK_PUBLIC = 0, EK_RELIN = 1, EK_ROTATION = 2, EK_CONJ = 3 };
@@ -36,6 +40,8 @@ struct EkFile {
     std::vector<uint64_t> moduli;
     std::vector<EkEntry> keys;
     uint64_t data_offset = 0;
+    bool compact = false;     // "FHELINEC": b halves only, a expanded from `seed`
+    uint8_t seed[32] = {};
 };
 
 struct File {
@@ -88,9 +94,12 @@ EkFile read_header(const char* path) {
     const uint64_t fsize = (uint64_t)st.st_size;
     uint8_t h[EK_HEADER];
     if (fsize < EK_HEADER || std::fread(h, 1, EK_HEADER, fh.f) != EK_HEADER) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
-    if (std::memcmp(h, EK_MAGIC, 8) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad magic");
-    if (get<uint32_t>(h, 8) != EK_VERSION) throw Error(FHELIN_ERR_ARG, "evaluation-key set: unsupported version");
     EkFile e;
+    if (std::memcmp(h, EC_MAGIC, 8) == 0) e.compact = true;
+    else if (std::memcmp(h, EK_MAGIC, 8) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad magic");
+    if (get<uint32_t>(h, 8) != (e.compact ? EC_VERSION : EK_VERSION)) throw Error(FHELIN_ERR_ARG, "evaluation-key set: unsupported version");
+    const uint64_t head = e.compact ? EC_HEADER : EK_HEADER;
+    if (e.compact && (fsize < EC_HEADER || std::fread(e.seed, 1, 32, fh.f) != 32)) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
     const uint32_t n_keys = get<uint32_t>(h, 12);
     for (int i = 0; i < 9; ++i) e.prm[i] = get<int32_t>(h, 16 + 4 * i);
     for (int i = 0; i < 7; ++i) e.boot[i] = get<int32_t>(h, 52 + 4 * i);
@@ -105,7 +114,7 @@ EkFile read_header(const char* path) {
     if (!boot_ok) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad bootstrap configuration");
     if (n_keys > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evaluation-key set: too many keys");
     const uint64_t N = 1ull << log_n, nm = (uint64_t)n_q + n_p;
-    const uint64_t table_end = EK_HEADER + 8 * nm + EK_ENTRY * (uint64_t)n_keys;
+    const uint64_t table_end = head + 8 * nm + EK_ENTRY * (uint64_t)n_keys;
     if (fsize < table_end) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated key table");
     e.moduli.resize(nm);
     if (std::fread(e.moduli.data(), 8, nm, fh.f) != nm) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated moduli");
@@ -127,7 +136,9 @@ EkFile read_header(const char* path) {
         x.digest = get<uint64_t>(r, 32);
         if (x.kind > EK_CONJ) throw Error(FHELIN_ERR_ARG, "evaluation-key set: unknown key kind");
         if (x.kind != EK_ROTATION && ++seen[x.kind] > 1) throw Error(FHELIN_ERR_ARG, "evaluation-key set: duplicate key");
-        const uint64_t want = x.kind == EK_PUBLIC ? 2 * (uint64_t)n_q * N : (uint64_t)x.digits * 2 * nm * N;
+        // the compact form stores the b halves only
+        const uint64_t halves = e.compact ? 1 : 2;
+        const uint64_t want = x.kind == EK_PUBLIC ? halves * (uint64_t)n_q * N : (uint64_t)x.digits * halves * nm * N;
         if ((x.kind == EK_PUBLIC) != (x.digits == 0) || x.digits > (uint32_t)n_q || x.words != want)
             throw Error(FHELIN_ERR_ARG, "evaluation-key set: key size does not match the parameters");
         const uint64_t g_want = x.kind == EK_CONJ ? 2 * N - 1 : 0;
@@ -230,6 +241,142 @@ bool fresh(const fhelin_ctx* c) {
     return true;
 }
 
+std::string key_what(uint32_t kind, uint64_t galois) {
+    return std::string(kind_name(kind)) + (kind == EK_ROTATION ? " (Galois element " + std::to_string(galois) + ")" : "");
+}
+
+// v1 (full keys) or compact (b halves and the key-set seed): the same table, digests of the full keys in both
+void save_set(fhelin_ctx* c, const char* path, bool compact) {
+    Context& x = c->ctx;
+    x.require_device();
+    x.sync();
+    const u64 g_conj = 2ull * x.N - 1;
+    std::vector<Seg> segs;
+    std::vector<EkEntry> ents;
+    std::vector<char> seeded;
+    auto add = [&](uint32_t kind, uint32_t digits, uint64_t g, u64* d, size_t words, bool sd) {
+        EkEntry e;
+        e.kind = kind;
+        e.digits = digits;
+        e.galois = g;
+        e.words = words;
+        ents.push_back(e);
+        segs.push_back({d, words});
+        seeded.push_back(sd);
+    };
+    if (c->cl.has_public_key())
+        add(EK_PUBLIC, 0, 0, const_cast<u64*>(c->cl.public_key()), (size_t)2 * (x.L + 1) * x.N, c->cl.public_key_seeded());
+    const KeyPtr& rk = c->ev.relin_key;
+    const KeyPtr& ck = c->ev.conj_key;
+    if (rk) add(EK_RELIN, rk->digits, 0, rk->d, rk->words(), rk->seeded);
+    if (ck) add(EK_CONJ, ck->digits, g_conj, ck->d, ck->words(), ck->seeded);
+    for (const auto& kv : c->ev.rot_keys)   // ordered by Galois element; the conjugation key is stored once, above
+        if (kv.second && kv.first != g_conj) add(EK_ROTATION, kv.second->digits, kv.first, kv.second->d, kv.second->words(), kv.second->seeded);
+    if (ents.empty()) throw Error(FHELIN_ERR_KEY, "evalkeys_save: the context holds no keys");
+    if (ents.size() > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evalkeys_save: too many keys");
+    if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "evalkeys_save: ring dimension below 2^12");
+    if (compact) {
+        if (!c->cl.has_key_seed())
+            throw Error(FHELIN_ERR_STATE, "evalkeys_save_compact: the keys are not seeded (fhelin_ctx_set_seeded_keys before fhelin_keygen)");
+        for (size_t k = 0; k < ents.size(); ++k)
+            if (!seeded[k])
+                throw Error(FHELIN_ERR_STATE, "evalkeys_save_compact: the " + key_what(ents[k].kind, ents[k].galois) +
+                                                  " is not seeded (imported or made outside seeded-key mode)");
+    }
+
+    std::vector<uint32_t> kinds;
+    for (const auto& e : ents) kinds.push_back(e.kind);
+    std::vector<uint64_t> digest;
+    std::vector<char> ok;
+    key_digests(x, segs, kinds, digest, ok);
+    for (size_t k = 0; k < ents.size(); ++k) {
+        if (!ok[k]) throw Error(FHELIN_ERR_INTERNAL, std::string("evalkeys_save: ") + kind_name(ents[k].kind) + " holds a residue out of range");
+        ents[k].digest = digest[k];
+    }
+    // what is written: every key whole, or the b half of every digit
+    std::vector<Seg> out;
+    if (compact) {
+        for (size_t k = 0; k < ents.size(); ++k) {
+            const size_t half = ents[k].kind == EK_PUBLIC ? (size_t)(x.L + 1) * x.N : (size_t)(x.L + 1 + x.K) * x.N;
+            const uint32_t nd = ents[k].kind == EK_PUBLIC ? 1 : ents[k].digits;
+            for (uint32_t j = 0; j < nd; ++j) out.push_back({segs[k].d + (size_t)2 * j * half, half});
+            ents[k].words /= 2;
+        }
+    } else {
+        out = segs;
+    }
+
+    const size_t nm = x.moduli.size();
+    const size_t head = compact ? EC_HEADER : EK_HEADER;
+    const uint64_t table_end = head + 8 * nm + EK_ENTRY * ents.size();
+    const uint64_t data_offset = (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN;
+    std::vector<uint8_t> h(data_offset, 0);
+    std::memcpy(h.data(), compact ? EC_MAGIC : EK_MAGIC, 8);
+    put<uint32_t>(h, 8, compact ? EC_VERSION : EK_VERSION);
+    put<uint32_t>(h, 12, (uint32_t)ents.size());
+    int32_t prm[9];
+    from_params(x.prm, prm);
+    std::memcpy(h.data() + 16, prm, sizeof(prm));
+    if (c->boot.ready()) {
+        const int32_t b[7] = {c->boot.budget_enc(), c->boot.budget_dec(), c->boot.slots(), c->boot.K, c->boot.R, c->boot.cheb_degree,
+                              c->boot.correction};
+        std::memcpy(h.data() + 52, b, sizeof(b));
+    }
+    put<uint64_t>(h, 80, data_offset);
+    if (compact) std::memcpy(h.data() + EK_HEADER, c->cl.key_seed(), 32);
+    std::memcpy(h.data() + head, x.moduli.data(), 8 * nm);
+    uint64_t at = data_offset;
+    for (size_t k = 0; k < ents.size(); ++k) {
+        ents[k].offset = at;
+        at += 8 * ents[k].words;
+        const size_t o = head + 8 * nm + EK_ENTRY * k;
+        put<uint32_t>(h, o, ents[k].kind);
+        put<uint32_t>(h, o + 4, ents[k].digits);
+        put<uint64_t>(h, o + 8, ents[k].galois);
+        put<uint64_t>(h, o + 16, ents[k].offset);
+        put<uint64_t>(h, o + 24, ents[k].words);
+        put<uint64_t>(h, o + 32, ents[k].digest);
+    }
+
+    bool written = false;
+    {
+        File fh(path, "wb");
+        if (!fh.f) throw Error(FHELIN_ERR_ARG, std::string("evalkeys_save: cannot create ") + path);
+        bool io_ok = std::fwrite(h.data(), 1, h.size(), fh.f) == h.size();
+        // payloads: device -> pinned buffer b while the host writes the other buffer's previous chunk
+        Pinned stg(x.stream);
+        int cur = 0;
+        size_t pend_bytes[2] = {};
+        for (const Seg& s : out) {
+            const size_t bytes = s.words * 8;
+            for (size_t off = 0; off < bytes && io_ok; off += EK_STAGE_BYTES) {
+                const size_t n = std::min(EK_STAGE_BYTES, bytes - off);
+                hip_check(hipMemcpyAsync(stg.p[cur], reinterpret_cast<const char*>(s.d) + off, n, hipMemcpyDeviceToHost, x.stream),
+                          "key download");
+                hip_check(hipEventRecord(stg.ev[cur], x.stream), "hipEventRecord(key staging)");
+                stg.used[cur] = true;
+                pend_bytes[cur] = n;
+                const int prev = cur ^ 1;
+                if (stg.used[prev]) {
+                    stg.wait(prev);
+                    io_ok = std::fwrite(stg.p[prev], 1, pend_bytes[prev], fh.f) == pend_bytes[prev];
+                }
+                cur = prev;
+            }
+        }
+        const int last = cur ^ 1;
+        if (io_ok && stg.used[last]) {
+            stg.wait(last);
+            io_ok = std::fwrite(stg.p[last], 1, pend_bytes[last], fh.f) == pend_bytes[last];
+        }
+        written = io_ok && std::fflush(fh.f) == 0;
+    }
+    if (!written) {
+        std::remove(path);
+        throw Error(FHELIN_ERR_ARG, std::string("evalkeys_save: write to ") + path + " failed");
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -258,108 +405,31 @@ int fhelin_evalkeys_info(const char* path, int32_t* boot7, int32_t* n_keys) {
 int fhelin_evalkeys_save(fhelin_ctx* c, const char* path) {
     if (!c || !path) return capi_fail(FHELIN_ERR_ARG, "null argument");
     FHELIN_TRY
-    Context& x = c->ctx;
-    x.require_device();
-    x.sync();
-    const u64 g_conj = 2ull * x.N - 1;
-    std::vector<Seg> segs;
-    std::vector<EkEntry> ents;
-    auto add = [&](uint32_t kind, uint32_t digits, uint64_t g, u64* d, size_t words) {
-        EkEntry e;
-        e.kind = kind;
-        e.digits = digits;
-        e.galois = g;
-        e.words = words;
-        ents.push_back(e);
-        segs.push_back({d, words});
-    };
-    if (c->cl.has_public_key()) add(EK_PUBLIC, 0, 0, const_cast<u64*>(c->cl.public_key()), (size_t)2 * (x.L + 1) * x.N);
-    if (c->ev.relin_key) add(EK_RELIN, c->ev.relin_key->digits, 0, c->ev.relin_key->d, c->ev.relin_key->words());
-    if (c->ev.conj_key) add(EK_CONJ, c->ev.conj_key->digits, g_conj, c->ev.conj_key->d, c->ev.conj_key->words());
-    for (const auto& kv : c->ev.rot_keys)   // ordered by Galois element; the conjugation key is stored once, above
-        if (kv.second && kv.first != g_conj) add(EK_ROTATION, kv.second->digits, kv.first, kv.second->d, kv.second->words());
-    if (ents.empty()) throw Error(FHELIN_ERR_KEY, "evalkeys_save: the context holds no keys");
-    if (ents.size() > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evalkeys_save: too many keys");
-    if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "evalkeys_save: ring dimension below 2^12");
-
-    std::vector<uint32_t> kinds;
-    for (const auto& e : ents) kinds.push_back(e.kind);
-    std::vector<uint64_t> digest;
-    std::vector<char> ok;
-    key_digests(x, segs, kinds, digest, ok);
-    for (size_t k = 0; k < ents.size(); ++k) {
-        if (!ok[k]) throw Error(FHELIN_ERR_INTERNAL, std::string("evalkeys_save: ") + kind_name(ents[k].kind) + " holds a residue out of range");
-        ents[k].digest = digest[k];
-    }
-
-    const size_t nm = x.moduli.size();
-    const uint64_t table_end = EK_HEADER + 8 * nm + EK_ENTRY * ents.size();
-    const uint64_t data_offset = (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN;
-    std::vector<uint8_t> h(data_offset, 0);
-    std::memcpy(h.data(), EK_MAGIC, 8);
-    put<uint32_t>(h, 8, EK_VERSION);
-    put<uint32_t>(h, 12, (uint32_t)ents.size());
-    int32_t prm[9];
-    from_params(x.prm, prm);
-    std::memcpy(h.data() + 16, prm, sizeof(prm));
-    if (c->boot.ready()) {
-        const int32_t b[7] = {c->boot.budget_enc(), c->boot.budget_dec(), c->boot.slots(), c->boot.K, c->boot.R, c->boot.cheb_degree,
-                              c->boot.correction};
-        std::memcpy(h.data() + 52, b, sizeof(b));
-    }
-    put<uint64_t>(h, 80, data_offset);
-    std::memcpy(h.data() + EK_HEADER, x.moduli.data(), 8 * nm);
-    uint64_t at = data_offset;
-    for (size_t k = 0; k < ents.size(); ++k) {
-        ents[k].offset = at;
-        at += 8 * ents[k].words;
-        const size_t o = EK_HEADER + 8 * nm + EK_ENTRY * k;
-        put<uint32_t>(h, o, ents[k].kind);
-        put<uint32_t>(h, o + 4, ents[k].digits);
-        put<uint64_t>(h, o + 8, ents[k].galois);
-        put<uint64_t>(h, o + 16, ents[k].offset);
-        put<uint64_t>(h, o + 24, ents[k].words);
-        put<uint64_t>(h, o + 32, ents[k].digest);
-    }
-
-    bool written = false;
-    {
-        File fh(path, "wb");
-        if (!fh.f) throw Error(FHELIN_ERR_ARG, std::string("evalkeys_save: cannot create ") + path);
-        bool io_ok = std::fwrite(h.data(), 1, h.size(), fh.f) == h.size();
-        // payloads: device -> pinned buffer b while the host writes the other buffer's previous chunk
-        Pinned stg(x.stream);
-        int cur = 0;
-        size_t pend_bytes[2] = {};
-        for (const Seg& s : segs) {
-            const size_t bytes = s.words * 8;
-            for (size_t off = 0; off < bytes && io_ok; off += EK_STAGE_BYTES) {
-                const size_t n = std::min(EK_STAGE_BYTES, bytes - off);
-                hip_check(hipMemcpyAsync(stg.p[cur], reinterpret_cast<const char*>(s.d) + off, n, hipMemcpyDeviceToHost, x.stream),
-                          "key download");
-                hip_check(hipEventRecord(stg.ev[cur], x.stream), "hipEventRecord(key staging)");
-                stg.used[cur] = true;
-                pend_bytes[cur] = n;
-                const int prev = cur ^ 1;
-                if (stg.used[prev]) {
-                    stg.wait(prev);
-                    io_ok = std::fwrite(stg.p[prev], 1, pend_bytes[prev], fh.f) == pend_bytes[prev];
-                }
-                cur = prev;
-            }
-        }
-        const int last = cur ^ 1;
-        if (io_ok && stg.used[last]) {
-            stg.wait(last);
-            io_ok = std::fwrite(stg.p[last], 1, pend_bytes[last], fh.f) == pend_bytes[last];
-        }
-        written = io_ok && std::fflush(fh.f) == 0;
-    }
-    if (!written) {
-        std::remove(path);
-        throw Error(FHELIN_ERR_ARG, std::string("evalkeys_save: write to ") + path + " failed");
-    }
+    save_set(c, path, false);
     FHELIN_CATCH
+}
+
+int fhelin_evalkeys_save_compact(fhelin_ctx* c, const char* path) {
+    if (!c || !path) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    save_set(c, path, true);
+    FHELIN_CATCH
+}
+
+int fhelin_ctx_set_seeded_keys(fhelin_ctx* c, int32_t on) {
+    if (!c) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    if (c->cl.eval_only()) throw Error(FHELIN_ERR_KEY, "set_seeded_keys: an evaluation context holds no secret and makes no keys");
+    if (!fresh(c)) throw Error(FHELIN_ERR_STATE, "set_seeded_keys: call it before keygen, while the context holds no key");
+    c->cl.set_seeded_keys(on != 0);
+    FHELIN_CATCH
+}
+
+int fhelin_ctx_key_set_seed(const fhelin_ctx* c, uint8_t* out32) {
+    if (!c || !out32) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    if (!c->cl.has_key_seed()) return capi_fail(FHELIN_ERR_STATE, "key_set_seed: the keys are not seeded");
+    std::memcpy(out32, c->cl.key_seed(), 32);
+    return FHELIN_OK;
 }
 
 int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
@@ -391,13 +461,38 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
     std::vector<uint32_t> kinds;
     for (size_t k = 0; k < e.keys.size(); ++k) {
         if (e.keys[k].kind == EK_PUBLIC) {
-            pk.d = x.dalloc<u64>(e.keys[k].words);
-            segs.push_back({pk.d, e.keys[k].words});
+            const size_t pk_words = (size_t)2 * (x.L + 1) * x.N;   // the whole key (a compact entry's words count its b half)
+            pk.d = x.dalloc<u64>(pk_words);
+            segs.push_back({pk.d, pk_words});
         } else {
             sw[k] = c->ev.new_key();
             segs.push_back({sw[k]->d, sw[k]->words()});
         }
         kinds.push_back(e.keys[k].kind);
+    }
+    // what the file holds: every key whole, or the b half of every digit (the a halves are expanded below)
+    std::vector<Seg> in;
+    std::vector<SeededEntry> tab;
+    if (e.compact) {
+        SamplerKey sk;
+        for (int w = 0; w < 8; ++w) sk.w[w] = get<uint32_t>(e.seed, 4 * w);
+        for (size_t k = 0; k < e.keys.size(); ++k) {
+            const bool pub = e.keys[k].kind == EK_PUBLIC;
+            const int ell = pub ? x.L + 1 : x.L + 1 + x.K;
+            const size_t half = (size_t)ell * x.N;
+            const uint32_t nd = pub ? 1 : e.keys[k].digits;
+            for (uint32_t j = 0; j < nd; ++j) {
+                in.push_back({segs[k].d + (size_t)2 * j * half, half});
+                SeededEntry se;
+                se.key = sk;
+                se.nonce = key_nonce(e.keys[k].kind, j, e.keys[k].galois);
+                se.dst = segs[k].d + (size_t)(2 * j + 1) * half;
+                se.ell = ell;
+                tab.push_back(se);
+            }
+        }
+    } else {
+        in = segs;
     }
     {
         File fh(path, "rb");
@@ -405,7 +500,7 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
         // file -> pinned buffer b while buffer b^1's previous chunk is on its way to the device
         Pinned stg(x.stream);
         int cur = 0;
-        for (const Seg& s : segs) {
+        for (const Seg& s : in) {
             const size_t bytes = s.words * 8;
             for (size_t off = 0; off < bytes; off += EK_STAGE_BYTES) {
                 const size_t n = std::min(EK_STAGE_BYTES, bytes - off);
@@ -418,18 +513,34 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
             }
         }
     }
+    if (!tab.empty()) {   // every a half of the set: one launch (per 65535 key digits), before the digests see the full keys
+        struct TabGuard {
+            Context& x;
+            SeededEntry* d = nullptr;
+            ~TabGuard() {
+                if (d) x.pool.free(d);
+            }
+        } dt{x};
+        dt.d = reinterpret_cast<SeededEntry*>(x.pool.alloc(tab.size() * sizeof(SeededEntry)));
+        hip_check(hipMemcpyAsync(dt.d, tab.data(), tab.size() * sizeof(SeededEntry), hipMemcpyHostToDevice, x.stream), "seed table upload");
+        const int max_ell = x.L + 1 + x.K;
+        for (size_t lo = 0; lo < tab.size(); lo += 65535)
+            launch_seeded_expand(x.dt, dt.d + lo, (int)std::min<size_t>(65535, tab.size() - lo), max_ell, x.stream);
+        hip_check(hipGetLastError(), "seeded expand kernel");
+    }
     std::vector<uint64_t> digest;
     std::vector<char> ok;
     key_digests(x, segs, kinds, digest, ok);
     for (size_t k = 0; k < e.keys.size(); ++k) {
         const auto& ek = e.keys[k];
-        std::string what = std::string(kind_name(ek.kind)) + (ek.kind == EK_ROTATION ? " (Galois element " + std::to_string(ek.galois) + ")" : "");
+        const std::string what = key_what(ek.kind, ek.galois);
         if (!ok[k]) throw Error(FHELIN_ERR_ARG, "evalkeys_load: " + what + " holds a residue not below its modulus");
         if (digest[k] != ek.digest) throw Error(FHELIN_ERR_ARG, "evalkeys_load: " + what + " does not match its digest");
     }
 
     // install
     for (size_t k = 0; k < e.keys.size(); ++k) {
+        if (sw[k]) sw[k]->seeded = e.compact;
         switch (e.keys[k].kind) {
             case EK_RELIN: c->ev.relin_key = sw[k]; break;
             case EK_CONJ:
@@ -440,8 +551,9 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
             default: break;
         }
     }
-    c->cl.install_public_key(pk.d);
+    c->cl.install_public_key(pk.d, e.compact);
     pk.d = nullptr;
+    if (e.compact) c->cl.install_key_seed(e.seed);
     if (e.boot[2] > 0) {   // the client's approximation parameters; fhelin_bootstrap_setup is the caller's (fhelin_evalkeys_info)
         c->boot.K = e.boot[3];
         c->boot.R = e.boot[4];

@@ -371,9 +371,10 @@ void Client::sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind) 
     c_.pool.free(dco);
 }
 
-void Client::install_public_key(u64* d_pk) {
+void Client::install_public_key(u64* d_pk, bool seeded) {
     if (pk) c_.pool.free(pk);
     pk = d_pk;
+    pk_seeded_ = seeded;
     eval_only_ = true;
 }
 
@@ -398,6 +399,14 @@ void Client::keygen() {
         }
         ++placed;
     }
+    if (seeded_keys_ && L1 > KEYGEN_MAX_Q) throw Error(FHELIN_ERR_ARG, "seeded keys: more than 64 Q limbs");
+    if (seeded_keys_) {   // the public key-set seed: the next four words of the stream, bytes as begin_call
+        for (int i = 0; i < 4; ++i) {
+            const u64 w = rng_.next();
+            for (int b = 0; b < 8; ++b) key_seed_[8 * i + b] = (uint8_t)(w >> (8 * b));
+        }
+        has_key_seed_ = true;
+    }
     if (!s_all) s_all = c_.dalloc<u64>((size_t)nl * N);
     u64* dco = c_.dalloc<u64>(2 * N);
     hip_check(hipMemcpyAsync(dco, co.data(), 2 * N * 8, hipMemcpyHostToDevice, c_.stream), "secret upload");
@@ -405,8 +414,21 @@ void Client::keygen() {
     launch_reduce_i128(c_.dt, s_all, dco, 0, nl, c_.stream);
     launch_ntt(c_.dt, LimbBatch{s_all, nl, nullptr, 0, nl}, false, c_.stream);
     c_.pool.free(dco);
-    // public key over Q: a uniform (sampled directly in NTT form), b = e - a s
     if (!pk) pk = c_.dalloc<u64>((size_t)2 * L1 * N);
+    if (seeded_keys_) {
+        // b = e - a s with a the expansion of (key-set seed, nonce of the public key) on the Q limbs, made in registers
+        u64* e = c_.dalloc<u64>((size_t)L1 * N);
+        sample_small_device(e, 1, L1, 0);
+        c_.ntt(LimbBatch{e, L1, nullptr, 0, L1}, false);
+        launch_seeded_keygen_combine(c_.dt, pk, s_all, nullptr, e, L1, 1, c_.alpha, L1, nullptr, key_seed_words(), 0, 0, c_.stream);
+        hip_check(hipGetLastError(), "seeded keygen kernels");
+        hip_check(hipMemsetAsync(e, 0, (size_t)L1 * N * sizeof(u64), c_.stream), "hipMemsetAsync(key noise)");
+        c_.pool.free(e);
+        pk_seeded_ = true;
+        return;
+    }
+    pk_seeded_ = false;
+    // public key over Q: a uniform (sampled directly in NTT form), b = e - a s
     std::vector<u64> a((size_t)L1 * N);
     for (int l = 0; l < L1; ++l)
         for (size_t i = 0; i < N; ++i) a[(size_t)l * N + i] = rng_.uniform(c_.chain.q[l]);
@@ -421,12 +443,47 @@ void Client::keygen() {
     c_.pool.free(e);
 }
 
-KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all) {
+SamplerKey Client::key_seed_words() const {
+    SamplerKey k;
+    for (int i = 0; i < 8; ++i)
+        k.w[i] = (u32)key_seed_[4 * i] | ((u32)key_seed_[4 * i + 1] << 8) | ((u32)key_seed_[4 * i + 2] << 16) | ((u32)key_seed_[4 * i + 3] << 24);
+    return k;
+}
+
+void Client::install_key_seed(const uint8_t seed[32]) {
+    std::memcpy(key_seed_, seed, 32);
+    has_key_seed_ = true;
+}
+
+KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois) {
     c_.require_device();
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "key switching keys need special primes (n_p >= 1)");
     const size_t N = c_.N;
     const int L1 = c_.L + 1, nl = L1 + c_.K;
     KeyPtr key = ev_.new_key();
+    if (seeded_keys_) {
+        if (!has_key_seed_) throw Error(FHELIN_ERR_STATE, "seeded keys: keygen() draws the key-set seed and has not run");
+        if (L1 > KEYGEN_MAX_Q) throw Error(FHELIN_ERR_ARG, "seeded keys: more than 64 Q limbs");
+        // every digit in one launch: e [digits][nl][N] from the device sampler, one forward NTT, then the fused combination
+        const size_t en = (size_t)key->digits * nl * N;
+        u64* e = c_.dalloc<u64>(en);
+        sample_small_device(e, key->digits, nl, 0);
+        c_.ntt(LimbBatch{e, key->digits * nl, nullptr, 0, nl}, false);
+        std::vector<u64> pm(L1);
+        for (int t = 0; t < L1; ++t) {
+            const u64 qt = c_.chain.q[t];
+            u64 m = 1;
+            for (u64 p : c_.chain.p) m = h_mulmod(m, p % qt, qt);
+            pm[t] = m;
+        }
+        launch_seeded_keygen_combine(c_.dt, key->d, s_to_all, s_from_all, e, nl, key->digits, c_.alpha, L1, pm.data(), key_seed_words(), kind,
+                                     galois, c_.stream);
+        hip_check(hipGetLastError(), "seeded keygen kernels");
+        hip_check(hipMemsetAsync(e, 0, en * sizeof(u64), c_.stream), "hipMemsetAsync(key noise)");
+        c_.pool.free(e);
+        key->seeded = true;
+        return key;
+    }
     std::vector<u64> a((size_t)nl * N);
     u64* e = c_.dalloc<u64>((size_t)nl * N);
     u64* tmp = c_.dalloc<u64>((size_t)nl * N);
@@ -469,7 +526,7 @@ void Client::gen_relin_key() {
     const int nl = c_.L + 1 + c_.K;
     u64* s2 = c_.dalloc<u64>((size_t)nl * c_.N);
     launch_ew_mul(c_.dt, s2, s_all, s_all, nl, nl, 0, nl, c_.stream);
-    ev_.relin_key = make_switch_key(s2, s_all);
+    ev_.relin_key = make_switch_key(s2, s_all, 1, 0);
     c_.pool.free(s2);
 }
 
@@ -487,7 +544,7 @@ void Client::gen_rotation_key(int index) {
     const u64 ginv = c_.galois_element(-index);
     u64* sp = c_.dalloc<u64>((size_t)nl * c_.N);
     launch_automorph(c_.dt, sp, s_all, c_.automorph_map(ginv), nl, c_.stream);
-    ev_.rot_keys[g] = make_switch_key(s_all, sp);
+    ev_.rot_keys[g] = make_switch_key(s_all, sp, 2, g);
     c_.pool.free(sp);
 }
 
@@ -500,7 +557,7 @@ void Client::gen_conj_key() {
     const int nl = c_.L + 1 + c_.K;
     u64* sp = c_.dalloc<u64>((size_t)nl * c_.N);
     launch_automorph(c_.dt, sp, s_all, c_.automorph_map(g), nl, c_.stream);
-    ev_.conj_key = make_switch_key(s_all, sp);
+    ev_.conj_key = make_switch_key(s_all, sp, 3, g);
     ev_.rot_keys[g] = ev_.conj_key;
     c_.pool.free(sp);
 }

@@ -42,11 +42,22 @@ public:
     bool keygen_run() const { return keygen_run_; }   // keygen() or import_secret() ever ran on this context
     bool has_public_key() const { return pk != nullptr; }
     const u64* public_key() const { return pk; }      // device [2][L+1][N]
-    void install_public_key(u64* d_pk);               // takes ownership (a pool block); makes this an evaluation context
+    // takes ownership (a pool block); makes this an evaluation context.  seeded: its a half is the key-set seed's expansion
+    void install_public_key(u64* d_pk, bool seeded = false);
     void gen_relin_key();                // EvalMultKeyGen
     void gen_rotation_key(int index);    // EvalRotateKeyGen for one index
     void gen_conj_key();
-    KeyPtr make_switch_key(const u64* s_from_all, const u64* s_to_all);  // device [L+1+k][N] NTT form
+    // device [L+1+k][N] NTT form.  kind / galois: the key's nonce fields in seeded-key mode (include/fhelin.h "Seeded evaluation keys")
+    KeyPtr make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois);
+
+    // Seeded-key mode (include/fhelin.h "Seeded evaluation keys"): keygen draws a public key-set seed and every key's a half is
+    // its expansion, made on the device by seeded_keygen_combine_kernel.  Off: key generation consumes the generator as before.
+    void set_seeded_keys(bool on) { seeded_keys_ = on; }
+    bool seeded_keys() const { return seeded_keys_; }
+    bool has_key_seed() const { return has_key_seed_; }
+    const uint8_t* key_seed() const { return key_seed_; }
+    bool public_key_seeded() const { return pk && pk_seeded_; }
+    void install_key_seed(const uint8_t seed[32]);    // an evaluation context loaded from a compact set
 
     PtPtr encode(const double* vals, int n, int level, int slots);
     CtPtr encrypt(const PtPtr& p, int drop = 0);   // drop: limbs left out below the plaintext's level (level plan)
@@ -90,6 +101,9 @@ private:
     bool eval_only_ = false, keygen_run_ = false;
     bool seeded_ = false;
     uint8_t call_seed_[32] = {};
+    bool seeded_keys_ = false, has_key_seed_ = false, pk_seeded_ = false;
+    uint8_t key_seed_[32] = {};
+    SamplerKey key_seed_words() const;
 };
 
 // special FFT helpers (shared by encode/decode); slots must be a power of two

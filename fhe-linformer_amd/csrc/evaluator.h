@@ -81,6 +81,7 @@ struct EvalKey {
     // key streams of ks_inner_multi are contiguous and only the digits are gathered.  Built on first use (Evaluator::permuted).
     mutable u64* d_perm = nullptr;
     int digits = 0;
+    bool seeded = false;   // every a half is the expansion of the key-set seed (include/fhelin.h "Seeded evaluation keys")
     ~EvalKey();
     size_t words() const { return (size_t)digits * 2 * (ctx->L + 1 + ctx->K) * ctx->N; }
 };

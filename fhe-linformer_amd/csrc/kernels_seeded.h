@@ -1,5 +1,6 @@
 // Launchers of the seeded-ciphertext kernels (kernels_seeded.hip): secret-key encryption with c1 expanded from a public seed,
-// and the expansion of c1 on import (include/fhelin.h "Compact ciphertexts" defines the expansion).
+// the expansion of c1 on import (include/fhelin.h "Compact ciphertexts" defines the expansion), and seeded key generation
+// (include/fhelin.h "Seeded evaluation keys": a key's a half is the expansion of the key-set seed and a per-digit nonce).
 #pragma once
 #include "kernels.h"
 #include "kernels_client.h"
@@ -24,5 +25,17 @@ void launch_seeded_expand(const DeviceTables& t, const SeededEntry* tab, int n_c
 // e [n_vec][ell][N], m at m + b * m_stride (all NTT form).  nonces: host array of n_vec values (passed as kernel arguments).
 void launch_sk_encrypt_combine(const DeviceTables& t, u64* ct, const u64* s, const u64* e, const u64* m, size_t m_stride, int ell,
                                const SamplerKey& key, const u64* nonces, int n_vec, hipStream_t st);
+
+// nonce of digit `digit` of a key (include/fhelin.h "Seeded evaluation keys"): kind 0 public, 1 relinearisation, 2 rotation,
+// 3 conjugation key
+inline u64 key_nonce(u64 kind, u64 digit, u64 galois) { return (kind << 56) | (digit << 40) | galois; }
+constexpr int KEYGEN_MAX_Q = 64;   // Q limbs of the P mod q_l table passed by value
+
+// key [digits][2][ell][N] <- per digit j: b = e_j - a_j s_to (+ (P mod q_l) s_from on the limbs [j alpha, min((j+1) alpha, n_q))),
+// a_j = the expansion of (seed, key_nonce(kind, j, galois)) on limbs 0..ell-1.  s_to, s_from [>= ell][N], e [digits][ell][N], all
+// NTT form; s_from null: no s_from term (the public key: ell = n_q, digits = 1).  p_mod_q: host array of n_q values.
+// grid (N/4/256, ell, digits)
+void launch_seeded_keygen_combine(const DeviceTables& t, u64* key, const u64* s_to, const u64* s_from, const u64* e, int ell, int digits,
+                                  int alpha, int n_q, const u64* p_mod_q, const SamplerKey& seed, u64 kind, u64 galois, hipStream_t st);
 
 }  // namespace fhelin

@@ -9,6 +9,9 @@
 //                                destination from a device table.  grid (N/4/256, max ell, n_ct)
 //  * sk_encrypt_combine_kernel : secret-key encryption, c0 = m - a s + e and c1 = a, with a produced in registers.
 //                                grid (N/4/256, ell, n_vec)
+//  * seeded_keygen_combine_kernel : one key of seeded key generation (include/fhelin.h "Seeded evaluation keys"), every digit in
+//                                one launch: b = e - a s_to (+ (P mod q_l) s_from on the digit's limbs), a in registers.
+//                                grid (N/4/256, ell, digits)
 // Cost: the 20 ChaCha rounds are ~1,000 32-bit VALU operations per 64-byte block against 32 bytes of c1 written per block (plus
 // the 128-bit Barrett reductions): both kernels are bound by the VALU, not by HBM.  No LDS, no MFMA.
 #include <hip/hip_runtime.h>
@@ -25,6 +28,9 @@ constexpr int SK_BATCH = 32;   // nonces passed by value per sk_encrypt_combine 
 
 struct NonceSet {
     u64 v[SK_BATCH];
+};
+struct PModSet {   // P mod q_l for the Q limbs
+    u64 v[KEYGEN_MAX_Q];
 };
 
 __device__ __forceinline__ Barrett seeded_barrett(const DeviceTables& t, int limb) {
@@ -85,6 +91,43 @@ __global__ __launch_bounds__(SE_THREADS) void sk_encrypt_combine_kernel(DeviceTa
     c1[1] = u64x2{a[2], a[3]};
 }
 
+// The limb index l = blockIdx.y is over Q then P (the key basis); digit j = blockIdx.z.  The s_from term, on limbs
+// [lo, hi) of digit j only, is a wave-uniform branch.
+__global__ __launch_bounds__(SE_THREADS) void seeded_keygen_combine_kernel(DeviceTables t, u64* __restrict__ key, const u64* __restrict__ s_to,
+                                                                            const u64* __restrict__ s_from, const u64* __restrict__ e, int ell,
+                                                                            int alpha, int n_q, SamplerKey seed, u64 nonce0, PModSet pm) {
+    const size_t N = (size_t)1 << t.log_n;
+    const u32 b = blockIdx.x * SE_THREADS + threadIdx.x;
+    if (b >= N / 4) return;
+    const int j = blockIdx.z, l = blockIdx.y;
+    const Barrett br = seeded_barrett(t, l);
+    u64 a[4];
+    seeded_residues4(seed, nonce0 | ((u64)j << 40), l, b, br, a);
+    const size_t at = (size_t)l * N + 4 * (size_t)b;
+    const u64x2* sp = reinterpret_cast<const u64x2*>(s_to + at);
+    const u64x2* ep = reinterpret_cast<const u64x2*>(e + (size_t)j * ell * N + at);
+    const u64x2 s0 = sp[0], s1 = sp[1], e0 = ep[0], e1 = ep[1];
+    const u64 sv[4] = {s0.x, s0.y, s1.x, s1.y}, ev[4] = {e0.x, e0.y, e1.x, e1.y};
+    u64 r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = sub_mod(ev[k], mul_mod(a[k], sv[k], br), br.q);
+    const int lo = j * alpha, hi = min((j + 1) * alpha, n_q);
+    if (s_from && l >= lo && l < hi) {
+        const u64x2* fp = reinterpret_cast<const u64x2*>(s_from + at);
+        const u64x2 f0 = fp[0], f1 = fp[1];
+        const u64 fv[4] = {f0.x, f0.y, f1.x, f1.y};
+        const u64 pml = pm.v[l];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = add_mod(r[k], mul_mod(pml, fv[k], br), br.q);
+    }
+    u64x2* kb = reinterpret_cast<u64x2*>(key + ((size_t)(2 * j) * ell) * N + at);
+    u64x2* ka = reinterpret_cast<u64x2*>(key + ((size_t)(2 * j + 1) * ell) * N + at);
+    kb[0] = u64x2{r[0], r[1]};
+    kb[1] = u64x2{r[2], r[3]};
+    ka[0] = u64x2{a[0], a[1]};
+    ka[1] = u64x2{a[2], a[3]};
+}
+
 }  // namespace
 
 void launch_seeded_expand(const DeviceTables& t, const SeededEntry* tab, int n_ct, int max_ell, hipStream_t s) {
@@ -104,6 +147,17 @@ void launch_sk_encrypt_combine(const DeviceTables& t, u64* ct, const u64* s, con
         hipLaunchKernelGGL(sk_encrypt_combine_kernel, dim3(bx, (unsigned)ell, (unsigned)n), dim3(SE_THREADS), 0, st, t,
                            ct + (size_t)lo * 2 * ell * N, s, e + (size_t)lo * ell * N, m + (size_t)lo * m_stride, m_stride, ell, key, ns);
     }
+}
+
+void launch_seeded_keygen_combine(const DeviceTables& t, u64* key, const u64* s_to, const u64* s_from, const u64* e, int ell, int digits,
+                                  int alpha, int n_q, const u64* p_mod_q, const SamplerKey& seed, u64 kind, u64 galois, hipStream_t st) {
+    if (ell < 1 || ell > t.n_limbs || digits < 1 || digits > 65535 || n_q < 1 || n_q > KEYGEN_MAX_Q || alpha < 1) return;   // callers check (client.cpp)
+    PModSet pm{};
+    if (s_from)
+        for (int l = 0; l < n_q; ++l) pm.v[l] = p_mod_q[l];
+    const unsigned bx = (unsigned)((((size_t)1 << t.log_n) / 4 + SE_THREADS - 1) / SE_THREADS);
+    hipLaunchKernelGGL(seeded_keygen_combine_kernel, dim3(bx, (unsigned)ell, (unsigned)digits), dim3(SE_THREADS), 0, st, t, key, s_to, s_from,
+                       e, ell, alpha, n_q, seed, key_nonce(kind, 0, galois), pm);
 }
 
 }  // namespace fhelin

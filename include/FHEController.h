@@ -190,6 +190,7 @@ public:
         cout << endl << "Ciphertexts depth: " << circuit_depth << ", available multiplications: " << 12 - 2 << endl;
         create(p);
         cout << "Context built, generating keys..." << endl;
+        apply_seeded_keys();
         fhelin_shim::check(fhelin_keygen(context), "KeyGen");
         fhelin_shim::check(fhelin_gen_relin_key(context), "EvalMultKeyGen");
         cout << "Generated." << endl;
@@ -237,6 +238,7 @@ public:
         p.dnum = digits_hks;
         circuit_depth = p.n_q - 1;
         create(p);
+        apply_seeded_keys();
         fhelin_shim::check(fhelin_keygen(context), "KeyGen");
         fhelin_shim::check(fhelin_gen_relin_key(context), "EvalMultKeyGen");
     }
@@ -262,6 +264,7 @@ public:
         context = nullptr;
         fhelin_shim::check(fhelin_ctx_create_seeded(&p, seed, &context), "GenCryptoContext");
         start_level_plan();
+        apply_seeded_keys();
         fhelin_shim::check(fhelin_keygen(context), "KeyGen");
         fhelin_shim::check(fhelin_gen_relin_key(context), "EvalMultKeyGen");
         if (verbose) cout << "CtoS: " << level_budget[0] << ", StoC: " << level_budget[1] << endl;
@@ -271,10 +274,15 @@ public:
      * generate_bootstrapping_and_rotation_keys, writes its public key and every switching key to ../<parameters_folder>/<filename>;
      * the server reads crypto-context.txt and that set and never opens secret-key.txt.  load_bootstrapping_and_rotation_keys then
      * works unchanged on the server (the keys it asks for are present); decrypt and the print* helpers throw, as OpenFHE does
-     * without a secret key. */
-    void save_evaluation_keys(const string& filename) {
+     * without a secret key.
+     * Seeded keys (include/fhelin.h "Seeded evaluation keys"): set_seeded_keys(true) before generate_context / load_context makes
+     * every key's uniform half the expansion of a public key-set seed; save_evaluation_keys(filename, true) then writes the compact
+     * set (b halves and the seed, half the bytes), which load_evaluation_context reads as it reads the full one. */
+    void set_seeded_keys(bool on) { seeded_keys = on; }
+    void save_evaluation_keys(const string& filename, bool compact = false) {
         const string path = "../" + parameters_folder + "/" + filename;
-        fhelin_shim::check(fhelin_evalkeys_save(context, path.c_str()), "Serialize(evaluation keys)");
+        fhelin_shim::check(compact ? fhelin_evalkeys_save_compact(context, path.c_str()) : fhelin_evalkeys_save(context, path.c_str()),
+                           "Serialize(evaluation keys)");
     }
     void load_evaluation_context(const string& filename, bool verbose = true) {
         fhelin_params p = read_crypto_context();
@@ -828,6 +836,10 @@ private:
         const char* seed = std::getenv("FHELIN_SEED");   // explicit deterministic TEST seed; default 0 = OS entropy
         p.seed = seed ? std::strtoull(seed, nullptr, 10) : 0ull;
         return p;
+    }
+    bool seeded_keys = false;   // set_seeded_keys: applied between context creation and keygen
+    void apply_seeded_keys() {
+        if (seeded_keys) fhelin_shim::check(fhelin_ctx_set_seeded_keys(context, 1), "SetSeededKeys");
     }
     void create(const fhelin_params& p) {
         fhelin_ctx_destroy(context);

@@ -507,6 +507,48 @@ int fhelin_ct_import_compact(fhelin_ctx* c, const uint8_t* const* blobs, const s
 int fhelin_debug_seeded_expand(fhelin_ctx* c, const uint8_t* seed32, uint64_t nonce0, int32_t ell, int32_t n_ct, int32_t reps,
                                uint64_t* out, float* ms);
 
+/* ---- seeded evaluation keys: half-size key sets -------------------------------------------------------
+ * Half of every key is its uniform part a.  In seeded-key mode a is not random data but the expansion of a public 32-byte
+ * KEY-SET SEED and a per-digit nonce, so a compact key set stores the b halves and the seed, and the loading context rebuilds
+ * every a on the device.
+ *
+ * Key-set seed.  Drawn in fhelin_keygen from the client's generator right after the secret is placed and before the public key:
+ * the next four u64 of the stream, written little-endian (byte 8 i + k = byte k of word i, as the per-call seeds of seeded
+ * encryption).  Two contexts made from the same secret seed therefore make identical keys.  The seed is public.
+ *
+ * Nonce of digit `digit` of a key:  nonce = (kind << 56) | (digit << 40) | galois, with kind 0 public key (digit 0, galois 0),
+ * 1 relinearisation key (galois 0), 2 rotation key (galois 5^r mod 2N), 3 conjugation key (galois 2N - 1, stored once).
+ *
+ * Expansion.  The formula of "Compact ciphertexts" above with the limb index over the whole key basis Q then P: residue j of limb
+ * l (0 <= l < n_q + n_p) of a digit's a half is (W[2k+1] * 2^64 + W[2k]) mod m_l, b = j / 4, k = j % 4, m_l the l-th modulus of Q
+ * then P, W the ChaCha20 block for key = seed, counter (l << 32) | b and stream = nonce.  The public key uses l < n_q only.
+ * The b halves are those of the full keys: b = -a s_to + e (+ (P mod q_t) s_from on the limbs t of digit j), e one rounded
+ * Gaussian (sigma 3.19) per digit.
+ *
+ * Compact key-set format, version 1: the evaluation-key format above with these changes.
+ *   offset  0  char[8]  magic "FHELINEC"
+ *           8  u32      version = 1
+ *          12 .. 95     as version 1 of "FHELINEK" (n_keys, parameters, bootstrapping, data_offset, reserved)
+ *          96  u8[32]   the key-set seed
+ *         128  u64[n_q + n_p]  the moduli, then the key table (40-byte entries, as version 1)
+ *   data_offset = (end of the key table) rounded up to a multiple of 4096.  An entry's `words` counts what is stored: the b halves
+ *   only, [digits][n_q + n_p][N] for a switching key (digit j's b half, then digit j + 1's) and [n_q][N] for the public key.  Its
+ *   `digest` is the version 1 digest of the FULL key (b and the expanded a, in version 1 storage order): the loader expands every
+ *   a before it digests, so a wrong seed, Galois element or expansion fails the digest, and a compact set's digests equal those
+ *   of the version 1 set of the same keys. */
+/* on: fhelin_keygen draws a key-set seed and every key the context makes afterwards is seeded (its a half made on the device from
+ * the seed, no host sampling).  Call before fhelin_keygen: after keygen, or once the context holds any key, FHELIN_ERR_STATE; on an
+ * evaluation context FHELIN_ERR_KEY.  Off (the default): key generation consumes the generator exactly as without this mode. */
+int fhelin_ctx_set_seeded_keys(fhelin_ctx* c, int32_t on);
+/* the public key-set seed (32 bytes); FHELIN_ERR_STATE when the keys are not seeded.  Works on a context loaded from a compact set. */
+int fhelin_ctx_key_set_seed(const fhelin_ctx* c, uint8_t* out32);
+/* write every key the context holds as a compact set.  FHELIN_ERR_KEY when it holds none; FHELIN_ERR_STATE, naming the key, when any
+ * key it holds is not seeded (made outside seeded-key mode, or installed with fhelin_key_import).  A context loaded from a compact
+ * set writes the identical bytes.  fhelin_evalkeys_save still writes version 1 (full keys) for every context.
+ * fhelin_evalkeys_params, _info and _load read both formats; loading a compact set streams the b halves, expands every a half in
+ * one launch, digests and installs as version 1 does (all or nothing). */
+int fhelin_evalkeys_save_compact(fhelin_ctx* c, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
