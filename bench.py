@@ -16,13 +16,19 @@ chain: depth 27 = 28 Q limbs, and the 7 special limbs OpenFHE's HYBRID rule give
 Sharding: independent samples, one per GPU per step (weak scaling), keys replicated, no data-path collective;
 one RCCL all_gather of the logits at the end.
 
-The same run also measures the second headline metric, limb-NTT/s at N=2^16 (fwd+inv NTT of 8 ciphertexts x
+A plain run does only what `value` needs: set-up (keys, the recorded level plan, the resident inputs), the warm-up and
+timed steps, `--dump-outputs`, the result line.  Everything else it can measure or check runs with `--full`: the
+circuit-oracle check of every timed sample, the other cells of `ms_per_sample_cells`, several samples per pass, the
+pass at the reference's ring N=2^15, samples in flight (`--inflight`), the client-ingest figures, the NTT section and
+`roofline`, the short op section and the CPU baseline.
+
+With `--full` the run also measures the second headline metric, limb-NTT/s at N=2^16 (fwd+inv NTT of 8 ciphertexts x
 2 x 24 limbs), which is where `roofline` (dominant kernel = the NTT tile passes) comes from.
-`--workload ntt` runs only that part (value = limb-NTT/s).
-`--workload ops` (and, in short form, every default run under the key "ops") times the leaf operations of SURVEY.md
+`--workload ntt` runs only that part (value = limb-NTT/s; `--full` adds the other batch sizes and the CPU baseline).
+`--workload ops` (and, in short form, every `--full` forward run under the key "ops") times the leaf operations of SURVEY.md
 §8(d) at fixed shapes (N=2^16, 24+6 limbs, batch 8, ell in {24,16,8}): ct x pt, rescale, rotate, mult+relin, the merged
 rotate-sum, rotsum(128,128), one matmulRE row and 128 batched rows — HIP-event time, algorithmic bytes by the §8(d)
-formulas and the resulting fraction of the HBM roofline per op.
+formulas and the resulting fraction of the HBM roofline per op (`--full` adds the NTT section and `roofline`).
 
 Multi-GPU: every rank creates the SAME keys (one key seed, checked by an all-gather of a key checksum) — keys are
 replicated, samples are sharded.  Default: one sample per GPU per step (weak scaling).  `--batch B`: a step is a batch of
@@ -71,8 +77,11 @@ def parse():
                     "is built with (reported as ms_per_sample_at_the_reference_ring_n15; `value` stays BASELINE's N=2^16)")
     ap.add_argument("--inflight", type=int, default=0, help="after the timed region (one sample in flight: `value`), also measure the "
                     "throughput with this many samples in flight on the GPU, one engine (context, stream, host thread) each; 0/1: skip")
-    ap.add_argument("--forward-only", action="store_true", help="profiling runs: only the timed forward passes (no eager comparison, "
-                    "no NTT / op sections, no CPU leg); prints a reduced line without `roofline`")
+    ap.add_argument("--full", action="store_true", help="besides `value`, everything else the benchmark measures or checks: the "
+                    "circuit-oracle check of every timed sample, the other ms_per_sample_cells, --throughput-batch, the N=2^15 ring, "
+                    "--inflight, the client-ingest figures, the NTT section + roofline, the op section, the CPU baseline (a plain run: `value` only)")
+    ap.add_argument("--forward-only", action="store_true", help="profiling runs: only the timed forward passes and the circuit-oracle "
+                    "check (no eager comparison, no NTT / op sections, no CPU leg); prints a reduced line without `roofline`")
     ap.add_argument("--key-seed", type=int, default=2024, help="deterministic key seed, the same on every rank (replicated keys)")
     ap.add_argument("--tokens", type=int, default=129, help="tokens per sample (S); S+1 rows incl. CLS, 128 < S+1 <= 256")
     ap.add_argument("--log-n", type=int, default=16)
@@ -101,6 +110,10 @@ def parse():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.workload != "forward" or args.micro):
         ap.error("--dump-outputs needs the forward workload")
+    if args.full and args.forward_only:
+        ap.error("--full and --forward-only exclude each other")
+    if args.inflight > 1 and not args.full:
+        ap.error("--inflight is a section of --full runs")
     return args
 
 
@@ -207,6 +220,35 @@ def ntt_section(eng, orc, np, batch, steps, warmup=3):
     assert np.array_equal(back, host), "INTT(NTT(x)) != x after the timed NTT region"
     buf.free()
     return 2 * nvec * steps, ms, one, nq
+
+
+def ntt_roofline(eng, n_ntt, ntt_ms, by_batch):
+    """`roofline` of the NTT section: the dominant kernel's algorithmic bytes per second against the HBM peak"""
+    alg_bytes = 16.0 * eng.N                            # SURVEY §8(d): read N + write N u64 per limb-NTT
+    achieved = n_ntt * alg_bytes / (ntt_ms * 1e-3) / 1e9
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "r04_pmc_traffic.json")   # PMC passes of this round's kernels (tools/profile_kernels.sh)
+    by_counters = None
+    if os.path.exists(tpath) and eng.log_n == 16:     # the counters were collected at N=2^16
+        try:
+            traffic = json.load(open(tpath)).get("ntt_bytes_per_limb_transform")
+            # what the HBM counters say the transforms move per second at the rate measured in THIS run (two tile passes, each reading
+            # and writing its vectors once: twice the algorithmic bytes), as a fraction of the peak
+            by_counters = round(traffic * n_ntt / (ntt_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+        except Exception:
+            traffic = None
+    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "frac_of_peak_by_counter_traffic": by_counters,
+                "kernel": "ntt_cols_kernel + ntt_rows_kernel (one limb-NTT = one tile pass of each)",
+                "limb_ntt_per_s_per_gpu": round(n_ntt / (ntt_ms * 1e-3), 1),
+                "limb_ntt_per_s_by_batch_of_ciphertexts": by_batch,
+                "algorithmic_bytes_per_limb_ntt": alg_bytes,
+                "traffic_source": "profiles/r04_pmc_traffic.json: rocprofv3 FETCH_SIZE x2 + WRITE_SIZE per launch / 768 limb vectors, measured in "
+                                  "round 4 on these kernels in separate --pmc passes (a static file: the bench run itself does not collect counters)",
+                "note": "64-bit modular-integer butterflies: bound by VALU issue slots (92 % busy; 14 instr per forward / 15 per inverse butterfly, "
+                        "9 of them 32x32 multiplies); 100 % VALU utilisation at the sustained 1.6 GHz would be 2.5 M limb-NTT/s = 0.31 of the HBM roofline "
+                        "(instruction-count bound in DESIGN.md 6b)"}
+    return roofline
 
 
 def cpu_ntt_baseline(eng, orc, np, one, nq, seconds, cores):
@@ -569,7 +611,9 @@ def main():
                        "hipMalloc_ms_per_sample": round(st["pool_malloc_ns"] / 1e6 / max(1, n_samples), 2),
                        "synthetic_token_generation_ms_per_sample": round(t_prep * 1e3 / max(1, n_samples), 2)}
         # the same ingestion into memory the pool already owns (a server that releases a sample's inputs when it is done):
-        # one extra sample encrypted and dropped, then timed three times
+        # one extra sample encrypted and dropped, then timed three times.  Every run does these (the figure is reported with
+        # --full): their encryptions advance the engine's random stream, which the passes' own fresh encryptions continue,
+        # so the timed steps' outputs depend on them
         def ingest_once():
             xs = pf.synthetic_tokens(S, 777)
             if use_plan:
@@ -642,29 +686,31 @@ def main():
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, np, logits=logits[-per_rank:], slots=list(last_slots))
         # parity of the timed path: EVERY timed sample vs the same op sequence in the clear (oracle/circuit_sim.py),
-        # after the timed region
-        err, err_sum = 0.0, 0.0
+        # after the timed region (--full, --forward-only)
+        err, err_sum = float("nan"), float("nan")
         assert len(timed_inputs) == len(logits) == n_timed
-        oracle_cache = {}
-        for x_i, lg in zip(timed_inputs, logits):
-            if id(x_i) not in oracle_cache:                    # a set that the steps cycled through more than once: one oracle pass
-                oracle_cache[id(x_i)] = lf.logits_from_slots(lf.forward(cs.SlotSimController(), w, *pf.client_inputs(w, x_i), None, args.variant))
-            ref = oracle_cache[id(x_i)]
-            e_i = float(np.max(np.abs(lg - ref)))
-            top2 = np.sort(ref)[-2:]
-            decided = (top2[1] - top2[0]) > 4e-2       # arg-max is only meaningful when the oracle's margin exceeds the tolerance
-            assert e_i < 2e-2, f"encrypted logits differ from the circuit oracle ({e_i})"
-            assert not decided or int(np.argmax(lg)) == int(np.argmax(ref)), "encrypted prediction differs from the circuit oracle"
-            err = max(err, e_i)
-            err_sum += e_i
+        if args.full or args.forward_only:
+            err, err_sum = 0.0, 0.0
+            oracle_cache = {}
+            for x_i, lg in zip(timed_inputs, logits):
+                if id(x_i) not in oracle_cache:                    # a set that the steps cycled through more than once: one oracle pass
+                    oracle_cache[id(x_i)] = lf.logits_from_slots(lf.forward(cs.SlotSimController(), w, *pf.client_inputs(w, x_i), None, args.variant))
+                ref = oracle_cache[id(x_i)]
+                e_i = float(np.max(np.abs(lg - ref)))
+                top2 = np.sort(ref)[-2:]
+                decided = (top2[1] - top2[0]) > 4e-2       # arg-max is only meaningful when the oracle's margin exceeds the tolerance
+                assert e_i < 2e-2, f"encrypted logits differ from the circuit oracle ({e_i})"
+                assert not decided or int(np.argmax(lg)) == int(np.argmax(ref)), "encrypted prediction differs from the circuit oracle"
+                err = max(err, e_i)
+                err_sum += e_i
         # the same pass with deferred rows OFF (every row of every batched call evaluated, read or not), outside the timed
         # region, for the record: the reference's CLS-only driver computes 129 query projections and 129 final token
         # expansions that nothing reads (src/main.cpp:183,:196,:416-424)
         eager_ms = float("nan")
         unplanned_ms = float("nan")
         literal_ms = float("nan")
-        if not args.forward_only:
-            leg_pool = {}
+        leg_pool = {}
+        if args.full:
 
             def timed_passes(fn, n=2, name=""):
                 for _ in range(3):                             # untimed: plaintext caches of this variant, and the device arena grown to
@@ -699,7 +745,7 @@ def main():
                 del enc_full
             else:
                 unplanned_ms, literal_ms = elapsed * 1e3 / (n_timed * (1 if row_mode else world)), eager_ms
-        else:
+        elif args.forward_only:
             if rank == 0:
                 print(json.dumps({"metric": "encrypted Linformer-d128 forward ms/sample (profiling run)",
                                   "value": round(elapsed * 1e3 / (n_timed * world), 2), "unit": "ms/sample", "n_gpus": world,
@@ -722,7 +768,7 @@ def main():
         # ---- secondary figure: B samples per pass through the SAME engine (BASELINE config 4's per-GPU unit; `value` above stays one sample per pass)
         fwd["tb"] = None
         Bt = args.throughput_batch
-        if Bt > 1 and world == 1 and not row_mode and not batched:
+        if args.full and Bt > 1 and world == 1 and not row_mode and not batched:
             eng.trim()
             t_lanes = 2 if Bt % 2 == 0 else 1                 # two sub-batches on two lanes (streams) of the one context
             tctl = lf.LanedBatchedController(eng, Bt, t_lanes) if t_lanes > 1 else lf.BatchedController(eng, Bt)
@@ -776,7 +822,7 @@ def main():
         # ---- the same pass at the ring the reference is BUILT with (src/FHEController.cpp:12-13: SetRingDim(1 << 15), 16384 slots = full packing;
         # BASELINE.json quotes N=2^16, which is `value`): a second engine, its own keys and level plan, a few passes after the timed region
         fwd["n15"] = None
-        if args.reference_ring and world == 1 and not row_mode and not batched and args.log_n == 16:
+        if args.full and args.reference_ring and world == 1 and not row_mode and not batched and args.log_n == 16:
             eng.trim()
             e15 = fa.Engine("bench", device=local_rank, seed=args.key_seed, log_n=15, n_q=n_q, n_p=n_p, special_bits=args.special_bits)
             e15.keygen()
@@ -823,22 +869,24 @@ def main():
             e15.close()
         # ---- K samples in flight on the one GPU, one engine EACH (replicated keys; off by default since round 4: the batched pass above shares one key set)
         fwd["inflight"] = None
-        if args.inflight > 1 and world == 1 and not row_mode:
+        if args.full and args.inflight > 1 and world == 1 and not row_mode:
             fwd["inflight"] = inflight_section(fa, lf, pf, np, eng, ctl, w, S, args, use_plan, n_client_sources, plan)
 
-    # ---- NTT section (second headline metric + roofline of the dominant kernel) -------------------------
-    if dist:
-        dist.barrier()
-    t0 = time.perf_counter()
-    n_ntt, ntt_ms, one, nq = ntt_section(eng, orc, np, args.ntt_batch, args.ntt_steps)
-    torch.cuda.synchronize()
-    ntt_elapsed = time.perf_counter() - t0
-    if dist:
-        ntt_ms = shard.max_over_ranks(dist, ntt_ms)
-    ntt_rate = n_ntt * world / (ntt_ms * 1e-3)
+    # ---- NTT section (second headline metric + roofline of the dominant kernel): --full, or the ntt workload's `value` ----
+    ntt_run = args.full or args.workload == "ntt"
+    if ntt_run:
+        if dist:
+            dist.barrier()
+        t0 = time.perf_counter()
+        n_ntt, ntt_ms, one, nq = ntt_section(eng, orc, np, args.ntt_batch, args.ntt_steps)
+        torch.cuda.synchronize()
+        ntt_elapsed = time.perf_counter() - t0
+        if dist:
+            ntt_ms = shard.max_over_ranks(dist, ntt_ms)
+        ntt_rate = n_ntt * world / (ntt_ms * 1e-3)
 
     ops = None
-    if rank == 0 and (args.workload == "ops" or (args.workload == "forward" and not args.no_ops and args.log_n == 16)):
+    if rank == 0 and (args.workload == "ops" or (args.full and args.workload == "forward" and not args.no_ops and args.log_n == 16)):
         full = args.workload == "ops"
         oe = eng
         if args.workload != "ops":
@@ -852,7 +900,7 @@ def main():
             oe.close()
 
     by_batch = None
-    if rank == 0 and args.ntt_batch == 8:
+    if rank == 0 and args.full and args.ntt_batch == 8:
         # SURVEY 8(d)'s other two batch sizes (one ciphertext; 64), outside the timed regions: the same section, fewer steps
         by_batch = {"8": round(n_ntt / (ntt_ms * 1e-3), 1)}
         for bsz, st in ((1, 30), (64, 4)):
@@ -860,30 +908,7 @@ def main():
             by_batch[str(bsz)] = round(nb / (msb * 1e-3), 1)
 
     if rank == 0:
-        alg_bytes = 16.0 * eng.N                            # read N + write N u64 per limb-NTT
-        achieved = n_ntt * alg_bytes / (ntt_ms * 1e-3) / 1e9
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "r04_pmc_traffic.json")   # PMC passes of this round's kernels (tools/profile_kernels.sh)
-        by_counters = None
-        if os.path.exists(tpath) and eng.log_n == 16:     # the counters were collected at N=2^16
-            try:
-                traffic = json.load(open(tpath)).get("ntt_bytes_per_limb_transform")
-                # what the HBM counters say the transforms move per second at the rate measured in THIS run (two tile passes, each reading
-                # and writing its vectors once: twice the algorithmic bytes), as a fraction of the peak
-                by_counters = round(traffic * n_ntt / (ntt_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-            except Exception:
-                traffic = None
-        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "frac_of_peak_by_counter_traffic": by_counters,
-                    "kernel": "ntt_cols_kernel + ntt_rows_kernel (one limb-NTT = one tile pass of each)",
-                    "limb_ntt_per_s_per_gpu": round(n_ntt / (ntt_ms * 1e-3), 1),
-                    "limb_ntt_per_s_by_batch_of_ciphertexts": by_batch,
-                    "algorithmic_bytes_per_limb_ntt": alg_bytes,
-                    "traffic_source": "profiles/r04_pmc_traffic.json: rocprofv3 FETCH_SIZE x2 + WRITE_SIZE per launch / 768 limb vectors, measured in "
-                                      "round 4 on these kernels in separate --pmc passes (a static file: the bench run itself does not collect counters)",
-                    "note": "64-bit modular-integer butterflies: bound by VALU issue slots (92 % busy; 14 instr per forward / 15 per inverse butterfly, "
-                            "9 of them 32x32 multiplies); 100 % VALU utilisation at the sustained 1.6 GHz would be 2.5 M limb-NTT/s = 0.31 of the HBM roofline "
-                            "(instruction-count bound in DESIGN.md 6b)"}
+        roofline = ntt_roofline(eng, n_ntt, ntt_ms, by_batch) if ntt_run else None
         if args.workload == "forward":
             value = fwd["elapsed"] * 1e3 / (args.steps * per_rank * (1 if row_mode else world))
             line = {
@@ -894,7 +919,7 @@ def main():
                 "vs_baseline": None, "dtype": "u64", "data": "synthetic",
                 "config": {"workload": f"forward ({'src/main.cpp' if args.variant == 'main' else 'src/main_2.cpp'} call sequence): {per_rank} sample(s)/GPU/step, S={args.tokens}+CLS tokens, d=128, k=32, FFN 512, 20 classes, "
                                        f"N=2^{eng.log_n}, 16384 slots, {eng.n_q}+{eng.n_p} limbs, dnum 4, {fwd['stats']['bootstrap']} bootstraps; "
-                                       f"deferred rows on, level plan {'on' if fwd['plan'] else 'off'} (ms_per_sample_cells has the other three combinations)",
+                                       f"deferred rows on, level plan {'on' if fwd['plan'] else 'off'} (with --full, ms_per_sample_cells has the other three combinations)",
                            "ops_per_sample": fwd["stats"],
                            "parallelism": (f"ONE sample per step, rows of its matmul / unwrap loops over {world} ranks, keys replicated"
                                            if row_mode else f"independent samples x{world}, keys replicated (one key seed)"),
@@ -906,61 +931,67 @@ def main():
                                                      "tests/test_batched_forward_gpu.py)" if fwd["batched"] else "one sample per pass"),
                            "distinct_input_sets_in_the_timed_region": fwd["n_sets"],
                            "device_pool": fwd["pool"],
-                           "device_pool_in_the_other_cells": fwd["leg_pool"],
                            "host_issue_ms_per_sample": round(fwd["host_enqueue_ms"], 2),
-                           "logit_err_vs_circuit_oracle": round(fwd["logit_err_vs_circuit_oracle"], 5),
-                           "logit_err_vs_circuit_oracle_mean": round(fwd["logit_err_mean"], 5),
-                           "logit_err_tolerance": 2e-2,
-                           # flat copies of ms_per_sample_cells (nested objects do not survive into the driver's parsed record)
-                           "ms_per_sample_rows_eager_plan_on": round(fwd["eager_ms"], 2),
-                           "ms_per_sample_rows_deferred_plan_off": round(fwd["unplanned_ms"], 2),
-                           "ms_per_sample_literal": round(fwd["literal_ms"], 2),
-                           "samples_checked_vs_circuit_oracle": fwd["samples_checked"],
                            "deferred_rows": "on: rows of matmulRE / unwrapExpanded / matmulRElarge are evaluated when read - rows no later call "
                                             "reads never; rows of matmulRElarge that generate_containers takes unread go through the fused "
                                             "container sum (DESIGN.md 7g: same slot values, checked bit for bit against the oracle's restatement); "
                                             "ops_per_sample counts what was executed",
-                           "ms_per_sample_with_every_row_evaluated": round(fwd["eager_ms"], 2),
                            "level_plan": ("off" if not fwd["plan"] else
                                           "on: one untimed pass of the same driver was recorded; fresh encryptions and bootstrap outputs start with "
-                                          "the limbs their consumers read (values unchanged up to noise; every timed sample is checked)"),
+                                          "the limbs their consumers read (values unchanged up to noise; a --full run checks every timed sample)"),
                            "level_plan_limbs_per_source": ({} if not fwd["plan"] else {
                                "client_encryptions": {str(k): fwd["plan"][:fwd["n_client_sources"]].count(k)
                                                       for k in sorted(set(fwd["plan"][:fwd["n_client_sources"]]))},
                                "server_sources_in_call_order": fwd["plan"][fwd["n_client_sources"]:]}),
-                           "ms_per_sample_without_level_plan": round(fwd["unplanned_ms"], 2),
-                           # the 2 x 2 of the two driver-level optimisations; `value` is the first cell
-                           "ms_per_sample_cells": {
-                               "value_is": "deferred_rows=on, level_plan=" + ("on" if fwd["plan"] else "off"),
-                               "deferred_rows=on,level_plan=on": round(value, 2) if fwd["plan"] else None,
-                               "deferred_rows=off,level_plan=on": round(fwd["eager_ms"], 2) if fwd["plan"] else None,
-                               "deferred_rows=on,level_plan=off": round(fwd["unplanned_ms"], 2),
-                               "deferred_rows=off,level_plan=off (every call of the reference's driver evaluated in full where it is made, at the driver's own levels)": round(fwd["literal_ms"], 2),
-                               "how": "value: the timed region (steps x passes, max over ranks); the other cells: 2 passes each after one untimed "
-                                      "pass, same build, same process, after the timed region"},
-                           "ms_per_sample_with_4_samples_per_pass": (fwd["tb"] or {}).get("ms_per_sample") if (fwd["tb"] or {}).get("samples_per_pass") == 4 else None,
-                           "throughput_with_several_samples_per_pass": fwd["tb"],
-                           "ms_per_sample_at_the_reference_ring_n15": (fwd["n15"] or {}).get("ms_per_sample"),
-                           "pass_at_the_reference_ring_n15": fwd["n15"],
-                           "throughput_with_samples_in_flight": fwd["inflight"],
-                           "client_ingest_ms_per_sample": round(fwd["client_ms"], 2),
-                           "client_ingest_note": "fhelin_client_ingest: positional embedding, the two Linformer projections, packing, encoding and encryption of the sample's "
-                                                 "194 inputs on the device, into pool-owned memory (3 timed repeats); "
-                                                 "first-touch figure below = the same while the pool grows through hipMalloc because "
-                                                 "every sample of the run stays resident",
-                           "client_ingest_first_touch_ms_per_sample": round(fwd["client_first_ms"], 2),
-                           "client_ingest_first_touch_pool_growth": fwd["client_pool"]},
-                "ntt": {"metric": f"NTT/s at N=2^{eng.log_n}", "value": round(ntt_rate, 1), "unit": "limb-NTT/s",
-                        "workload": f"fwd+inv NTT of {args.ntt_batch} ciphertexts x 2 polys x {nq} limbs per GPU"},
-                "roofline": roofline,
+                           "sections": ("full" if args.full else "value only (--full adds the circuit-oracle check, the other ms_per_sample_cells, "
+                                        "several samples per pass, the N=2^15 ring, the client-ingest figures, the NTT section + roofline, the op section, "
+                                        "the CPU baseline)")},
             }
+            if args.full:
+                line["config"].update({
+                    "device_pool_in_the_other_cells": fwd["leg_pool"],
+                    "logit_err_vs_circuit_oracle": round(fwd["logit_err_vs_circuit_oracle"], 5),
+                    "logit_err_vs_circuit_oracle_mean": round(fwd["logit_err_mean"], 5),
+                    "logit_err_tolerance": 2e-2,
+                    # flat copies of ms_per_sample_cells (for readers of the line that keep only its flat fields)
+                    "ms_per_sample_rows_eager_plan_on": round(fwd["eager_ms"], 2),
+                    "ms_per_sample_rows_deferred_plan_off": round(fwd["unplanned_ms"], 2),
+                    "ms_per_sample_literal": round(fwd["literal_ms"], 2),
+                    "samples_checked_vs_circuit_oracle": fwd["samples_checked"],
+                    "ms_per_sample_with_every_row_evaluated": round(fwd["eager_ms"], 2),
+                    "ms_per_sample_without_level_plan": round(fwd["unplanned_ms"], 2),
+                    # the 2 x 2 of the two driver-level optimisations; `value` is the first cell
+                    "ms_per_sample_cells": {
+                        "value_is": "deferred_rows=on, level_plan=" + ("on" if fwd["plan"] else "off"),
+                        "deferred_rows=on,level_plan=on": round(value, 2) if fwd["plan"] else None,
+                        "deferred_rows=off,level_plan=on": round(fwd["eager_ms"], 2) if fwd["plan"] else None,
+                        "deferred_rows=on,level_plan=off": round(fwd["unplanned_ms"], 2),
+                        "deferred_rows=off,level_plan=off (every call of the reference's driver evaluated in full where it is made, at the driver's own levels)": round(fwd["literal_ms"], 2),
+                        "how": "value: the timed region (steps x passes, max over ranks); the other cells: 2 passes each after one untimed "
+                               "pass, same build, same process, after the timed region"},
+                    "ms_per_sample_with_4_samples_per_pass": (fwd["tb"] or {}).get("ms_per_sample") if (fwd["tb"] or {}).get("samples_per_pass") == 4 else None,
+                    "throughput_with_several_samples_per_pass": fwd["tb"],
+                    "ms_per_sample_at_the_reference_ring_n15": (fwd["n15"] or {}).get("ms_per_sample"),
+                    "pass_at_the_reference_ring_n15": fwd["n15"],
+                    "throughput_with_samples_in_flight": fwd["inflight"],
+                    "client_ingest_ms_per_sample": round(fwd["client_ms"], 2),
+                    "client_ingest_note": "fhelin_client_ingest: positional embedding, the two Linformer projections, packing, encoding and encryption of the sample's "
+                                          "194 inputs on the device, into pool-owned memory (3 timed repeats); "
+                                          "first-touch figure below = the same while the pool grows through hipMalloc because "
+                                          "every sample of the run stays resident",
+                    "client_ingest_first_touch_ms_per_sample": round(fwd["client_first_ms"], 2),
+                    "client_ingest_first_touch_pool_growth": fwd["client_pool"]})
+                line["ntt"] = {"metric": f"NTT/s at N=2^{eng.log_n}", "value": round(ntt_rate, 1), "unit": "limb-NTT/s",
+                               "workload": f"fwd+inv NTT of {args.ntt_batch} ciphertexts x 2 polys x {nq} limbs per GPU"}
+                line["roofline"] = roofline
         elif args.workload == "ops":
             best = max(ops, key=lambda r: r["frac"])
             line = {"metric": "leaf operations at N=2^16, 24+6 limbs (SURVEY 8(d))", "value": best["GBps"], "unit": "GB/s (best op, algorithmic)",
                     "n_gpus": world, "steps": 10, "warmup": 2, "ms_per_step": None, "higher_is_better": True, "scaling": "weak",
                     "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-                    "config": {"workload": "ops: ct x pt, ct + ct, rescale, rotate, mult+relin, merged rotate-sum, rotsum(128,128), matmulRE row / 128 rows; batch 8; ell 24/16/8"},
-                    "roofline": roofline}
+                    "config": {"workload": "ops: ct x pt, ct + ct, rescale, rotate, mult+relin, merged rotate-sum, rotsum(128,128), matmulRE row / 128 rows; batch 8; ell 24/16/8"}}
+            if roofline is not None:
+                line["roofline"] = roofline
         else:
             line = {
                 "metric": f"NTT/s at N=2^{eng.log_n} (limb-NTTs per second)", "value": round(ntt_rate, 1), "unit": "limb-NTT/s",
@@ -970,7 +1001,7 @@ def main():
                            "parallelism": f"independent ciphertexts x{world}"},
                 "roofline": roofline,
             }
-        if not args.no_cpu_baseline and world == 1 and args.workload != "ops":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload != "ops":
             if args.workload == "forward":
                 res = cpu_forward_baseline(eng, orc, np, fwd["stats"], args.cpu_seconds, cores)
                 ms_all, detail = res["all"]
