@@ -216,6 +216,10 @@ def load_library():
         "fhelin_compact_info": (i32, [vp, C.c_size_t, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "fhelin_ct_import_compact": (i32, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), i32, C.POINTER(vp)]),
         "fhelin_debug_seeded_expand": (i32, [vp, vp, C.c_uint64, i32, i32, i32, vp, f32p]),
+        "fhelin_client_ingest_wrapped": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(vp),
+                                               C.POINTER(i32), vp]),
+        "fhelin_wrapped_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, i32]),
+        "fhelin_unwrap_inputs": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -607,6 +611,45 @@ class Engine:
         if want_proj:
             res["x_in"], res["proj"] = proj[:S + 1], proj[S + 1:]
         return res
+
+    def client_ingest_wrapped(self, cls, pos, E_w, E_b, F_w, F_b, emb=None, tokens=None, table=None, level=0, targets=None, want_proj=False):
+        """client_ingest's sample as wrapped ciphertexts (include/fhelin.h "Wrapped inputs"): a list of wrapped handles (<= 128 inputs
+        each); targets [64 + S + 1] (optional): limbs per input.  want_proj: (handles, x_in, proj)"""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        cls, pos, E_w, E_b, F_w, F_b = f(cls), f(pos), f(E_w), f(E_b), f(F_w), f(F_b)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        if emb is not None:
+            emb = f(emb)
+            S, tok, tab, vocab = emb.shape[0], None, None, 0
+        else:
+            tok = np.ascontiguousarray(tokens, dtype=np.int32)
+            tab = f(table)
+            S, vocab = tok.shape[0], tab.shape[0]
+        if pos.shape[0] < S or pos.shape[1] != 128 or E_w.shape != F_w.shape or E_w.shape[0] != 32 or E_w.shape[1] < S + 1 or cls.size != 128 \
+                or E_b.size != 32 or F_b.size != 32:
+            raise FhelinError(1, "client_ingest_wrapped: pos needs >= S rows of 128, E_w / F_w [32][>= S + 1], E_b / F_b [32], cls [128]")
+        n = 64 + S + 1
+        tg = None
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32)
+            if tg.size != n:
+                raise FhelinError(1, "client_ingest_wrapped: one target per input")
+        outs = self._outs(n)
+        n_out = C.c_int32()
+        proj = np.empty((S + 1 + 64, 128)) if want_proj else None
+        self._ck(self.lib.fhelin_client_ingest_wrapped(self.h, p(emb), p(tok), p(tab), vocab, S, p(cls), p(pos), p(E_w), p(E_b), p(F_w),
+                                                       p(F_b), E_w.shape[1], level, p(tg), outs, C.byref(n_out), p(proj)))
+        cts = self._cts(outs, n_out.value)
+        return (cts, proj[:S + 1], proj[S + 1:]) if want_proj else cts
+
+    def unwrap_inputs(self, wrapped):
+        """wrapped handles of one or more samples -> their expanded inputs, sample by sample in read order"""
+        ws = list(wrapped)
+        total = sum(w.wrapped_info()["count"] for w in ws)
+        arr = (C.c_void_p * max(len(ws), 1))(*[w.h for w in ws])
+        outs = self._outs(total)
+        self._ck(self.lib.fhelin_unwrap_inputs(self.h, arr, len(ws), outs))
+        return self._cts(outs, total)
 
     def set_host_encode(self, on):
         self._ck(self.lib.fhelin_ctx_set_host_encode(self.h, 1 if on else 0))
@@ -1075,6 +1118,13 @@ class Ct:
         hi, lo = C.c_double(), C.c_double()
         self.eng._ck(self.eng.lib.fhelin_ct_scale(self.h, C.byref(hi), C.byref(lo)))
         return hi.value, lo.value
+
+    def wrapped_info(self):
+        """a wrapped input ciphertext: dict(count, total, ell = the inputs' limbs, positions)"""
+        i = [C.c_int32() for _ in range(3)]
+        pos = np.zeros(128, dtype=np.int32)
+        self.eng._ck(self.eng.lib.fhelin_wrapped_info(self.h, C.byref(i[0]), C.byref(i[1]), C.byref(i[2]), pos.ctypes.data_as(C.c_void_p), 128))
+        return dict(count=i[0].value, total=i[1].value, ell=i[2].value, positions=pos[:i[0].value].tolist())
 
     def compact_bytes(self):
         n = C.c_size_t()

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <vector>
 #include "capi_internal.h"
 #include "kernels_keys.h"
 #include "kernels_seeded.h"
@@ -21,7 +22,9 @@ namespace {
 
 constexpr char CC_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'C', 'C'};
 constexpr uint32_t CC_VERSION = 1;
-constexpr size_t CC_FIXED = 96;   // header bytes before the moduli
+constexpr uint32_t CC_VERSION_WRAPPED = 2;   // a wrapped input (include/fhelin.h "Wrapped inputs")
+constexpr size_t CC_FIXED = 96;   // header bytes before the moduli (version 1)
+constexpr size_t CC_FIXED_WRAPPED = 104;     // version 2: + count, total
 
 struct CcHeader {
     int32_t log_n = 0, ell = 0, deg = 0, slots = 0;
@@ -30,6 +33,9 @@ struct CcHeader {
     uint8_t seed[32] = {};
     const uint64_t* moduli = nullptr;   // [ell], inside the blob (may be unaligned: read with memcpy)
     const uint8_t* c0 = nullptr;        // [ell][N] u64, inside the blob
+    uint32_t version = 1;
+    int32_t count = 0, total = 0;       // version 2
+    std::vector<int> pos;               // version 2: the inputs' positions, [count]
 };
 
 template <class T> T get(const uint8_t* b, size_t off) {
@@ -40,14 +46,19 @@ template <class T> T get(const uint8_t* b, size_t off) {
 template <class T> void put(uint8_t* b, size_t off, T v) { std::memcpy(b + off, &v, sizeof(T)); }
 
 size_t cc_bytes(int log_n, int ell) { return CC_FIXED + 8 * (size_t)ell + 8 * (size_t)ell * ((size_t)1 << log_n); }
+size_t cc_header_wrapped(int ell, int count) { return CC_FIXED_WRAPPED + 8 * (size_t)ell + 8 * (((size_t)count + 1) / 2); }
+size_t cc_bytes_wrapped(int log_n, int ell, int count) { return cc_header_wrapped(ell, count) + 8 * (size_t)ell * ((size_t)1 << log_n); }
 
 // every field validated against the others and against the blob's size; nothing about a context (host-only)
 CcHeader read_header(const uint8_t* b, size_t bytes) {
     if (!b) throw Error(FHELIN_ERR_ARG, "compact ciphertext: null blob");
     if (bytes < CC_FIXED) throw Error(FHELIN_ERR_ARG, "compact ciphertext: truncated header");
     if (std::memcmp(b, CC_MAGIC, 8) != 0) throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad magic");
-    if (get<uint32_t>(b, 8) != CC_VERSION) throw Error(FHELIN_ERR_ARG, "compact ciphertext: unsupported version");
+    const uint32_t version = get<uint32_t>(b, 8);
+    if (version != CC_VERSION && version != CC_VERSION_WRAPPED) throw Error(FHELIN_ERR_ARG, "compact ciphertext: unsupported version");
+    if (version == CC_VERSION_WRAPPED && bytes < CC_FIXED_WRAPPED) throw Error(FHELIN_ERR_ARG, "compact ciphertext: truncated header");
     CcHeader h;
+    h.version = version;
     h.log_n = get<int32_t>(b, 16);
     h.ell = get<int32_t>(b, 20);
     h.deg = get<int32_t>(b, 24);
@@ -58,15 +69,34 @@ CcHeader read_header(const uint8_t* b, size_t bytes) {
     std::memcpy(h.seed, b + 56, 32);
     h.digest = get<uint64_t>(b, 88);
     if (h.log_n < 12 || h.log_n > 17 || h.ell < 1 || h.ell > 64) throw Error(FHELIN_ERR_ARG, "compact ciphertext: ring dimension or limb count out of range");
-    if (get<uint32_t>(b, 12) != CC_FIXED + 8 * (uint32_t)h.ell) throw Error(FHELIN_ERR_ARG, "compact ciphertext: header size does not match the limb count");
-    if (bytes != cc_bytes(h.log_n, h.ell)) throw Error(FHELIN_ERR_ARG, "compact ciphertext: size does not match the header (truncated?)");
+    size_t head = CC_FIXED + 8 * (size_t)h.ell;
+    if (version == CC_VERSION_WRAPPED) {
+        h.count = get<int32_t>(b, 96);
+        h.total = get<int32_t>(b, 100);
+        if (h.ell < 2 || h.count < 1 || h.count > 128 || h.total < h.count || h.total > 65535)
+            throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad wrapped limb count, input count or total");
+        head = cc_header_wrapped(h.ell, h.count);
+    }
+    if (get<uint32_t>(b, 12) != head) throw Error(FHELIN_ERR_ARG, "compact ciphertext: header size does not match the limb count");
+    if (bytes != (version == CC_VERSION ? cc_bytes(h.log_n, h.ell) : cc_bytes_wrapped(h.log_n, h.ell, h.count)))
+        throw Error(FHELIN_ERR_ARG, "compact ciphertext: size does not match the header (truncated?)");
+    if (version == CC_VERSION_WRAPPED) {
+        const size_t at = CC_FIXED_WRAPPED + 8 * (size_t)h.ell;
+        for (int t = 0; t < h.count; ++t) {
+            const int32_t v = get<int32_t>(b, at + 4 * (size_t)t);
+            if (v < 0 || v >= h.total || (t && v <= h.pos.back())) throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad input positions");
+            h.pos.push_back(v);
+        }
+        for (size_t k = at + 4 * (size_t)h.count; k < head; ++k)
+            if (b[k]) throw Error(FHELIN_ERR_ARG, "compact ciphertext: nonzero padding");
+    }
     if (h.deg < 1 || h.deg > 2 || h.slots < 1 || (h.slots & (h.slots - 1)) || h.slots > (1 << (h.log_n - 1)))
         throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad degree or slot count");
     if (!(std::isfinite(h.scale_hi) && h.scale_hi > 0 && std::isfinite(h.scale_lo) && std::fabs(h.scale_lo) <= std::ldexp(h.scale_hi, -52)))
         throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad scale");
     if (h.digest >= KEY_DIGEST_P) throw Error(FHELIN_ERR_ARG, "compact ciphertext: bad digest field");
-    h.moduli = reinterpret_cast<const uint64_t*>(b + CC_FIXED);
-    h.c0 = b + CC_FIXED + 8 * (size_t)h.ell;
+    h.moduli = reinterpret_cast<const uint64_t*>(b + (version == CC_VERSION ? CC_FIXED : CC_FIXED_WRAPPED));
+    h.c0 = b + head;
     return h;
 }
 
@@ -85,7 +115,8 @@ int fhelin_ct_compact_bytes(const fhelin_ct* ct, size_t* bytes) {
     if (!ct || !bytes) return capi_fail(FHELIN_ERR_ARG, "null argument");
     // a deferred handle is an operation's result: never a seeded encryption
     if (!ct->p || !ct->p->seeded) return capi_fail(FHELIN_ERR_STATE, "compact form: only an unmodified seeded (secret-key) encryption has one");
-    *bytes = cc_bytes(ct->p->ctx->prm.log_n, ct->p->ell);
+    *bytes = ct->p->wrapped() ? cc_bytes_wrapped(ct->p->ctx->prm.log_n, ct->p->ell, (int)ct->p->wrap_pos.size())
+                              : cc_bytes(ct->p->ctx->prm.log_n, ct->p->ell);
     return FHELIN_OK;
 }
 
@@ -93,12 +124,14 @@ int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, s
     if (!c || !ct || !out) return capi_fail(FHELIN_ERR_ARG, "null argument");
     FHELIN_TRY
     if (!ct->p || !ct->p->seeded) throw Error(FHELIN_ERR_STATE, "compact form: only an unmodified seeded (secret-key) encryption has one");
-    if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
-    const CtPtr& p = ct_in(c, ct);
-    c->plan.check_terminal(*p, 2);
+    const bool wrapped = ct->p->wrapped();   // version 2; a wrapped input is not a value of the pass (no level-plan terminal)
+    if (!wrapped && c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
+    const CtPtr& p = wrapped ? ct->p : ct_in(c, ct);
+    if (!wrapped) c->plan.check_terminal(*p, 2);
     Context& x = c->ctx;
-    const int ell = p->ell;
-    const size_t N = x.N, bytes = cc_bytes(x.prm.log_n, ell);
+    const int ell = p->ell, count = (int)p->wrap_pos.size();
+    const size_t N = x.N, bytes = wrapped ? cc_bytes_wrapped(x.prm.log_n, ell, count) : cc_bytes(x.prm.log_n, ell);
+    const size_t head = wrapped ? cc_header_wrapped(ell, count) : CC_FIXED + 8 * (size_t)ell;
     if (cap < bytes) throw Error(FHELIN_ERR_ARG, "export_compact: buffer too small");
     if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "export_compact: ring dimension below 2^12");
     // c0's digest on the device, c0 itself straight into the blob; one synchronisation
@@ -108,7 +141,7 @@ int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, s
     hip_check(hipGetLastError(), "compact digest kernels");
     std::vector<u64> h(2 * (size_t)ell);
     hip_check(hipMemcpyAsync(h.data(), dg, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "compact digest download");
-    hip_check(hipMemcpyAsync(out + CC_FIXED + 8 * (size_t)ell, p->d, (size_t)ell * N * 8, hipMemcpyDeviceToHost, x.stream), "compact export");
+    hip_check(hipMemcpyAsync(out + head, p->d, (size_t)ell * N * 8, hipMemcpyDeviceToHost, x.stream), "compact export");
     hip_check(hipStreamSynchronize(x.stream), "compact export sync");
     x.pool.free(part);
     x.pool.free(dg);
@@ -118,8 +151,8 @@ int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, s
         acc += (u128)h[2 * j] * key_weight_vec((u32)j);
     }
     std::memcpy(out, CC_MAGIC, 8);
-    put<uint32_t>(out, 8, CC_VERSION);
-    put<uint32_t>(out, 12, (uint32_t)(CC_FIXED + 8 * ell));
+    put<uint32_t>(out, 8, wrapped ? CC_VERSION_WRAPPED : CC_VERSION);
+    put<uint32_t>(out, 12, (uint32_t)head);
     const int32_t shape[4] = {x.prm.log_n, ell, p->deg, p->slots};
     std::memcpy(out + 16, shape, sizeof(shape));
     const double hi = (double)p->scale, lo = (double)(p->scale - (long double)hi);   // as fhelin_ct_scale
@@ -128,7 +161,16 @@ int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, s
     put<uint64_t>(out, 48, p->nonce);
     std::memcpy(out + 56, p->seed, 32);
     put<uint64_t>(out, 88, (uint64_t)(acc % KEY_DIGEST_P));
-    std::memcpy(out + CC_FIXED, x.chain.q.data(), 8 * (size_t)ell);
+    if (!wrapped) {
+        std::memcpy(out + CC_FIXED, x.chain.q.data(), 8 * (size_t)ell);
+    } else {
+        put<int32_t>(out, 96, count);
+        put<int32_t>(out, 100, p->wrap_total);
+        std::memcpy(out + CC_FIXED_WRAPPED, x.moduli.data(), 8 * (size_t)ell);   // the first ell moduli of Q then P
+        const size_t at = CC_FIXED_WRAPPED + 8 * (size_t)ell;
+        std::memset(out + at, 0, head - at);
+        for (int t = 0; t < count; ++t) put<int32_t>(out, at + 4 * (size_t)t, p->wrap_pos[t]);
+    }
     FHELIN_CATCH
 }
 
@@ -158,8 +200,9 @@ int fhelin_ct_import_compact(fhelin_ctx* c, const uint8_t* const* blobs, const s
         const CcHeader& h = hs[i];
         const std::string at = "import_compact: blob " + std::to_string(i) + ": ";
         if (h.log_n != x.prm.log_n) throw Error(FHELIN_ERR_ARG, at + "made for another ring dimension");
-        if (h.ell > x.L + 1) throw Error(FHELIN_ERR_ARG, at + "more limbs than the context's chain");
-        if (std::memcmp(h.moduli, x.chain.q.data(), 8 * (size_t)h.ell) != 0) throw Error(FHELIN_ERR_ARG, at + "moduli do not match the context");
+        // version 2 (wrapped): ell <= n_q + 1, the first ell moduli of Q then P (the extra limb of an input at n_q limbs is p_0)
+        if (h.ell > x.L + 1 + (h.version == CC_VERSION_WRAPPED && x.K > 0 ? 1 : 0)) throw Error(FHELIN_ERR_ARG, at + "more limbs than the context's chain");
+        if (std::memcmp(h.moduli, x.moduli.data(), 8 * (size_t)h.ell) != 0) throw Error(FHELIN_ERR_ARG, at + "moduli do not match the context");
     }
     // 2. one batch allocation per limb count; c0 of every blob uploaded into its ciphertext
     std::map<int, std::vector<int>> groups;
@@ -181,6 +224,10 @@ int fhelin_ct_import_compact(fhelin_ctx* c, const uint8_t* const* blobs, const s
         ct.deg = h.deg;
         ct.slots = h.slots;
         ct.scale = (long double)h.scale_hi + (long double)h.scale_lo;
+        if (h.version == CC_VERSION_WRAPPED) {
+            ct.wrap_pos = h.pos;
+            ct.wrap_total = h.total;
+        }
         hip_check(hipMemcpyAsync(ct.d, h.c0, (size_t)h.ell * N * 8, hipMemcpyHostToDevice, x.stream), "compact upload");
         for (int w = 0; w < 8; ++w) tab[i].key.w[w] = get<uint32_t>(h.seed, 4 * w);
         tab[i].nonce = h.nonce;

@@ -186,6 +186,11 @@ int fhelin_decrypt(fhelin_ctx* c, const fhelin_ct* ct, double* out, int32_t slot
     NEED(c && ct && out);
     FHELIN_TRY
     if (c->cl.eval_only()) throw Error(FHELIN_ERR_KEY, "decrypt: an evaluation context holds no secret key");
+    if (ct->p && ct->p->wrapped()) {   // a wrapped input: its extra limb left out, the slots in the wrapped layout
+        auto v = c->cl.decrypt(ct->p, slots);
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+        return FHELIN_OK;
+    }
     if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
     c->plan.check_terminal(*ct_in(c, ct), 2);
     auto v = c->cl.decrypt(ct_in(c, ct), slots);
@@ -261,7 +266,7 @@ int fhelin_ct_info(const fhelin_ct* ct, int32_t* npoly, int32_t* ell, int32_t* l
     }
     if (npoly) *npoly = ct->p->npoly;
     if (ell) *ell = ct->p->ell;
-    if (level) *level = ct->p->level();
+    if (level) *level = ct->p->level() + (ct->p->wrapped() ? 1 : 0);   // a wrapped input: its inputs' level (ell counts the extra limb)
     if (deg) *deg = ct->p->deg;
     if (scale) *scale = (double)ct->p->scale;
     if (slots) *slots = ct->p->slots;

@@ -110,6 +110,10 @@ struct fhelin_ctx {
     hipEvent_t lane_mark[fhelin::DevicePool::MAX_LANES] = {};   // fhelin_ctx_lane_mark: a point in a lane's stream others can wait for
     bool lane_marked[fhelin::DevicePool::MAX_LANES] = {};
     fhelin::LevelPlan plan;
+    // the unwrap of wrapped inputs (capi_wrapped.cpp): the mask (1 in the slots = 0 mod 128) and the tables of a rescale that drops p_0
+    fhelin::PtPtr wrap_mask;
+    const fhelin::u64* p0_qlinv = nullptr;   // [n_q][2] p_0^-1 mod q_t, Shoup
+    const fhelin::u64* p0_qlmod = nullptr;   // [n_q]    p_0 mod q_t
     explicit fhelin_ctx(const fhelin::Params& p);
 };
 // Rows of a batched composite whose evaluation is DEFERRED until a row is consumed (fhelin_fc_matmul_pt,
@@ -228,6 +232,9 @@ inline fhelin_ct* wrap(fhelin_ctx* c, const CtPtr& p) {
     return h;
 }
 inline const CtPtr& ct_in(fhelin_ctx* c, const fhelin_ct* h) {
+    if (h->p && h->p->wrapped())
+        throw Error(FHELIN_ERR_ARG, "a wrapped input ciphertext is accepted by fhelin_unwrap_inputs, fhelin_decrypt, fhelin_ct_info, compact "
+                                    "export and free only");
     note_input(c, h);
     force(c, h);
     Ciphertext& ct = *h->p;

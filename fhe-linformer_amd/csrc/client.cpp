@@ -696,12 +696,36 @@ std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_pe
 // limbs vector v starts lower by (level plan); vectors of one level share the batched encryptor.
 std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, const double* table, int vocab, int S, const double* cls,
                                          const double* pos, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
-                                         int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out) {
-    if (seeded_ ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+                                         int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out,
+                                         const std::vector<int>* wrap_ell) {
+    if (wrap_ell && eval_only_) throw Error(FHELIN_ERR_KEY, "wrapped inputs are secret-key encryptions: an evaluation context holds no secret");
+    if ((seeded_ || wrap_ell) ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     const int slots = 1 << c_.prm.log_slots, S1 = S + 1, n_vec = 64 + S1;
     if (slots != 16384) throw Error(FHELIN_ERR_ARG, "ingest: the expanded layout needs 16384 slots (128 x 128)");
     if (S < 1 || S1 > w_cols || (!emb && !(tokens && table && vocab > 0))) throw Error(FHELIN_ERR_ARG, "ingest: bad token count / inputs");
     if (level < 0 || level > c_.L || (int)drop.size() != n_vec) throw Error(FHELIN_ERR_ARG, "ingest: level out of range");
+    // wrapped: groups of <= 128 inputs that share a target, in read order (runs of one target follow its first input)
+    std::vector<int> wrap_group_ell, wrap_pos;   // per wrapped vector: the inputs' limbs; [n_w][128] input positions (-1 = none)
+    if (wrap_ell) {
+        if ((int)wrap_ell->size() != n_vec) throw Error(FHELIN_ERR_ARG, "ingest: one target per input");
+        for (int v : *wrap_ell)
+            if (v < 1 || v > c_.L + 1) throw Error(FHELIN_ERR_ARG, "ingest: wrapped target limbs out of range [1, n_q]");
+        std::vector<char> taken(n_vec, 0);
+        for (int i = 0; i < n_vec; ++i) {
+            if (taken[i]) continue;
+            int t = 128;
+            for (int j = i; j < n_vec; ++j) {
+                if (taken[j] || (*wrap_ell)[j] != (*wrap_ell)[i]) continue;
+                if (t == 128) {
+                    wrap_group_ell.push_back((*wrap_ell)[i]);
+                    wrap_pos.resize(wrap_pos.size() + 128, -1);
+                    t = 0;
+                }
+                wrap_pos[wrap_pos.size() - 128 + t++] = j;
+                taken[j] = 1;
+            }
+        }
+    }
     hipStream_t s = c_.stream;
     // every temporary of the sample - the embeddings, x_in, the projections, the expanded packing: the client's PLAINTEXT - is wiped
     // before its block goes back to the recycled pool, and freed on every path out of this function (an exception included)
@@ -742,8 +766,16 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
     double* proj = (double*)tmp.get((size_t)64 * 128 * 8);
     launch_ingest_xin(x_in, d_emb, d_tok, d_tab, d_cls, d_pos, S, s);
     launch_ingest_project(proj, x_in, d_Ew, d_Eb, d_Fw, d_Fb, w_cols, S1, s);
-    double* dv = (double*)tmp.get((size_t)n_vec * slots * 16);
-    launch_ingest_expand(dv, proj, x_in, S1, slots, s);
+    double* dv = nullptr;
+    const int n_w = (int)wrap_group_ell.size();
+    if (!wrap_ell) {
+        dv = (double*)tmp.get((size_t)n_vec * slots * 16);
+        launch_ingest_expand(dv, proj, x_in, S1, slots, s);
+    } else {
+        dv = (double*)tmp.get((size_t)n_w * slots * 16);
+        const int* d_pos = (const int*)up(wrap_pos.data(), wrap_pos.size() * sizeof(int));
+        launch_ingest_wrap(dv, proj, x_in, d_pos, n_w, slots, s);
+    }
     hip_check(hipGetLastError(), "ingest kernels");
     if (proj_out) {   // test hook: x_in rows then the 64 projected rows, as computed on the device
         proj_out->resize((size_t)(S1 + 64) * 128);
@@ -751,6 +783,39 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
         hip_check(hipMemcpyAsync(proj_out->data() + (size_t)S1 * 128, proj, (size_t)64 * 128 * 8, hipMemcpyDeviceToHost, s), "ingest download");
     }
     hip_check(hipStreamSynchronize(s), "ingest sync");   // the host buffers are the caller's: done with them
+    if (wrap_ell) {
+        // seeded secret-key encryption over the first ell + 1 moduli of Q then P at the scale of a fresh encryption at ell limbs;
+        // wrapped vectors of one target are consecutive (grouping above) and share the batched encoder and encryptor
+        struct SeededMode {
+            bool& f;
+            bool was;
+            ~SeededMode() { f = was; }
+        } mode{seeded_, seeded_};
+        seeded_ = true;
+        begin_call();
+        std::vector<CtPtr> out;
+        for (int w0 = 0; w0 < n_w;) {
+            const int ell = wrap_group_ell[w0], ell1 = ell + 1;
+            int n = 0;
+            while (w0 + n < n_w && n < 32 && wrap_group_ell[w0 + n] == ell) ++n;
+            const size_t pn = (size_t)ell1 * c_.N;
+            const long double scale = c_.sf_real[c_.L + 1 - ell];
+            u64* enc = (u64*)tmp.get((size_t)n * pn * sizeof(u64));
+            encode_complex_on_device(c_, enc, dv + (size_t)w0 * slots * 2, n, slots, ell1, scale);
+            std::vector<CtPtr> part;
+            u64 nonces[32];
+            for (int k = 0; k < n; ++k) nonces[k] = (u64)(w0 + k);
+            encrypt_encoded(enc, pn, n, ell1, scale, slots, part, nonces);
+            for (int k = 0; k < n; ++k) {
+                Ciphertext& ct = *part[k];
+                for (int t = 0; t < 128 && wrap_pos[(size_t)(w0 + k) * 128 + t] >= 0; ++t) ct.wrap_pos.push_back(wrap_pos[(size_t)(w0 + k) * 128 + t]);
+                ct.wrap_total = n_vec;
+                out.push_back(part[k]);
+            }
+            w0 += n;
+        }
+        return out;
+    }
     begin_call();
     std::vector<CtPtr> out(n_vec);
     std::vector<char> seen(n_vec, 0);
@@ -810,7 +875,7 @@ std::vector<double> Client::decrypt(const CtPtr& cin, int slots) {
     while (ct->deg > 1 && ct->ell > 2) ct = ev_.rescale(ct);
     if (slots <= 0) slots = ct->slots > 0 ? ct->slots : (1 << c_.prm.log_slots);
     const size_t N = c_.N;
-    const int ell = ct->ell, nl = std::min(ell, 2);
+    const int ell = ct->ell - (ct->wrapped() ? 1 : 0), nl = std::min(ell, 2);   // a wrapped input's extra limb is left out
     CtPtr ph = phase(ct, nl);
     u64* m = ph->d;
     c_.ntt(LimbBatch{m, nl, nullptr, 0, nl}, true);

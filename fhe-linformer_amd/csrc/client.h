@@ -68,7 +68,10 @@ public:
     std::vector<CtPtr> encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots, const int* nonce_of = nullptr);
     std::vector<CtPtr> ingest_sample(const double* emb, const int* tokens, const double* table, int vocab, int S, const double* cls,
                                      const double* pos, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
-                                     int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out = nullptr);
+                                     int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out = nullptr,
+                                     const std::vector<int>* wrap_ell = nullptr);
+    // wrap_ell (include/fhelin.h "Wrapped inputs"): the limbs every input is wanted at; the result is then the WRAPPED ciphertexts (runs
+    // of inputs of one target in read order, <= 128 each, over ell + 1 limbs), always seeded secret-key encryptions; drop is ignored
     // test hook: the sampler's raw output, n_poly polynomials of N centred coefficients (kind 0 Gaussian, 1 ternary)
     std::vector<long> debug_sample(int kind, int n_poly);
     std::vector<double> decrypt(const CtPtr& c, int slots);

@@ -56,7 +56,8 @@ CtPtr Evaluator::clone(const CtPtr& a) {
 
 std::vector<CtPtr> Evaluator::new_ct_batch(int count, int npoly, int ell, int deg, long double scale, int slots) {
     c_.require_device();
-    if (count < 1 || ell < 1 || ell > c_.L + 1 || npoly < 1 || npoly > 3) throw Error(FHELIN_ERR_ARG, "new_ct_batch: bad shape");
+    // ell = L + 2: wrapped inputs over q_0..q_L, p_0 (include/fhelin.h "Wrapped inputs")
+    if (count < 1 || ell < 1 || ell > c_.L + 1 + (c_.K > 0 ? 1 : 0) || npoly < 1 || npoly > 3) throw Error(FHELIN_ERR_ARG, "new_ct_batch: bad shape");
     auto blk = std::make_shared<DevBlock>();
     blk->ctx = &c_;
     const size_t words = (size_t)npoly * ell * c_.N;
@@ -854,16 +855,16 @@ std::vector<CtPtr> Evaluator::rotate_each(const std::vector<CtPtr>& vin, const s
 // each polynomial -> lifted [P][ell-1][N].  The lift rides in the load of the transform's first pass (LimbBatch::lift_qlm)
 // when the dropped modulus is below twice every remaining one (x mod q_j is then one conditional subtraction); otherwise,
 // or with FHELIN_FUSE_LIFT=0, the separate lift kernel runs first.  Same residues either way.
-void Evaluator::lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const NttEpilogue* ep) {
+void Evaluator::lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const NttEpilogue* ep, const u64* qlm_row) {
     auto ntt = [&](const LimbBatch& b) {
         if (ep)
             c_.ntt_epilogue(b, *ep);
         else
             c_.ntt(b, false);
     };
-    const u64* qlm = c_.d_qlmod + (size_t)(ell - 1) * (c_.L + 1);
+    const u64* qlm = qlm_row ? qlm_row : c_.d_qlmod + (size_t)(ell - 1) * (c_.L + 1);
     bool fuse = c_.fuse_lift;
-    for (int j = 0; j + 1 < ell && fuse; ++j) fuse = c_.chain.q[ell - 1] < 2 * c_.chain.q[j];
+    for (int j = 0; j + 1 < ell && fuse; ++j) fuse = c_.moduli[ell - 1] < 2 * c_.chain.q[j];
     if (fuse) {
         LimbBatch fb{lifted, P * (ell - 1), nullptr, 0, ell - 1, last};
         fb.lift_qlm = qlm;
@@ -876,9 +877,9 @@ void Evaluator::lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const
 }
 
 // K5 step 4 rides in the row pass of the lift's NTT (FHELIN_FUSE_FINISH=0: rescale_finish_kernel reads the stored transform)
-void Evaluator::rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell) {
+void Evaluator::rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell, const u64* qlinv_row, const u64* qlm_row) {
     const size_t N = c_.N;
-    const u64* qlinv = c_.d_qlinv + (size_t)(ell - 1) * (c_.L + 1) * 2;
+    const u64* qlinv = qlinv_row ? qlinv_row : c_.d_qlinv + (size_t)(ell - 1) * (c_.L + 1) * 2;
     u64* lifted = c_.dalloc<u64>((size_t)P * (ell - 1) * N);
     if (c_.fuse_finish) {
         NttEpilogue ep;
@@ -888,9 +889,9 @@ void Evaluator::rescale_finish(u64* out, const u64* c, const u64* last, int P, i
         ep.out_stride = (size_t)2 * (ell - 1) * N;
         ep.w = qlinv;
         ep.ell = ell - 1;
-        lift_and_ntt(lifted, last, P, ell, &ep);
+        lift_and_ntt(lifted, last, P, ell, &ep, qlm_row);
     } else {
-        lift_and_ntt(lifted, last, P, ell);
+        lift_and_ntt(lifted, last, P, ell, nullptr, qlm_row);
         launch_rescale_finish(c_.dt, out, c, lifted, P, ell, qlinv, c_.stream);
     }
     c_.pool.free(lifted);

@@ -39,6 +39,12 @@ struct Ciphertext {
     bool seeded = false;
     u64 nonce = 0;
     uint8_t seed[32] = {};
+    // set only for a WRAPPED input (include/fhelin.h "Wrapped inputs"): ell = the inputs' limbs + 1 (limb ids 0..ell-1 of Q then P, so
+    // the extra limb of an input at n_q limbs is p_0); slot column t < wrap_pos.size() holds input wrap_pos[t] of a sample of
+    // wrap_total inputs (read order).  Only the unwrap, decryption, compact export and fhelin_ct_info accept one.
+    std::vector<int> wrap_pos;
+    int wrap_total = 0;
+    bool wrapped() const { return !wrap_pos.empty(); }
     ~Ciphertext();
     int level() const { return ctx->L + 1 - ell; }
     size_t words() const { return (size_t)npoly * ell * ctx->N; }
@@ -272,9 +278,11 @@ public:
 
     // raw, no bookkeeping (parity tests): exactly the residue functions of the oracle
     CtPtr raw_rescale(const CtPtr& a);
-    void lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const NttEpilogue* ep = nullptr);
+    // qlm_row / qlinv_row (optional): the tables of a dropped modulus that is not q_{ell-1} of the chain (the unwrap drops p_0 from a
+    // wrapped input over q_0..q_{n_q-1}, p_0: limb id ell-1 is then p_0's) - q_drop mod q_t and (q_drop^-1 mod q_t, Shoup)
+    void lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const NttEpilogue* ep = nullptr, const u64* qlm_row = nullptr);
     // K5 steps 2-4: out [P][ell-1][N] = (c - NTT(centred lift of last)) * q_{ell-1}^-1, c [P][ell][N]
-    void rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell);
+    void rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell, const u64* qlinv_row = nullptr, const u64* qlm_row = nullptr);
     CtPtr raw_rotate(const CtPtr& a, u64 galois, const EvalKey& key, bool accumulate = false);
     CtPtr rotate_add(const CtPtr& a, int index);            // a + rot(a, index), one fused key switch (rotsum step :833)
     CtPtr raw_mult_relin(const CtPtr& a, const CtPtr& b, const EvalKey& key);

@@ -33,4 +33,7 @@ void launch_ingest_xin(double* x_in, const double* emb, const int* tokens, const
 void launch_ingest_project(double* proj, const double* x_in, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
                            int w_cols, int S1, hipStream_t s);
 void launch_ingest_expand(double* out, const double* proj, const double* x_in, int S1, int slots, hipStream_t s);
+// the wrapped layout (include/fhelin.h "Wrapped inputs"): out [n_w][slots][2], slot j*128 + t of vector w = input pos[w][t] [j]
+// (inputs numbered as in launch_ingest_expand: E rows, F rows, tokens); pos [n_w][128] on the device, -1 = empty column
+void launch_ingest_wrap(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int slots, hipStream_t s);
 }  // namespace fhelin

@@ -279,7 +279,26 @@ __global__ void ingest_expand_kernel(double* __restrict__ out, const double* __r
     o.y = 0.0;
     reinterpret_cast<double2*>(out)[(size_t)v * slots + slot] = o;
 }
+// Wrapped layout (include/fhelin.h "Wrapped inputs"): vector w holds up to 128 inputs, slot j*128 + t = row pos[w][t] [j];
+// pos [n_w][128] (-1: no input, the slot column stays 0).  Same sources and order as ingest_expand_kernel.
+__global__ void ingest_wrap_kernel(double* __restrict__ out, const double* __restrict__ proj, const double* __restrict__ x_in,
+                                   const int* __restrict__ pos, int slots) {
+    const int w = blockIdx.y;
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= slots) return;
+    const int j = slot >> 7, t = slot & 127;
+    const int v = pos[w * 128 + t];
+    double2 o;
+    o.x = 0.0;
+    o.y = 0.0;
+    if (v >= 0 && j < 128) o.x = (v < 64 ? proj + (size_t)v * 128 : x_in + (size_t)(v - 64) * 128)[j];
+    reinterpret_cast<double2*>(out)[(size_t)w * slots + slot] = o;
+}
 }  // namespace
+void launch_ingest_wrap(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int slots, hipStream_t s) {
+    if (n_w < 1) return;
+    hipLaunchKernelGGL(ingest_wrap_kernel, dim3((slots + 255) / 256, n_w), dim3(256), 0, s, out, proj, x_in, pos, slots);
+}
 void launch_ingest_xin(double* x_in, const double* emb, const int* tokens, const double* table, const double* cls, const double* pos,
                        int S, hipStream_t s) {
     hipLaunchKernelGGL(ingest_xin_kernel, dim3(S + 1), dim3(128), 0, s, x_in, emb, tokens, table, cls, pos, S);

@@ -37,6 +37,19 @@ void launch_tensor_items(const DeviceTables& t, const EwItems& it, int ell, hipS
 void launch_automorph(const DeviceTables& t, u64* out, const u64* in, const u32* map, int nvec, hipStream_t s);
 // the same gather, every word stored as pack30(word) (low 30 bits | next 30 bits << 32): operands of launch_ks_inner_multi
 void launch_automorph_pack30(const DeviceTables& t, u64* out, const u64* in, const u32* map, int nvec, hipStream_t s);
+// one row of the unwrap's masked product (include/fhelin.h "Wrapped inputs"): dst [2][ell][N] = the first ell limbs of src [2][src_ell][N]
+// times mask_t, mask_t[l][n] = mask[l][map[n]] (the stored mask [ell][N], NTT form, read through the automorphism map of rotation -t)
+struct WrapMaskRow {
+    const u64* src;
+    u64* dst;
+    const u64* mask;
+    const u32* map;
+    int32_t ell;
+    int32_t src_ell;
+};
+static_assert(sizeof(WrapMaskRow) == 40, "WrapMaskRow is 40 bytes");
+// every row in ONE launch, rows: device table [n_rows]
+void launch_wrap_mask(const DeviceTables& t, const WrapMaskRow* rows, int n_rows, int max_ell, hipStream_t s);
 void launch_rescale_lift(const DeviceTables& t, u64* lifted, const u64* last, int npoly, int ell, const u64* qlmod_row, hipStream_t s);
 void launch_rescale_finish(const DeviceTables& t, u64* out, const u64* c, const u64* lifted, int npoly, int ell, const u64* qlinv_row,
                            hipStream_t s);

@@ -620,6 +620,29 @@ __global__ __launch_bounds__(256) void rescale_lift_kernel(DeviceTables t, u64* 
     reinterpret_cast<u64x2*>(lifted)[(size_t)v * row + n2] = r;
 }
 
+// Masked product of the unwrap (include/fhelin.h "Wrapped inputs"): row r = the first ell limbs of the wrapped ciphertext src
+// [2][src_ell][N] (src_ell >= ell: fewer when a level plan lowers the input) times mask_t, where
+// mask_t is the stored mask (slots = 0 mod 128, NTT form over the same limbs) read through the automorphism map of rotation -t:
+// mask_t[l][n] = mask[l][map[n]].  dst [2][ell][N].  grid (N/512, max ell, rows); each thread two adjacent residues of one limb.
+__global__ __launch_bounds__(256) void wrap_mask_kernel(DeviceTables t, const WrapMaskRow* __restrict__ rows) {
+    const WrapMaskRow r = rows[blockIdx.z];
+    const int l = blockIdx.y;
+    if (l >= r.ell) return;
+    const size_t N = (size_t)1 << t.log_n;
+    const size_t j = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    const Barrett br = load_barrett(t, l);
+    const u64* m = r.mask + (size_t)l * N;
+    const u64 m0 = m[r.map[j]], m1 = m[r.map[j + 1]];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const u64x2 x = *reinterpret_cast<const u64x2*>(r.src + ((size_t)p * r.src_ell + l) * N + j);
+        u64x2 y;
+        y.x = mul_mod(x.x, m0, br);
+        y.y = mul_mod(x.y, m1, br);
+        *reinterpret_cast<u64x2*>(r.dst + ((size_t)p * r.ell + l) * N + j) = y;
+    }
+}
+
 // K9 ModRaise: centred lift of a single-limb polynomial (coefficient form, modulus q_src) into nl limbs.
 // src [npoly][N] -> out [npoly][nl][N]
 __global__ __launch_bounds__(256) void modraise_kernel(DeviceTables t, u64* out, const u64* src, int src_limb, int nl) {
@@ -796,6 +819,10 @@ void launch_automorph(const DeviceTables& t, u64* out, const u64* in, const u32*
 void launch_automorph_pack30(const DeviceTables& t, u64* out, const u64* in, const u32* map, int nvec, hipStream_t s) {
     if (nvec <= 0) return;
     hipLaunchKernelGGL(automorph_pack30_kernel, grid2(t.log_n, nvec), dim3(256), 0, s, t, out, in, map);
+}
+void launch_wrap_mask(const DeviceTables& t, const WrapMaskRow* rows, int n_rows, int max_ell, hipStream_t s) {
+    if (n_rows < 1 || n_rows > 65535 || max_ell < 1 || max_ell > t.n_limbs) return;   // callers check (capi_wrapped.cpp)
+    hipLaunchKernelGGL(wrap_mask_kernel, dim3((1u << t.log_n) / 512, (unsigned)max_ell, (unsigned)n_rows), dim3(256), 0, s, t, rows);
 }
 void launch_rescale_lift(const DeviceTables& t, u64* lifted, const u64* last, int npoly, int ell, const u64* qlmod_row, hipStream_t s) {
     hipLaunchKernelGGL(rescale_lift_kernel, grid2(t.log_n, npoly * (ell - 1)), dim3(256), 0, s, t, lifted, last, ell - 1, qlmod_row);

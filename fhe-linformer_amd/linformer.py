@@ -79,7 +79,11 @@ class GpuController:
         """all inputs of a sample in one batched client call (encode + sample + encrypt on the GPU)"""
         return self.e.encrypt_batch(np.stack([expanded(np.asarray(v) * scale) for v in rows]), 0, SLOTS)
 
-    def client_ingest(self, w, x_emb):
+    def client_ingest(self, w, x_emb, wrapped=False):
+        if wrapped:   # a few wrapped ciphertexts on the wire, unwrapped by the server (include/fhelin.h "Wrapped inputs")
+            cts = self.e.unwrap_inputs(self.e.client_ingest_wrapped(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"],
+                                                                    emb=x_emb))
+            return {"inputs_E": cts[:32], "inputs_F": cts[32:64], "inputs": cts[64:]}
         return self.e.client_ingest(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], emb=x_emb)
 
     def read_plain_input(self, m, level=0, scale=1.0):
@@ -324,7 +328,14 @@ class BatchedController:
         cts = [self.e.encrypt_batch(np.stack([expanded(np.asarray(v) * scale) for v in rows]), 0, SLOTS) for rows in rows_per_sample]
         return [Batch(cts[x][i] for x in range(self.B)) for i in range(len(cts[0]))]
 
-    def client_ingest_batch(self, w, x_embs):
+    def client_ingest_batch(self, w, x_embs, wrapped=False):
+        if wrapped:   # every sample's wrapped ciphertexts unwrapped in ONE call: the key switches carry the rows of all samples
+            ws = [self.e.client_ingest_wrapped(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], emb=x) for x in x_embs]
+            cts = self.e.unwrap_inputs([h for s in ws for h in s])
+            n = len(cts) // len(ws)
+            encs = [{"inputs_E": cts[x * n:x * n + 32], "inputs_F": cts[x * n + 32:x * n + 64], "inputs": cts[x * n + 64:(x + 1) * n]}
+                    for x in range(len(ws))]
+            return batch_inputs(encs)
         encs = [self.e.client_ingest(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], emb=x) for x in x_embs]
         return batch_inputs(encs)
 
@@ -521,10 +532,18 @@ def encrypt_inputs(ctl, x_in, X_E, X_F):
             "inputs": cts[64:]}                                                             # :169-173
 
 
-def ingest_sample(ctl, w, x_emb):
+def ingest_sample(ctl, w, x_emb, wrapped=False):
     """client side of one sample from its token embeddings x_emb [S,128] (dimReduce.py:141-160 + main.cpp:159-173).  A controller
     with `client_ingest` (the GPU engine: fhelin_client_ingest) does positional embedding, both Linformer projections, packing,
-    encoding and encryption on the device; any other controller gets the NumPy statement of the same lines."""
+    encoding and encryption on the device; any other controller gets the NumPy statement of the same lines.
+    wrapped: the sample travels as a few wrapped ciphertexts that the server unwraps (include/fhelin.h "Wrapped inputs"); a
+    BatchedController then takes x_emb as the list of its B samples' embeddings."""
+    if wrapped:
+        if hasattr(ctl, "client_ingest_batch"):
+            return ctl.client_ingest_batch(w, x_emb, wrapped=True)
+        if hasattr(ctl, "client_ingest"):
+            return ctl.client_ingest(w, x_emb, wrapped=True)
+        raise TypeError("ingest_sample(wrapped=True) needs a GPU controller")
     if hasattr(ctl, "client_ingest"):
         return ctl.client_ingest(w, x_emb)
     S = x_emb.shape[0]

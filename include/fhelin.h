@@ -549,6 +549,56 @@ int fhelin_ctx_key_set_seed(const fhelin_ctx* c, uint8_t* out32);
  * one launch, digests and installs as version 1 does (all or nothing). */
 int fhelin_evalkeys_save_compact(fhelin_ctx* c, const char* path);
 
+/* ---- wrapped inputs: a sample uploaded as a few ciphertexts, unwrapped on the server -------------------------------------
+ * Layout.  A WRAPPED ciphertext holds count <= 128 inputs of one sample (inputs numbered in the driver's read order: the 32
+ * E-projected rows, the 32 F-projected rows, the S + 1 tokens; total = 64 + S + 1): slot j*128 + t = row_t[j] for t < count, the
+ * other slots 0 (the reference's wrapUpExpanded, src/FHEController.cpp:1070).  Unwrap output t has exactly the slot values of
+ * read_expanded_input(row_t): slot j*128 + k = row_t[j] for all k < 128.
+ * Levels.  Inputs wanted at ell limbs travel over the FIRST ell + 1 MODULI OF Q THEN P: q_0..q_ell for ell < n_q, and
+ * q_0..q_{n_q-1}, p_0 for ell = n_q.  The client encrypts at Delta_ell, the 80-bit scale of a fresh encryption at ell limbs.  The
+ * server multiplies by the 0/1 mask of slot column t encoded at scale q_drop (the extra limb's modulus) and drops that limb as a
+ * rescale does: each output has ell limbs, degree 1, the slot count and the bit-identical scale of a fresh encryption at ell limbs.
+ * Encryption.  Always a seeded secret-key encryption ("Compact ciphertexts" above); the expansion of c1 runs over the absolute limb
+ * index 0..ell of Q then P (the p_0 limb is limb n_q), as for seeded keys.  One fresh seed per call; nonce = the wrapped
+ * ciphertext's index within the call.
+ * Grouping.  The inputs of one target limb count share wrapped ciphertexts, at most 128 each, filled in read order.  The targets are
+ * taken in the order of their first input, and all ciphertexts of one target come out before those of the next.  A wrapped handle
+ * carries count, total and its inputs' positions.  Encoding and encryption run once per run of up to 32 ciphertexts of one target
+ * (at the headline ring: one run per target, so 1 without a level plan and 2 under one).
+ * Unwrap.  out_t = sum_{k<128} rot(x_t, t - k) with x_t the masked drop; with t = a + 8b + 64c that is three merged rotate-and-sum
+ * key switches (fhelin_rotate_sum), offsets {a-7..a}, 8{b-7..b} and {64c-64, 64c} without the identity term: every offset is a
+ * +-1..7, +-8..56 (step 8) or +-64, all in the circuit's rotation key list.  A missing key: FHELIN_ERR_KEY naming its index.
+ * Handles.  A wrapped handle is accepted by fhelin_unwrap_inputs, fhelin_decrypt (the extra limb left out; the slots come back in
+ * the wrapped layout), fhelin_ct_info (ell counts the extra limb; level is the inputs' level), fhelin_ct_scale, fhelin_wrapped_info, the compact functions and
+ * fhelin_ct_free; every other entry point returns FHELIN_ERR_ARG.
+ * Compact form, version 2 (a wrapped ciphertext; version 1 above is unchanged; exactly H + 8 ell N bytes, H = 104 + 8 ell + 8 ceil(count / 2)):
+ *   offset  0 .. 95  as version 1 with version = 2 and header bytes = H; ell = the stored limbs (the inputs' limbs + 1, >= 2)
+ *          96  u32      count (1 .. 128)
+ *         100  u32      total (count .. 65535): inputs of the sample
+ *         104  u64[ell] the first ell moduli of Q then P
+ *   104 + 8 ell  u32[count] the inputs' positions (strictly increasing, < total), zero padding to H
+ *   then   u64[ell][N]  c0, NTT form (digest as version 1, over the ell limb vectors)
+ * Import (fhelin_ct_import_compact) checks both versions with the same all-or-nothing digest and range checks and makes wrapped
+ * handles of version 2 blobs. */
+/* The client side of one sample (fhelin_client_ingest's arguments) as wrapped ciphertexts.  targets [64 + S + 1] (optional): the limbs
+ * each input is wanted at (1 .. n_q); NULL: n_q - level for all, or, while a level plan is applied on this context, the plan's targets
+ * of the sources the unwrap will produce (read, not consumed: this call is no level-plan source).  outs must hold 64 + S + 1 handles;
+ * *n_out = wrapped ciphertexts made.  Needs the secret key (FHELIN_ERR_KEY on an evaluation context) and n_p >= 1. */
+int fhelin_client_ingest_wrapped(fhelin_ctx* c, const double* emb, const int32_t* tokens, const double* table, int32_t vocab, int32_t S,
+                                 const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w,
+                                 const double* F_b, int32_t w_cols, int32_t level, const int32_t* targets, fhelin_ct** outs,
+                                 int32_t* n_out, double* proj_out);
+/* count, total, the inputs' limbs (stored limbs - 1) and positions (min(cap, count) of them) of a wrapped handle; FHELIN_ERR_ARG otherwise */
+int fhelin_wrapped_info(const fhelin_ct* ct, int32_t* count, int32_t* total, int32_t* ell, int32_t* positions, int32_t cap);
+/* n wrapped handles -> sum of their counts outputs.  Consecutive handles whose counts add up to their total are one sample (B samples of
+ * a batched pass in one call); outs: sample by sample, each in read order - the handles fhelin_client_ingest would have given.  The
+ * masked drop of every input is one launch; the replications of all inputs share batched key switches.  The outputs are level-plan
+ * sources with the ordinals fhelin_client_ingest's outputs have (a plan recorded with either applies to the other).  Applying, an
+ * output whose input was wrapped above its planned limbs tau is made at tau directly: the masked product reads the first tau + 1
+ * limbs, with the mask encoded at Delta_tau q_tau / Delta_ell, and the output has the fresh scale Delta_tau, as fhelin_client_ingest's
+ * planned output.  Works on an evaluation context that holds the circuit's rotation keys. */
+int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t n, fhelin_ct** outs);
+
 #ifdef __cplusplus
 }
 #endif
