@@ -517,6 +517,21 @@ int fhelin_debug_pool_selftest(uint64_t seed, int32_t n_ops, uint64_t device_byt
         out[1] = pool.reserved_peak;
         out[2] = pool.malloc_calls;
         out[3] = oom;
+        {   // the owner type: a scope that is left by an exception gives back what it still owns, and nothing that was handed on
+            const size_t live_before = pool.bytes_live();
+            struct Unwind {};
+            char* handed = nullptr;
+            try {
+                Scratch<char> a(pool, 4096), b(pool, size_t(1) << 20), c(pool, 256);
+                Scratch<char> empty;
+                handed = b.release();
+                a.reset();
+                throw Unwind();
+            } catch (const Unwind&) {
+            }
+            pool.free(handed);
+            if (pool.bytes_live() != live_before) throw Error(FHELIN_ERR_INTERNAL, "pool selftest: scratch owners left blocks live after an exception");
+        }
         for (uintptr_t a : order) pool.free(reinterpret_cast<void*>(a));
         // everything free: every slab is ONE free range again (coalescing), and a trim hands all of it back
         out[4] = pool.free_ranges() == pool.slabs() && pool.bytes_live() == 0 ? 1 : 0;

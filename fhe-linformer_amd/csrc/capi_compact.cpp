@@ -14,10 +14,6 @@
 
 using namespace fhelin;
 
-#if !defined(__BYTE_ORDER__) || __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
-#error "compact ciphertexts are written in host byte order, which must be little-endian"
-#endif
-
 namespace {
 
 constexpr char CC_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'C', 'C'};
@@ -37,13 +33,6 @@ struct CcHeader {
     int32_t count = 0, total = 0;       // version 2
     std::vector<int> pos;               // version 2: the inputs' positions, [count]
 };
-
-template <class T> T get(const uint8_t* b, size_t off) {
-    T v;
-    std::memcpy(&v, b + off, sizeof(T));
-    return v;
-}
-template <class T> void put(uint8_t* b, size_t off, T v) { std::memcpy(b + off, &v, sizeof(T)); }
 
 size_t cc_bytes(int log_n, int ell) { return CC_FIXED + 8 * (size_t)ell + 8 * (size_t)ell * ((size_t)1 << log_n); }
 size_t cc_header_wrapped(int ell, int count) { return CC_FIXED_WRAPPED + 8 * (size_t)ell + 8 * (((size_t)count + 1) / 2); }
@@ -135,21 +124,19 @@ int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, s
     if (cap < bytes) throw Error(FHELIN_ERR_ARG, "export_compact: buffer too small");
     if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "export_compact: ring dimension below 2^12");
     // c0's digest on the device, c0 itself straight into the blob; one synchronisation
-    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, ell));
-    u64* dg = x.dalloc<u64>(2 * (size_t)ell);
+    Scratch<u64> part = x.scratch<u64>(key_digest_scratch_words(x.N, ell));
+    Scratch<u64> dg = x.scratch<u64>(2 * (size_t)ell);
     launch_key_digest(x.dt, p->d, ell, 0, ell, part, dg, x.stream);
     hip_check(hipGetLastError(), "compact digest kernels");
     std::vector<u64> h(2 * (size_t)ell);
     hip_check(hipMemcpyAsync(h.data(), dg, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "compact digest download");
     hip_check(hipMemcpyAsync(out + head, p->d, (size_t)ell * N * 8, hipMemcpyDeviceToHost, x.stream), "compact export");
     hip_check(hipStreamSynchronize(x.stream), "compact export sync");
-    x.pool.free(part);
-    x.pool.free(dg);
-    u128 acc = 0;
-    for (int j = 0; j < ell; ++j) {
-        if (!h[2 * j + 1]) throw Error(FHELIN_ERR_INTERNAL, "export_compact: c0 holds a residue out of range");
-        acc += (u128)h[2 * j] * key_weight_vec((u32)j);
-    }
+    part.reset();
+    dg.reset();
+    bool in_range;
+    const u64 digest = fold_key_digest(h.data(), (size_t)ell, in_range);
+    if (!in_range) throw Error(FHELIN_ERR_INTERNAL, "export_compact: c0 holds a residue out of range");
     std::memcpy(out, CC_MAGIC, 8);
     put<uint32_t>(out, 8, wrapped ? CC_VERSION_WRAPPED : CC_VERSION);
     put<uint32_t>(out, 12, (uint32_t)head);
@@ -160,7 +147,7 @@ int fhelin_ct_export_compact(fhelin_ctx* c, const fhelin_ct* ct, uint8_t* out, s
     put<double>(out, 40, lo);
     put<uint64_t>(out, 48, p->nonce);
     std::memcpy(out + 56, p->seed, 32);
-    put<uint64_t>(out, 88, (uint64_t)(acc % KEY_DIGEST_P));
+    put<uint64_t>(out, 88, digest);
     if (!wrapped) {
         std::memcpy(out + CC_FIXED, x.chain.q.data(), 8 * (size_t)ell);
     } else {
@@ -236,19 +223,9 @@ int fhelin_ct_import_compact(fhelin_ctx* c, const uint8_t* const* blobs, const s
     }
     // 3. range check + digest of every c0 (one launch pair per limb count: c0 vectors ell apart in groups of 2 ell), then every c1
     // in one launch; one synchronisation for the call
-    struct Scratch {
-        Context& x;
-        std::vector<void*> d;
-        ~Scratch() {
-            for (void* p : d) x.pool.free(p);
-        }
-    } sc{x, {}};
-    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, max_vec));
-    sc.d.push_back(part);
-    u64* dg = x.dalloc<u64>(2 * (size_t)n * max_ell);
-    sc.d.push_back(dg);
-    SeededEntry* d_tab = x.dalloc<SeededEntry>((size_t)n);
-    sc.d.push_back(d_tab);
+    Scratch<u64> part = x.scratch<u64>(key_digest_scratch_words(x.N, max_vec));
+    Scratch<u64> dg = x.scratch<u64>(2 * (size_t)n * max_ell);
+    Scratch<SeededEntry> d_tab = x.scratch<SeededEntry>((size_t)n);
     hip_check(hipMemcpyAsync(d_tab, tab.data(), (size_t)n * sizeof(SeededEntry), hipMemcpyHostToDevice, x.stream), "seed table upload");
     std::vector<size_t> dg_at(n);   // first digest vector of blob i
     size_t v0 = 0;
@@ -265,13 +242,10 @@ int fhelin_ct_import_compact(fhelin_ctx* c, const uint8_t* const* blobs, const s
     hip_check(hipStreamSynchronize(x.stream), "compact import sync");
     // 4. all or nothing: a handle only when every blob passed
     for (int i = 0; i < n; ++i) {
-        u128 acc = 0;
-        for (int j = 0; j < hs[i].ell; ++j) {
-            const size_t v = dg_at[i] + j;
-            if (!h[2 * v + 1]) throw Error(FHELIN_ERR_ARG, "import_compact: blob " + std::to_string(i) + " holds a residue not below its modulus");
-            acc += (u128)h[2 * v] * key_weight_vec((u32)j);
-        }
-        if ((uint64_t)(acc % KEY_DIGEST_P) != hs[i].digest) throw Error(FHELIN_ERR_ARG, "import_compact: blob " + std::to_string(i) + " does not match its digest");
+        bool in_range;
+        const u64 digest = fold_key_digest(&h[2 * dg_at[i]], (size_t)hs[i].ell, in_range);
+        if (!in_range) throw Error(FHELIN_ERR_ARG, "import_compact: blob " + std::to_string(i) + " holds a residue not below its modulus");
+        if (digest != hs[i].digest) throw Error(FHELIN_ERR_ARG, "import_compact: blob " + std::to_string(i) + " does not match its digest");
     }
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, cts[i]);   // imported: not a level-plan source, never lowered
     FHELIN_CATCH
@@ -285,8 +259,8 @@ int fhelin_debug_seeded_expand(fhelin_ctx* c, const uint8_t* seed32, uint64_t no
     x.require_device();
     if (ell < 1 || ell > x.L + 1 || n_ct < 1 || n_ct > 65535 || reps < 0) throw Error(FHELIN_ERR_ARG, "debug_seeded_expand: bad shape");
     const size_t words = (size_t)ell * x.N;
-    u64* d = x.dalloc<u64>(words * n_ct);
-    SeededEntry* d_tab = x.dalloc<SeededEntry>((size_t)n_ct);
+    Scratch<u64> d = x.scratch<u64>(words * n_ct);
+    Scratch<SeededEntry> d_tab = x.scratch<SeededEntry>((size_t)n_ct);
     std::vector<SeededEntry> tab(n_ct);
     for (int i = 0; i < n_ct; ++i) {
         for (int w = 0; w < 8; ++w) tab[i].key.w[w] = get<uint32_t>(seed32, 4 * w);
@@ -312,8 +286,6 @@ int fhelin_debug_seeded_expand(fhelin_ctx* c, const uint8_t* seed32, uint64_t no
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     if (ms) *ms = reps > 0 ? t / (float)reps : 0.0f;
-    x.pool.free(d);
-    x.pool.free(d_tab);
     FHELIN_CATCH
 }
 

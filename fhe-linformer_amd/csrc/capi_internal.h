@@ -1,5 +1,6 @@
 // Shared plumbing for the extern "C" translation units.
 #pragma once
+#include <cstring>
 #include <exception>
 #include <string>
 #include "context.h"
@@ -7,6 +8,7 @@
 #include "client.h"
 #include "composite.h"
 #include "bootstrap.h"
+#include "kernels_keys.h"
 
 namespace fhelin {
 // Profile-guided level planning (include/fhelin.h fhelin_level_plan_*).
@@ -158,8 +160,30 @@ struct fhelin_pt {
     fhelin::PtPtr p;
 };
 
+#if !defined(__BYTE_ORDER__) || __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
+#error "evaluation-key sets and compact ciphertexts are written in host byte order, which must be little-endian"
+#endif
+
 namespace fhelin {
 int capi_fail(int code, const std::string& msg);
+// fields of the file and blob formats (capi_keys.cpp, capi_compact.cpp), at any alignment
+template <class T> T get(const uint8_t* b, size_t off) {
+    T v;
+    std::memcpy(&v, b + off, sizeof(T));
+    return v;
+}
+template <class T> void put(uint8_t* b, size_t off, T v) { std::memcpy(b + off, &v, sizeof(T)); }
+// the per-vector device digests h[n_vec][2] (launch_key_digest: digest, range flag) of one key or one c0 folded into its digest;
+// in_range: every residue below its limb's modulus
+inline u64 fold_key_digest(const u64* h, size_t n_vec, bool& in_range) {
+    u128 acc = 0;
+    in_range = true;
+    for (size_t j = 0; j < n_vec; ++j) {
+        acc += (u128)h[2 * j] * key_weight_vec((u32)j);
+        if (!h[2 * j + 1]) in_range = false;
+    }
+    return (u64)(acc % KEY_DIGEST_P);
+}
 // evaluate the listed rows of a deferred group in ONE batched call (capi_composite.cpp)
 void force_rows(fhelin_ctx* c, LazyRows& g, const std::vector<int>& idx);
 // the same for several groups at once; groups that are the same call on different inputs (one call per sample of a batch) share

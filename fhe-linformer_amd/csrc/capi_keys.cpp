@@ -16,10 +16,6 @@
 
 using namespace fhelin;
 
-#if !defined(__BYTE_ORDER__) || __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
-#error "the evaluation-key set is written in host byte order, which must be little-endian"
-#endif
-
 namespace {
 
 constexpr char EK_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'K'};
@@ -76,13 +72,6 @@ void from_params(const Params& q, int32_t* p) {
     const int32_t v[9] = {q.log_n, q.n_q, q.first_bits, q.scale_bits, q.n_p, q.special_bits, q.dnum, q.log_slots, q.hamming};
     std::memcpy(p, v, sizeof(v));
 }
-
-template <class T> T get(const uint8_t* b, size_t off) {
-    T v;
-    std::memcpy(&v, b + off, sizeof(T));
-    return v;
-}
-template <class T> void put(std::vector<uint8_t>& b, size_t off, T v) { std::memcpy(b.data() + off, &v, sizeof(T)); }
 
 // header + moduli + key table, every field validated against the others and against the file's size: a malformed set is
 // FHELIN_ERR_ARG before anything is allocated
@@ -205,8 +194,8 @@ void key_digests(Context& x, const std::vector<Seg>& segs, const std::vector<uin
     digest.assign(segs.size(), 0);
     ok.assign(segs.size(), 1);
     if (!total) return;
-    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, (int)max_vec));
-    u64* out = x.dalloc<u64>(2 * total);
+    Scratch<u64> part = x.scratch<u64>(key_digest_scratch_words(x.N, (int)max_vec));
+    Scratch<u64> out = x.scratch<u64>(2 * total);
     size_t v0 = 0;
     for (size_t k = 0; k < segs.size(); ++k) {
         const int n_vec = (int)(segs[k].words / N);
@@ -218,17 +207,14 @@ void key_digests(Context& x, const std::vector<Seg>& segs, const std::vector<uin
     std::vector<u64> h(2 * total);
     hip_check(hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "key digest download");
     hip_check(hipStreamSynchronize(x.stream), "key digest sync");
-    x.pool.free(part);
-    x.pool.free(out);
+    part.reset();
+    out.reset();
     v0 = 0;
     for (size_t k = 0; k < segs.size(); ++k) {
         const size_t n_vec = segs[k].words / N;
-        u128 acc = 0;
-        for (size_t j = 0; j < n_vec; ++j) {
-            acc += (u128)h[2 * (v0 + j)] * key_weight_vec((u32)j);
-            if (!h[2 * (v0 + j) + 1]) ok[k] = 0;
-        }
-        digest[k] = (u64)(acc % KEY_DIGEST_P);
+        bool in_range;
+        digest[k] = fold_key_digest(&h[2 * v0], n_vec, in_range);
+        ok[k] = in_range ? 1 : 0;
         v0 += n_vec;
     }
 }
@@ -312,8 +298,8 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
     const uint64_t data_offset = (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN;
     std::vector<uint8_t> h(data_offset, 0);
     std::memcpy(h.data(), compact ? EC_MAGIC : EK_MAGIC, 8);
-    put<uint32_t>(h, 8, compact ? EC_VERSION : EK_VERSION);
-    put<uint32_t>(h, 12, (uint32_t)ents.size());
+    put<uint32_t>(h.data(), 8, compact ? EC_VERSION : EK_VERSION);
+    put<uint32_t>(h.data(), 12, (uint32_t)ents.size());
     int32_t prm[9];
     from_params(x.prm, prm);
     std::memcpy(h.data() + 16, prm, sizeof(prm));
@@ -322,7 +308,7 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
                               c->boot.correction};
         std::memcpy(h.data() + 52, b, sizeof(b));
     }
-    put<uint64_t>(h, 80, data_offset);
+    put<uint64_t>(h.data(), 80, data_offset);
     if (compact) std::memcpy(h.data() + EK_HEADER, c->cl.key_seed(), 32);
     std::memcpy(h.data() + head, x.moduli.data(), 8 * nm);
     uint64_t at = data_offset;
@@ -330,12 +316,12 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
         ents[k].offset = at;
         at += 8 * ents[k].words;
         const size_t o = head + 8 * nm + EK_ENTRY * k;
-        put<uint32_t>(h, o, ents[k].kind);
-        put<uint32_t>(h, o + 4, ents[k].digits);
-        put<uint64_t>(h, o + 8, ents[k].galois);
-        put<uint64_t>(h, o + 16, ents[k].offset);
-        put<uint64_t>(h, o + 24, ents[k].words);
-        put<uint64_t>(h, o + 32, ents[k].digest);
+        put<uint32_t>(h.data(), o, ents[k].kind);
+        put<uint32_t>(h.data(), o + 4, ents[k].digits);
+        put<uint64_t>(h.data(), o + 8, ents[k].galois);
+        put<uint64_t>(h.data(), o + 16, ents[k].offset);
+        put<uint64_t>(h.data(), o + 24, ents[k].words);
+        put<uint64_t>(h.data(), o + 32, ents[k].digest);
     }
 
     bool written = false;
@@ -448,22 +434,16 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
         if (k.kind != EK_PUBLIC && (int)k.digits != digits)
             throw Error(FHELIN_ERR_ARG, "evalkeys_load: switching key digit count does not match the context");
 
-    // destinations: nothing is installed until every key has passed (the guards free the blocks on any failure)
-    struct PkGuard {
-        Context& x;
-        u64* d = nullptr;
-        ~PkGuard() {
-            if (d) x.pool.free(d);
-        }
-    } pk{x};
+    // destinations: nothing is installed until every key has passed (their owners free the blocks on any failure)
+    Scratch<u64> pk;
     std::vector<KeyPtr> sw(e.keys.size());
     std::vector<Seg> segs;
     std::vector<uint32_t> kinds;
     for (size_t k = 0; k < e.keys.size(); ++k) {
         if (e.keys[k].kind == EK_PUBLIC) {
             const size_t pk_words = (size_t)2 * (x.L + 1) * x.N;   // the whole key (a compact entry's words count its b half)
-            pk.d = x.dalloc<u64>(pk_words);
-            segs.push_back({pk.d, pk_words});
+            pk = x.scratch<u64>(pk_words);
+            segs.push_back({pk, pk_words});
         } else {
             sw[k] = c->ev.new_key();
             segs.push_back({sw[k]->d, sw[k]->words()});
@@ -514,18 +494,11 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
         }
     }
     if (!tab.empty()) {   // every a half of the set: one launch (per 65535 key digits), before the digests see the full keys
-        struct TabGuard {
-            Context& x;
-            SeededEntry* d = nullptr;
-            ~TabGuard() {
-                if (d) x.pool.free(d);
-            }
-        } dt{x};
-        dt.d = reinterpret_cast<SeededEntry*>(x.pool.alloc(tab.size() * sizeof(SeededEntry)));
-        hip_check(hipMemcpyAsync(dt.d, tab.data(), tab.size() * sizeof(SeededEntry), hipMemcpyHostToDevice, x.stream), "seed table upload");
+        Scratch<SeededEntry> dt = x.scratch<SeededEntry>(tab.size());
+        hip_check(hipMemcpyAsync(dt, tab.data(), tab.size() * sizeof(SeededEntry), hipMemcpyHostToDevice, x.stream), "seed table upload");
         const int max_ell = x.L + 1 + x.K;
         for (size_t lo = 0; lo < tab.size(); lo += 65535)
-            launch_seeded_expand(x.dt, dt.d + lo, (int)std::min<size_t>(65535, tab.size() - lo), max_ell, x.stream);
+            launch_seeded_expand(x.dt, dt + lo, (int)std::min<size_t>(65535, tab.size() - lo), max_ell, x.stream);
         hip_check(hipGetLastError(), "seeded expand kernel");
     }
     std::vector<uint64_t> digest;
@@ -551,8 +524,7 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
             default: break;
         }
     }
-    c->cl.install_public_key(pk.d, e.compact);
-    pk.d = nullptr;
+    c->cl.install_public_key(pk.release(), e.compact);
     if (e.compact) c->cl.install_key_seed(e.seed);
     if (e.boot[2] > 0) {   // the client's approximation parameters; fhelin_bootstrap_setup is the caller's (fhelin_evalkeys_info)
         c->boot.K = e.boot[3];
@@ -572,18 +544,18 @@ int fhelin_debug_key_digest(fhelin_ctx* c, const uint64_t* words, int32_t n_limb
     if (n_limbs < 1 || limb_first < 0 || limb_first + n_limbs > x.L + 1 + x.K) throw Error(FHELIN_ERR_ARG, "debug_key_digest: limbs out of range");
     if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "debug_key_digest: ring dimension below 2^12");
     const size_t n = (size_t)n_limbs * x.N;
-    u64* d = x.dalloc<u64>(n);
-    u64* part = x.dalloc<u64>(key_digest_scratch_words(x.N, n_limbs));
-    u64* out = x.dalloc<u64>(2 * (size_t)n_limbs);
+    Scratch<u64> d = x.scratch<u64>(n);
+    Scratch<u64> part = x.scratch<u64>(key_digest_scratch_words(x.N, n_limbs));
+    Scratch<u64> out = x.scratch<u64>(2 * (size_t)n_limbs);
     hip_check(hipMemcpyAsync(d, words, n * 8, hipMemcpyHostToDevice, x.stream), "debug digest upload");
     launch_key_digest(x.dt, d, n_limbs, limb_first, n_limbs, part, out, x.stream);
     hip_check(hipGetLastError(), "key digest kernels");
     std::vector<u64> h(2 * (size_t)n_limbs);
     hip_check(hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "debug digest download");
     hip_check(hipStreamSynchronize(x.stream), "debug digest sync");
-    x.pool.free(d);
-    x.pool.free(part);
-    x.pool.free(out);
+    d.reset();
+    part.reset();
+    out.reset();
     for (int i = 0; i < n_limbs; ++i) {
         out_digests[i] = h[2 * i];
         out_ok[i] = (int32_t)h[2 * i + 1];

@@ -181,13 +181,7 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
     // masked product, one launch: rows grouped by their output limb count (each group one block, rows in output order inside it)
     std::map<int, std::vector<int>> by_ell;   // output limbs + 1 -> rows
     for (int r = 0; r < R; ++r) by_ell[out_ell[r] + 1].push_back(r);
-    struct Blocks {
-        Context& x;
-        std::vector<void*> d;
-        ~Blocks() {
-            for (void* p : d) x.pool.free(p);
-        }
-    } blk{x, {}};
+    std::vector<Scratch<u64>> blk;   // the products, one block per limb count: held until the call returns
     std::vector<WrapMaskRow> tab(R);
     std::map<int, u64*> prod;
     const PtPtr& mask = mask_of(c);
@@ -195,8 +189,8 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
     int max_ell = 0;
     for (auto& g : by_ell) {
         const int ell1 = g.first, tau = ell1 - 1;
-        u64* d = x.dalloc<u64>(g.second.size() * 2 * (size_t)ell1 * N);
-        blk.d.push_back(d);
+        blk.push_back(x.scratch<u64>(g.second.size() * 2 * (size_t)ell1 * N));
+        u64* d = blk.back();
         prod[ell1] = d;
         for (size_t k = 0; k < g.second.size(); ++k) {
             const Row& r = rows[g.second[k]];
@@ -212,8 +206,7 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
         max_ell = std::max(max_ell, ell1);
     }
     if (R > 65535) throw Error(FHELIN_ERR_ARG, "unwrap: at most 65535 inputs per call");
-    WrapMaskRow* d_tab = x.dalloc<WrapMaskRow>((size_t)R);
-    blk.d.push_back(d_tab);
+    Scratch<WrapMaskRow> d_tab = x.scratch<WrapMaskRow>((size_t)R);
     hip_check(hipMemcpyAsync(d_tab, tab.data(), (size_t)R * sizeof(WrapMaskRow), hipMemcpyHostToDevice, x.stream), "unwrap row table");
     launch_wrap_mask(x.dt, d_tab, R, max_ell, x.stream);
     hip_check(hipGetLastError(), "unwrap mask kernel");
@@ -232,7 +225,7 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
         for (size_t k0 = 0; k0 < g.second.size(); k0 += (size_t)c->ev.batch_limit) {
             const int B = (int)std::min(g.second.size() - k0, (size_t)c->ev.batch_limit), P = 2 * B;
             const u64* base_d = prod[ell1] + k0 * 2 * (size_t)ell1 * N;
-            u64* last = x.dalloc<u64>((size_t)P * N);
+            Scratch<u64> last = x.scratch<u64>((size_t)P * N);
             LimbBatch lb{last, P, nullptr, ell1 - 1, 1, base_d + (size_t)(ell1 - 1) * N};
             lb.src_group = 1;
             lb.src_group_stride = (size_t)ell1 * N;
@@ -240,7 +233,7 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
             std::vector<CtPtr> o = c->ev.new_ct_batch(B, 2, ell, 1, scale, slots);
             c->ev.rescale_finish(o[0]->d, base_d, last, P, ell1, qlinv, qlm);
             hip_check(hipGetLastError(), "unwrap limb drop");
-            x.pool.free(last);
+            last.reset();
             x.stats.rescale += (u64)B;
             x.stats.rescale_limbs += (u64)B * ell1;
             for (int b = 0; b < B; ++b) xs[g.second[k0 + b]] = o[b];

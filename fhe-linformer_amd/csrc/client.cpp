@@ -226,7 +226,7 @@ void encode_batch_device(Context& c, u64* dst, const double* re, const double* i
     if (ell < 1 || ell > c.L + 1 + c.K) throw Error(FHELIN_ERR_ARG, "encode: level out of range");
     if (n_vec < 1) return;
     const size_t words = (size_t)2 * slots;                 // one complex vector, in doubles
-    double* dv = reinterpret_cast<double*>(c.dalloc<u64>(words * n_vec));
+    Scratch<double> dv = c.scratch<double>(words * n_vec);
     std::vector<u64> host(words);
     for (int b = 0; b < n_vec; ++b) {                       // through the pinned staging ring: no stream drain
         double* h = reinterpret_cast<double*>(host.data());
@@ -234,10 +234,9 @@ void encode_batch_device(Context& c, u64* dst, const double* re, const double* i
             h[2 * i] = i < n_per ? re[(size_t)b * n_per + i] : 0.0;
             h[2 * i + 1] = (im && i < n_per) ? im[(size_t)b * n_per + i] : 0.0;
         }
-        c.upload_async(reinterpret_cast<u64*>(dv) + words * b, host.data(), words);
+        c.upload_async(reinterpret_cast<u64*>(dv.get()) + words * b, host.data(), words);
     }
     encode_complex_on_device(c, dst, dv, n_vec, slots, ell, scale);
-    c.pool.free(dv);
 }
 
 // dv [n_vec][slots][2] complex slot values already on the device (overwritten) -> dst [n_vec][ell][N] encodings, NTT form
@@ -282,7 +281,7 @@ std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>
         ld_to_i128((long double)v[i].first * scale, coeffs[2 * (i * gap)], coeffs[2 * (i * gap) + 1]);
         ld_to_i128((long double)v[i].second * scale, coeffs[2 * (i * gap + N / 2)], coeffs[2 * (i * gap + N / 2) + 1]);
     }
-    u64* dco = c.dalloc<u64>(2 * N);
+    Scratch<u64> dco = c.scratch<u64>(2 * N);
     c.upload_async(dco, coeffs.data(), 2 * N);  // pinned staging: no stream drain (the GPU keeps its queue)
     auto e = std::make_shared<Encoding>();
     e->ctx = &c;
@@ -293,7 +292,6 @@ std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>
     c.stats.encode += 1;
     c.ntt(LimbBatch{e->d, ell, nullptr, 0, ell}, false);
     hip_check(hipGetLastError(), "encode kernels");
-    c.pool.free(dco);
     return e;
 }
 
@@ -359,7 +357,7 @@ void Client::sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind) 
         co[2 * i] = (u64)v;
         co[2 * i + 1] = v < 0 ? ~0ull : 0;
     }
-    u64* dco = c_.dalloc<u64>(2 * N);
+    Scratch<u64> dco = c_.scratch<u64>(2 * N);
     c_.upload_async(dco, co.data(), 2 * N);
     launch_reduce_i128(c_.dt, dst, dco, 0, nlimbs_q, c_.stream);
     launch_ntt(c_.dt, LimbBatch{dst, nlimbs_q, nullptr, 0, nlimbs_q}, false, c_.stream);
@@ -368,7 +366,6 @@ void Client::sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind) 
         launch_reduce_i128(c_.dt, dp, dco, c_.L + 1, c_.K, c_.stream);
         launch_ntt(c_.dt, LimbBatch{dp, c_.K, nullptr, c_.L + 1, c_.K}, false, c_.stream);
     }
-    c_.pool.free(dco);
 }
 
 void Client::install_public_key(u64* d_pk, bool seeded) {
@@ -408,22 +405,22 @@ void Client::keygen() {
         has_key_seed_ = true;
     }
     if (!s_all) s_all = c_.dalloc<u64>((size_t)nl * N);
-    u64* dco = c_.dalloc<u64>(2 * N);
+    Scratch<u64> dco = c_.scratch<u64>(2 * N);
     hip_check(hipMemcpyAsync(dco, co.data(), 2 * N * 8, hipMemcpyHostToDevice, c_.stream), "secret upload");
     hip_check(hipStreamSynchronize(c_.stream), "secret sync");
     launch_reduce_i128(c_.dt, s_all, dco, 0, nl, c_.stream);
     launch_ntt(c_.dt, LimbBatch{s_all, nl, nullptr, 0, nl}, false, c_.stream);
-    c_.pool.free(dco);
+    dco.reset();
     if (!pk) pk = c_.dalloc<u64>((size_t)2 * L1 * N);
     if (seeded_keys_) {
         // b = e - a s with a the expansion of (key-set seed, nonce of the public key) on the Q limbs, made in registers
-        u64* e = c_.dalloc<u64>((size_t)L1 * N);
+        Scratch<u64> e = c_.scratch<u64>((size_t)L1 * N);
         sample_small_device(e, 1, L1, 0);
         c_.ntt(LimbBatch{e, L1, nullptr, 0, L1}, false);
         launch_seeded_keygen_combine(c_.dt, pk, s_all, nullptr, e, L1, 1, c_.alpha, L1, nullptr, key_seed_words(), 0, 0, c_.stream);
         hip_check(hipGetLastError(), "seeded keygen kernels");
         hip_check(hipMemsetAsync(e, 0, (size_t)L1 * N * sizeof(u64), c_.stream), "hipMemsetAsync(key noise)");
-        c_.pool.free(e);
+        e.reset();
         pk_seeded_ = true;
         return;
     }
@@ -435,12 +432,11 @@ void Client::keygen() {
     u64* pa = pk + (size_t)L1 * N;
     hip_check(hipMemcpyAsync(pa, a.data(), a.size() * 8, hipMemcpyHostToDevice, c_.stream), "pk upload");
     hip_check(hipStreamSynchronize(c_.stream), "pk sync");
-    u64* e = c_.dalloc<u64>((size_t)L1 * N);
+    Scratch<u64> e = c_.scratch<u64>((size_t)L1 * N);
     sample_small_to_ntt(e, L1, false, 0);
     launch_ew_mul(c_.dt, pk, pa, s_all, L1, L1, 0, L1, c_.stream);
     launch_ew_sub(c_.dt, pk, e, pk, L1, L1, 0, L1, c_.stream);
     hip_check(hipGetLastError(), "keygen kernels");
-    c_.pool.free(e);
 }
 
 SamplerKey Client::key_seed_words() const {
@@ -466,7 +462,7 @@ KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 k
         if (L1 > KEYGEN_MAX_Q) throw Error(FHELIN_ERR_ARG, "seeded keys: more than 64 Q limbs");
         // every digit in one launch: e [digits][nl][N] from the device sampler, one forward NTT, then the fused combination
         const size_t en = (size_t)key->digits * nl * N;
-        u64* e = c_.dalloc<u64>(en);
+        Scratch<u64> e = c_.scratch<u64>(en);
         sample_small_device(e, key->digits, nl, 0);
         c_.ntt(LimbBatch{e, key->digits * nl, nullptr, 0, nl}, false);
         std::vector<u64> pm(L1);
@@ -480,13 +476,13 @@ KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 k
                                      galois, c_.stream);
         hip_check(hipGetLastError(), "seeded keygen kernels");
         hip_check(hipMemsetAsync(e, 0, en * sizeof(u64), c_.stream), "hipMemsetAsync(key noise)");
-        c_.pool.free(e);
+        e.reset();
         key->seeded = true;
         return key;
     }
     std::vector<u64> a((size_t)nl * N);
-    u64* e = c_.dalloc<u64>((size_t)nl * N);
-    u64* tmp = c_.dalloc<u64>((size_t)nl * N);
+    Scratch<u64> e = c_.scratch<u64>((size_t)nl * N);
+    Scratch<u64> tmp = c_.scratch<u64>((size_t)nl * N);
     for (int j = 0; j < key->digits; ++j) {
         u64* kb = key->d + (size_t)(2 * j) * nl * N;
         u64* ka = key->d + (size_t)(2 * j + 1) * nl * N;
@@ -513,8 +509,6 @@ KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 k
         launch_ew_add(c_.dt, kb + (size_t)lo * N, kb + (size_t)lo * N, tmp, hi - lo, hi - lo, lo, hi - lo, c_.stream);
     }
     hip_check(hipGetLastError(), "make_switch_key kernels");
-    c_.pool.free(e);
-    c_.pool.free(tmp);
     return key;
 }
 
@@ -524,10 +518,9 @@ void Client::gen_relin_key() {
         throw Error(FHELIN_ERR_KEY, eval_only_ ? "relinearisation key not in the evaluation-key set" : "keygen() has not been called");
     }
     const int nl = c_.L + 1 + c_.K;
-    u64* s2 = c_.dalloc<u64>((size_t)nl * c_.N);
+    Scratch<u64> s2 = c_.scratch<u64>((size_t)nl * c_.N);
     launch_ew_mul(c_.dt, s2, s_all, s_all, nl, nl, 0, nl, c_.stream);
     ev_.relin_key = make_switch_key(s2, s_all, 1, 0);
-    c_.pool.free(s2);
 }
 
 void Client::gen_rotation_key(int index) {
@@ -542,10 +535,9 @@ void Client::gen_rotation_key(int index) {
     const int nl = c_.L + 1 + c_.K;
     // key switches from s to sigma_{g^-1}(s); applying sigma_g afterwards restores s (oracle orc_rotate)
     const u64 ginv = c_.galois_element(-index);
-    u64* sp = c_.dalloc<u64>((size_t)nl * c_.N);
+    Scratch<u64> sp = c_.scratch<u64>((size_t)nl * c_.N);
     launch_automorph(c_.dt, sp, s_all, c_.automorph_map(ginv), nl, c_.stream);
     ev_.rot_keys[g] = make_switch_key(s_all, sp, 2, g);
-    c_.pool.free(sp);
 }
 
 void Client::gen_conj_key() {
@@ -555,11 +547,10 @@ void Client::gen_conj_key() {
     }
     const u64 g = 2ull * c_.N - 1;  // X -> X^{-1}; its own inverse
     const int nl = c_.L + 1 + c_.K;
-    u64* sp = c_.dalloc<u64>((size_t)nl * c_.N);
+    Scratch<u64> sp = c_.scratch<u64>((size_t)nl * c_.N);
     launch_automorph(c_.dt, sp, s_all, c_.automorph_map(g), nl, c_.stream);
     ev_.conj_key = make_switch_key(s_all, sp, 3, g);
     ev_.rot_keys[g] = ev_.conj_key;
-    c_.pool.free(sp);
 }
 
 PtPtr Client::encode(const double* vals, int n, int level, int slots) {
@@ -588,12 +579,12 @@ void Client::sample_small_device(u64* dst, int n_poly, int ell, int kind) {
 std::vector<long> Client::debug_sample(int kind, int n_poly) {
     c_.require_device();
     const size_t N = c_.N;
-    u64* d = c_.dalloc<u64>((size_t)n_poly * N);
+    Scratch<u64> d = c_.scratch<u64>((size_t)n_poly * N);
     sample_small_device(d, n_poly, 1, kind);
     std::vector<u64> h((size_t)n_poly * N);
     hip_check(hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, c_.stream), "sample download");
     hip_check(hipStreamSynchronize(c_.stream), "sample sync");
-    c_.pool.free(d);
+    d.reset();
     const u64 q0 = c_.chain.q[0];
     std::vector<long> out(h.size());
     for (size_t i = 0; i < h.size(); ++i) out[i] = h[i] > q0 / 2 ? -(long)(q0 - h[i]) : (long)h[i];
@@ -627,14 +618,14 @@ void Client::encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int e
         for (int i = 0; i < 8; ++i)
             key.w[i] = (u32)call_seed_[4 * i] | ((u32)call_seed_[4 * i + 1] << 8) | ((u32)call_seed_[4 * i + 2] << 16) |
                        ((u32)call_seed_[4 * i + 3] << 24);
-        u64* e = c.dalloc<u64>((size_t)n_vec * pn);              // e [n_vec][ell][N]
+        Scratch<u64> e = c.scratch<u64>((size_t)n_vec * pn);              // e [n_vec][ell][N]
         sample_small_device(e, n_vec, ell, 0);
         c.ntt(LimbBatch{e, n_vec * ell, nullptr, 0, ell}, false);
         launch_sk_encrypt_combine(c.dt, cts[0]->d, s_all, e, enc, enc_stride, ell, key, nonces, n_vec, c.stream);
         hip_check(hipGetLastError(), "secret-key encrypt kernels");
         // the encryption noise does not stay behind in a recycled pool block
         hip_check(hipMemsetAsync(e, 0, (size_t)n_vec * pn * sizeof(u64), c.stream), "hipMemsetAsync(encryption noise)");
-        c.pool.free(e);
+        e.reset();
         for (int b = 0; b < n_vec; ++b) {
             cts[b]->seeded = true;
             cts[b]->nonce = nonces[b];
@@ -643,7 +634,7 @@ void Client::encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int e
         for (auto& ct : cts) out.push_back(ct);
         return;
     }
-    u64* rnd = c.dalloc<u64>((size_t)3 * n_vec * pn);       // u | e0 | e1, each [n_vec][ell][N]
+    Scratch<u64> rnd = c.scratch<u64>((size_t)3 * n_vec * pn);       // u | e0 | e1, each [n_vec][ell][N]
     sample_small_device(rnd, n_vec, ell, 1);
     sample_small_device(rnd + (size_t)n_vec * pn, 2 * n_vec, ell, 0);
     c.ntt(LimbBatch{rnd, 3 * n_vec * ell, nullptr, 0, ell}, false);
@@ -652,7 +643,7 @@ void Client::encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int e
     hip_check(hipGetLastError(), "encrypt kernels");
     // the encryption randomness (u, e0, e1) does not stay behind in a recycled pool block
     hip_check(hipMemsetAsync(rnd, 0, (size_t)3 * n_vec * pn * sizeof(u64), c.stream), "hipMemsetAsync(encryption randomness)");
-    c.pool.free(rnd);
+    rnd.reset();
     for (auto& ct : cts) out.push_back(ct);
 }
 
@@ -681,12 +672,11 @@ std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_pe
     const int CHUNK = 32;                                    // bounds the temporaries (4 polynomials per vector in flight)
     for (int lo = 0; lo < n_vec; lo += CHUNK) {
         const int n = std::min(CHUNK, n_vec - lo);
-        u64* enc = c_.dalloc<u64>((size_t)n * pn);
+        Scratch<u64> enc = c_.scratch<u64>((size_t)n * pn);
         encode_batch_device(c_, enc, vals + (size_t)lo * n_per, nullptr, n, n_per, slots, ell, scale);
         u64 nonces[CHUNK];
         for (int k = 0; k < n; ++k) nonces[k] = nonce_of ? (u64)nonce_of[lo + k] : (u64)(lo + k);
         encrypt_encoded(enc, pn, n, ell, scale, slots, out, nonces);
-        c_.pool.free(enc);
     }
     return out;
 }
@@ -732,17 +722,13 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
     struct Temps {
         Context& c;
         hipStream_t s;
-        std::vector<std::pair<void*, size_t>> blocks;
+        std::vector<std::pair<Scratch<char>, size_t>> blocks;
         void* get(size_t bytes) {
-            void* d = c.pool.alloc(bytes);
-            blocks.emplace_back(d, bytes);
-            return d;
+            blocks.emplace_back(c.scratch<char>(bytes), bytes);
+            return blocks.back().first.get();
         }
-        ~Temps() {
-            for (auto& b : blocks) {
-                (void)hipMemsetAsync(b.first, 0, b.second, s);
-                try { c.pool.free(b.first); } catch (...) {}
-            }
+        ~Temps() {   // the wipes are queued first; the blocks' owners free them behind
+            for (auto& b : blocks) (void)hipMemsetAsync(b.first.get(), 0, b.second, s);
         }
     } tmp{c_, s, {}};
     auto up = [&](const void* h, size_t bytes) {
@@ -860,10 +846,9 @@ CtPtr Client::phase(const CtPtr& ct, int nl) {
     // m = c0 + c1 s (+ c2 s^2) on the first nl limbs
     launch_ew_muladd(c_.dt, m, ct->d, ct->d + pn, s_all, nl, nl, 0, nl, c_.stream);
     if (ct->npoly == 3) {
-        u64* s2 = c_.dalloc<u64>((size_t)nl * c_.N);
+        Scratch<u64> s2 = c_.scratch<u64>((size_t)nl * c_.N);
         launch_ew_mul(c_.dt, s2, s_all, s_all, nl, nl, 0, nl, c_.stream);
         launch_ew_muladd(c_.dt, m, m, ct->d + 2 * pn, s2, nl, nl, 0, nl, c_.stream);
-        c_.pool.free(s2);
     }
     hip_check(hipGetLastError(), "phase kernels");
     return o;

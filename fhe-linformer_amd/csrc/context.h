@@ -111,6 +111,47 @@ private:
     void raw_free(void* p);
 };
 
+// Owner of one block of pool scratch: freed when it goes out of scope (also when an exception unwinds through it), by reset()
+// for an early free, handed on by release().  An empty one frees nothing.  Two rules keep the pool's behaviour predictable:
+// the scope closes (or reset() is called) where the block is no longer needed - a block held across a later allocation raises the
+// pool's peak - and under the lane the block was allocated under, because a free under a foreign lane parks the block behind an
+// event (DevicePool::free).
+template <class T>
+class Scratch {
+public:
+    Scratch() = default;
+    Scratch(DevicePool& pool, size_t count) : pool_(&pool), p_(static_cast<T*>(pool.alloc(count * sizeof(T)))) {}
+    Scratch(Scratch&& o) noexcept : pool_(o.pool_), p_(o.release()) {}
+    Scratch& operator=(Scratch&& o) noexcept {
+        if (this != &o) {
+            drop();
+            pool_ = o.pool_;
+            p_ = o.release();
+        }
+        return *this;
+    }
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { drop(); }
+    operator T*() const& { return p_; }
+    operator T*() && = delete;   // a temporary's block would be gone before the pointer is used
+    T* get() const { return p_; }
+    void reset() {               // early free; errors surface as from DevicePool::free
+        if (T* p = release()) pool_->free(p);
+    }
+    T* release() noexcept {
+        T* p = p_;
+        p_ = nullptr;
+        return p;
+    }
+private:
+    void drop() noexcept {
+        try { reset(); } catch (...) {}
+    }
+    DevicePool* pool_ = nullptr;
+    T* p_ = nullptr;
+};
+
 // Per-level constants of hybrid key switching / rescale, resident on the device.
 struct LevelTables {
     int ell = 0;        // live Q limbs
@@ -227,7 +268,8 @@ struct Context {
     Context& operator=(const Context&) = delete;
 
     void require_device() const;
-    template <class T> T* dalloc(size_t count) { return static_cast<T*>(pool.alloc(count * sizeof(T))); }
+    template <class T> T* dalloc(size_t count) { return static_cast<T*>(pool.alloc(count * sizeof(T))); }   // for blocks with an owner of their own
+    template <class T> Scratch<T> scratch(size_t count) { return Scratch<T>(pool, count); }
     template <class T> const T* upload_table(const std::vector<T>& v);
     int limb_id_q(int i) const { return i; }
     int limb_id_p(int j) const { return L + 1 + j; }

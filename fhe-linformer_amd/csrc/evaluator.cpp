@@ -143,10 +143,8 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "hybrid key switching needs at least one special prime");
     if (B < 1) return;
     const size_t N = c_.N;
-    const int K = c_.K, L1 = c_.L + 1;
-    const LevelTables& lt = c_.lvl[ell];
-    const int nt = ell + K;
-    KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, c_stride, out_stride, add_stride, post_stride};
+    const int K = c_.K;
+    KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, c_stride, out_stride, add_stride, post_stride};
     const bool shared = rows && rows->shared_input;
     if (rows) {
         sh.per_row = 1;
@@ -156,68 +154,114 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
             sh.map_row[b] = rows->maps[b];
         }
     }
-    const int Bu = shared ? 1 : B;  // polynomials that go through ModUp
     KsShape shu = sh;
-    shu.batch = Bu;
-    hipStream_t s = c_.stream;
-    u64* cc = c_.dalloc<u64>((size_t)Bu * ell * N);
+    shu.batch = shared ? 1 : B;  // polynomials that go through ModUp
     c_.stats.keyswitch += (u64)B;
     c_.stats.keyswitch_limbs += (u64)B * ell;
+    Scratch<u64> ext = modup(shu, c_ntt, true);   // digits times 2^64: launch_ks_inner ends in redc128
+    Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
+    Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
+    launch_ks_inner(c_.dt, sh, accQ, accP, ext, key ? key->d : nullptr, c_ntt, c_.stream);
+    // the finish in the row pass of NTT(conv): always for an identity output map (relinearisation); for a rotation (written through
+    // the inverse automorphism map) only with FHELIN_FUSE_MODDOWN=1
+    const bool identity = !map && !rows;
+    moddown(sh, accQ, accP, out, add0, add1, map, post, c_.fuse_moddown || (c_.fuse_finish && identity));
+    launch_ok("keyswitch");
+}
+
+// ------------------------------------------------------------------------------------------------ key-switch stages
+// Every hybrid key switch of this file is ModUp -> its own inner product(s) -> one of the two tails below.  A change to the
+// pipeline (what the conversions compute, where a transform's epilogue takes over a finish) belongs HERE, once.
+
+// ModUp of up.batch polynomials of up.ell limbs, NTT form at src, up.c_stride words apart (group2 > 0: only within runs of group2
+// polynomials; the runs lie group2_stride apart): coefficient form, basis conversion of every digit to the other limbs of QP, forward NTT
+// of the converted limbs.  Returns the digits [up.batch][beta][ell+K][N], lazily reduced (below 2^60: only the inner products
+// read them); times_r2: times 2^64, for launch_ks_inner over the keys as they are stored.
+Scratch<u64> Evaluator::modup(const KsShape& up, const u64* src, bool times_r2, int group2, size_t group2_stride) {
+    const size_t N = c_.N;
+    const int n = up.batch, ell = up.ell, nt = ell + c_.K;
+    const LevelTables& lt = c_.lvl[ell];
+    Scratch<u64> cc = c_.scratch<u64>((size_t)n * ell * N);
     {
-        // out of place: cc = INTT(c); the inputs of a batch are strided (c1 of consecutive ciphertexts)
-        LimbBatch ib{cc, Bu * ell, nullptr, 0, ell, c_ntt};
-        if (Bu > 1 && c_stride != (size_t)ell * N) {
+        // out of place: cc = INTT(src); the inputs of a batch are strided (c1 of consecutive ciphertexts)
+        LimbBatch ib{cc, n * ell, nullptr, 0, ell, src};
+        if (n > 1 && up.c_stride != (size_t)ell * N) {
             ib.src_group = ell;
-            ib.src_group_stride = c_stride;
+            ib.src_group_stride = up.c_stride;
+        }
+        if (group2 > 0) {
+            ib.src_group2 = group2;
+            ib.src_group2_stride = group2_stride;
         }
         c_.ntt(ib, true);
     }
-    u64* ext = c_.dalloc<u64>((size_t)Bu * lt.beta * nt * N);
-    launch_modup_conv(c_.dt, shu, ext, cc, c_ntt, lt.up_hatinv, lt.up_hatmod_r2, s);   // digits times 2^64: launch_ks_inner ends in redc128
-    LimbBatch eb{ext, Bu * lt.beta * nt, lt.ext_limb_tab, 0, 1};
+    Scratch<u64> ext = c_.scratch<u64>((size_t)n * lt.beta * nt * N);
+    launch_modup_conv(c_.dt, up, ext, cc, src, lt.up_hatinv, times_r2 ? lt.up_hatmod_r2 : lt.up_hatmod, c_.stream);
+    LimbBatch eb{ext, n * lt.beta * nt, lt.ext_limb_tab, 0, 1};
     eb.tab_len = lt.beta * nt;
-    eb.lazy_out = true;  // only K7 reads the digits: it takes any residue below 2^60
-    c_.ntt(eb, false, Bu * (lt.beta * nt - ell));
-    u64* accQ = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-    u64* accP = c_.dalloc<u64>((size_t)B * 2 * K * N);
-    launch_ks_inner(c_.dt, sh, accQ, accP, ext, key ? key->d : nullptr, c_ntt, s);
-    c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, L1, K}, true);
-    u64* conv = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-    launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, s);
-    // K8b rides in the row pass of NTT(conv): (accQ - NTT(conv)) * P^-1 + add (+ post) is formed in registers — NTT(conv) never
-    // goes to memory.  Always for an identity output map (relinearisation); for a rotation (written through the inverse
-    // automorphism map) only with FHELIN_FUSE_MODDOWN=1.
-    const bool identity = !map && !rows;
-    if (c_.fuse_moddown || (c_.fuse_finish && identity)) {
+    eb.lazy_out = true;  // only the inner products read the digits: they take any residue below 2^60
+    c_.ntt(eb, false, n * (lt.beta * nt - ell));
+    return ext;
+}
+
+// ModDown of the accumulator pair accQ [sh.batch][2][ell][N], accP [sh.batch][2][K][N] (accP is transformed in place):
+// out = (accQ - NTT(conv(INTT(accP)))) * P^-1 + add0/add1 (+ post), written through `map` / the rows' maps.
+// row_pass: the finish rides in the row pass of NTT(conv) - (accQ - NTT(conv)) * P^-1 + add (+ post) is formed in registers and
+// NTT(conv) never goes to memory; else launch_moddown_finish reads the stored transform.
+// finish (optional): called with NTT(conv) [sh.batch][2][ell][N] in place of the one launch_moddown_finish over all rows (a caller whose
+// rows need several finish launches over slices); out .. post are then unused.
+void Evaluator::moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map,
+                        const u64* post, bool row_pass, const std::function<void(const u64* conv)>& finish) {
+    const size_t N = c_.N;
+    const int B = sh.batch, ell = sh.ell, K = c_.K;
+    c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, c_.L + 1, K}, true);
+    Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * ell * N);
+    launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, c_.stream);
+    const LimbBatch cb{conv, B * 2 * ell, nullptr, 0, ell};
+    if (row_pass) {
         NttEpilogue ep;
         ep.acc = accQ;
         ep.acc_poly_stride = (size_t)ell * N;
         ep.out = out;
-        ep.out_stride = out_stride;
+        ep.out_stride = sh.out_stride;
         ep.w = c_.d_pinv;
         ep.ell = ell;
         ep.add0 = add0;
         ep.add1 = add1;
-        ep.add_stride = add_stride;
+        ep.add_stride = sh.add_stride;
         ep.post = post;
-        ep.post_stride = post_stride;
-        if (rows) {
+        ep.post_stride = sh.post_stride;
+        if (sh.per_row) {
             ep.per_row = 1;
-            for (int b = 0; b < B; ++b) ep.invmap_row[b] = c_.automorph_inverse_of(rows->maps[b]);
+            for (int b = 0; b < B; ++b) ep.invmap_row[b] = c_.automorph_inverse_of(sh.map_row[b]);
         } else if (map) {
             ep.invmap = c_.automorph_inverse_of(map);
         }
-        c_.ntt_epilogue(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, ep);
-    } else {
-        c_.ntt(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, false);
-        launch_moddown_finish(c_.dt, sh, out, accQ, conv, c_.d_pinv, add0, add1, map, post, s);
+        c_.ntt_epilogue(cb, ep);
+        return;
     }
-    launch_ok("keyswitch");
-    c_.pool.free(cc);
-    c_.pool.free(ext);
-    c_.pool.free(accQ);
-    c_.pool.free(accP);
-    c_.pool.free(conv);
+    c_.ntt(cb, false);
+    if (finish) finish(conv);
+    else launch_moddown_finish(c_.dt, sh, out, accQ, conv, c_.d_pinv, add0, add1, map, post, c_.stream);
+}
+
+// ModDown and rescale as ONE basis conversion (sh.ell >= 2, K + 1 <= 16): P and the top limb of the accumulator pair are dropped together,
+// out [sh.batch][2][ell-1][N] (sh.out_stride apart) = (accQ - NTT(conv(INTT(accP), INTT(top limb of accQ)))) * (P q_top)^-1
+void Evaluator::moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out) {
+    const size_t N = c_.N;
+    const int B = sh.batch, ell = sh.ell, K = c_.K;
+    const LevelTables& lt = c_.lvl[ell];
+    c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, c_.L + 1, K}, true);
+    Scratch<u64> top = c_.scratch<u64>((size_t)B * 2 * N);
+    {
+        LimbBatch tb{top, B * 2, nullptr, ell - 1, 1, accQ + (size_t)(ell - 1) * N};
+        tb.src_group = 1;
+        tb.src_group_stride = (size_t)ell * N;
+        c_.ntt(tb, true);
+    }
+    Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * (ell - 1) * N);
+    launch_moddown_rescale_conv(c_.dt, sh, conv, accP, top, lt.md_hatinv, lt.md_hatmod, lt.md_mmod, c_.stream);
+    moddown_rescale_finish(sh, out, accQ, conv, lt.md_minv);
 }
 
 // the row pass of NTT(conv) finishes (accQ - NTT(conv)) * minv into out (FHELIN_FUSE_FINISH=0: moddown_rescale_finish_kernel)
@@ -292,7 +336,6 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
         const int B = (int)chunk.size(), ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
         const LevelTables& lt = c_.lvl[ell];
-        const int nt = ell + K;
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
         const u64* base = chunk[0]->d;
         KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, ctw, ctw, pn, ctw};
@@ -310,47 +353,24 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
         while ((1 << steps) < R + 1) ++steps;
         c_.stats.keyswitch += (u64)B * steps;
         c_.stats.keyswitch_limbs += (u64)B * steps * ell;
-        // ModUp of c1, once for all rotations
-        u64* cc = c_.dalloc<u64>((size_t)B * ell * N);
         {
-            LimbBatch ib{cc, B * ell, nullptr, 0, ell, base + pn};
-            if (B > 1) {
-                ib.src_group = ell;
-                ib.src_group_stride = ctw;
+            Scratch<u64> ext = modup(sh, base + pn, false);   // of c1, once for all rotations
+            // all rotated inner products, gathered and accumulated in the extended basis; the c0 parts likewise
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
+            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
+            Scratch<u64> c0sum;
+            if (c_.fuse_gather) {
+                sh.gsrc = base;      // the epilogue gathers the rotated c0 parts itself
+                sh.gsrc_stride = ctw;
+            } else {
+                c0sum = c_.scratch<u64>((size_t)B * ell * N);
+                launch_gather_sum(c_.dt, sh, c0sum, base, ctw, s);
             }
-            c_.ntt(ib, true);
+            // one ModDown; the epilogue adds the gathered c0 parts and the unrotated input
+            moddown(sh, accQ, accP, o[0]->d, c0sum, nullptr, nullptr, base);
+            launch_ok("rotate_sum_batch");
         }
-        u64* ext = c_.dalloc<u64>((size_t)B * lt.beta * nt * N);
-        launch_modup_conv(c_.dt, sh, ext, cc, base + pn, lt.up_hatinv, lt.up_hatmod, s);
-        LimbBatch eb{ext, B * lt.beta * nt, lt.ext_limb_tab, 0, 1};
-        eb.tab_len = lt.beta * nt;
-        eb.lazy_out = true;
-        c_.ntt(eb, false, B * (lt.beta * nt - ell));
-        // all rotated inner products, gathered and accumulated in the extended basis; the c0 parts likewise
-        u64* accQ = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-        u64* accP = c_.dalloc<u64>((size_t)B * 2 * K * N);
-        launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-        u64* c0sum = nullptr;
-        if (c_.fuse_gather) {
-            sh.gsrc = base;      // the epilogue gathers the rotated c0 parts itself
-            sh.gsrc_stride = ctw;
-        } else {
-            c0sum = c_.dalloc<u64>((size_t)B * ell * N);
-            launch_gather_sum(c_.dt, sh, c0sum, base, ctw, s);
-        }
-        // one ModDown; the epilogue adds the gathered c0 parts and the unrotated input
-        c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, L1, K}, true);
-        u64* conv = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-        launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, s);
-        c_.ntt(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, false);
-        launch_moddown_finish(c_.dt, sh, o[0]->d, accQ, conv, c_.d_pinv, c0sum, nullptr, nullptr, base, s);
-        launch_ok("rotate_sum_batch");
-        c_.pool.free(cc);
-        c_.pool.free(ext);
-        c_.pool.free(accQ);
-        c_.pool.free(accP);
-        if (c0sum) c_.pool.free(c0sum);
-        c_.pool.free(conv);
         for (int b = 0; b < B; ++b) {
             o[b]->scale = vin[idx[b]]->scale;
             out[idx[b]] = o[b];
@@ -449,7 +469,6 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
         const int B = (int)chunk.size(), ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
         const LevelTables& lt = c_.lvl[ell];
-        const int nt = ell + K;
         const long double sf = c_.sf_real[chunk[0]->level()];
         const bool merged = rescale_out && ell >= 2 && K + 1 <= 16;
         if (rescale_out && !merged) throw Error(FHELIN_ERR_STATE, "hoisted_dot_rows: no limb left to drop");
@@ -480,64 +499,26 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
             c_.stats.rescale += (u64)B;
             c_.stats.rescale_limbs += (u64)B * ell;
         }
-        // ModUp of c1, once for all rotations
-        u64* cc = c_.dalloc<u64>((size_t)B * ell * N);
         {
-            LimbBatch ib{cc, B * ell, nullptr, 0, ell, base + pn};
-            if (B > 1) {
-                ib.src_group = ell;
-                ib.src_group_stride = ctw;
+            Scratch<u64> ext = modup(sh, base + pn, false);   // of c1, once for all rotations
+            // sum_r V_r . sigma_r(d * evk_r) in the extended basis: the merged inner product with the folded keys
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
+            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
+            if (!merged) {
+                // what does not pass through the key switch: V_0 (c0, c1) + sum_r V_r sigma_r(c0)
+                Scratch<u64> pre = c_.scratch<u64>((size_t)B * ctw);
+                launch_hoist_addends(c_.dt, sh, h, pre, base, s);
+                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, pre);   // one ModDown
+            } else {
+                // the same addends times P into the accumulator's Q part, then P and the top limb are dropped together
+                h.acc = accQ;
+                h.pmod = c_.d_pmod;
+                launch_hoist_addends(c_.dt, sh, h, nullptr, base, s);
+                moddown_rescale(sh, accQ, accP, o[0]->d);
             }
-            c_.ntt(ib, true);
+            launch_ok("hoisted_dot_rows");
         }
-        u64* ext = c_.dalloc<u64>((size_t)B * lt.beta * nt * N);
-        launch_modup_conv(c_.dt, sh, ext, cc, base + pn, lt.up_hatinv, lt.up_hatmod, s);
-        LimbBatch eb{ext, B * lt.beta * nt, lt.ext_limb_tab, 0, 1};
-        eb.tab_len = lt.beta * nt;
-        eb.lazy_out = true;
-        c_.ntt(eb, false, B * (lt.beta * nt - ell));
-        // sum_r V_r . sigma_r(d * evk_r) in the extended basis: the merged inner product with the folded keys
-        u64* accQ = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-        u64* accP = c_.dalloc<u64>((size_t)B * 2 * K * N);
-        launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-        u64* pre = nullptr;
-        u64* conv = nullptr;
-        u64* top = nullptr;
-        if (!merged) {
-            // what does not pass through the key switch: V_0 (c0, c1) + sum_r V_r sigma_r(c0)
-            pre = c_.dalloc<u64>((size_t)B * ctw);
-            launch_hoist_addends(c_.dt, sh, h, pre, base, s);
-            // one ModDown
-            c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, L1, K}, true);
-            conv = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-            launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, s);
-            c_.ntt(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, false);
-            launch_moddown_finish(c_.dt, sh, o[0]->d, accQ, conv, c_.d_pinv, nullptr, nullptr, nullptr, pre, s);
-        } else {
-            // the same addends times P into the accumulator's Q part, then P and the top limb are dropped together
-            h.acc = accQ;
-            h.pmod = c_.d_pmod;
-            launch_hoist_addends(c_.dt, sh, h, nullptr, base, s);
-            c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, L1, K}, true);
-            top = c_.dalloc<u64>((size_t)B * 2 * N);
-            {
-                LimbBatch tb{top, B * 2, nullptr, ell - 1, 1, accQ + (size_t)(ell - 1) * N};
-                tb.src_group = 1;
-                tb.src_group_stride = pn;
-                c_.ntt(tb, true);
-            }
-            conv = c_.dalloc<u64>((size_t)B * 2 * (ell - 1) * N);
-            launch_moddown_rescale_conv(c_.dt, sh, conv, accP, top, lt.md_hatinv, lt.md_hatmod, lt.md_mmod, s);
-            moddown_rescale_finish(sh, o[0]->d, accQ, conv, lt.md_minv);
-        }
-        launch_ok("hoisted_dot_rows");
-        c_.pool.free(cc);
-        c_.pool.free(ext);
-        c_.pool.free(accQ);
-        c_.pool.free(accP);
-        if (pre) c_.pool.free(pre);
-        if (top) c_.pool.free(top);
-        c_.pool.free(conv);
         for (int b = 0; b < B; ++b) {
             o[b]->scale = x[idx[b]]->scale * sf;
             if (merged) o[b]->scale = o[b]->scale / (long double)c_.chain.q[ell - 1];
@@ -584,57 +565,36 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
         const int nt = ell + K;
         hipStream_t s = c_.stream;
         const u64* base = chunk[0]->d;
-        // ModUp of the R inputs as one batch
-        KsShape up{ell, K, c_.alpha, lt.beta, L1, R, ctw, 0, 0, 0};
-        u64* cc = c_.dalloc<u64>((size_t)R * ell * N);
-        {
-            LimbBatch ib{cc, R * ell, nullptr, 0, ell, base + pn};
-            ib.src_group = ell;
-            ib.src_group_stride = ctw;
-            c_.ntt(ib, true);
-        }
-        u64* ext = c_.dalloc<u64>((size_t)R * lt.beta * nt * N);
-        launch_modup_conv(c_.dt, up, ext, cc, base + pn, lt.up_hatinv, lt.up_hatmod, s);
-        LimbBatch eb{ext, R * lt.beta * nt, lt.ext_limb_tab, 0, 1};
-        eb.tab_len = lt.beta * nt;
-        eb.lazy_out = true;
-        c_.ntt(eb, false, R * (lt.beta * nt - ell));
-        // one accumulator for all R rotated inner products, one ModDown
-        KsShape sh{ell, K, c_.alpha, lt.beta, L1, 1, 0, ctw, pn, 0};
-        sh.n_rot = R;
-        sh.rot_ext_stride = (size_t)lt.beta * nt * N;
-        sh.rot_input_stride = ctw;
-        for (int r = 0; r < R; ++r) {
-            const u64 g = c_.galois_element(ridx[first + r]);
-            sh.map_rot[r] = c_.automorph_map(g);
-            sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
-        }
-        c_.stats.keyswitch += (u64)R;
-        c_.stats.keyswitch_limbs += (u64)R * ell;
-        u64* accQ = c_.dalloc<u64>((size_t)2 * ell * N);
-        u64* accP = c_.dalloc<u64>((size_t)2 * K * N);
-        launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-        u64* c0sum = nullptr;
-        if (c_.fuse_gather) {
-            sh.gsrc = base;
-            sh.gsrc_stride = 0;
-        } else {
-            c0sum = c_.dalloc<u64>((size_t)ell * N);
-            launch_gather_sum(c_.dt, sh, c0sum, base, 0, s);
-        }
-        c_.ntt(LimbBatch{accP, 2 * K, nullptr, L1, K}, true);
-        u64* conv = c_.dalloc<u64>((size_t)2 * ell * N);
-        launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, s);
-        c_.ntt(LimbBatch{conv, 2 * ell, nullptr, 0, ell}, false);
         CtPtr o = new_ct(2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
-        launch_moddown_finish(c_.dt, sh, o->d, accQ, conv, c_.d_pinv, c0sum, nullptr, nullptr, nullptr, s);
-        launch_ok("rotate_each_sum");
-        c_.pool.free(cc);
-        c_.pool.free(ext);
-        c_.pool.free(accQ);
-        c_.pool.free(accP);
-        if (c0sum) c_.pool.free(c0sum);
-        c_.pool.free(conv);
+        {
+            // ModUp of the R inputs as one batch
+            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, R, ctw, 0, 0, 0}, base + pn, false);
+            // one accumulator for all R rotated inner products, one ModDown
+            KsShape sh{ell, K, c_.alpha, lt.beta, L1, 1, 0, ctw, pn, 0};
+            sh.n_rot = R;
+            sh.rot_ext_stride = (size_t)lt.beta * nt * N;
+            sh.rot_input_stride = ctw;
+            for (int r = 0; r < R; ++r) {
+                const u64 g = c_.galois_element(ridx[first + r]);
+                sh.map_rot[r] = c_.automorph_map(g);
+                sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
+            }
+            c_.stats.keyswitch += (u64)R;
+            c_.stats.keyswitch_limbs += (u64)R * ell;
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)2 * K * N);
+            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
+            Scratch<u64> c0sum;
+            if (c_.fuse_gather) {
+                sh.gsrc = base;
+                sh.gsrc_stride = 0;
+            } else {
+                c0sum = c_.scratch<u64>((size_t)ell * N);
+                launch_gather_sum(c_.dt, sh, c0sum, base, 0, s);
+            }
+            moddown(sh, accQ, accP, o->d, c0sum, nullptr, nullptr, nullptr);
+            launch_ok("rotate_each_sum");
+        }
         acc = acc ? add(acc, o) : o;
     }
     return acc;
@@ -699,53 +659,31 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
             row_stride = (size_t)R * ctw;
         }
         const u64* base = flat[0]->d;
-        KsShape up{ell, K, c_.alpha, lt.beta, L1, B * R, ctw, 0, 0, 0};
-        u64* cc = c_.dalloc<u64>((size_t)B * R * ell * N);
-        {
-            LimbBatch ib{cc, B * R * ell, nullptr, 0, ell, base + pn};
-            ib.src_group = ell;
-            ib.src_group_stride = ctw;
-            if (row_stride != (size_t)R * ctw) {
-                ib.src_group2 = R;
-                ib.src_group2_stride = row_stride;
-            }
-            c_.ntt(ib, true);
-        }
-        u64* ext = c_.dalloc<u64>((size_t)B * R * lt.beta * nt * N);
-        launch_modup_conv(c_.dt, up, ext, cc, base + pn, lt.up_hatinv, lt.up_hatmod, s);
-        LimbBatch eb{ext, B * R * lt.beta * nt, lt.ext_limb_tab, 0, 1};
-        eb.tab_len = lt.beta * nt;
-        eb.lazy_out = true;
-        c_.ntt(eb, false, B * R * (lt.beta * nt - ell));
-        KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, row_stride, ctw, pn, 0};
-        sh.n_rot = R;
-        sh.rot_ext_stride = (size_t)lt.beta * nt * N;
-        sh.rot_input_stride = ctw;
-        sh.ext_batch_stride = (size_t)R * lt.beta * nt * N;
-        for (int r = 0; r < R; ++r) {
-            const u64 g = c_.galois_element(ridx[r]);
-            sh.map_rot[r] = c_.automorph_map(g);
-            sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
-        }
-        sh.gsrc = base;
-        sh.gsrc_stride = row_stride;
-        c_.stats.keyswitch += (u64)B * R;
-        c_.stats.keyswitch_limbs += (u64)B * R * ell;
-        u64* accQ = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-        u64* accP = c_.dalloc<u64>((size_t)B * 2 * K * N);
-        launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-        c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, L1, K}, true);
-        u64* conv = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-        launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, s);
-        c_.ntt(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, false);
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell, f->deg, f->scale, f->slots);
-        launch_moddown_finish(c_.dt, sh, o[0]->d, accQ, conv, c_.d_pinv, nullptr, nullptr, nullptr, nullptr, s);
-        launch_ok("rotate_each_sum_rows");
-        c_.pool.free(cc);
-        c_.pool.free(ext);
-        c_.pool.free(accQ);
-        c_.pool.free(accP);
-        c_.pool.free(conv);
+        {
+            const bool spaced = row_stride != (size_t)R * ctw;   // the rows' runs of R terms lie further apart than the terms
+            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B * R, ctw, 0, 0, 0}, base + pn, false, spaced ? R : 0,
+                                     spaced ? row_stride : 0);
+            KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, row_stride, ctw, pn, 0};
+            sh.n_rot = R;
+            sh.rot_ext_stride = (size_t)lt.beta * nt * N;
+            sh.rot_input_stride = ctw;
+            sh.ext_batch_stride = (size_t)R * lt.beta * nt * N;
+            for (int r = 0; r < R; ++r) {
+                const u64 g = c_.galois_element(ridx[r]);
+                sh.map_rot[r] = c_.automorph_map(g);
+                sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
+            }
+            sh.gsrc = base;
+            sh.gsrc_stride = row_stride;
+            c_.stats.keyswitch += (u64)B * R;
+            c_.stats.keyswitch_limbs += (u64)B * R * ell;
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
+            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
+            moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr);
+            launch_ok("rotate_each_sum_rows");
+        }
         for (int b = 0; b < B; ++b) out[lo + b] = o[b];
     }
     // unrotated terms are plain additions, in the order rotate_each_sum adds them: plain terms first, then the rotated sum
@@ -880,7 +818,7 @@ void Evaluator::lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const
 void Evaluator::rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell, const u64* qlinv_row, const u64* qlm_row) {
     const size_t N = c_.N;
     const u64* qlinv = qlinv_row ? qlinv_row : c_.d_qlinv + (size_t)(ell - 1) * (c_.L + 1) * 2;
-    u64* lifted = c_.dalloc<u64>((size_t)P * (ell - 1) * N);
+    Scratch<u64> lifted = c_.scratch<u64>((size_t)P * (ell - 1) * N);
     if (c_.fuse_finish) {
         NttEpilogue ep;
         ep.acc = c;
@@ -894,14 +832,13 @@ void Evaluator::rescale_finish(u64* out, const u64* c, const u64* last, int P, i
         lift_and_ntt(lifted, last, P, ell, nullptr, qlm_row);
         launch_rescale_finish(c_.dt, out, c, lifted, P, ell, qlinv, c_.stream);
     }
-    c_.pool.free(lifted);
 }
 
 CtPtr Evaluator::raw_rescale(const CtPtr& a) {
     const int ell = a->ell, P = a->npoly;
     if (ell < 2) throw Error(FHELIN_ERR_STATE, "rescale: no limb left to drop");
     const size_t N = c_.N;
-    u64* last = c_.dalloc<u64>((size_t)P * N);
+    Scratch<u64> last = c_.scratch<u64>((size_t)P * N);
     c_.stats.rescale += 1;
     c_.stats.rescale_limbs += (u64)ell;
     {
@@ -914,7 +851,6 @@ CtPtr Evaluator::raw_rescale(const CtPtr& a) {
     CtPtr o = new_ct(P, ell - 1, a->deg, a->scale, a->slots);
     rescale_finish(o->d, a->d, last, P, ell);
     launch_ok("rescale");
-    c_.pool.free(last);
     return o;
 }
 
@@ -1033,90 +969,62 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
         const int rows = B * R;
         c_.stats.keyswitch += (u64)rows;
         c_.stats.keyswitch_limbs += (u64)rows * ell;
-        // ModUp of the B inputs' c1, once
-        KsShape up{ell, K, c_.alpha, lt.beta, L1, B, ctw, 0, 0, 0};
-        u64* cc = c_.dalloc<u64>((size_t)B * ell * N);
+        std::vector<CtPtr> o = new_ct_batch(rows, 2, ell, xs[lo]->deg, xs[lo]->scale, xs[lo]->slots);
         {
-            LimbBatch ib{cc, B * ell, nullptr, 0, ell, base + pn};
-            if (B > 1) {
-                ib.src_group = ell;
-                ib.src_group_stride = ctw;
-            }
-            c_.ntt(ib, true);
-        }
-        u64* ext = c_.dalloc<u64>((size_t)B * lt.beta * nt * N);
-        launch_modup_conv(c_.dt, up, ext, cc, base + pn, lt.up_hatinv, lt.up_hatmod_r2, s);   // digits times 2^64: launch_ks_inner ends in redc128
-        LimbBatch eb{ext, B * lt.beta * nt, lt.ext_limb_tab, 0, 1};
-        eb.tab_len = lt.beta * nt;
-        eb.lazy_out = true;
-        c_.ntt(eb, false, B * (lt.beta * nt - ell));
-        // inner products: per input, rows of <= MAX_ROWS indices with their own keys, all reading that input's digits
-        u64* accQ = c_.dalloc<u64>((size_t)rows * 2 * ell * N);
-        u64* accP = c_.dalloc<u64>((size_t)rows * 2 * K * N);
-        // ONE launch per chunk of <= MAX_ROWS indices over ALL inputs (KsShape::row_mod): row (i, r) = rotation r of input i; in the
-        // XCD-aware block order a key tile is fetched once for all inputs and a digit tile once for all indices
-        auto row_shape = [&](int first, int cnt) {
-            KsShape sh{ell, K, c_.alpha, lt.beta, L1, B * cnt, ctw, ctw, ctw, 0};
-            sh.per_row = 1;
-            sh.shared_input = 1;
-            sh.row_mod = cnt;
-            sh.ext_batch_stride = (size_t)lt.beta * nt * N;
-            for (int b = 0; b < cnt; ++b) {
-                sh.evk_row[b] = keys[first + b]->d;
-                sh.map_row[b] = maps[first + b];
-            }
-            return sh;
-        };
-        const bool one_chunk = R <= (int)KsShape::MAX_ROWS;     // rows then lie [input][index] as the outputs do
-        if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), accQ, accP, ext, nullptr, base + pn, s);
-        else
-            for (int i = 0; i < B; ++i)
-                for (int first = 0; first < R; first += KsShape::MAX_ROWS) {
-                    const int cnt = std::min(R - first, (int)KsShape::MAX_ROWS);
-                    const size_t row0 = (size_t)i * R + first;
-                    KsShape sh1{ell, K, c_.alpha, lt.beta, L1, cnt, 0, ctw, 0, 0};
-                    sh1.per_row = 1;
-                    sh1.shared_input = 1;
-                    for (int b = 0; b < cnt; ++b) {
-                        sh1.evk_row[b] = keys[first + b]->d;
-                        sh1.map_row[b] = maps[first + b];
+            // ModUp of the B inputs' c1, once; digits times 2^64: launch_ks_inner ends in redc128
+            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B, ctw, 0, 0, 0}, base + pn, true);
+            // inner products: per input, rows of <= MAX_ROWS indices with their own keys, all reading that input's digits
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)rows * 2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)rows * 2 * K * N);
+            // ONE launch per chunk of <= MAX_ROWS indices over ALL inputs (KsShape::row_mod): row (i, r) = rotation r of input i; in the
+            // XCD-aware block order a key tile is fetched once for all inputs and a digit tile once for all indices
+            auto row_shape = [&](int first, int cnt) {
+                KsShape sh{ell, K, c_.alpha, lt.beta, L1, B * cnt, ctw, ctw, ctw, 0};
+                sh.per_row = 1;
+                sh.shared_input = 1;
+                sh.row_mod = cnt;
+                sh.ext_batch_stride = (size_t)lt.beta * nt * N;
+                for (int b = 0; b < cnt; ++b) {
+                    sh.evk_row[b] = keys[first + b]->d;
+                    sh.map_row[b] = maps[first + b];
+                }
+                return sh;
+            };
+            // R > MAX_ROWS: per input and per chunk of <= MAX_ROWS indices, launch(shape, first row of the chunk, input)
+            auto for_row_chunks = [&](auto&& launch) {
+                for (int i = 0; i < B; ++i)
+                    for (int first = 0; first < R; first += KsShape::MAX_ROWS) {
+                        const int cnt = std::min(R - first, (int)KsShape::MAX_ROWS);
+                        KsShape sh1{ell, K, c_.alpha, lt.beta, L1, cnt, 0, ctw, 0, 0};
+                        sh1.per_row = 1;
+                        sh1.shared_input = 1;
+                        for (int b = 0; b < cnt; ++b) {
+                            sh1.evk_row[b] = keys[first + b]->d;
+                            sh1.map_row[b] = maps[first + b];
+                        }
+                        launch(sh1, (size_t)i * R + first, i);
                     }
+            };
+            const bool one_chunk = R <= (int)KsShape::MAX_ROWS;     // rows then lie [input][index] as the outputs do
+            if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), accQ, accP, ext, nullptr, base + pn, s);
+            else
+                for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
                     launch_ks_inner(c_.dt, sh1, accQ + row0 * 2 * ell * N, accP + row0 * 2 * K * N, ext + (size_t)i * lt.beta * nt * N, nullptr,
                                     base + pn + (size_t)i * ctw, s);
-                }
-        // ONE ModDown over all rows
-        KsShape dn{ell, K, c_.alpha, lt.beta, L1, rows, 0, ctw, 0, 0};
-        c_.ntt(LimbBatch{accP, rows * 2 * K, nullptr, L1, K}, true);
-        u64* conv = c_.dalloc<u64>((size_t)rows * 2 * ell * N);
-        launch_moddown_conv(c_.dt, dn, conv, accP, c_.d_phatinv, c_.d_phatmod, s);
-        c_.ntt(LimbBatch{conv, rows * 2 * ell, nullptr, 0, ell}, false);
-        std::vector<CtPtr> o = new_ct_batch(rows, 2, ell, xs[lo]->deg, xs[lo]->scale, xs[lo]->slots);
-        // the epilogue adds the input's c0 (gathered through each row's map)
-        if (one_chunk) {
-            launch_moddown_finish(c_.dt, row_shape(0, R), o[0]->d, accQ, conv, c_.d_pinv, base, nullptr, nullptr, nullptr, s);
-        } else {
-            for (int i = 0; i < B; ++i)
-                for (int first = 0; first < R; first += KsShape::MAX_ROWS) {
-                    const int cnt = std::min(R - first, (int)KsShape::MAX_ROWS);
-                    const size_t row0 = (size_t)i * R + first;
-                    KsShape sh1{ell, K, c_.alpha, lt.beta, L1, cnt, 0, ctw, 0, 0};
-                    sh1.per_row = 1;
-                    sh1.shared_input = 1;
-                    for (int b = 0; b < cnt; ++b) {
-                        sh1.evk_row[b] = keys[first + b]->d;
-                        sh1.map_row[b] = maps[first + b];
-                    }
-                    // add_stride 0 = the same c0 for every row
-                    launch_moddown_finish(c_.dt, sh1, o[row0]->d, accQ + row0 * 2 * ell * N, conv + row0 * 2 * ell * N, c_.d_pinv,
-                                          base + (size_t)i * ctw, nullptr, nullptr, nullptr, s);
-                }
+                });
+            // ONE ModDown over all rows; the epilogue adds the input's c0 (gathered through each row's map)
+            moddown(KsShape{ell, K, c_.alpha, lt.beta, L1, rows, 0, ctw, 0, 0}, accQ, accP, nullptr, nullptr, nullptr, nullptr, nullptr, false,
+                    [&](const u64* conv) {
+                        if (one_chunk) launch_moddown_finish(c_.dt, row_shape(0, R), o[0]->d, accQ, conv, c_.d_pinv, base, nullptr, nullptr, nullptr, s);
+                        else
+                            for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
+                                // add_stride 0 = the same c0 for every row
+                                launch_moddown_finish(c_.dt, sh1, o[row0]->d, accQ + row0 * 2 * ell * N, conv + row0 * 2 * ell * N, c_.d_pinv,
+                                                      base + (size_t)i * ctw, nullptr, nullptr, nullptr, s);
+                            });
+                    });
+            launch_ok("rotate_many_batch");
         }
-        launch_ok("rotate_many_batch");
-        c_.pool.free(cc);
-        c_.pool.free(ext);
-        c_.pool.free(accQ);
-        c_.pool.free(accP);
-        c_.pool.free(conv);
         for (int i = 0; i < B; ++i)
             for (int r = 0; r < R; ++r) {
                 o[(size_t)i * R + r]->scale = xs[lo + i]->scale;
@@ -1147,7 +1055,7 @@ std::vector<CtPtr> Evaluator::rescale_batch(const std::vector<CtPtr>& vin) {
         if (ell < 2) throw Error(FHELIN_ERR_STATE, "rescale: no limb left to drop");
         const size_t N = c_.N;
         const u64* base = chunk[0]->d;
-        u64* last = c_.dalloc<u64>((size_t)P * N);
+        Scratch<u64> last = c_.scratch<u64>((size_t)P * N);
         c_.stats.rescale += (u64)B;
         c_.stats.rescale_limbs += (u64)B * ell;
         LimbBatch lb{last, P, nullptr, ell - 1, 1, base + (size_t)(ell - 1) * N};
@@ -1157,7 +1065,7 @@ std::vector<CtPtr> Evaluator::rescale_batch(const std::vector<CtPtr>& vin) {
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell - 1, 1, 0, chunk[0]->slots);
         rescale_finish(o[0]->d, base, last, P, ell);
         launch_ok("rescale_batch");
-        c_.pool.free(last);
+        last.reset();
         for (int b = 0; b < B; ++b) {
             const CtPtr& a = vin[idx[b]];
             o[b]->scale = a->scale / (long double)c_.chain.q[ell - 1];
@@ -1645,7 +1553,6 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
         const size_t pn = (size_t)ell * N;
         const long double sc = x[first]->scale * y[first]->scale;
         const LevelTables& lt = c_.lvl[ell];
-        const int nt = ell + K;
         std::vector<CtPtr> d = new_ct_batch(B, 3, ell, 2, 0, x[first]->slots);   // tensor products, contiguous [B][3][ell][N]
         for (int k0 = 0; k0 < B; k0 += EwItems::MAX_ITEMS) {
             EwItems it;
@@ -1672,47 +1579,18 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
         c_.stats.rescale += (u64)B;
         c_.stats.rescale_limbs += (u64)B * ell;
         const u64* c_ntt = d[0]->d + 2 * pn;
-        u64* cc = c_.dalloc<u64>((size_t)B * ell * N);
-        {
-            LimbBatch ib{cc, B * ell, nullptr, 0, ell, c_ntt};
-            if (B > 1) {
-                ib.src_group = ell;
-                ib.src_group_stride = 3 * pn;
-            }
-            c_.ntt(ib, true);
-        }
-        u64* ext = c_.dalloc<u64>((size_t)B * lt.beta * nt * N);
-        launch_modup_conv(c_.dt, sh, ext, cc, c_ntt, lt.up_hatinv, lt.up_hatmod_r2, s);   // digits times 2^64: launch_ks_inner ends in redc128
-        LimbBatch eb{ext, B * lt.beta * nt, lt.ext_limb_tab, 0, 1};
-        eb.tab_len = lt.beta * nt;
-        eb.lazy_out = true;
-        c_.ntt(eb, false, B * (lt.beta * nt - ell));
-        u64* accQ = c_.dalloc<u64>((size_t)B * 2 * ell * N);
-        u64* accP = c_.dalloc<u64>((size_t)B * 2 * K * N);
-        launch_ks_inner(c_.dt, sh, accQ, accP, ext, relin_key->d, c_ntt, s);
-        // X_Q = f acc_Q + P (f (d0, d1) + constant - subtrahend),  X_P = f acc_P
-        launch_affine_acc(c_.dt, sh, accQ, d[0]->d, sadj.empty() ? nullptr : sadj[0]->d, cst, cadd != 0.0 ? 1 : 0, f, c_.d_pmod, s);
-        if (f == 2) launch_ew_add(c_.dt, accP, accP, accP, B * 2 * K, B * 2 * K, L1, K, s);
-        // P and the top limb dropped together
-        c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, L1, K}, true);
-        u64* top = c_.dalloc<u64>((size_t)B * 2 * N);
-        {
-            LimbBatch tb{top, B * 2, nullptr, ell - 1, 1, accQ + (size_t)(ell - 1) * N};
-            tb.src_group = 1;
-            tb.src_group_stride = pn;
-            c_.ntt(tb, true);
-        }
-        u64* conv = c_.dalloc<u64>((size_t)B * 2 * (ell - 1) * N);
-        launch_moddown_rescale_conv(c_.dt, sh, conv, accP, top, lt.md_hatinv, lt.md_hatmod, lt.md_mmod, s);
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell - 1, 1, 0, x[first]->slots);
-        moddown_rescale_finish(sh, o[0]->d, accQ, conv, lt.md_minv);
-        launch_ok("mult_affine_rescale_batch");
-        c_.pool.free(cc);
-        c_.pool.free(ext);
-        c_.pool.free(accQ);
-        c_.pool.free(accP);
-        c_.pool.free(top);
-        c_.pool.free(conv);
+        {
+            Scratch<u64> ext = modup(sh, c_ntt, true);   // digits times 2^64: launch_ks_inner ends in redc128
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
+            launch_ks_inner(c_.dt, sh, accQ, accP, ext, relin_key->d, c_ntt, s);
+            // X_Q = f acc_Q + P (f (d0, d1) + constant - subtrahend),  X_P = f acc_P
+            launch_affine_acc(c_.dt, sh, accQ, d[0]->d, sadj.empty() ? nullptr : sadj[0]->d, cst, cadd != 0.0 ? 1 : 0, f, c_.d_pmod, s);
+            if (f == 2) launch_ew_add(c_.dt, accP, accP, accP, B * 2 * K, B * 2 * K, L1, K, s);
+            moddown_rescale(sh, accQ, accP, o[0]->d);   // P and the top limb dropped together
+            launch_ok("mult_affine_rescale_batch");
+        }
         for (int k = 0; k < B; ++k) {
             const size_t i = idx[k];
             o[k]->scale = x[i]->scale * y[i]->scale / (long double)c_.chain.q[ell - 1];
@@ -1762,11 +1640,10 @@ CtPtr Evaluator::raw_mult_relin(const CtPtr& a, const CtPtr& b, const EvalKey& k
     if (a->npoly != 2 || b->npoly != 2 || a->ell != b->ell) throw Error(FHELIN_ERR_STATE, "mult: operands must be 2-component, same level");
     const int ell = a->ell;
     const size_t pn = (size_t)ell * c_.N;
-    u64* d = c_.dalloc<u64>(3 * pn);
+    Scratch<u64> d = c_.scratch<u64>(3 * pn);
     launch_tensor(c_.dt, d, a->d, b->d, ell, c_.stream);
     CtPtr o = new_ct(2, ell, a->deg + b->deg, a->scale * b->scale, a->slots);
     keyswitch(d + 2 * pn, ell, key, o->d, d, d + pn, nullptr);
-    c_.pool.free(d);
     return o;
 }
 
@@ -1776,7 +1653,7 @@ CtPtr Evaluator::raw_modraise(const CtPtr& a, int new_ell) {
     const size_t N = c_.N;
     const int P = a->npoly;
     hipStream_t s = c_.stream;
-    u64* coef = c_.dalloc<u64>((size_t)P * N);
+    Scratch<u64> coef = c_.scratch<u64>((size_t)P * N);
     // INTT of the q0 limb of every polynomial, out of place (the input is immutable)
     LimbBatch ib{coef, P, nullptr, 0, 1, a->d};
     c_.ntt(ib, true);
@@ -1784,7 +1661,6 @@ CtPtr Evaluator::raw_modraise(const CtPtr& a, int new_ell) {
     launch_modraise(c_.dt, up->d, coef, P, 0, new_ell, s);
     c_.ntt(LimbBatch{up->d, P * new_ell, nullptr, 0, new_ell}, false);
     launch_ok("modraise");
-    c_.pool.free(coef);
     return up;
 }
 
@@ -1801,13 +1677,13 @@ std::vector<CtPtr> Evaluator::raw_modraise_batch(const std::vector<CtPtr>& vin, 
     const size_t N = c_.N;
     const int B = (int)in.size(), P = in[0]->npoly * B;
     hipStream_t s = c_.stream;
-    u64* coef = c_.dalloc<u64>((size_t)P * N);
+    Scratch<u64> coef = c_.scratch<u64>((size_t)P * N);
     c_.ntt(LimbBatch{coef, P, nullptr, 0, 1, in[0]->d}, true);
     std::vector<CtPtr> up = new_ct_batch(B, in[0]->npoly, new_ell, 1, 0, in[0]->slots);
     launch_modraise(c_.dt, up[0]->d, coef, P, 0, new_ell, s);
     c_.ntt(LimbBatch{up[0]->d, P * new_ell, nullptr, 0, new_ell}, false);
     launch_ok("modraise_batch");
-    c_.pool.free(coef);
+    coef.reset();
     for (int b = 0; b < B; ++b) {
         up[b]->deg = vin[b]->deg;
         up[b]->scale = vin[b]->scale;
@@ -1931,7 +1807,7 @@ std::vector<CtPtr> Evaluator::scaled_diff_batch(const std::vector<CtPtr>& u, con
             k[2] = rc;
             k[3] = h_shoup(rc, q);
         }
-    u64* dk = c_.dalloc<u64>(consts.size());
+    Scratch<u64> dk = c_.scratch<u64>(consts.size());
     for (size_t off = 0; off < consts.size(); off += 2 * c_.N)   // upload_async takes <= 2N words per call
         c_.upload_async(dk + off, consts.data() + off, std::min(consts.size() - off, (size_t)2 * c_.N));
     std::vector<CtPtr> out = new_ct_batch((int)B, npoly, ell, 1, 0, u[0]->slots);
@@ -1948,7 +1824,7 @@ std::vector<CtPtr> Evaluator::scaled_diff_batch(const std::vector<CtPtr>& u, con
         launch_ew_scaled_diff(c_.dt, d, dk + lo * ell * 4, c_.stream);
     }
     launch_ok("scaled_diff_batch");
-    c_.pool.free(dk);
+    dk.reset();
     for (size_t i = 0; i < B; ++i) {
         out[i]->deg = raise_deg ? u[i]->deg + 1 : u[i]->deg;
         out[i]->scale = scales[i];

@@ -2,6 +2,7 @@
 // operations the reference reaches through OpenFHE's CryptoContext (reference src/FHEController.cpp
 // :409-436 add/mult/rotate, FLEXIBLEAUTO level + scale bookkeeping implied by :18-24).
 #pragma once
+#include <functional>
 #include <map>
 #include <memory>
 #include <vector>
@@ -295,6 +296,11 @@ private:
     void keyswitch_impl(int batch, const KsRows* rows, const u64* c_ntt, size_t c_stride, int ell, const EvalKey* key, u64* out,
                         size_t out_stride, const u64* add0, const u64* add1, size_t add_stride, const u32* map, const u64* post,
                         size_t post_stride);
+    // the stages every key switch is built from (evaluator.cpp "key-switch stages"): the place to change the pipeline
+    Scratch<u64> modup(const KsShape& up, const u64* src, bool times_r2, int group2 = 0, size_t group2_stride = 0);
+    void moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
+                 bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr);
+    void moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out);
     // NTT(conv) [batch][2][ell-1][N] and the merged ModDown + rescale finish into out (launch_moddown_rescale_finish)
     void moddown_rescale_finish(const KsShape& sh, u64* out, const u64* accQ, u64* conv, const u64* minv);
     typedef std::vector<CtPtr> CtRow;  // one value per input ciphertext

@@ -88,7 +88,7 @@ CtPtr Evaluator::lincomb_at(const std::vector<CtPtr>& terms_in, const std::vecto
         real_to_scalars(c_, (long double)c0 * out_scale, ell, one);
         for (int l = 0; l < ell; ++l) sc[(size_t)n * ell + l] = one.v[2 * l];
     }
-    u64* dsc = c_.dalloc<u64>(sc.size());
+    Scratch<u64> dsc = c_.scratch<u64>(sc.size());
     c_.upload_async(dsc, sc.data(), sc.size());
     LinComb lc;
     lc.n = n;
@@ -97,7 +97,6 @@ CtPtr Evaluator::lincomb_at(const std::vector<CtPtr>& terms_in, const std::vecto
     CtPtr o = new_ct(x->npoly, ell, 2, out_scale, x->slots);
     launch_ew_lincomb(c_.dt, o->d, lc, dsc, ell, c_.stream, ell < x->ell ? x->ell : 0);
     hip_check(hipGetLastError(), "lincomb");
-    c_.pool.free(dsc);
     return o;
 }
 
