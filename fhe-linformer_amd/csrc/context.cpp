@@ -331,6 +331,7 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
         if (const char* e = std::getenv("FHELIN_FUSE_FINISH")) fuse_finish = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_HOST_ENCODE")) host_encode = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_GATHER")) fuse_gather = std::atoi(e) != 0;
+        if (const char* e = std::getenv("FHELIN_ROT_GATHER")) rot_gather = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_LIFT")) fuse_lift = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_LDS_DIGITS")) lds_digits = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_NTT_TRACE")) trace_small_ntt = std::atoi(e);
@@ -687,7 +688,15 @@ const u32* Context::automorph_map(u64 g) {
     }
     automorph_inverse[d] = di;
     automorph_inverse[di] = d;
+    automorph_ginv[d] = (u32)gi;
+    automorph_ginv[di] = (u32)g;
     return d;
+}
+
+u32 Context::automorph_ginv_of(const u32* map) const {
+    auto it = automorph_ginv.find(map);
+    if (it == automorph_ginv.end()) throw Error(FHELIN_ERR_INTERNAL, "automorphism map without a registered Galois element");
+    return it->second;
 }
 
 const u32* Context::automorph_inverse_of(const u32* map) {

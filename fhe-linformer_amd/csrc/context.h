@@ -278,6 +278,8 @@ struct Context {
     const u32* automorph_map(u64 galois);          // device map for the NTT-domain permutation
     const u32* automorph_inverse_of(const u32* map);  // the map of the inverse automorphism (built together with `map`)
     std::map<const u32*, const u32*> automorph_inverse;
+    u32 automorph_ginv_of(const u32* map) const;      // g^-1 mod 2N of the map's Galois element g (KsShape::ginv)
+    std::map<const u32*, u32> automorph_ginv;
     // Row-pass epilogues (kernels.h NttEpilogue): the forward NTT that feeds a rescale, a merged ModDown + rescale or a ModDown
     // finishes it in registers instead of storing the transform for a separate streaming kernel.  Bit-identical either way.
     // FHELIN_FUSE_FINISH=0: the separate kernels (rescale_finish, moddown_rescale_finish, moddown_finish) everywhere (A/B).
@@ -291,6 +293,12 @@ struct Context {
     // FHELIN_FUSE_GATHER=0: the rotated c0 parts of a merged rotation sum go through their own gather-and-sum kernel instead of
     // the ModDown epilogue (bit-identical; kept for A/B measurements)
     bool fuse_gather = true;
+    // Rotations gather at the inner product, so that every ModDown is the identity one that the row pass of NTT(conv) finishes
+    // (needs fuse_finish).  A merged rotation sum: launch_ks_inner_multi adds P * sum_r sigma_r(c0) to the
+    // accumulator's Q part while it has the maps in hand.  A plain rotation: launch_ks_inner reads digits, own limb and c0 through
+    // the map and the key's permuted copy (EvalKey::d_perm), launch_moddown_conv converts with the signs of sigma_g (KsShape::gather).
+    // FHELIN_ROT_GATHER=0: both end in moddown_finish_kernel, which gathers (A/B).  Bit-identical either way.
+    bool rot_gather = true;
     bool fuse_lift = true;      // rescale: centred lift formed in the NTT's first-pass load (FHELIN_FUSE_LIFT)
     bool lds_digits = true;     // merged rotate-and-sum: digit tiles staged once in LDS when every rotation keeps tiles in place (FHELIN_LDS_DIGITS)
     struct FftDev {

@@ -158,14 +158,35 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     shu.batch = shared ? 1 : B;  // polynomials that go through ModUp
     c_.stats.keyswitch += (u64)B;
     c_.stats.keyswitch_limbs += (u64)B * ell;
-    Scratch<u64> ext = modup(shu, c_ntt, true);   // digits times 2^64: launch_ks_inner ends in redc128
+    const bool identity = !map && !rows;
+    const bool gather = !identity && !add1 && rot_in_gather();
+    const u64* evk = key ? key->d : nullptr;
+    if (gather) {   // the rotation is applied while the inner product loads its operands; c0 (add0) enters accQ there, times P
+        sh.gather = 1;
+        if (rows) {
+            for (int b = 0; b < B; ++b) {
+                sh.evk_row[b] = permuted(*rows->keys[b], rows->maps[b]);
+                sh.ginv_row[b] = c_.automorph_ginv_of(rows->maps[b]);
+            }
+        } else {
+            evk = permuted(*key, map);
+            sh.map_row[0] = map;
+            sh.ginv = c_.automorph_ginv_of(map);
+        }
+        if (add0) {
+            sh.gsrc = add0;
+            sh.gsrc_stride = add_stride;
+            sh.gsrc_pmod = c_.d_pmod;
+        }
+    }
+    Scratch<u64> ext = modup(shu, c_ntt, !gather);   // digits times 2^64 for the keys as they are stored: launch_ks_inner ends in redc128
     Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
     Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-    launch_ks_inner(c_.dt, sh, accQ, accP, ext, key ? key->d : nullptr, c_ntt, c_.stream);
-    // the finish in the row pass of NTT(conv): always for an identity output map (relinearisation); for a rotation (written through
-    // the inverse automorphism map) only with FHELIN_FUSE_MODDOWN=1
-    const bool identity = !map && !rows;
-    moddown(sh, accQ, accP, out, add0, add1, map, post, c_.fuse_moddown || (c_.fuse_finish && identity));
+    launch_ks_inner(c_.dt, sh, accQ, accP, ext, evk, c_ntt, c_.stream);
+    // the finish in the row pass of NTT(conv): for an identity output map (relinearisation) and for a rotation gathered above; a rotation
+    // written through the inverse automorphism map only with FHELIN_FUSE_MODDOWN=1
+    if (gather) moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, true);
+    else moddown(sh, accQ, accP, out, add0, add1, map, post, c_.fuse_moddown || (c_.fuse_finish && identity));
     launch_ok("keyswitch");
 }
 
@@ -206,14 +227,18 @@ Scratch<u64> Evaluator::modup(const KsShape& up, const u64* src, bool times_r2, 
 
 // ModDown of the accumulator pair accQ [sh.batch][2][ell][N], accP [sh.batch][2][K][N] (accP is transformed in place):
 // out = (accQ - NTT(conv(INTT(accP)))) * P^-1 + add0/add1 (+ post), written through `map` / the rows' maps.
+// sh.gather: the pair was gathered through the rotation's map by launch_ks_inner (c0 included): the conversion takes the signs of the
+// automorphism into account (launch_moddown_conv) and the output map is the identity - row_pass, no map, no add0.
 // row_pass: the finish rides in the row pass of NTT(conv) - (accQ - NTT(conv)) * P^-1 + add (+ post) is formed in registers and
-// NTT(conv) never goes to memory; else launch_moddown_finish reads the stored transform.
+// NTT(conv) never goes to memory; else launch_moddown_finish reads the stored transform.  The row pass knows no gather: the c0 parts
+// of a merged rotation sum (sh.gsrc) must then be in accQ already, times P (sh.gsrc_pmod, launch_ks_inner_multi).
 // finish (optional): called with NTT(conv) [sh.batch][2][ell][N] in place of the one launch_moddown_finish over all rows (a caller whose
 // rows need several finish launches over slices); out .. post are then unused.
 void Evaluator::moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map,
                         const u64* post, bool row_pass, const std::function<void(const u64* conv)>& finish) {
     const size_t N = c_.N;
     const int B = sh.batch, ell = sh.ell, K = c_.K;
+    if (row_pass && sh.gsrc && !sh.gsrc_pmod) throw Error(FHELIN_ERR_INTERNAL, "moddown: the row pass cannot gather");
     c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, c_.L + 1, K}, true);
     Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * ell * N);
     launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, c_.stream);
@@ -231,7 +256,9 @@ void Evaluator::moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out,
         ep.add_stride = sh.add_stride;
         ep.post = post;
         ep.post_stride = sh.post_stride;
-        if (sh.per_row) {
+        if (sh.gather) {
+            // the accumulator pair and the conversion are sigma_g of the ungathered ones already: identity output
+        } else if (sh.per_row) {
             ep.per_row = 1;
             for (int b = 0; b < B; ++b) ep.invmap_row[b] = c_.automorph_inverse_of(sh.map_row[b]);
         } else if (map) {
@@ -358,17 +385,20 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
             // all rotated inner products, gathered and accumulated in the extended basis; the c0 parts likewise
             Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
             Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
+            const bool rp = sum_in_row_pass();
+            if (c_.fuse_gather) {
+                sh.gsrc = base;      // the rotated c0 parts: gathered by the inner product (times P, into accQ) or by moddown_finish
+                sh.gsrc_stride = ctw;
+                if (rp) sh.gsrc_pmod = c_.d_pmod;
+            }
             launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
             Scratch<u64> c0sum;
-            if (c_.fuse_gather) {
-                sh.gsrc = base;      // the epilogue gathers the rotated c0 parts itself
-                sh.gsrc_stride = ctw;
-            } else {
+            if (!c_.fuse_gather) {
                 c0sum = c_.scratch<u64>((size_t)B * ell * N);
                 launch_gather_sum(c_.dt, sh, c0sum, base, ctw, s);
             }
-            // one ModDown; the epilogue adds the gathered c0 parts and the unrotated input
-            moddown(sh, accQ, accP, o[0]->d, c0sum, nullptr, nullptr, base);
+            // one ModDown; its finish adds the unrotated input (and the gathered c0 parts, where the accumulator does not hold them)
+            moddown(sh, accQ, accP, o[0]->d, c0sum, nullptr, nullptr, base, rp);
             launch_ok("rotate_sum_batch");
         }
         for (int b = 0; b < B; ++b) {
@@ -509,7 +539,7 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
                 // what does not pass through the key switch: V_0 (c0, c1) + sum_r V_r sigma_r(c0)
                 Scratch<u64> pre = c_.scratch<u64>((size_t)B * ctw);
                 launch_hoist_addends(c_.dt, sh, h, pre, base, s);
-                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, pre);   // one ModDown
+                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, pre, sum_in_row_pass());   // one ModDown
             } else {
                 // the same addends times P into the accumulator's Q part, then P and the top limb are dropped together
                 h.acc = accQ;
@@ -583,16 +613,19 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
             c_.stats.keyswitch_limbs += (u64)R * ell;
             Scratch<u64> accQ = c_.scratch<u64>((size_t)2 * ell * N);
             Scratch<u64> accP = c_.scratch<u64>((size_t)2 * K * N);
-            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-            Scratch<u64> c0sum;
+            const bool rp = sum_in_row_pass();
             if (c_.fuse_gather) {
                 sh.gsrc = base;
                 sh.gsrc_stride = 0;
-            } else {
+                if (rp) sh.gsrc_pmod = c_.d_pmod;
+            }
+            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
+            Scratch<u64> c0sum;
+            if (!c_.fuse_gather) {
                 c0sum = c_.scratch<u64>((size_t)ell * N);
                 launch_gather_sum(c_.dt, sh, c0sum, base, 0, s);
             }
-            moddown(sh, accQ, accP, o->d, c0sum, nullptr, nullptr, nullptr);
+            moddown(sh, accQ, accP, o->d, c0sum, nullptr, nullptr, nullptr, rp);
             launch_ok("rotate_each_sum");
         }
         acc = acc ? add(acc, o) : o;
@@ -674,14 +707,16 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
                 sh.map_rot[r] = c_.automorph_map(g);
                 sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
             }
+            const bool rp = sum_in_row_pass();
             sh.gsrc = base;
             sh.gsrc_stride = row_stride;
+            if (rp) sh.gsrc_pmod = c_.d_pmod;
             c_.stats.keyswitch += (u64)B * R;
             c_.stats.keyswitch_limbs += (u64)B * R * ell;
             Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
             Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
             launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-            moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr);
+            moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, rp);
             launch_ok("rotate_each_sum_rows");
         }
         for (int b = 0; b < B; ++b) out[lo + b] = o[b];
@@ -943,6 +978,9 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
     }
     const int R = (int)todo.size();
     if (R == 0) return out;
+    // the rotations gather at the inner product when ONE launch covers every index (KsShape::ginv_row); more than MAX_ROWS indices keep
+    // the finishing kernel, which takes its rows in slices
+    const bool gather = rot_in_gather() && R <= (int)KsShape::MAX_ROWS;
     std::vector<const EvalKey*> keys;
     std::vector<const u32*> maps;
     for (size_t k : todo) {
@@ -971,8 +1009,8 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
         c_.stats.keyswitch_limbs += (u64)rows * ell;
         std::vector<CtPtr> o = new_ct_batch(rows, 2, ell, xs[lo]->deg, xs[lo]->scale, xs[lo]->slots);
         {
-            // ModUp of the B inputs' c1, once; digits times 2^64: launch_ks_inner ends in redc128
-            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B, ctw, 0, 0, 0}, base + pn, true);
+            // ModUp of the B inputs' c1, once; digits times 2^64 for the keys as they are stored: launch_ks_inner ends in redc128
+            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B, ctw, 0, 0, 0}, base + pn, !gather);
             // inner products: per input, rows of <= MAX_ROWS indices with their own keys, all reading that input's digits
             Scratch<u64> accQ = c_.scratch<u64>((size_t)rows * 2 * ell * N);
             Scratch<u64> accP = c_.scratch<u64>((size_t)rows * 2 * K * N);
@@ -1006,23 +1044,39 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
                     }
             };
             const bool one_chunk = R <= (int)KsShape::MAX_ROWS;     // rows then lie [input][index] as the outputs do
-            if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), accQ, accP, ext, nullptr, base + pn, s);
-            else
-                for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
-                    launch_ks_inner(c_.dt, sh1, accQ + row0 * 2 * ell * N, accP + row0 * 2 * K * N, ext + (size_t)i * lt.beta * nt * N, nullptr,
-                                    base + pn + (size_t)i * ctw, s);
-                });
-            // ONE ModDown over all rows; the epilogue adds the input's c0 (gathered through each row's map)
-            moddown(KsShape{ell, K, c_.alpha, lt.beta, L1, rows, 0, ctw, 0, 0}, accQ, accP, nullptr, nullptr, nullptr, nullptr, nullptr, false,
-                    [&](const u64* conv) {
-                        if (one_chunk) launch_moddown_finish(c_.dt, row_shape(0, R), o[0]->d, accQ, conv, c_.d_pinv, base, nullptr, nullptr, nullptr, s);
-                        else
-                            for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
-                                // add_stride 0 = the same c0 for every row
-                                launch_moddown_finish(c_.dt, sh1, o[row0]->d, accQ + row0 * 2 * ell * N, conv + row0 * 2 * ell * N, c_.d_pinv,
-                                                      base + (size_t)i * ctw, nullptr, nullptr, nullptr, s);
-                            });
+            if (gather) {
+                // every row gathers through its map at the inner product (its input's c0 included, times P); ONE identity ModDown over all rows
+                KsShape sh = row_shape(0, R);
+                sh.gather = 1;
+                for (int b = 0; b < R; ++b) {
+                    sh.evk_row[b] = permuted(*keys[b], maps[b]);
+                    sh.ginv_row[b] = c_.automorph_ginv_of(maps[b]);
+                }
+                sh.gsrc = base;
+                sh.gsrc_stride = ctw;
+                sh.gsrc_pmod = c_.d_pmod;
+                launch_ks_inner(c_.dt, sh, accQ, accP, ext, nullptr, base + pn, s);
+                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, true);
+            } else {
+                if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), accQ, accP, ext, nullptr, base + pn, s);
+                else
+                    for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
+                        launch_ks_inner(c_.dt, sh1, accQ + row0 * 2 * ell * N, accP + row0 * 2 * K * N, ext + (size_t)i * lt.beta * nt * N, nullptr,
+                                        base + pn + (size_t)i * ctw, s);
                     });
+                // ONE ModDown over all rows; the epilogue adds the input's c0 (gathered through each row's map)
+                moddown(KsShape{ell, K, c_.alpha, lt.beta, L1, rows, 0, ctw, 0, 0}, accQ, accP, nullptr, nullptr, nullptr, nullptr, nullptr, false,
+                        [&](const u64* conv) {
+                            if (one_chunk)
+                                launch_moddown_finish(c_.dt, row_shape(0, R), o[0]->d, accQ, conv, c_.d_pinv, base, nullptr, nullptr, nullptr, s);
+                            else
+                                for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
+                                    // add_stride 0 = the same c0 for every row
+                                    launch_moddown_finish(c_.dt, sh1, o[row0]->d, accQ + row0 * 2 * ell * N, conv + row0 * 2 * ell * N,
+                                                          c_.d_pinv, base + (size_t)i * ctw, nullptr, nullptr, nullptr, s);
+                                });
+                        });
+            }
             launch_ok("rotate_many_batch");
         }
         for (int i = 0; i < B; ++i)

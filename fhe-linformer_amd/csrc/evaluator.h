@@ -85,7 +85,8 @@ struct EvalKey {
     u64* d = nullptr;  // [dnum][2][L+1+k][N] NTT form; component 0 = b, 1 = a
     // the same key with every limb vector gathered through the key's own automorphism map (d_perm[v][n] = d[v][map_g[n]]):
     // the merged rotation sums apply sigma_g to the inner product d * evk BEFORE the shared ModDown, so with this copy the
-    // key streams of ks_inner_multi are contiguous and only the digits are gathered.  Built on first use (Evaluator::permuted).
+    // key streams of ks_inner_multi are contiguous and only the digits are gathered.  A plain rotation gathers at its inner product
+    // too and reads the same copy (KsShape::gather).  Built on first use (Evaluator::permuted).
     mutable u64* d_perm = nullptr;
     int digits = 0;
     bool seeded = false;   // every a half is the expansion of the key-set seed (include/fhelin.h "Seeded evaluation keys")
@@ -301,6 +302,11 @@ private:
     void moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
                  bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr);
     void moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out);
+    // a merged rotation sum ends in the identity ModDown of the row pass, its rotated c0 parts added to the accumulator by the inner product
+    bool sum_in_row_pass() const { return c_.fuse_finish && c_.rot_gather; }
+    // a plain rotation gathers at the inner product and ends in the same identity ModDown (KsShape::gather); FHELIN_FUSE_MODDOWN=1 keeps
+    // its scattered epilogue
+    bool rot_in_gather() const { return c_.fuse_finish && c_.rot_gather && !c_.fuse_moddown; }
     // NTT(conv) [batch][2][ell-1][N] and the merged ModDown + rescale finish into out (launch_moddown_rescale_finish)
     void moddown_rescale_finish(const KsShape& sh, u64* out, const u64* accQ, u64* conv, const u64* minv);
     typedef std::vector<CtPtr> CtRow;  // one value per input ciphertext

@@ -178,6 +178,19 @@ struct KsShape {
     // c0 parts, gathered in place of a separate gather-and-sum pass); rotation r reads gsrc + r * rot_input_stride
     const u64* gsrc = nullptr;
     size_t gsrc_stride = 0;   // per batch row
+    // gsrc_pmod != nullptr ([L+1][2] P mod q_t, shoup): launch_ks_inner_multi adds P * that sum to component 0 of accQ itself (it walks
+    // the same maps), so that the ModDown that follows is the identity one without a gather; launch_moddown_finish then leaves gsrc alone
+    const u64* gsrc_pmod = nullptr;
+    // gather = 1: a plain rotation whose automorphism is applied by launch_ks_inner (digits, own limb and c0 read through the row's map
+    // - map_row[0] without per_row -, keys in the layout of EvalKey::d_perm, digits NOT times 2^64; c0 = gsrc + input * gsrc_stride enters
+    // accQ times gsrc_pmod).  The accumulator pair is then sigma_g of the ungathered one, and launch_moddown_conv takes the signs of
+    // sigma_g in the coefficient domain into account: coefficient n of INTT(accP) is MINUS the source's where (ginv * n mod 2N) >= N
+    // (ginv = g^-1 mod 2N; ginv_row resolved like map_row), and the fast basis conversion does not commute with that negation.  The
+    // kernel un-negates its sources there, converts, and negates the result: exactly sigma_g(conv), so that the identity ModDown of the
+    // row pass writes what launch_moddown_finish writes through the map.
+    int gather = 0;
+    u32 ginv = 0;
+    u32 ginv_row[MAX_ROWS] = {};
     // basis-conversion kernels: targets per block (set by the launchers).  Every chunk of targets re-reads the conversion's source limbs,
     // so a launch that fills the GPU anyway (many rows) takes ALL targets in one block - sources read once - and only small launches
     // are cut into chunks of 16 for parallelism
@@ -188,6 +201,7 @@ struct KsShape {
 void launch_modup_conv(const DeviceTables& t, const KsShape& sh, u64* ext, const u64* cc, const u64* c_ntt, const u64* hatinv,
                        const u64* hatmod, hipStream_t s);
 // K7: accQ [2][ell][N], accP [2][k][N] <- sum_j ext[j][t] * evk[j][comp][limb(t)]
+//     (sh.gather: the same at the positions of the row's automorphism map, + P * c0 there - see KsShape::gather)
 void launch_ks_inner(const DeviceTables& t, const KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt,
                      hipStream_t s);
 // K7 for a sum of rotations: acc_c[t][n] = sum_r sum_j d_j[t][m_r(n)] * evk_{r,j,c}[t][m_r(n)],  m_r = map_rot[r]: the
@@ -216,9 +230,9 @@ struct HoistAdd {
 };
 void launch_hoist_addends(const DeviceTables& t, const KsShape& sh, const HoistAdd& h, u64* pre, const u64* ct, hipStream_t s);
 // out[v][n] = sum_r in[v][map_rot[r][n]]  for v in [0, nvec) (the c0 parts of the rotated copies), per batch row
-// (FHELIN_FUSE_GATHER=0 only: by default the sum rides in launch_moddown_finish, KsShape::gsrc)
+// (FHELIN_FUSE_GATHER=0 only: by default the sum rides in launch_ks_inner_multi or launch_moddown_finish, KsShape::gsrc)
 void launch_gather_sum(const DeviceTables& t, const KsShape& sh, u64* out, const u64* in, size_t in_stride, hipStream_t s);
-// K8a: accP coefficient form [2][k][N] -> conv [2][ell][N] (coefficient form)
+// K8a: accP coefficient form [2][k][N] -> conv [2][ell][N] (coefficient form); sh.gather: with the signs of the row's automorphism
 void launch_moddown_conv(const DeviceTables& t, const KsShape& sh, u64* conv, const u64* accP, const u64* phatinv, const u64* phatmod,
                          hipStream_t s);
 // ModDown and rescale as ONE basis conversion: with B = (p_0..p_{k-1}, q_{ell-1}), M = P q_{ell-1} and X the accumulator over

@@ -107,15 +107,27 @@ __device__ __forceinline__ KsBlock ks_block(const KsShape& sh, int rows = 0) {
     return k;
 }
 
+// r = mask_bit(lane) ? b : a with the lane mask in SGPRs (the VCC form of v_cndmask issues ~5x slower on gfx950)
+__device__ __forceinline__ u32 sel_mask(u32 a, u32 b, unsigned long long mask) {
+    u32 r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(mask));
+    return r;
+}
+
 // grid (N/512, ell + k)
+// GATHER (KsShape::gather): the inner product of a plain rotation at the positions map[n] - the coefficient pair (2m, 2m+1) comes with ONE
+// 16-byte load at map[2m] >> 1, swapped in registers when map[2m] is odd (see ks_inner_multi_kernel); the keys come permuted, pre-split and
+// times 2^64 (EvalKey::d_perm), so their loads stay contiguous and neither the digits nor the ciphertext's own limb carry the factor.
+template <bool GATHER>
 __global__ __launch_bounds__(256) void ks_inner_kernel(DeviceTables t, KsShape sh, u64* __restrict__ accQ, u64* __restrict__ accP, const u64* __restrict__ ext,
                                                        const u64* __restrict__ evk, const u64* __restrict__ c_ntt) {
     const int nt = sh.ell + sh.k;
     const KsBlock kb_ = ks_block(sh);
     const int bi = kb_.bi, tt = kb_.tt;
     const int limb = tt < sh.ell ? tt : sh.L1 + (tt - sh.ell);
+    const int in = sh.row_mod ? bi / sh.row_mod : bi;            // the input of batch row bi
+    const int ri = sh.per_row ? (sh.row_mod ? bi % sh.row_mod : bi) : 0;   // its entry of the per-row tables
     if (sh.row_mod) {
-        const int in = bi / sh.row_mod;
         ext += (size_t)in * sh.ext_batch_stride;
         c_ntt += (size_t)in * sh.c_stride;
         evk = sh.evk_row[bi % sh.row_mod];
@@ -137,28 +149,47 @@ __global__ __launch_bounds__(256) void ks_inner_kernel(DeviceTables t, KsShape s
     const u64x2* K = reinterpret_cast<const u64x2*>(evk);
     u64 lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};  // b.x, b.y, a.x, a.y
     const u64 monR = t.mont[2 * limb], monRs = t.mont[2 * limb + 1];
+    size_t nd = n2;                                  // pair index of the digit loads
+    [[maybe_unused]] u32 m0 = 0;
+    [[maybe_unused]] unsigned long long swp = 0;     // lanes whose pair arrives swapped
+    if constexpr (GATHER) {
+        m0 = sh.map_row[ri][2 * n2];
+        nd = m0 >> 1;
+        swp = __ballot((m0 & 1) != 0);
+    }
     for (int j0 = 0; j0 < sh.beta; j0 += 8) {
         Acc30 b0 = {0, 0, 0}, b1 = {0, 0, 0}, a0 = {0, 0, 0}, a1 = {0, 0, 0};
         const int j1 = min(sh.beta, j0 + 8);
         for (int j = j0; j < j1; ++j) {
-            u64x2 d = j == own ? reinterpret_cast<const u64x2*>(c_ntt)[(size_t)tt * row + n2] : E[((size_t)j * nt + tt) * row + n2];
-            if (j == own) {   // the digits of this kernel's ModUp come times 2^64 (LevelTables::up_hatmod_r2); the ciphertext's own limb gets the factor here
-                d.x = mul_shoup(d.x, monR, monRs, br.q);
-                d.y = mul_shoup(d.y, monR, monRs, br.q);
-            }
+            u64x2 d = j == own ? reinterpret_cast<const u64x2*>(c_ntt)[(size_t)tt * row + nd] : E[((size_t)j * nt + tt) * row + nd];
             const u64x2 kb = K[(size_t)(2 * j) * kstride + (size_t)limb * row + n2];
             const u64x2 ka = K[(size_t)(2 * j + 1) * kstride + (size_t)limb * row + n2];
-            u32 dx0, dx1, dy0, dy1, k0, k1;
-            split30(d.x, dx0, dx1);
-            split30(d.y, dy0, dy1);
-            split30(kb.x, k0, k1);
-            mac30(b0, dx0, dx1, k0, k1);
-            split30(kb.y, k0, k1);
-            mac30(b1, dy0, dy1, k0, k1);
-            split30(ka.x, k0, k1);
-            mac30(a0, dx0, dx1, k0, k1);
-            split30(ka.y, k0, k1);
-            mac30(a1, dy0, dy1, k0, k1);
+            if constexpr (GATHER) {
+                u32 p0, p1, q0, q1;
+                split30(d.x, p0, p1);
+                split30(d.y, q0, q1);
+                const u32 dx0 = sel_mask(p0, q0, swp), dx1 = sel_mask(p1, q1, swp), dy0 = sel_mask(q0, p0, swp), dy1 = sel_mask(q1, p1, swp);
+                mac30(b0, dx0, dx1, (u32)kb.x, (u32)(kb.x >> 32));
+                mac30(b1, dy0, dy1, (u32)kb.y, (u32)(kb.y >> 32));
+                mac30(a0, dx0, dx1, (u32)ka.x, (u32)(ka.x >> 32));
+                mac30(a1, dy0, dy1, (u32)ka.y, (u32)(ka.y >> 32));
+            } else {
+                if (j == own) {   // the digits of this kernel's ModUp come times 2^64 (LevelTables::up_hatmod_r2); the ciphertext's own limb gets the factor here
+                    d.x = mul_shoup(d.x, monR, monRs, br.q);
+                    d.y = mul_shoup(d.y, monR, monRs, br.q);
+                }
+                u32 dx0, dx1, dy0, dy1, k0, k1;
+                split30(d.x, dx0, dx1);
+                split30(d.y, dy0, dy1);
+                split30(kb.x, k0, k1);
+                mac30(b0, dx0, dx1, k0, k1);
+                split30(kb.y, k0, k1);
+                mac30(b1, dy0, dy1, k0, k1);
+                split30(ka.x, k0, k1);
+                mac30(a0, dx0, dx1, k0, k1);
+                split30(ka.y, k0, k1);
+                mac30(a1, dy0, dy1, k0, k1);
+            }
         }
         acc30_flush(b0, lo[0], hi[0]);
         acc30_flush(b1, lo[1], hi[1]);
@@ -172,6 +203,14 @@ __global__ __launch_bounds__(256) void ks_inner_kernel(DeviceTables t, KsShape s
     ra.x = redc128(lo[2], hi[2], br.q, qi);
     ra.y = redc128(lo[3], hi[3], br.q, qi);
     if (tt < sh.ell) {
+        if constexpr (GATHER) {
+            if (sh.gsrc_pmod) {   // + P * sigma_g(c0): the addend passes through the ModDown with the rest
+                const u64x2 gp = reinterpret_cast<const u64x2*>(sh.gsrc + (size_t)in * sh.gsrc_stride)[(size_t)tt * row + nd];
+                const u64 w = sh.gsrc_pmod[2 * tt], ws = sh.gsrc_pmod[2 * tt + 1];
+                rb.x = add_mod(rb.x, mul_shoup((m0 & 1) ? gp.y : gp.x, w, ws, br.q), br.q);
+                rb.y = add_mod(rb.y, mul_shoup((m0 & 1) ? gp.x : gp.y, w, ws, br.q), br.q);
+            }
+        }
         u64x2* O = reinterpret_cast<u64x2*>(accQ);
         O[(size_t)tt * row + n2] = rb;
         O[(size_t)(sh.ell + tt) * row + n2] = ra;
@@ -181,13 +220,6 @@ __global__ __launch_bounds__(256) void ks_inner_kernel(DeviceTables t, KsShape s
         O[(size_t)pj * row + n2] = rb;
         O[(size_t)(sh.k + pj) * row + n2] = ra;
     }
-}
-
-// r = mask_bit(lane) ? b : a with the lane mask in SGPRs (the VCC form of v_cndmask issues ~5x slower on gfx950)
-__device__ __forceinline__ u32 sel_mask(u32 a, u32 b, unsigned long long mask) {
-    u32 r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(mask));
-    return r;
 }
 
 // grid (N/512, batch*(ell + k)): the coefficient pair (2m, 2m+1) per thread.  In the bit-reversed evaluation order an
@@ -332,6 +364,36 @@ __global__ __launch_bounds__(256) void ks_inner_multi_kernel(DeviceTables t, KsS
         j = jn;
         m_cur = mn;
     }
+    // the rotated c0 parts of a merged sum (KsShape::gsrc_pmod), for the Q limbs: map entries and gathers go out in groups of four
+    // INDEPENDENT loads (a group's spare entries repeat its first rotation and count as zero) - one rotation at a time the two dependent
+    // round trips per rotation stood in line at the end of every wave (+22 % on the kernel at three rotations)
+    u64 gx[ROWS], gy[ROWS];
+#pragma unroll
+    for (int q = 0; q < ROWS; ++q) gx[q] = gy[q] = 0;
+    if (sh.gsrc_pmod && tt < sh.ell) {
+        for (int r0 = 0; r0 < sh.n_rot; r0 += 4) {
+            int rr[4];
+            u32 mm[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                rr[i] = r0 + i < sh.n_rot ? r0 + i : r0;
+                mm[i] = map_of(rr[i]);
+            }
+#pragma unroll
+            for (int q = 0; q < ROWS; ++q) {
+                const u64* __restrict__ g = sh.gsrc + (size_t)(live[q] ? bi + q : bi) * sh.gsrc_stride + (size_t)tt * N;
+                u64x2 gp[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) gp[i] = reinterpret_cast<const u64x2*>(g + (size_t)rr[i] * sh.rot_input_stride)[mm[i] >> 1];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const bool on = r0 + i < sh.n_rot, odd = (mm[i] & 1) != 0;
+                    gx[q] = add_mod(gx[q], on ? (odd ? gp[i].y : gp[i].x) : 0, br.q);
+                    gy[q] = add_mod(gy[q], on ? (odd ? gp[i].x : gp[i].y) : 0, br.q);
+                }
+            }
+        }
+    }
 #pragma unroll
     for (int q = 0; q < ROWS; ++q) {
         if (!live[q]) continue;
@@ -346,6 +408,11 @@ __global__ __launch_bounds__(256) void ks_inner_multi_kernel(DeviceTables t, KsS
         ra.x = redc128(lo[q][2], hi[q][2], br.q, qi);
         ra.y = redc128(lo[q][3], hi[q][3], br.q, qi);
         if (tt < sh.ell) {
+            if (sh.gsrc_pmod) {   // + P * sum_r sigma_r(c0): the addend passes through the ModDown with the rest (KsShape::gsrc_pmod)
+                const u64 w = sh.gsrc_pmod[2 * tt], ws = sh.gsrc_pmod[2 * tt + 1];
+                rb.x = add_mod(rb.x, mul_shoup(gx[q], w, ws, br.q), br.q);
+                rb.y = add_mod(rb.y, mul_shoup(gy[q], w, ws, br.q), br.q);
+            }
             u64x2* O = reinterpret_cast<u64x2*>(accQ + (size_t)(bi + q) * 2 * sh.ell * N);
             O[(size_t)tt * row + n2] = rb;
             O[(size_t)(sh.ell + tt) * row + n2] = ra;
@@ -375,15 +442,20 @@ __global__ __launch_bounds__(256) void gather_sum_kernel(DeviceTables t, KsShape
 }
 
 // grid (N/256, 2, ceil(ell/TCH)).  MAXK = number of special limbs (exact for k <= 8, then FULL: no per-source conditions)
-template <int MAXK, bool FULL>
+// SIGNED (KsShape::gather): accP holds sigma_g of the accumulator; where sigma_g negates (neg) the sources are un-negated, converted
+// and the result negated, which is sigma_g of the plain conversion - conv(p - x) alone is off by a multiple of P.
+template <int MAXK, bool FULL, bool SIGNED>
 __device__ __forceinline__ void moddown_body(const DeviceTables& t, const KsShape& sh, u64* __restrict__ conv, const u64* __restrict__ accP,
-                                             const u64* __restrict__ phatinv, const u64* __restrict__ phatmod, int c, size_t n) {
+                                             const u64* __restrict__ phatinv, const u64* __restrict__ phatmod, int c, size_t n, bool neg) {
     const size_t N = (size_t)1 << t.log_n;
     u32 z0[MAXK], z1[MAXK];
 #pragma unroll
     for (int p = 0; p < MAXK; ++p) {
         if (FULL || p < sh.k) {
-            split30(mul_shoup(accP[((size_t)c * sh.k + p) * N + n], phatinv[2 * p], phatinv[2 * p + 1], t.moduli[sh.L1 + p]), z0[p], z1[p]);
+            const u64 m = t.moduli[sh.L1 + p];
+            u64 x = accP[((size_t)c * sh.k + p) * N + n];
+            if constexpr (SIGNED) x = neg && x ? m - x : x;
+            split30(mul_shoup(x, phatinv[2 * p], phatinv[2 * p + 1], m), z0[p], z1[p]);
         } else {
             z0[p] = z1[p] = 0;
         }
@@ -404,11 +476,13 @@ __device__ __forceinline__ void moddown_body(const DeviceTables& t, const KsShap
                 }
             acc30_flush(acc, slo, shi);
         }
-        dst[(size_t)tt * N] = redc128(slo, shi, qt, qti);   // phatmod holds the constants times 2^64
+        u64 r = redc128(slo, shi, qt, qti);   // phatmod holds the constants times 2^64
+        if constexpr (SIGNED) r = neg && r ? qt - r : r;
+        dst[(size_t)tt * N] = r;
     }
 }
 
-template <int MAXK>
+template <int MAXK, bool SIGNED = false>
 __global__ __launch_bounds__(256) void moddown_conv_kernel(DeviceTables t, KsShape sh, u64* __restrict__ conv, const u64* __restrict__ accP, const u64* __restrict__ phatinv,
                                                            const u64* __restrict__ phatmod) {
     const int bi = blockIdx.y >> 1, c = blockIdx.y & 1;
@@ -416,10 +490,15 @@ __global__ __launch_bounds__(256) void moddown_conv_kernel(DeviceTables t, KsSha
     const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
     accP += (size_t)bi * 2 * sh.k * N;
     conv += (size_t)bi * 2 * sh.ell * N;
+    bool neg = false;
+    if constexpr (SIGNED) {
+        const u32 gi = sh.per_row ? sh.ginv_row[sh.row_mod ? bi % sh.row_mod : bi] : sh.ginv;
+        neg = ((gi * (u32)n) & (u32)(2 * N - 1)) >= (u32)N;   // 2N divides 2^32: the wrapped product keeps the residue
+    }
     if (sh.k == MAXK)
-        moddown_body<MAXK, true>(t, sh, conv, accP, phatinv, phatmod, c, n);
+        moddown_body<MAXK, true, SIGNED>(t, sh, conv, accP, phatinv, phatmod, c, n, neg);
     else
-        moddown_body<MAXK, false>(t, sh, conv, accP, phatinv, phatmod, c, n);
+        moddown_body<MAXK, false, SIGNED>(t, sh, conv, accP, phatinv, phatmod, c, n, neg);
 }
 
 // grid (N/512, 2*ell)
@@ -464,7 +543,7 @@ __global__ __launch_bounds__(256) void moddown_finish_kernel(DeviceTables t, KsS
         r.x = add_mod(r.x, p.x, q);
         r.y = add_mod(r.y, p.y, q);
     }
-    if (sh.gsrc && c == 0) {  // merged rotation sum: + sum_r sigma_r(c0), gathered here
+    if (sh.gsrc && !sh.gsrc_pmod && c == 0) {  // merged rotation sum: + sum_r sigma_r(c0), gathered here
         const u64* __restrict__ g = sh.gsrc + (size_t)bi * sh.gsrc_stride + (size_t)tt * N;
         for (int rr = 0; rr < sh.n_rot; ++rr) {
             const u64* __restrict__ gr = g + (size_t)rr * sh.rot_input_stride;
@@ -682,7 +761,10 @@ void launch_modup_conv(const DeviceTables& t, const KsShape& sh_in, u64* ext, co
 void launch_ks_inner(const DeviceTables& t, const KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt,
                      hipStream_t s) {
     dim3 g((1u << t.log_n) / 512, (unsigned)(sh.batch * (sh.ell + sh.k)));
-    hipLaunchKernelGGL(ks_inner_kernel, g, dim3(256), 0, s, t, sh, accQ, accP, ext, evk, c_ntt);
+    if (sh.gather)
+        hipLaunchKernelGGL(ks_inner_kernel<true>, g, dim3(256), 0, s, t, sh, accQ, accP, ext, evk, c_ntt);
+    else
+        hipLaunchKernelGGL(ks_inner_kernel<false>, g, dim3(256), 0, s, t, sh, accQ, accP, ext, evk, c_ntt);
 }
 void launch_ks_inner_multi(const DeviceTables& t, const KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* c_ntt,
                            hipStream_t s) {
@@ -712,12 +794,19 @@ void launch_moddown_conv(const DeviceTables& t, const KsShape& sh_in, u64* conv,
     const unsigned nx = (1u << t.log_n) / 256;
     sh.tch = conv_tch(nx * (unsigned)(2 * sh.batch), sh.ell);
     dim3 g(nx, (unsigned)(2 * sh.batch), (unsigned)((sh.ell + sh.tch - 1) / sh.tch));
-#define FHELIN_MODDOWN_CASE(K) case K: hipLaunchKernelGGL((moddown_conv_kernel<K>), g, dim3(256), 0, s, t, sh, conv, accP, phatinv, phatmod); break;
-    switch (sh.k) {
-        FHELIN_MODDOWN_CASE(1) FHELIN_MODDOWN_CASE(2) FHELIN_MODDOWN_CASE(3) FHELIN_MODDOWN_CASE(4)
-        FHELIN_MODDOWN_CASE(5) FHELIN_MODDOWN_CASE(6) FHELIN_MODDOWN_CASE(7) FHELIN_MODDOWN_CASE(8)
-        default: hipLaunchKernelGGL((moddown_conv_kernel<16>), g, dim3(256), 0, s, t, sh, conv, accP, phatinv, phatmod); break;
+#define FHELIN_MODDOWN_CASE(K, S) case K: hipLaunchKernelGGL((moddown_conv_kernel<K, S>), g, dim3(256), 0, s, t, sh, conv, accP, phatinv, phatmod); break;
+#define FHELIN_MODDOWN_SWITCH(S)                                                                                                                \
+    switch (sh.k) {                                                                                                                             \
+        FHELIN_MODDOWN_CASE(1, S) FHELIN_MODDOWN_CASE(2, S) FHELIN_MODDOWN_CASE(3, S) FHELIN_MODDOWN_CASE(4, S)                                 \
+        FHELIN_MODDOWN_CASE(5, S) FHELIN_MODDOWN_CASE(6, S) FHELIN_MODDOWN_CASE(7, S) FHELIN_MODDOWN_CASE(8, S)                                 \
+        default: hipLaunchKernelGGL((moddown_conv_kernel<16, S>), g, dim3(256), 0, s, t, sh, conv, accP, phatinv, phatmod); break;              \
     }
+    if (sh.gather) {
+        FHELIN_MODDOWN_SWITCH(true)
+    } else {
+        FHELIN_MODDOWN_SWITCH(false)
+    }
+#undef FHELIN_MODDOWN_SWITCH
 #undef FHELIN_MODDOWN_CASE
 }
 void launch_moddown_finish(const DeviceTables& t, const KsShape& sh, u64* out, const u64* accQ, const u64* conv, const u64* pinv,
