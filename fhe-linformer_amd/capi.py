@@ -150,6 +150,8 @@ def load_library():
         "fhelin_mult_plain_batch": (i32, [vp, C.POINTER(vp), i32, vp, C.POINTER(vp)]),
         "fhelin_mult_batch": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp)]),
         "fhelin_add_batch": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp)]),
+        "fhelin_mult_affine_batch": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(vp),
+                                           C.POINTER(i32), C.POINTER(vp)]),
         "fhelin_level_reduce": (i32, [vp, vp, i32, C.POINTER(vp)]),
         "fhelin_raw_rescale": (i32, [vp, vp, C.POINTER(vp)]),
         "fhelin_raw_rotate": (i32, [vp, vp, i32, C.POINTER(vp)]),
@@ -769,6 +771,18 @@ class Engine:
         outs = self._outs(len(a))
         self._ck(self.lib.fhelin_mult_batch(self.h, self._harr(a), self._harr(b), len(a), outs))
         return self._cts(outs, len(a))
+
+    def mult_affine_batch(self, a, b, f, cadd, addend=None, negate=None):
+        """rescale(f[i] * a[i] * b[i] + cadd[i] +- addend[i]) through one batched key switch (addend[i] may be None); the residues of
+        mult_batch, add_batch, add_real / sub, rescale"""
+        n = len(a)
+        outs = self._outs(n)
+        fa = (C.c_int32 * n)(*[int(v) for v in f])
+        ca = (C.c_double * n)(*[float(v) for v in cadd])
+        ad = (C.c_void_p * n)(*[(x.h if x is not None else None) for x in (addend or [None] * n)])
+        ng = (C.c_int32 * n)(*[int(bool(v)) for v in (negate or [0] * n)])
+        self._ck(self.lib.fhelin_mult_affine_batch(self.h, self._harr(a), self._harr(b), n, fa, ca, ad, ng, outs))
+        return self._cts(outs, n)
 
     def add_batch(self, a, b):
         outs = self._outs(len(a))

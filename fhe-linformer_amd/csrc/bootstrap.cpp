@@ -355,6 +355,16 @@ std::vector<CtPtr> Bootstrapper::eval_mod(const std::vector<CtPtr>& xs) {
             u = ev_.mult_affine_rescale_batch(u, u, 2, -1.0, {});
             continue;
         }
+        // a step whose result the NEXT step squares is rescaled by that step's operand preparation, as it stands: rescaling it here gives
+        // those residues, and the exact merged form does it inside the ModDown (Evaluator::mult_affine_batch; FHELIN_EXACT_PRODUCTS=0 keeps
+        // the sequence below).  The last step's result stays at degree 2 for its consumer.
+        if (i + 1 < R && ev_.exact_products_on()) {
+            Evaluator::AffineSpec sq;
+            sq.f = 2;
+            sq.cadd = -1.0;
+            u = ev_.mult_affine_batch(u, u, std::vector<Evaluator::AffineSpec>(u.size(), sq));
+            continue;
+        }
         std::vector<CtPtr> t = ev_.mult_batch(u, u);
         t = ev_.add_batch(t, t);
         for (size_t k = 0; k < t.size(); ++k) u[k] = ev_.add_real(t[k], -1.0);

@@ -383,6 +383,23 @@ int fhelin_mult_batch(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct*
     emit(c, c->ev.mult_batch(vec_of(c, a, n), vec_of(c, b, n)), outs);
     FHELIN_CATCH
 }
+int fhelin_mult_affine_batch(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct* const* b, int32_t n, const int32_t* f, const double* cadd,
+                             const fhelin_ct* const* addend, const int32_t* negate, fhelin_ct** outs) {
+    NEED(c && a && b && f && cadd && outs && n >= 0 && (!addend || negate));
+    FHELIN_TRY
+    std::vector<Evaluator::AffineSpec> spec(n);
+    for (int i = 0; i < n; ++i) {
+        spec[i].f = f[i];
+        spec[i].cadd = cadd[i];
+        if (addend && addend[i]) {
+            force_many(c, &addend[i], 1);
+            spec[i].addend = ct_in(c, addend[i]);
+            spec[i].negate = negate[i] != 0;
+        }
+    }
+    emit(c, c->ev.mult_affine_batch(vec_of(c, a, n), vec_of(c, b, n), spec), outs);
+    FHELIN_CATCH
+}
 int fhelin_add_batch(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct* const* b, int32_t n, fhelin_ct** outs) {
     NEED(c && a && b && outs && n >= 0);
     FHELIN_TRY

@@ -514,6 +514,10 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
             lt.md_hatmod = upload_table(mhm);
             lt.md_minv = upload_table(minv);
             lt.md_mmod = upload_table(mmod);
+            std::vector<int> xtab(K + 1);
+            for (int j = 0; j < K; ++j) xtab[j] = limb_id_p(j);
+            xtab[K] = limb_id_q(e1);
+            lt.mdx_limb_tab = upload_table(xtab);
         }
     }
 }

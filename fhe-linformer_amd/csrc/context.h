@@ -168,6 +168,7 @@ struct LevelTables {
     const u64* md_hatmod = nullptr;   // [k+1][ell-1]  (M/b) mod q_t, pre-split (pack30)
     const u64* md_minv = nullptr;     // [ell-1][2]    M^{-1} mod q_t, shoup
     const u64* md_mmod = nullptr;     // [ell-1]       M mod q_t (the centred conversion takes one off per source above b/2)
+    const int* mdx_limb_tab = nullptr;   // [k+1] limb ids p_0..p_{k-1}, q_{ell-1}: the inverse transform of the exact merged tail (Evaluator::moddown_rescale_exact)
 };
 
 // host-side operation counters (bench.py scales the CPU baseline sample with these)

@@ -291,6 +291,25 @@ void Evaluator::moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u
     moddown_rescale_finish(sh, out, accQ, conv, lt.md_minv);
 }
 
+// ModDown, the affine step and the rescale of a relinearised product with their own two roundings, from ONE inverse and ONE forward
+// transform (sh.ell >= 2, K + 1 <= 16; kernels_elem.h "the EXACT merged tail").  accQ [sh.batch][2][ell][N] holds X_Q on the limbs below
+// the top one, accP [sh.batch][2][K+1][N] the special limbs as the inner product left them and X_Q,top (launch_affine_acc_items); f2: the
+// items whose factor is 2.  out [sh.batch][2][ell-1][N] = the residues of rescale(ModDown + affine step).
+void Evaluator::moddown_rescale_exact(const KsShape& sh, const u64* accQ, u64* accP, u64* out, u32 f2) {
+    const size_t N = c_.N;
+    const int B = sh.batch, ell = sh.ell, K = c_.K;
+    const LevelTables& lt = c_.lvl[ell];
+    {
+        LimbBatch ib{accP, B * 2 * (K + 1), lt.mdx_limb_tab, 0, 1};
+        ib.tab_len = K + 1;
+        c_.ntt(ib, true);
+    }
+    Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * (ell - 1) * N);
+    launch_moddown_rescale_exact_conv(c_.dt, sh, f2, conv, accP, c_.d_phatinv, c_.d_phatmod, c_.d_pinv, c_.d_pmod,
+                                      c_.d_qlmod + (size_t)(ell - 1) * (c_.L + 1), c_.stream);
+    moddown_rescale_finish(sh, out, accQ, conv, lt.md_minv);   // md_minv = (P q_top)^-1 mod q_t
+}
+
 // the row pass of NTT(conv) finishes (accQ - NTT(conv)) * minv into out (FHELIN_FUSE_FINISH=0: moddown_rescale_finish_kernel)
 void Evaluator::moddown_rescale_finish(const KsShape& sh, u64* out, const u64* accQ, u64* conv, const u64* minv) {
     const int e1 = sh.ell - 1;
@@ -1514,9 +1533,7 @@ std::vector<CtPtr> Evaluator::add_sub_batch(const std::vector<CtPtr>& a, const s
     return out;
 }
 
-std::vector<CtPtr> Evaluator::mult_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b) {
-    if (a.size() != b.size()) throw Error(FHELIN_ERR_ARG, "mult_batch: operand count mismatch");
-    if (!relin_key) throw Error(FHELIN_ERR_KEY, "no relinearisation key (EvalMultKeyGen not called)");
+void Evaluator::product_operands(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, std::vector<CtPtr>& x, std::vector<CtPtr>& y) {
     const size_t n = a.size();
     // operands of degree 2 are rescaled first (every distinct ciphertext once), then brought to a common level per pair
     std::vector<CtPtr> in;
@@ -1531,12 +1548,20 @@ std::vector<CtPtr> Evaluator::mult_batch(const std::vector<CtPtr>& a, const std:
         }
     std::vector<CtPtr> resc = in.empty() ? std::vector<CtPtr>() : rescale_batch(in);
     auto ready = [&](const CtPtr& c) { return c->deg >= 2 ? resc[slot[c.get()]] : c; };
-    std::vector<CtPtr> x, y, out(n), ra(n), rb(n);
+    std::vector<CtPtr> ra(n), rb(n);
     for (size_t i = 0; i < n; ++i) {
         ra[i] = ready(a[i]);
         rb[i] = ready(b[i]);
     }
     match_batch(ra, rb, x, y);   // the level adjustments of all pairs of a round together (one batched rescale per target level)
+}
+
+std::vector<CtPtr> Evaluator::mult_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b) {
+    if (a.size() != b.size()) throw Error(FHELIN_ERR_ARG, "mult_batch: operand count mismatch");
+    if (!relin_key) throw Error(FHELIN_ERR_KEY, "no relinearisation key (EvalMultKeyGen not called)");
+    const size_t n = a.size();
+    std::vector<CtPtr> x, y, out(n);
+    product_operands(a, b, x, y);
     std::vector<char> done(n, 0);
     for (size_t first = 0; first < n; ++first) {
         if (done[first]) continue;
@@ -1644,6 +1669,140 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
             if (f == 2) launch_ew_add(c_.dt, accP, accP, accP, B * 2 * K, B * 2 * K, L1, K, s);
             moddown_rescale(sh, accQ, accP, o[0]->d);   // P and the top limb dropped together
             launch_ok("mult_affine_rescale_batch");
+        }
+        for (int k = 0; k < B; ++k) {
+            const size_t i = idx[k];
+            o[k]->scale = x[i]->scale * y[i]->scale / (long double)c_.chain.q[ell - 1];
+            out[i] = o[k];
+            done[i] = 1;
+        }
+    }
+    return out;
+}
+
+std::vector<CtPtr> Evaluator::mult_affine_unmerged(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<AffineSpec>& spec) {
+    std::vector<CtPtr> t = mult_batch(a, b);
+    const size_t n = t.size();
+    {   // factor 2: t + t, all such items in one batched addition
+        std::vector<size_t> pos;
+        std::vector<CtPtr> sel;
+        for (size_t i = 0; i < n; ++i)
+            if (spec[i].f == 2) {
+                pos.push_back(i);
+                sel.push_back(t[i]);
+            }
+        if (!sel.empty()) {
+            const std::vector<CtPtr> r = add_batch(sel, sel);
+            for (size_t j = 0; j < pos.size(); ++j) t[pos[j]] = r[j];
+        }
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (spec[i].cadd != 0.0) t[i] = add_real(t[i], spec[i].cadd);
+    for (const bool neg : {true, false}) {   // the subtrahends in one sub_batch, the addends in one add_batch
+        std::vector<size_t> pos;
+        std::vector<CtPtr> sel, ad;
+        for (size_t i = 0; i < n; ++i)
+            if (spec[i].addend && spec[i].negate == neg) {
+                pos.push_back(i);
+                sel.push_back(t[i]);
+                ad.push_back(spec[i].addend);
+            }
+        if (sel.empty()) continue;
+        const std::vector<CtPtr> r = neg ? sub_batch(sel, ad) : add_batch(sel, ad);
+        for (size_t j = 0; j < pos.size(); ++j) t[pos[j]] = r[j];
+    }
+    return rescale_batch(t);
+}
+
+std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<AffineSpec>& spec) {
+    if (a.size() != b.size() || spec.size() != a.size()) throw Error(FHELIN_ERR_ARG, "mult_affine_batch: operand count mismatch");
+    if (!relin_key) throw Error(FHELIN_ERR_KEY, "no relinearisation key (EvalMultKeyGen not called)");
+    for (const AffineSpec& sp : spec) {
+        if (sp.f != 1 && sp.f != 2) throw Error(FHELIN_ERR_ARG, "mult_affine_batch: factor 1 or 2");
+        if (sp.addend && sp.addend->npoly != 2) throw Error(FHELIN_ERR_STATE, "add: component count mismatch");
+    }
+    if (!exact_products_on()) return mult_affine_unmerged(a, b, spec);
+    const size_t n = a.size();
+    std::vector<CtPtr> x, y, out(n);
+    product_operands(a, b, x, y);
+    // where the sequence would adjust the PRODUCT to its addend, or has no limb to drop, it runs itself (on the prepared operands: its own
+    // preparation finds nothing left to do)
+    for (size_t i = 0; i < n; ++i)
+        if (x[i]->ell < 2 || (spec[i].addend && spec[i].addend->ell < x[i]->ell)) return mult_affine_unmerged(x, y, spec);
+    const size_t N = c_.N;
+    const int K = c_.K, L1 = c_.L + 1;
+    hipStream_t s = c_.stream;
+    const int limit = std::min(batch_limit, (int)AffineItems::MAX_ITEMS);
+    std::vector<char> done(n, 0);
+    for (size_t first = 0; first < n; ++first) {
+        if (done[first]) continue;
+        std::vector<size_t> idx;
+        for (size_t i = first; i < n && (int)idx.size() < limit; ++i)
+            if (!done[i] && x[i]->ell == x[first]->ell) idx.push_back(i);
+        const int B = (int)idx.size(), ell = x[first]->ell;
+        const size_t pn = (size_t)ell * N;
+        std::vector<CtPtr> d = new_ct_batch(B, 3, ell, 2, 0, x[first]->slots);   // tensor products, contiguous [B][3][ell][N]
+        {
+            EwItems it;
+            it.n = B;
+            for (int k = 0; k < B; ++k) {
+                it.out[k] = d[k]->d;
+                it.a[k] = x[idx[k]]->d;
+                it.b[k] = y[idx[k]]->d;
+            }
+            launch_tensor_items(c_.dt, it, ell, s);
+        }
+        // the affine parts at their products' (limbs, degree 2, scale): the addend as match() brings it to the product, the constant as add_real forms it
+        AffineItems items;
+        std::vector<CtPtr> adj(B);
+        std::map<std::pair<const Ciphertext*, long double>, CtPtr> adjusted;
+        std::vector<u64> cst((size_t)B * ell, 0);
+        for (int k = 0; k < B; ++k) {
+            const size_t i = idx[k];
+            const AffineSpec& sp = spec[i];
+            const long double sc = x[i]->scale * y[i]->scale;
+            if (sp.f == 2) items.f2 |= 1u << k;
+            if (sp.addend) {
+                const CtPtr& ad = sp.addend;
+                // a degree-1 addend that several items bring to the same (limbs, scale) - T_1 of a row, for every odd power of a round - is
+                // adjusted once (one integer multiply, no rescale: the counters do not see it)
+                const std::pair<const Ciphertext*, long double> key{ad.get(), sc};
+                auto hit = ad->deg == 1 ? adjusted.find(key) : adjusted.end();
+                if (hit != adjusted.end()) {
+                    adj[k] = hit->second;
+                } else {
+                    adj[k] = ad->ell == ell && ad->deg == 2 ? ad : adjust(ad, ell, 2, sc);
+                    if (ad->deg == 1) adjusted[key] = adj[k];
+                }
+                items.add[k] = adj[k]->d;
+                if (sp.negate) items.neg |= 1u << k;
+            }
+            if (sp.cadd != 0.0) {
+                ScalarSet one;
+                real_to_scalars(c_, (long double)sp.cadd * sc, ell, one);
+                for (int l = 0; l < ell; ++l) cst[(size_t)k * ell + l] = one.v[2 * l];
+                items.cst |= 1u << k;
+            }
+        }
+        Scratch<u64> dcst = c_.scratch<u64>(cst.size());
+        if (items.cst) c_.upload_async(dcst, cst.data(), cst.size());
+        KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, L1, B, 3 * pn, (size_t)2 * (ell - 1) * N, pn, 0};
+        sh.accp_limbs = K + 1;
+        // counted as the unmerged sequence counts: one key switch and one rescale per product
+        c_.stats.keyswitch += (u64)B;
+        c_.stats.keyswitch_limbs += (u64)B * ell;
+        c_.stats.rescale += (u64)B;
+        c_.stats.rescale_limbs += (u64)B * ell;
+        const u64* c_ntt = d[0]->d + 2 * pn;
+        std::vector<CtPtr> o = new_ct_batch(B, 2, ell - 1, 1, 0, x[first]->slots);
+        {
+            Scratch<u64> ext = modup(sh, c_ntt, true);   // digits times 2^64: launch_ks_inner ends in redc128
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * (K + 1) * N);
+            launch_ks_inner(c_.dt, sh, accQ, accP, ext, relin_key->d, c_ntt, s);
+            launch_affine_acc_items(c_.dt, sh, items, accQ, accP, d[0]->d, dcst, c_.d_pmod, s);
+            moddown_rescale_exact(sh, accQ, accP, o[0]->d, items.f2);
+            launch_ok("mult_affine_batch");
         }
         for (int k = 0; k < B; ++k) {
             const size_t i = idx[k];

@@ -235,6 +235,25 @@ public:
     // orc_mult_affine_rescale).  Output: degree 1, one limb fewer, scale a.scale * b.scale / q_top.
     std::vector<CtPtr> mult_affine_rescale_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, int f, double cadd,
                                                  const std::vector<CtPtr>& sub);
+    // The same power steps with the residues of the UNMERGED sequence, bit for bit (on by default; FHELIN_EXACT_PRODUCTS=0: the sequence
+    // itself - mult_batch, add_batch, add_real / sub_batch, rescale_batch).  out[i] = rescale(f_i a[i] b[i] + cadd_i +- addend_i): every
+    // item has its own factor, constant and addend, so the even and the odd powers of a round share ONE batched key switch.  The affine
+    // part enters the accumulator times P as in mult_affine_rescale_batch, but ModDown and rescale keep their two roundings: the tail
+    // (moddown_rescale_exact) forms the rescale's centred lift from the top limb of the ModDown's result, which it obtains in coefficient
+    // form from the SAME inverse transform that serves the special limbs, and one forward transform carries conversion and lift together
+    // (DESIGN.md 6g).  Operand preparation is mult_batch's own (product_operands); an addend is brought to its product's (limbs, degree
+    // 2, scale) as sub_batch / add_batch bring it there; a call with an addend of fewer limbs than its product (where those would adjust
+    // the product instead) runs the sequence.
+    struct AffineSpec {
+        int f = 1;          // 1 or 2
+        double cadd = 0;    // real constant added to every slot
+        CtPtr addend;       // optional
+        bool negate = false;   // the addend is subtracted
+    };
+    bool exact_products = true;
+    // the knob, and a shape the tail takes (1..15 special primes); a product with a single limb fails as its rescale would
+    bool exact_products_on() const { return exact_products && c_.K >= 1 && c_.K + 1 <= 16; }
+    std::vector<CtPtr> mult_affine_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<AffineSpec>& spec);
     // the same Chebyshev series on several ciphertexts at once: every product of the evaluation runs as mult_batch over
     // all ciphertexts AND all independent nodes of the same depth (baby powers of one doubling round)
     std::vector<CtPtr> eval_chebyshev_many(const std::vector<CtPtr>& xs, const std::vector<double>& coeffs, double a, double b);
@@ -302,6 +321,11 @@ private:
     void moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
                  bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr);
     void moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out);
+    void moddown_rescale_exact(const KsShape& sh, const u64* accQ, u64* accP, u64* out, u32 f2);
+    // operands of a batched product as mult_batch takes them: degree 2 rescaled first (every distinct ciphertext once), pairs matched
+    void product_operands(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, std::vector<CtPtr>& x, std::vector<CtPtr>& y);
+    // the unmerged sequence of mult_affine_batch: mult_batch, add_batch (factor 2), add_real per item, sub_batch / add_batch, rescale_batch
+    std::vector<CtPtr> mult_affine_unmerged(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<AffineSpec>& spec);
     // a merged rotation sum ends in the identity ModDown of the row pass, its rotated c0 parts added to the accumulator by the inner product
     bool sum_in_row_pass() const { return c_.fuse_finish && c_.rot_gather; }
     // a plain rotation gathers at the inner product and ends in the same identity ModDown (KsShape::gather); FHELIN_FUSE_MODDOWN=1 keeps

@@ -195,6 +195,9 @@ struct KsShape {
     // so a launch that fills the GPU anyway (many rows) takes ALL targets in one block - sources read once - and only small launches
     // are cut into chunks of 16 for parallelism
     int tch = 16;
+    // launch_ks_inner: limbs per component of accP (0: k).  The exact ModDown + rescale keeps one more slot per component, for the
+    // accumulator's top Q limb (launch_affine_acc_items), so that ONE inverse transform covers the special limbs and that limb
+    int accp_limbs = 0;
 };
 // K6: cc [ell][N] coefficient form, c_ntt [ell][N] NTT form -> ext [beta][ell+k][N]
 //     (own-digit slots stay unused — K7 reads c_ntt there; the others get the fast-basis-extended values, coefficient form)
@@ -256,6 +259,26 @@ void launch_moddown_rescale_conv(const DeviceTables& t, const KsShape& sh, u64* 
                                  const u64* hatmod, const u64* mmod, hipStream_t s);
 void launch_moddown_rescale_finish(const DeviceTables& t, const KsShape& sh, u64* out, const u64* accQ, const u64* conv, const u64* minv,
                                    hipStream_t s);
+// ---- the EXACT merged tail (Evaluator::moddown_rescale_exact): the residues of ModDown, affine step, rescale - two roundings, the same ones
+// - from one inverse and one forward transform.  With X_Q = f accQ + P (f d + cst +- addend) (per item) and conv = conv(INTT(accP)):
+//     x_top = (INTT(X_Q,top) - f conv_top) P^-1  mod q_top           (= the coefficients of the unmerged result's top limb)
+//     out_t = (X_Q,t - NTT(f conv_t + [P]_t lift_t(x_top))) (P q_top)^-1      t < ell - 1,  lift = the centred lift of the rescale
+// conv is taken from accP itself and multiplied by f afterwards: the fast basis conversion does not commute with f on its sources.
+// Per-item affine step: item b has its own factor (f2 bit: 2, else 1), constant (cst bit: consts[b][t], device array [batch][ell]) and
+// addend (add[b], [2][ell][N] at the product's shape, or null; neg bit: subtracted).
+struct AffineItems {
+    static constexpr int MAX_ITEMS = 32;
+    const u64* add[MAX_ITEMS] = {};
+    u32 f2 = 0, neg = 0, cst = 0;
+};
+// accQ[b][c][t] = X_Q for t < ell - 1; X_Q,top goes to slot k of accP [batch][2][k+1][N] (KsShape::accp_limbs = k + 1), whose special
+// limbs stay as the inner product left them.  d: the tensor block [batch][3][ell][N].
+void launch_affine_acc_items(const DeviceTables& t, const KsShape& sh, const AffineItems& it, u64* accQ, u64* accP, const u64* d,
+                             const u64* consts, const u64* pmod, hipStream_t s);
+// accP [batch][2][k+1][N] in coefficient form (special limbs, then X_Q,top) -> conv [batch][2][ell-1][N] = f conv_t + [P]_t lift_t(x_top),
+// coefficient form; phatinv / phatmod: the tables of launch_moddown_conv, pinv / pmod: [L+1][2], qlm: q_top mod q_t (row ell-1 of d_qlmod)
+void launch_moddown_rescale_exact_conv(const DeviceTables& t, const KsShape& sh, u32 f2, u64* conv, const u64* accP, const u64* phatinv,
+                                       const u64* phatmod, const u64* pinv, const u64* pmod, const u64* qlm, hipStream_t s);
 // K8b: out[c][t][j] = (accQ[c][t][m] - conv[c][t][m]) * P^{-1} + add_c[t][m] (+ post[c][t][j]),  m = map ? map[j] : j
 void launch_moddown_finish(const DeviceTables& t, const KsShape& sh, u64* out, const u64* accQ, const u64* conv, const u64* pinv,
                            const u64* add0, const u64* add1, const u32* map, const u64* post, hipStream_t s);

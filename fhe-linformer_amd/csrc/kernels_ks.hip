@@ -140,7 +140,8 @@ __global__ __launch_bounds__(256) void ks_inner_kernel(DeviceTables t, KsShape s
     }
     const int own = tt < sh.ell ? tt / sh.alpha : -1;  // the digit that contains target limb tt (its slot in ext is unused)
     accQ += (size_t)bi * 2 * sh.ell * ((size_t)1 << t.log_n);
-    accP += (size_t)bi * 2 * sh.k * ((size_t)1 << t.log_n);
+    const int pk = sh.accp_limbs ? sh.accp_limbs : sh.k;   // limbs per component of accP
+    accP += (size_t)bi * 2 * pk * ((size_t)1 << t.log_n);
     const Barrett br = load_barrett(t, limb);
     const size_t row = ((size_t)1 << t.log_n) >> 1;
     const size_t n2 = (size_t)kb_.bx * 256 + threadIdx.x;
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(256) void ks_inner_kernel(DeviceTables t, KsShape s
         u64x2* O = reinterpret_cast<u64x2*>(accP);
         const int pj = tt - sh.ell;
         O[(size_t)pj * row + n2] = rb;
-        O[(size_t)(sh.k + pj) * row + n2] = ra;
+        O[(size_t)(pk + pj) * row + n2] = ra;
     }
 }
 
@@ -688,6 +689,116 @@ __global__ __launch_bounds__(256) void moddown_rescale_conv_kernel(DeviceTables 
     }
 }
 
+// Per-item affine step of the exact merged tail (launch_affine_acc_items): grid (N/512, batch * 2 * ell).  X_Q = f accQ + P (f d + cst +- addend)
+// in place - the top limb's into slot k of accP instead.  The special limbs of accP stay as they are: the tail scales their CONVERSION by f.
+__global__ __launch_bounds__(256) void affine_acc_items_kernel(DeviceTables t, KsShape sh, AffineItems it, u64* __restrict__ accQ, u64* __restrict__ accP,
+                                                               const u64* __restrict__ d, const u64* __restrict__ consts, const u64* __restrict__ pmod) {
+    const int bi = blockIdx.y / (2 * sh.ell), v = blockIdx.y % (2 * sh.ell);
+    const int c = v / sh.ell, tt = v % sh.ell;
+    const bool f2 = (it.f2 >> bi) & 1;
+    const size_t row = ((size_t)1 << t.log_n) >> 1;
+    const size_t n2 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const u64 q = t.moduli[tt];
+    u64x2 x = reinterpret_cast<const u64x2*>(d)[(((size_t)bi * 3 + c) * sh.ell + tt) * row + n2];
+    if (f2) {
+        x.x = add_mod(x.x, x.x, q);
+        x.y = add_mod(x.y, x.y, q);
+    }
+    if (c == 0 && ((it.cst >> bi) & 1)) {
+        const u64 k = consts[(size_t)bi * sh.ell + tt];
+        x.x = add_mod(x.x, k, q);
+        x.y = add_mod(x.y, k, q);
+    }
+    const u64* __restrict__ add = it.add[bi];
+    if (add) {
+        const u64x2 sv = reinterpret_cast<const u64x2*>(add)[((size_t)c * sh.ell + tt) * row + n2];
+        if ((it.neg >> bi) & 1) {
+            x.x = sub_mod(x.x, sv.x, q);
+            x.y = sub_mod(x.y, sv.y, q);
+        } else {
+            x.x = add_mod(x.x, sv.x, q);
+            x.y = add_mod(x.y, sv.y, q);
+        }
+    }
+    u64x2* A = reinterpret_cast<u64x2*>(accQ) + (((size_t)bi * 2 + c) * sh.ell + tt) * row + n2;
+    u64x2 a = *A;
+    if (f2) {
+        a.x = add_mod(a.x, a.x, q);
+        a.y = add_mod(a.y, a.y, q);
+    }
+    const u64 w = pmod[2 * tt], ws = pmod[2 * tt + 1];
+    a.x = add_mod(a.x, mul_shoup(x.x, w, ws, q), q);
+    a.y = add_mod(a.y, mul_shoup(x.y, w, ws, q), q);
+    if (tt == sh.ell - 1)   // the tail transforms it back together with the special limbs
+        reinterpret_cast<u64x2*>(accP)[(((size_t)bi * 2 + c) * (sh.k + 1) + sh.k) * row + n2] = a;
+    else
+        *A = a;
+}
+
+// Conversion of the exact merged tail (launch_moddown_rescale_exact_conv): grid (N/256, batch * 2, ceil((ell-1)/TCH)).  conv_t and
+// conv_top are the sums of moddown_body (same tables, same reduction: canonical); every block of a column recomputes conv_top.
+template <int MAXK, bool FULL>
+__device__ __forceinline__ void moddown_exact_body(const DeviceTables& t, const KsShape& sh, bool f2, u64* __restrict__ dst, const u64* __restrict__ src,
+                                                   const u64* __restrict__ phatinv, const u64* __restrict__ phatmod, const u64* __restrict__ pinv,
+                                                   const u64* __restrict__ pmod, const u64* __restrict__ qlm) {
+    const size_t N = (size_t)1 << t.log_n;
+    u32 z0[MAXK], z1[MAXK];
+#pragma unroll
+    for (int p = 0; p < MAXK; ++p) {
+        if (FULL || p < sh.k) {
+            split30(mul_shoup(src[(size_t)p * N], phatinv[2 * p], phatinv[2 * p + 1], t.moduli[sh.L1 + p]), z0[p], z1[p]);
+        } else {
+            z0[p] = z1[p] = 0;
+        }
+    }
+    auto conv_to = [&](int tt, u64 qt) {
+        const u64 qti = t.qinv[tt];
+        u64 slo = 0, shi = 0;
+#pragma unroll
+        for (int p0 = 0; p0 < MAXK; p0 += 8) {
+            Acc30 acc = {0, 0, 0};
+#pragma unroll
+            for (int p = p0; p < p0 + 8 && p < MAXK; ++p)
+                if (FULL || p < sh.k) {
+                    const u64 h = phatmod[(size_t)p * sh.L1 + tt];  // pre-split on the host (pack30)
+                    mac30(acc, z0[p], z1[p], (u32)h, (u32)(h >> 32));
+                }
+            acc30_flush(acc, slo, shi);
+        }
+        const u64 r = redc128(slo, shi, qt, qti);   // phatmod holds the constants times 2^64
+        return f2 ? add_mod(r, r, qt) : r;
+    };
+    // x_top: the coefficient of the unmerged result's top limb, and whether its centred representative is negative
+    const int top = sh.ell - 1;
+    const u64 qtop = t.moduli[top];
+    const u64 xt = mul_shoup(sub_mod(src[(size_t)sh.k * N], conv_to(top, qtop), qtop), pinv[2 * top], pinv[2 * top + 1], qtop);
+    const bool high = xt > (qtop >> 1);
+    const int t0 = blockIdx.z * sh.tch, t1 = min(top, t0 + sh.tch);
+    for (int tt = t0; tt < t1; ++tt) {
+        const Barrett br = load_barrett(t, tt);
+        u64 lift = barrett_reduce128(xt, 0, br);
+        if (high) lift = sub_mod(lift, qlm[tt], br.q);   // == rescale_lift_kernel
+        dst[(size_t)tt * N] = add_mod(conv_to(tt, br.q), mul_shoup(lift, pmod[2 * tt], pmod[2 * tt + 1], br.q), br.q);
+    }
+}
+
+template <int MAXK>
+__global__ __launch_bounds__(256) void moddown_rescale_exact_conv_kernel(DeviceTables t, KsShape sh, u32 f2_mask, u64* __restrict__ conv,
+                                                                         const u64* __restrict__ accP, const u64* __restrict__ phatinv,
+                                                                         const u64* __restrict__ phatmod, const u64* __restrict__ pinv,
+                                                                         const u64* __restrict__ pmod, const u64* __restrict__ qlm) {
+    const int bi = blockIdx.y >> 1;
+    const size_t N = (size_t)1 << t.log_n;
+    const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool f2 = (f2_mask >> bi) & 1;
+    const u64* src = accP + (size_t)blockIdx.y * (sh.k + 1) * N + n;
+    u64* dst = conv + (size_t)blockIdx.y * (sh.ell - 1) * N + n;
+    if (sh.k == MAXK)
+        moddown_exact_body<MAXK, true>(t, sh, f2, dst, src, phatinv, phatmod, pinv, pmod, qlm);
+    else
+        moddown_exact_body<MAXK, false>(t, sh, f2, dst, src, phatinv, phatmod, pinv, pmod, qlm);
+}
+
 // grid (N/512, batch * 2 * (ell-1))
 __global__ __launch_bounds__(256) void moddown_rescale_finish_kernel(DeviceTables t, KsShape sh, u64* __restrict__ out, const u64* __restrict__ accQ,
                                                                      const u64* __restrict__ conv, const u64* __restrict__ minv) {
@@ -737,6 +848,25 @@ void launch_moddown_rescale_conv(const DeviceTables& t, const KsShape& sh_in, u6
     sh.tch = conv_tch(nx * (unsigned)(sh.batch * 2), sh.ell - 1);
     dim3 g(nx, (unsigned)(sh.batch * 2), (unsigned)((sh.ell - 1 + sh.tch - 1) / sh.tch));
     hipLaunchKernelGGL(moddown_rescale_conv_kernel, g, dim3(256), 0, s, t, sh, conv, accP, top, hatinv, hatmod, mmod);
+}
+void launch_affine_acc_items(const DeviceTables& t, const KsShape& sh, const AffineItems& it, u64* accQ, u64* accP, const u64* d,
+                             const u64* consts, const u64* pmod, hipStream_t s) {
+    dim3 g((1u << t.log_n) / 512, (unsigned)(sh.batch * 2 * sh.ell));
+    hipLaunchKernelGGL(affine_acc_items_kernel, g, dim3(256), 0, s, t, sh, it, accQ, accP, d, consts, pmod);
+}
+void launch_moddown_rescale_exact_conv(const DeviceTables& t, const KsShape& sh_in, u32 f2, u64* conv, const u64* accP, const u64* phatinv,
+                                       const u64* phatmod, const u64* pinv, const u64* pmod, const u64* qlm, hipStream_t s) {
+    KsShape sh = sh_in;
+    const unsigned nx = (1u << t.log_n) / 256;
+    sh.tch = conv_tch(nx * (unsigned)(sh.batch * 2), sh.ell - 1);
+    dim3 g(nx, (unsigned)(sh.batch * 2), (unsigned)((sh.ell - 1 + sh.tch - 1) / sh.tch));
+#define FHELIN_MDX_CASE(K) case K: hipLaunchKernelGGL((moddown_rescale_exact_conv_kernel<K>), g, dim3(256), 0, s, t, sh, f2, conv, accP, phatinv, phatmod, pinv, pmod, qlm); break;
+    switch (sh.k) {
+        FHELIN_MDX_CASE(1) FHELIN_MDX_CASE(2) FHELIN_MDX_CASE(3) FHELIN_MDX_CASE(4)
+        FHELIN_MDX_CASE(5) FHELIN_MDX_CASE(6) FHELIN_MDX_CASE(7) FHELIN_MDX_CASE(8)
+        default: hipLaunchKernelGGL((moddown_rescale_exact_conv_kernel<16>), g, dim3(256), 0, s, t, sh, f2, conv, accP, phatinv, phatmod, pinv, pmod, qlm); break;
+    }
+#undef FHELIN_MDX_CASE
 }
 void launch_moddown_rescale_finish(const DeviceTables& t, const KsShape& sh, u64* out, const u64* accQ, const u64* conv, const u64* minv,
                                    hipStream_t s) {

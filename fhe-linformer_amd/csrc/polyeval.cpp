@@ -489,25 +489,20 @@ std::vector<CtPtr> Evaluator::eval_chebyshev_many(const std::vector<CtPtr>& xs, 
                 for (size_t j = 0; j < opos.size(); ++j) t[opos[j]] = r[j];
             }
         } else {
-            t = mult_batch(lhs, rhs);
-            t = add_batch(t, t);
-            CtRow odd_a, odd_b;
-            std::vector<size_t> odd_pos;
+            // the whole round - even powers rescale(2 T_j T_k - 1), odd powers rescale(2 T_j T_k - T_1) - through ONE batched key switch
+            // (mult_affine_batch; FHELIN_EXACT_PRODUCTS=0: mult_batch, add_batch, add_real / sub_batch, rescale_batch - the same residues)
+            std::vector<AffineSpec> spec(lhs.size());
             for (int k = h + 1; k <= k_hi; ++k)
                 for (size_t i = 0; i < rows; ++i, ++p) {
+                    spec[p].f = 2;
                     if (k % 2 == 0) {
-                        t[p] = add_real(t[p], -1.0);
+                        spec[p].cadd = -1.0;
                     } else {
-                        odd_a.push_back(t[p]);
-                        odd_b.push_back(T[1][i]);
-                        odd_pos.push_back(p);
+                        spec[p].addend = T[1][i];
+                        spec[p].negate = true;
                     }
                 }
-            if (!odd_a.empty()) {
-                CtRow d = sub_batch(odd_a, odd_b);
-                for (size_t j = 0; j < odd_pos.size(); ++j) t[odd_pos[j]] = d[j];
-            }
-            t = rescale_batch(t);
+            t = mult_affine_batch(lhs, rhs, spec);
         }
         p = 0;
         for (int k = h + 1; k <= k_hi; ++k) {
@@ -522,10 +517,10 @@ std::vector<CtPtr> Evaluator::eval_chebyshev_many(const std::vector<CtPtr>& xs, 
             G[2 * m] = mult_affine_rescale_batch(G[m], G[m], 2, -1.0, {});
             continue;
         }
-        CtRow t = mult_batch(G[m], G[m]);
-        t = add_batch(t, t);
-        for (size_t i = 0; i < rows; ++i) t[i] = add_real(t[i], -1.0);
-        G[2 * m] = rescale_batch(t);
+        AffineSpec sq;   // rescale(2 T_m^2 - 1)
+        sq.f = 2;
+        sq.cadd = -1.0;
+        G[2 * m] = mult_affine_batch(G[m], G[m], std::vector<AffineSpec>(rows, sq));
     }
     // the baby powers as they are: cheb_recurse brings the ones a leaf needs to that leaf's level
     std::vector<CtRow> babies(T.begin(), T.begin() + baby);   // index 0 unused

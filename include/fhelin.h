@@ -265,6 +265,12 @@ int fhelin_rescale_batch(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, fh
 int fhelin_mult_plain_batch(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, const fhelin_pt* p, fhelin_ct** outs);
 int fhelin_mult_batch(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct* const* b, int32_t n, fhelin_ct** outs);
 int fhelin_add_batch(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct* const* b, int32_t n, fhelin_ct** outs);
+/* outs[i] = Rescale(f[i] * EvalMult(a[i], b[i]) + cadd[i] +- addend[i]): relinearised products that are rescaled right away (the power
+ * steps T_2k = 2 T_k^2 - 1, T_(j+k) = 2 T_j T_k - T_(j-k) of a Chebyshev evaluation), all through ONE batched key switch.  f[i] is 1 or 2;
+ * addend may be null, and so may each addend[i]; negate[i] != 0 subtracts the addend.  The residues are those of fhelin_mult_batch,
+ * fhelin_add_batch, fhelin_add_real / fhelin_add_batch, rescale - bit for bit; FHELIN_EXACT_PRODUCTS=0 runs that sequence itself. */
+int fhelin_mult_affine_batch(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct* const* b, int32_t n, const int32_t* f, const double* cadd,
+                             const fhelin_ct* const* addend, const int32_t* negate, fhelin_ct** outs);
 int fhelin_level_reduce(fhelin_ctx* c, const fhelin_ct* a, int32_t new_ell, fhelin_ct** out);
 
 /* ---- the same residue functions without scale/level bookkeeping (bit-exact parity vs oracle/) -- */
