@@ -439,6 +439,13 @@ class Engine:
                 "pool_reserved_peak_bytes", "pool_trims"]
         return {k: int(v) for k, v in zip(keys, out)}
 
+    def cache_stats(self):
+        """the plaintext cache of fhelin_encode and the pool's bytes in use right now (fhelin_stats [16..18]; not part of stats(),
+        whose keys are per-sample operation counters)"""
+        out = np.zeros(19, dtype=np.uint64)
+        self._ck(self.lib.fhelin_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), 19, 0))
+        return {"pt_cache_bytes": int(out[16]), "pool_live_bytes": int(out[17]), "pt_cache_entries": int(out[18])}
+
     # ---- keys
     def keygen(self):
         self._ck(self.lib.fhelin_keygen(self.h))
@@ -1095,10 +1102,14 @@ class Pt:
     def __init__(self, eng, h):
         self.eng, self.h = eng, h
 
+    def free(self):
+        if self.h and self.eng.h:
+            self.eng.lib.fhelin_pt_free(self.h)
+        self.h = None
+
     def __del__(self):
         try:
-            if self.h and self.eng.h:
-                self.eng.lib.fhelin_pt_free(self.h)
+            self.free()
         except Exception:
             pass
         self.h = None

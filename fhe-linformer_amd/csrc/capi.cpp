@@ -115,6 +115,7 @@ void fhelin_ctx_destroy(fhelin_ctx* c) {
     if (c)
         for (hipEvent_t e : c->lane_mark)
             if (e) (void)hipEventDestroy(e);
+    if (c) c->pt_cache.clear();
     delete c;
 }
 
@@ -320,6 +321,7 @@ int fhelin_ctx_trim(fhelin_ctx* c) {
     c->ctx.require_device();
     if (c->any_pending()) flush_heavy_all(c, true);
     c->ctx.sync();
+    c->pt_cache.clear();   // the caller asks for memory back: the cached plaintexts' encodings go first (live handles keep theirs)
     c->ctx.pool.trim();
     FHELIN_CATCH
 }
@@ -422,6 +424,11 @@ int fhelin_stats(fhelin_ctx* c, uint64_t* out, int32_t cap, int32_t reset) {
             }
         }
         if (reset) p.malloc_calls = p.malloc_bytes = p.malloc_ns = 0;
+    }
+    if (cap >= 18) {   // device bytes of the encodings the plaintext cache holds; bytes the pool has handed out and not got back
+        out[16] = c->pt_cache.bytes_held();
+        out[17] = c->ctx.pool.bytes_live();
+        if (cap >= 19) out[18] = c->pt_cache.lru.size();   // plaintexts it holds
     }
     if (reset) s = OpStats();
     return FHELIN_OK;

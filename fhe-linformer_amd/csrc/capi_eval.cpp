@@ -1,7 +1,10 @@
 // extern "C" boundary, part 2: keys, plaintexts, ciphertexts, leveled evaluation.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include "capi_internal.h"
 
 using namespace fhelin;
@@ -15,6 +18,88 @@ static KeyPtr& key_slot(fhelin_ctx* c, int kind, int index) {
     if (kind == 2) return c->ev.conj_key;
     throw Error(FHELIN_ERR_ARG, "unknown key kind");
 }
+
+// ---- content-keyed plaintext cache (capi_internal.h PtCache)
+namespace fhelin {
+namespace {
+uint64_t hash_words(const double* v, size_t n) {   // the value BYTES, eight at a time
+    uint64_t h = 0xcbf29ce484222325ull ^ (uint64_t)n;
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t w;
+        std::memcpy(&w, v + i, sizeof w);
+        h = (h ^ w) * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+    }
+    return h;
+}
+}  // namespace
+
+PtCache::PtCache() {
+    if (const char* e = std::getenv("FHELIN_PT_CACHE")) on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("FHELIN_PT_CACHE_MB")) {
+        const long long mb = std::atoll(e);
+        if (mb >= 0) cap_bytes = (size_t)mb << 20;
+    }
+}
+
+size_t PtCache::bytes_held() const {
+    size_t b = 0;
+    for (const Entry& e : lru)
+        for (const auto& enc : e.p->cache) b += (size_t)enc->ell * e.p->ctx->N * sizeof(u64);
+    return b;
+}
+
+void PtCache::evict_last() {
+    auto last = std::prev(lru.end());
+    auto range = by_hash.equal_range(last->hash);
+    for (auto it = range.first; it != range.second; ++it)
+        if (it->second == last) {
+            by_hash.erase(it);
+            break;
+        }
+    lru.erase(last);
+}
+
+void PtCache::clear() {
+    by_hash.clear();
+    lru.clear();
+}
+
+// a handle of its own on the cached plaintext `master`: the values copied as Client::encode copies them, the encodings shared (Plaintext::shared)
+static PtPtr handle_on(const PtPtr& master) {
+    auto p = std::make_shared<Plaintext>();
+    p->ctx = master->ctx;
+    p->values = master->values;
+    p->slots = master->slots;
+    p->level = master->level;
+    p->shared = master;
+    return p;
+}
+
+PtPtr PtCache::encode(Client& cl, int default_slots, const double* vals, int n, int level, int slots) {
+    if (!on) return cl.encode(vals, n, level, slots);
+    const int want_slots = slots;
+    if (slots <= 0) slots = default_slots;
+    const size_t used = (size_t)std::max(0, std::min(n, slots));   // the values past `slots` never reach the plaintext
+    const uint64_t h = hash_words(vals, used) ^ ((uint64_t)(uint32_t)n << 32) ^ ((uint64_t)(uint32_t)slots << 8) ^ (uint64_t)(uint32_t)level;
+    auto range = by_hash.equal_range(h);
+    for (auto it = range.first; it != range.second; ++it) {
+        const Entry& e = *it->second;
+        if (e.n == n && e.p->slots == slots && e.p->level == level && (size_t)e.p->values.size() >= used &&
+            (used == 0 || std::memcmp(e.p->values.data(), vals, used * sizeof(double)) == 0)) {
+            lru.splice(lru.begin(), lru, it->second);   // iterators stay valid
+            return handle_on(lru.front().p);
+        }
+    }
+    PtPtr p = cl.encode(vals, n, level, want_slots);   // validates its arguments: nothing invalid is ever cached
+    // whole plaintexts go, least recently used first, while the encodings held exceed the cap (the new one holds none yet); a handle
+    // that still refers to one keeps it and its encodings alive, the cache only forgets it
+    while (!lru.empty() && (lru.size() >= MAX_ENTRIES || bytes_held() > cap_bytes)) evict_last();
+    lru.push_front(Entry{n, h, p});
+    by_hash.emplace(h, lru.begin());
+    return handle_on(p);
+}
+}  // namespace fhelin
 
 extern "C" {
 
@@ -83,7 +168,7 @@ int fhelin_encode(fhelin_ctx* c, const double* vals, int32_t n, int32_t level, i
     NEED(c && out && (vals || n == 0));
     FHELIN_TRY
     auto* h = new fhelin_pt;
-    h->p = c->cl.encode(vals, n, level, slots);
+    h->p = c->pt_cache.encode(c->cl, 1 << c->ctx.prm.log_slots, vals, n, level, slots);
     *out = h;
     FHELIN_CATCH
 }

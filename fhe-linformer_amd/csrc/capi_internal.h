@@ -2,7 +2,9 @@
 #pragma once
 #include <cstring>
 #include <exception>
+#include <list>
 #include <string>
+#include <unordered_map>
 #include "context.h"
 #include "evaluator.h"
 #include "client.h"
@@ -92,6 +94,35 @@ struct LazyHeavy {
     int lane = 0;                           // the lane (stream) the call was made under: it is evaluated there (fhelin_ctx_set_lane)
 };
 }
+// Plaintexts by CONTENT (fhelin_encode): a model's weights, biases and the drivers' masks are the same slot values in every pass, and a
+// server holds one model for every sample.  The cache keeps one Plaintext per (n, slots, level hint, value bytes); every encode gives a
+// handle of its own whose Plaintext::shared points at it, so that Plaintext::at takes the device encodings made by the handles of
+// earlier passes and launches nothing.  Only an encoding at exactly the asked (limb count, scale) is shared - the bytes the handle would
+// have made itself - so every operation reads what it read without the cache.  A hash hit is CONFIRMED against the stored values byte
+// for byte (memcmp: -0.0 and NaN payloads stay distinct), as Composite::relarge_src_ does.
+// Bounded: whole plaintexts go least recently used first once the encodings held exceed cap_bytes (a handle that still refers to an
+// evicted plaintext keeps it alive; the cache only forgets it).  One engine per thread: no lock.  FHELIN_PT_CACHE=0: every encode makes
+// a plaintext of its own; FHELIN_PT_CACHE_MB: the cap (default 1024).
+namespace fhelin {
+struct PtCache {
+    struct Entry {
+        int n = 0;          // values the caller gave
+        uint64_t hash = 0;  // of the bytes of the values that count (the first min(n, slots))
+        PtPtr p;            // slots, level hint and the values themselves (no imaginary part: fhelin_encode takes real vectors)
+    };
+    static constexpr size_t MAX_ENTRIES = 4096;   // plaintexts that were never used hold no encoding: bounded by count
+    bool on = true;
+    size_t cap_bytes = (size_t)1 << 30;
+    std::list<Entry> lru;                         // most recently used first
+    std::unordered_multimap<uint64_t, std::list<Entry>::iterator> by_hash;
+    PtCache();
+    PtPtr encode(Client& cl, int default_slots, const double* vals, int n, int level, int slots);
+    size_t bytes_held() const;                    // device bytes of the encodings of the cached plaintexts
+    void clear();
+private:
+    void evict_last();
+};
+}  // namespace fhelin
 // opaque handle behind include/fhelin.h's `fhelin_ctx`
 struct fhelin_ctx {
     fhelin::Context ctx;
@@ -112,6 +143,7 @@ struct fhelin_ctx {
     hipEvent_t lane_mark[fhelin::DevicePool::MAX_LANES] = {};   // fhelin_ctx_lane_mark: a point in a lane's stream others can wait for
     bool lane_marked[fhelin::DevicePool::MAX_LANES] = {};
     fhelin::LevelPlan plan;
+    fhelin::PtCache pt_cache;   // declared after ctx: gone before the device pool is torn down
     // the unwrap of wrapped inputs (capi_wrapped.cpp): the mask (1 in the slots = 0 mod 128) and the tables of a rescale that drops p_0
     fhelin::PtPtr wrap_mask;
     const fhelin::u64* p0_qlinv = nullptr;   // [n_q][2] p_0^-1 mod q_t, Shoup

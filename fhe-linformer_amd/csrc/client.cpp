@@ -315,12 +315,33 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
             order(cache[0]);
             return cache[0];
         }
-    auto e = encode_to_device(*ctx, values, imag, slots, ell, scale);
-    e->made_lane = ctx->pool.cur_lane;
-    e->lanes_ordered = 1u << e->made_lane;
-    if (ctx->n_lanes > 0) {
-        hip_check(hipEventCreateWithFlags(&e->ready, hipEventDisableTiming), "hipEventCreate(encoding)");
-        hip_check(hipEventRecord(e->ready, ctx->stream), "hipEventRecord(encoding)");
+    auto sync_all = [&]() {
+        hip_check(hipStreamSynchronize(ctx->main_stream), "encoding eviction sync");
+        for (int k = 1; k <= ctx->n_lanes; ++k) hip_check(hipStreamSynchronize(ctx->lane_stream[k]), "encoding eviction sync (lane)");
+    };
+    std::shared_ptr<Encoding> e;
+    if (shared)   // an earlier handle of the same values has made exactly this encoding: nothing to launch
+        for (size_t i = 0; i < shared->cache.size() && !e; ++i)
+            if (shared->cache[i]->ell == ell && shared->cache[i]->scale == scale) {
+                if (i) std::rotate(shared->cache.begin(), shared->cache.begin() + i, shared->cache.begin() + i + 1);
+                e = shared->cache[0];
+                order(e);
+            }
+    if (!e) {
+        e = encode_to_device(*ctx, values, imag, slots, ell, scale);
+        e->made_lane = ctx->pool.cur_lane;
+        e->lanes_ordered = 1u << e->made_lane;
+        if (ctx->n_lanes > 0) {
+            hip_check(hipEventCreateWithFlags(&e->ready, hipEventDisableTiming), "hipEventCreate(encoding)");
+            hip_check(hipEventRecord(e->ready, ctx->stream), "hipEventRecord(encoding)");
+        }
+        if (shared) {
+            shared->cache.insert(shared->cache.begin(), e);
+            if (shared->cache.size() > MAX_SHARED_ENCODINGS) {   // as below: the copy that goes may still be read by work in flight
+                sync_all();
+                shared->cache.pop_back();
+            }
+        }
     }
     cache.insert(cache.begin(), e);
     // one entry per (limb count, scale) the plaintext has been used at: bounded by the chain length in principle, capped here
@@ -329,8 +350,7 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
     if (cache.size() > MAX_ENCODINGS) {
         // the evicted copy may still be read by work in flight on any stream: its block must not go back to a pool before that
         // work is done (rare: more than MAX_ENCODINGS distinct levels for one plaintext)
-        hip_check(hipStreamSynchronize(ctx->main_stream), "encoding eviction sync");
-        for (int k = 1; k <= ctx->n_lanes; ++k) hip_check(hipStreamSynchronize(ctx->lane_stream[k]), "encoding eviction sync (lane)");
+        sync_all();
         cache.pop_back();
     }
     return e;

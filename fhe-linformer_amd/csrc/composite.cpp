@@ -25,6 +25,7 @@ Composite::Composite(Evaluator& ev, Client& cl) : ev_(ev), cl_(cl) {
     if (const char* e = std::getenv("FHELIN_MERGED_PRODUCTS")) ev_.merged_products = std::atoi(e) != 0;
     if (const char* e = std::getenv("FHELIN_EXACT_PRODUCTS")) ev_.exact_products = std::atoi(e) != 0;
     if (const char* e = std::getenv("FHELIN_CHEB_LEAF_AT")) ev_.cheb_leaf_at_product = std::atoi(e) != 0;
+    if (const char* e = std::getenv("FHELIN_ADJUST_ITEMS")) ev_.adjust_items = std::atoi(e) != 0;
     if (const char* b = std::getenv("FHELIN_BATCH")) {
         int v = std::atoi(b);
         if (v >= 1 && v <= 256) ev_.batch_limit = v;

@@ -335,6 +335,7 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
         if (const char* e = std::getenv("FHELIN_FUSE_LIFT")) fuse_lift = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_LDS_DIGITS")) lds_digits = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_NTT_TRACE")) trace_small_ntt = std::atoi(e);
+        if (const char* e = std::getenv("FHELIN_SCALAR_TRACE")) trace_scalar = std::atoi(e);
         if (const char* e = std::getenv("FHELIN_HOST_WAITS")) trace_waits = std::atoi(e) != 0;
     }
     hip_check(hipEventCreate(&ev_start), "hipEventCreate");
@@ -572,6 +573,13 @@ Context::~Context() {
         for (size_t i = 0; i < v.size() && i < 40; ++i)
             fprintf(stderr, "  %8llu %9llu  %s\n", (unsigned long long)v[i].second.first, (unsigned long long)v[i].second.second, v[i].first.c_str());
     }
+    if (trace_scalar && !scalar_sites.empty()) {
+        std::vector<std::pair<std::string, std::pair<u64, u64>>> v(scalar_sites.begin(), scalar_sites.end());
+        std::sort(v.begin(), v.end(), [](const auto& a, const auto& b) { return a.second.first > b.second.first; });
+        fprintf(stderr, "[fhelin] single-ciphertext integer / constant multiplies (ew_scalar_kernel) by call stack (launches, limb vectors):\n");
+        for (size_t i = 0; i < v.size() && i < 40; ++i)
+            fprintf(stderr, "  %8llu %9llu  %s\n", (unsigned long long)v[i].second.first, (unsigned long long)v[i].second.second, v[i].first.c_str());
+    }
     if (has_device) {
         (void)hipSetDevice(prm.device);
         (void)hipDeviceSynchronize();
@@ -610,11 +618,12 @@ void Context::sync() {
     }
 }
 
-void Context::note_small_ntt(int nvec) {
+// the demangled names of the callers' frames first .. 8, innermost first
+__attribute__((noinline)) static std::string call_stack_key(int first) {
     void* fr[12];
     const int n = backtrace(fr, 12);
     std::string key;
-    for (int i = 2; i < n && i < 9; ++i) {
+    for (int i = first; i < n && i < 9; ++i) {
         Dl_info info;
         std::string name = "?";
         if (dladdr(fr[i], &info) && info.dli_sname) {
@@ -625,9 +634,19 @@ void Context::note_small_ntt(int nvec) {
             const size_t par = name.find('(');
             if (par != std::string::npos) name.resize(par);
         }
-        key += (i > 2 ? " < " : "") + name;
+        key += (i > first ? " < " : "") + name;
     }
-    auto& e = small_ntt_sites[key];
+    return key;
+}
+
+void Context::note_small_ntt(int nvec) {
+    auto& e = small_ntt_sites[call_stack_key(3)];
+    e.first += 1;
+    e.second += (u64)nvec;
+}
+
+void Context::note_scalar(int nvec) {
+    auto& e = scalar_sites[call_stack_key(2)];
     e.first += 1;
     e.second += (u64)nvec;
 }

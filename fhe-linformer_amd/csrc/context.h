@@ -327,6 +327,9 @@ struct Context {
     int trace_small_ntt = 0;
     std::map<std::string, std::pair<u64, u64>> small_ntt_sites;   // call stack -> (launches, limb vectors)
     void note_small_ntt(int nvec);
+    int trace_scalar = 0;                                         // FHELIN_SCALAR_TRACE=1: the same table for the launches of ew_scalar_kernel
+    std::map<std::string, std::pair<u64, u64>> scalar_sites;
+    void note_scalar(int nvec);
     void ntt_epilogue(const LimbBatch& b, const NttEpilogue& ep) {
         stats.limb_ntt += (u64)b.nvec;
         if (trace_small_ntt && b.nvec <= trace_small_ntt) note_small_ntt(b.nvec);

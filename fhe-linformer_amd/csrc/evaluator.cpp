@@ -1935,6 +1935,7 @@ CtPtr Evaluator::mult_int(const CtPtr& a, u64 k, bool raise_deg, long double new
         sc.v[2 * i + 1] = h_shoup(v, q);
     }
     CtPtr o = new_ct(a->npoly, ell, raise_deg ? a->deg + 1 : a->deg, new_scale, a->slots);
+    if (c_.trace_scalar) c_.note_scalar(a->npoly * ell);
     launch_ew_scalar(c_.dt, o->d, a->d, sc, a->npoly * ell, 0, ell, c_.stream, ell < a->ell ? a->ell : 0);
     launch_ok("mult_int");
     return o;
@@ -1962,31 +1963,70 @@ std::vector<CtPtr> Evaluator::adjust_deg1_batch(const std::vector<CtPtr>& v, int
         pos.push_back(i);
     }
     if (!src.empty()) {
-        // the integer products land in ONE block (ell + 1 limbs each: only what the rescale reads), so that the batched rescale takes
-        // them as they stand
-        bool same = true;
-        for (const CtPtr& c : src) same = same && c->npoly == src[0]->npoly;
-        std::vector<CtPtr> blk = same ? new_ct_batch((int)src.size(), src[0]->npoly, ell + 1, 2, 0, src[0]->slots) : std::vector<CtPtr>();
-        for (size_t j = 0; j < src.size(); ++j) {
-            const CtPtr& cur = src[j];
-            const long double qdrop = (long double)c_.chain.q[ell];
-            const u64 k = (u64)llroundl(scales[pos[j]] * qdrop / cur->scale);
-            if (!same) {
-                pending.push_back(mult_int(cur, k, true, cur->scale * (long double)k, ell + 1));
+        // the integer products land in ONE block per component count (ell + 1 limbs each: only what the rescale reads), so that the
+        // batched rescale takes them as they stand
+        const long double qdrop = (long double)c_.chain.q[ell];
+        const int lim = ell + 1;
+        pending.assign(src.size(), CtPtr());
+        std::map<int, std::vector<size_t>> by_npoly;
+        for (size_t j = 0; j < src.size(); ++j) by_npoly[src[j]->npoly].push_back(j);
+        for (const auto& g : by_npoly) {
+            const std::vector<size_t>& idx = g.second;
+            const size_t B = idx.size();
+            const int npoly = g.first;
+            if (B == 1 && by_npoly.size() > 1) {   // a single ciphertext of its shape: no block to share
+                const CtPtr& cur = src[idx[0]];
+                const u64 k = (u64)llroundl(scales[pos[idx[0]]] * qdrop / cur->scale);
+                pending[idx[0]] = mult_int(cur, k, true, cur->scale * (long double)k, lim);
                 continue;
             }
-            ScalarSet sc;
-            for (int l = 0; l <= ell; ++l) {
-                const u64 q = c_.chain.q[l], r = k % q;
-                sc.v[2 * l] = r;
-                sc.v[2 * l + 1] = h_shoup(r, q);
+            std::vector<CtPtr> blk = new_ct_batch((int)B, npoly, lim, 2, 0, src[idx[0]]->slots);
+            const bool items = adjust_items && B > 1;
+            std::vector<u64> consts(items ? B * lim * 2 : 0);
+            for (size_t b = 0; b < B; ++b) {
+                const CtPtr& cur = src[idx[b]];
+                const u64 k = (u64)llroundl(scales[pos[idx[b]]] * qdrop / cur->scale);
+                const CtPtr& o = blk[b];
+                o->deg = cur->deg + 1;
+                o->scale = cur->scale * (long double)k;
+                o->slots = cur->slots;
+                pending[idx[b]] = o;
+                if (items) {
+                    for (int l = 0; l < lim; ++l) {
+                        const u64 q = c_.chain.q[l], r = k % q;
+                        consts[(b * lim + l) * 2] = r;
+                        consts[(b * lim + l) * 2 + 1] = h_shoup(r, q);
+                    }
+                    continue;
+                }
+                ScalarSet sc;
+                for (int l = 0; l < lim; ++l) {
+                    const u64 q = c_.chain.q[l], r = k % q;
+                    sc.v[2 * l] = r;
+                    sc.v[2 * l + 1] = h_shoup(r, q);
+                }
+                if (c_.trace_scalar) c_.note_scalar(npoly * lim);
+                launch_ew_scalar(c_.dt, o->d, cur->d, sc, npoly * lim, 0, lim, c_.stream, lim < cur->ell ? cur->ell : 0);
             }
-            CtPtr o = blk[j];
-            o->deg = cur->deg + 1;
-            o->scale = cur->scale * (long double)k;
-            o->slots = cur->slots;
-            launch_ew_scalar(c_.dt, o->d, cur->d, sc, cur->npoly * (ell + 1), 0, ell + 1, c_.stream, ell + 1 < cur->ell ? cur->ell : 0);
-            pending.push_back(o);
+            if (!items) continue;
+            // every product of the group in one launch per EwScalarItems::MAX_ITEMS ciphertexts: the constants of (ciphertext, limb)
+            // travel as a device table, uploaded once
+            Scratch<u64> dk = c_.scratch<u64>(consts.size());
+            for (size_t off = 0; off < consts.size(); off += 2 * c_.N)   // upload_async takes <= 2N words per call
+                c_.upload_async(dk + off, consts.data() + off, std::min(consts.size() - off, (size_t)2 * c_.N));
+            for (size_t lo = 0; lo < B; lo += EwScalarItems::MAX_ITEMS) {
+                EwScalarItems d;
+                d.n = (int)std::min(B - lo, (size_t)EwScalarItems::MAX_ITEMS);
+                d.npoly = npoly;
+                d.ell = lim;
+                for (int k = 0; k < d.n; ++k) {
+                    d.a[k] = src[idx[lo + k]]->d;
+                    d.in_limbs[k] = src[idx[lo + k]]->ell;
+                }
+                launch_ew_scalar_items(c_.dt, d, blk[lo]->d, dk + lo * lim * 2, c_.stream);
+            }
+            launch_ok("adjust_deg1_batch");
+            dk.reset();
         }
         launch_ok("adjust_deg1_batch");
     }

@@ -77,6 +77,12 @@ struct Plaintext {
     static constexpr size_t MAX_ENCODINGS = 16;
     std::vector<std::shared_ptr<Encoding>> cache;   // most recently used first (Plaintext::at)
     std::shared_ptr<Encoding> at(int ell, long double scale);
+    // set on a handle of the content-keyed plaintext cache (capi_internal.h PtCache): the cache's own plaintext of the same values.  An
+    // encoding this handle has not used yet is taken from there when one exists at EXACTLY this (limb count, scale) - the bytes this
+    // handle would have made itself - and every encoding made here is left there for the handles of later passes.  The handle's own
+    // list, and with it which of two nearly equal scales an operation gets, is what it would be without the cache.
+    std::shared_ptr<Plaintext> shared;
+    static constexpr size_t MAX_SHARED_ENCODINGS = 64;
 };
 typedef std::shared_ptr<Plaintext> PtPtr;
 
@@ -114,6 +120,7 @@ public:
     bool cheb_leaf_at_product = true;   // r-leaves of the Paterson-Stockmeyer tree born at their product's (limbs, scale); FHELIN_CHEB_LEAF_AT=0: level-adjusted afterwards
     bool cheb_leaf_classes = true;   // a Chebyshev leaf's babies aligned to the deepest power IT uses (one level saved: OpenFHE's depth); FHELIN_CHEB_LEAF_CLASSES=0: all babies at one level
     bool cheb_rounds = true;   // Paterson-Stockmeyer products in rounds (polyeval.cpp cheb_recurse); FHELIN_CHEB_ROUNDS=0: one at a time
+    bool adjust_items = true;  // the integer products of a batched level adjustment in one launch per 32 ciphertexts (adjust_deg1_batch); FHELIN_ADJUST_ITEMS=0: one launch each
     int batch_limit = 32;   // rows processed per batched key switch (FHELIN_BATCH overrides; 16 / 24 / 32 / 48 / 64 re-measured at the end of round 2: DESIGN.md)
     CtPtr clone(const CtPtr& a);
     KeyPtr new_key();

@@ -85,6 +85,20 @@ struct EwScaledDiff {
     const u64* w[MAX_ITEMS];
 };
 void launch_ew_scaled_diff(const DeviceTables& t, const EwScaledDiff& d, const u64* consts, hipStream_t s);
+// Integer multiples of up to MAX_ITEMS ciphertexts in ONE launch, written into one dense block (the products of a batched level
+// adjustment, which the batched rescale takes as they stand, Evaluator::adjust_deg1_batch):
+//     out[i][c][l] = (k_{i,l} * a_i[c][l]) mod q_l,   c < npoly, l < ell
+// a_i: [npoly][in_limbs[i]][N] with in_limbs[i] >= ell (the limbs above ell are not read); out: [n][npoly][ell][N];
+// consts: device array [n][ell][2] = (k mod q_l, shoup) per item and limb.  Canonical output, the residues of launch_ew_scalar.
+struct EwScalarItems {
+    static constexpr int MAX_ITEMS = EwItems::MAX_ITEMS;
+    int n = 0;
+    int npoly = 0;
+    int ell = 0;
+    int in_limbs[MAX_ITEMS];
+    const u64* a[MAX_ITEMS];
+};
+void launch_ew_scalar_items(const DeviceTables& t, const EwScalarItems& d, u64* out, const u64* consts, hipStream_t s);
 // out[v] = sum_i a_i[v] * b_i[v % b_vecs] over the n items (n <= MAX_ITEMS): an inner product of ciphertexts with plaintexts in
 // one pass (the diagonal sums of the bootstrapping linear transforms, wrapUpRepeated, matmulCRlarge) instead of n product
 // launches and a tree of additions.  128-bit accumulation, one reduction: the canonical residue of the sum.

@@ -463,6 +463,27 @@ __global__ __launch_bounds__(256) void ew_scalar_kernel(DeviceTables t, u64* out
     reinterpret_cast<u64x2*>(out)[(size_t)v * row + n2] = r;
 }
 
+// out[i][c][l] = k_{i,l} * a_i[c][l]  for l < d.ell, c < d.npoly; grid (N/512, n * npoly * ell).  Item i reads its own source, whose
+// polynomials are in_limbs[i] >= ell limbs apart (the limbs above ell are not touched), and writes its slot of ONE dense block.  The
+// constant pair of (item, limb) is wave-uniform (scalar loads); the same mul_shoup as ew_scalar_kernel: the same canonical residues.
+__global__ __launch_bounds__(256) void ew_scalar_items_kernel(DeviceTables t, EwScalarItems d, u64* __restrict__ out,
+                                                              const u64* __restrict__ consts) {
+    const int vecs = d.npoly * d.ell;
+    const int item = blockIdx.y / vecs, v = blockIdx.y % vecs;
+    const int limb = v % d.ell;
+    const u64 q = t.moduli[limb];
+    const u64* k = consts + ((size_t)item * d.ell + limb) * 2;
+    const u64 w = k[0], ws = k[1];
+    const size_t n2 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t row = ((size_t)1 << t.log_n) >> 1;
+    const size_t vin = (size_t)(v / d.ell) * d.in_limbs[item] + limb;
+    const u64x2 x = reinterpret_cast<const u64x2*>(d.a[item])[vin * row + n2];
+    u64x2 r;
+    r.x = mul_shoup(x.x, w, ws, q);
+    r.y = mul_shoup(x.y, w, ws, q);
+    reinterpret_cast<u64x2*>(out)[((size_t)item * vecs + v) * row + n2] = r;
+}
+
 // out_i[v] = a_{i,l} * u_i[v] - c_{i,l} * w_i[v]  (l = v % ell); grid (N/512, n * vecs).  The four constants of (item, limb) are
 // wave-uniform (scalar loads); u and w stream through 16-byte accesses.
 __global__ __launch_bounds__(256) void ew_scaled_diff_kernel(DeviceTables t, EwScaledDiff d, const u64* __restrict__ consts) {
@@ -791,6 +812,10 @@ void launch_ew_scalar(const DeviceTables& t, u64* out, const u64* a, const Scala
                       int in_limbs) {
     if (nvec <= 0) return;
     hipLaunchKernelGGL(ew_scalar_kernel, grid2(t.log_n, nvec), dim3(256), 0, s, t, out, a, sc, limb_first, limb_count, in_limbs);
+}
+void launch_ew_scalar_items(const DeviceTables& t, const EwScalarItems& d, u64* out, const u64* consts, hipStream_t s) {
+    if (d.n <= 0 || d.npoly <= 0 || d.ell <= 0) return;
+    hipLaunchKernelGGL(ew_scalar_items_kernel, grid2(t.log_n, d.n * d.npoly * d.ell), dim3(256), 0, s, t, d, out, consts);
 }
 void launch_ew_scaled_diff(const DeviceTables& t, const EwScaledDiff& d, const u64* consts, hipStream_t s) {
     if (d.n <= 0 || d.vecs <= 0 || d.ell <= 0) return;

@@ -29,6 +29,7 @@ CtPtr Evaluator::mult_real(const CtPtr& a, double cst) {
     ScalarSet sc;
     real_to_scalars(c_, (long double)cst * sf, x->ell, sc);
     CtPtr o = new_ct(x->npoly, x->ell, x->deg + 1, x->scale * sf, x->slots);
+    if (c_.trace_scalar) c_.note_scalar(x->npoly * x->ell);
     launch_ew_scalar(c_.dt, o->d, x->d, sc, x->npoly * x->ell, 0, x->ell, c_.stream);
     hip_check(hipGetLastError(), "mult_real");
     return o;

@@ -155,7 +155,9 @@ int fhelin_ntt(fhelin_ctx* c, uint64_t* d_data, int32_t nvec, int32_t limb_first
  * [7] sum of live limbs over rescales, [8] sum of live limbs over ct x pt products, and with cap >= 12 the growth of the
  * device pool: [9] blocks obtained from hipMalloc, [10] their bytes, [11] host nanoseconds spent inside hipMalloc, and with
  * cap >= 16: [12] bytes the pool holds from the driver now, [13] / [14] high-water marks of bytes in use / held since the last
- * reset, [15] out-of-memory events (everything idle handed back: a device-wide synchronisation each) */
+ * reset, [15] out-of-memory events (everything idle handed back: a device-wide synchronisation each), and with cap >= 18:
+ * [16] device bytes of the encodings the plaintext cache holds (fhelin_encode), [17] bytes the pool has handed out and not got back, and with
+ * cap >= 19: [18] plaintexts the cache holds */
 int fhelin_stats(fhelin_ctx* c, uint64_t* out, int32_t cap, int32_t reset);
 /* host-side self-test of the device memory arena (slabs, best fit, coalescing) against a pretend device of device_bytes: n_ops random
  * allocations / frees in the engine's size mix; checks that blocks never overlap, lie inside a slab, that freeing everything leaves one
@@ -177,6 +179,10 @@ int fhelin_key_export(fhelin_ctx* c, int32_t kind, int32_t index, uint64_t* out,
 int fhelin_key_import(fhelin_ctx* c, int32_t kind, int32_t index, const uint64_t* in, size_t words);
 
 /* ---- plaintexts: context->MakeCKKSPackedPlaintext(vec, 1, level, nullptr, slots)  :353,:368 ---- */
+/* Plaintexts are cached per context BY CONTENT: a second encode of the same (n, slots, level, value bytes) gives a handle that shares the
+ * first one's device encodings at exactly equal (limbs, scale) (a model's weights and masks are encoded once, not once per pass).  `vals` is copied: changing the array
+ * afterwards changes nothing.  fhelin_pt_free drops the handle's reference only; the cache itself is bounded (FHELIN_PT_CACHE_MB, default
+ * 1024, least recently used plaintext first) and emptied by fhelin_ctx_trim and fhelin_ctx_destroy.  FHELIN_PT_CACHE=0: no cache. */
 int fhelin_encode(fhelin_ctx* c, const double* vals, int32_t n, int32_t level, int32_t slots, fhelin_pt** out);
 void fhelin_pt_free(fhelin_pt* p);
 /* the residues [ell][N] (NTT form) this plaintext multiplies / adds with at `ell` live limbs and real scaling factor
