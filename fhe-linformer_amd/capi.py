@@ -222,6 +222,9 @@ def load_library():
                                                C.POINTER(i32), vp]),
         "fhelin_wrapped_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, i32]),
         "fhelin_unwrap_inputs": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp)]),
+        "fhelin_sanitize": (i32, [vp, C.POINTER(vp), i32, vp, i32, i32, C.POINTER(vp)]),
+        "fhelin_debug_flood": (i32, [vp, vp, C.c_uint64, i32, i32, vp, C.c_size_t]),
+        "fhelin_decrypt_flooded": (i32, [vp, vp, i32, C.POINTER(C.c_double), i32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -659,6 +662,37 @@ class Engine:
         outs = self._outs(total)
         self._ck(self.lib.fhelin_unwrap_inputs(self.h, arr, len(ws), outs))
         return self._cts(outs, total)
+
+    # ---- sanitised replies (include/fhelin.h "Sanitised replies")
+    def sanitize(self, cts, mask=None, flood_bits=0, out_ell=2):
+        """the reply form of result ciphertexts: degree 2 rescaled, the optional 0/1 mask (a Pt, or slot values) applied, the first
+        out_ell limbs kept, a fresh public-key encryption of zero and a flood term uniform on [-2^flood_bits, 2^flood_bits) added -
+        one fused launch for the whole list.  A single Ct gives a single Ct.  Works on an evaluation context."""
+        single = isinstance(cts, Ct)
+        v = [cts] if single else list(cts)
+        pt = None
+        if mask is not None:
+            pt = mask if isinstance(mask, Pt) else self.encode(mask)
+        outs = self._outs(len(v))
+        arr = (C.c_void_p * max(len(v), 1))(*[c.h for c in v])
+        self._ck(self.lib.fhelin_sanitize(self.h, arr, len(v), pt.h if pt is not None else None, int(flood_bits), int(out_ell), outs))
+        r = self._cts(outs, len(v))
+        return r[0] if single else r
+
+    def debug_flood(self, key, stream, flood_bits, ell=None):
+        """the wide sampler alone for an explicit 32-byte ChaCha20 key and stream: residues [ell][N], coefficient form"""
+        ell = self.n_q if ell is None else int(ell)
+        kb = (C.c_uint8 * 32)(*bytes(key))
+        out = np.empty((max(ell, 0), self.N), dtype=np.uint64)
+        self._ck(self.lib.fhelin_debug_flood(self.h, kb, int(stream), int(flood_bits), ell, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def decrypt_flooded(self, ct, flood_bits, slots=0):
+        """noise-flooding decryption: decrypt with one flood polynomial added to the phase before the download; flood_bits=0 is decrypt"""
+        n = slots or ct.slots or (1 << self.params.log_slots)
+        out = np.empty(n, dtype=np.float64)
+        self._ck(self.lib.fhelin_decrypt_flooded(self.h, ct.h, int(flood_bits), out.ctypes.data_as(C.POINTER(C.c_double)), n))
+        return out
 
     def set_host_encode(self, on):
         self._ck(self.lib.fhelin_ctx_set_host_encode(self.h, 1 if on else 0))

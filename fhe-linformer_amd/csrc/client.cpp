@@ -596,6 +596,115 @@ void Client::sample_small_device(u64* dst, int n_poly, int ell, int kind) {
     launch_sample_small(c_.dt, dst, key, (sample_calls_++) << 32, kind, ell, n_poly, c_.stream);
 }
 
+SamplerKey Client::draw_sampler_key() {
+    SamplerKey key;   // as sample_small_device: a fresh ChaCha20 key per call from the context's own generator
+    for (int i = 0; i < 4; ++i) {
+        const u64 w = rng_.next();
+        key.w[2 * i] = (u32)w;
+        key.w[2 * i + 1] = (u32)(w >> 32);
+    }
+    return key;
+}
+
+void Client::sample_flood_device(u64* dst, int n_poly, int ell, int flood_bits, bool gauss) {
+    const SamplerKey key = draw_sampler_key();
+    const u64 flood_stream = (sample_calls_++) << 32, gauss_stream = (sample_calls_++) << 32;   // two distinct stream ranges
+    launch_sample_flood(c_.dt, dst, key, flood_stream, gauss_stream, flood_bits, gauss, ell, n_poly, c_.stream);
+}
+
+void Client::check_flood(int flood_bits, int nl, const char* who) const {
+    if (flood_bits < 0 || flood_bits > 62) throw Error(FHELIN_ERR_ARG, std::string(who) + ": flood_bits must lie in [0, 62]");
+    long double bits = 0;
+    for (int l = 0; l < nl; ++l) bits += log2l((long double)c_.chain.q[l]);
+    if (flood_bits > 0 && !((long double)(flood_bits + 2) < bits))
+        throw Error(FHELIN_ERR_ARG, std::string(who) + ": 2^(flood_bits + 2) must stay below the product of the limbs kept");
+}
+
+std::vector<u64> Client::debug_flood(const uint8_t key[32], u64 stream, int flood_bits, int ell) {
+    c_.require_device();
+    if (flood_bits < 1 || flood_bits > 62) throw Error(FHELIN_ERR_ARG, "debug_flood: flood_bits must lie in [1, 62]");
+    if (ell < 1 || ell > c_.L + 1) throw Error(FHELIN_ERR_ARG, "debug_flood: limb count out of range");
+    SamplerKey k;
+    for (int i = 0; i < 8; ++i)
+        k.w[i] = (u32)key[4 * i] | ((u32)key[4 * i + 1] << 8) | ((u32)key[4 * i + 2] << 16) | ((u32)key[4 * i + 3] << 24);
+    const size_t n = (size_t)ell * c_.N;
+    Scratch<u64> d = c_.scratch<u64>(n);
+    launch_sample_flood(c_.dt, d, k, stream, 0, flood_bits, false, ell, 1, c_.stream);
+    hip_check(hipGetLastError(), "flood sampler");
+    std::vector<u64> h(n);
+    hip_check(hipMemcpyAsync(h.data(), d, n * 8, hipMemcpyDeviceToHost, c_.stream), "flood download");
+    hip_check(hipStreamSynchronize(c_.stream), "flood sync");
+    return h;
+}
+
+std::vector<CtPtr> Client::sanitize(const std::vector<CtPtr>& vin, const PtPtr& mask, int flood_bits, int out_ell) {
+    Context& c = c_;
+    c.require_device();
+    if (!pk) throw Error(FHELIN_ERR_KEY, "sanitize: the context holds no public key (keygen, or an evaluation-key set)");
+    if (out_ell <= 0) out_ell = 2;
+    if (out_ell > c.L + 1) throw Error(FHELIN_ERR_ARG, "sanitize: out_ell above the chain's limbs");
+    check_flood(flood_bits, out_ell, "sanitize");
+    // every refusal before any device work
+    for (const CtPtr& ct : vin) {
+        if (!ct || ct->wrapped()) throw Error(FHELIN_ERR_ARG, "sanitize: a wrapped input ciphertext is not a result");
+        if (ct->npoly != 2) throw Error(FHELIN_ERR_ARG, "sanitize: a 3-component ciphertext must be relinearised first");
+        const int left = ct->ell - std::max(0, ct->deg - 1) - (mask ? 1 : 0);
+        if (left < out_ell) throw Error(FHELIN_ERR_ARG, "sanitize: too few limbs for the rescale, the mask and out_ell");
+    }
+    std::vector<CtPtr> x = vin;
+    auto rescale_where = [&](int min_deg) {   // batched, every ciphertext above degree 1 (as decrypt rescales its input)
+        for (;;) {
+            std::vector<CtPtr> need;
+            std::vector<size_t> at;
+            for (size_t i = 0; i < x.size(); ++i)
+                if (x[i]->deg >= min_deg) {
+                    need.push_back(x[i]);
+                    at.push_back(i);
+                }
+            if (need.empty()) return;
+            std::vector<CtPtr> r = ev_.rescale_batch(need);
+            for (size_t k = 0; k < at.size(); ++k) x[at[k]] = r[k];
+        }
+    };
+    rescale_where(2);
+    if (mask) {
+        x = ev_.mult_plain_batch(x, mask);
+        rescale_where(2);
+    }
+    const size_t N = c.N, pn = (size_t)out_ell * N;
+    const int L1 = c.L + 1;
+    std::vector<CtPtr> out;
+    const int CHUNK = 32;                                    // bounds the temporaries (3 polynomials per ciphertext in flight)
+    for (size_t lo = 0; lo < x.size(); lo += CHUNK) {
+        const int n = (int)std::min<size_t>(CHUNK, x.size() - lo);
+        std::vector<CtPtr> cts = ev_.new_ct_batch(n, 2, out_ell, 1, x[lo]->scale, x[lo]->slots);
+        std::vector<RerandItem> tab(n);
+        for (int b = 0; b < n; ++b) {
+            const Ciphertext& in = *x[lo + b];
+            cts[b]->scale = in.scale;
+            cts[b]->slots = in.slots;
+            tab[b].in = in.d;
+            tab[b].out = cts[b]->d;
+            tab[b].in_ell = in.ell;
+        }
+        Scratch<RerandItem> d_tab = c.scratch<RerandItem>((size_t)n);
+        hip_check(hipMemcpyAsync(d_tab, tab.data(), (size_t)n * sizeof(RerandItem), hipMemcpyHostToDevice, c.stream), "sanitize item table");
+        Scratch<u64> rnd = c.scratch<u64>((size_t)3 * n * pn);           // u | e0 + f | e1, each [n][out_ell][N]
+        sample_small_device(rnd, n, out_ell, 1);
+        if (flood_bits > 0) sample_flood_device(rnd + (size_t)n * pn, n, out_ell, flood_bits, true);
+        else sample_small_device(rnd + (size_t)n * pn, n, out_ell, 0);
+        sample_small_device(rnd + (size_t)2 * n * pn, n, out_ell, 0);
+        c.ntt(LimbBatch{rnd, 3 * n * out_ell, nullptr, 0, out_ell}, false);
+        launch_rerandomize_combine(c.dt, d_tab, pk, rnd, rnd + (size_t)n * pn, rnd + (size_t)2 * n * pn, out_ell, L1, n, c.stream);
+        hip_check(hipGetLastError(), "sanitize kernels");
+        // the randomness (u, e0 + f, e1) does not stay behind in a recycled pool block
+        hip_check(hipMemsetAsync(rnd, 0, (size_t)3 * n * pn * sizeof(u64), c.stream), "hipMemsetAsync(sanitize randomness)");
+        rnd.reset();
+        for (auto& ct : cts) out.push_back(ct);
+    }
+    return out;
+}
+
 std::vector<long> Client::debug_sample(int kind, int n_poly) {
     c_.require_device();
     const size_t N = c_.N;
@@ -874,8 +983,9 @@ CtPtr Client::phase(const CtPtr& ct, int nl) {
     return o;
 }
 
-std::vector<double> Client::decrypt(const CtPtr& cin, int slots) {
+std::vector<double> Client::decrypt(const CtPtr& cin, int slots, int flood_bits) {
     if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+    if (flood_bits < 0 || flood_bits > 62) throw Error(FHELIN_ERR_ARG, "decrypt_flooded: flood_bits must lie in [0, 62]");
     CtPtr ct = cin;
     while (ct->deg > 1 && ct->ell > 2) ct = ev_.rescale(ct);
     if (slots <= 0) slots = ct->slots > 0 ? ct->slots : (1 << c_.prm.log_slots);
@@ -884,6 +994,14 @@ std::vector<double> Client::decrypt(const CtPtr& cin, int slots) {
     CtPtr ph = phase(ct, nl);
     u64* m = ph->d;
     c_.ntt(LimbBatch{m, nl, nullptr, 0, nl}, true);
+    if (flood_bits > 0) {   // noise-flooding decryption: phase + f in coefficient form, on the limbs that are read
+        check_flood(flood_bits, nl, "decrypt_flooded");
+        Scratch<u64> f = c_.scratch<u64>((size_t)nl * N);
+        sample_flood_device(f, 1, nl, flood_bits, false);
+        launch_ew_add(c_.dt, m, m, f, nl, nl, 0, nl, c_.stream);
+        hip_check(hipGetLastError(), "decrypt flood kernels");
+        hip_check(hipMemsetAsync(f, 0, (size_t)nl * N * sizeof(u64), c_.stream), "hipMemsetAsync(decrypt flood)");
+    }
     std::vector<u64> h((size_t)nl * N);
     hip_check(hipMemcpyAsync(h.data(), m, h.size() * 8, hipMemcpyDeviceToHost, c_.stream), "decrypt download");
     hip_check(hipStreamSynchronize(c_.stream), "decrypt sync");

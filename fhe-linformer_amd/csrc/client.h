@@ -74,7 +74,15 @@ public:
     // of inputs of one target in read order, <= 128 each, over ell + 1 limbs), always seeded secret-key encryptions; drop is ignored
     // test hook: the sampler's raw output, n_poly polynomials of N centred coefficients (kind 0 Gaussian, 1 ternary)
     std::vector<long> debug_sample(int kind, int n_poly);
-    std::vector<double> decrypt(const CtPtr& c, int slots);
+    // flood_bits > 0 (include/fhelin.h "Sanitised replies"): one uniform polynomial on [-2^flood_bits, 2^flood_bits) is added to the phase
+    // on the device, after the inverse NTT and before the download; 0: the plain decryption, unchanged
+    std::vector<double> decrypt(const CtPtr& c, int slots, int flood_bits = 0);
+    // Reply sanitisation (include/fhelin.h "Sanitised replies"): degree-2 inputs rescaled, the optional 0/1 mask applied (product +
+    // rescale), then out_b = first out_ell limbs of x_b + Enc_pk(0) + flood in ONE fused launch for the whole batch; the randomness
+    // scratch is wiped.  Needs the public key only (works on an evaluation context).
+    std::vector<CtPtr> sanitize(const std::vector<CtPtr>& v, const PtPtr& mask, int flood_bits, int out_ell);
+    // test hook: the flood sampler alone for an explicit ChaCha20 key and stream, residues [ell][N] (coefficient form)
+    std::vector<u64> debug_flood(const uint8_t key[32], u64 stream, int flood_bits, int ell);
     CtPtr phase(const CtPtr& c, int nlimbs);   // c0 + c1 s (+ c2 s^2) on the first nlimbs limbs, NTT form, 1 component
 
     // raw import/export of key material (parity tests feed identical arrays to the oracle)
@@ -96,6 +104,10 @@ private:
     void sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind);  // kind 0 gaussian, 1 ternary (host sampler: key generation)
     // device sampler (encryption randomness): dst [n_poly][ell][N] coefficient form; a fresh ChaCha20 key per call
     void sample_small_device(u64* dst, int n_poly, int ell, int kind);
+    // the wide sampler (launch_sample_flood), keyed as sample_small_device; gauss: e0 + f as one polynomial
+    void sample_flood_device(u64* dst, int n_poly, int ell, int flood_bits, bool gauss);
+    SamplerKey draw_sampler_key();
+    void check_flood(int flood_bits, int nl, const char* who) const;   // 0..62 and 2^(flood_bits + 2) below q_0 .. q_{nl-1}
     // c0 = b u + e0 + m, c1 = a u + e1 for n_vec encodings enc [n_vec][ell][N] (enc_stride words apart; 0 = one shared encoding)
     // seeded mode: c0 = m - a s + e, c1 = a instead; nonces [n_vec] are the vectors' output indices within the current call
     void encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out,

@@ -21,6 +21,24 @@ void launch_sample_small(const DeviceTables& t, u64* out, const SamplerKey& key,
 void launch_encrypt_combine(const DeviceTables& t, u64* ct, const u64* pk, const u64* u, const u64* e0, const u64* e1, const u64* m, int ell,
                             int L1, size_t m_stride, int n_vec, hipStream_t s);
 
+// out [n_poly][ell][N] (coefficient form): coefficient i of polynomial p = (W >> (63 - flood_bits)) - 2^flood_bits reduced into
+// [0, q_l), W = little-endian u64 word i % 8 of ChaCha20 block i / 8 of stream stream_base + p; 1 <= flood_bits <= 62.
+// gauss: plus a rounded Gaussian (sigma 3.19, launch_sample_small kind 0) from stream gauss_stream_base + p
+void launch_sample_flood(const DeviceTables& t, u64* out, const SamplerKey& key, u64 stream_base, u64 gauss_stream_base, int flood_bits,
+                         bool gauss, int ell, int n_poly, hipStream_t s);
+// one ciphertext of a re-randomised batch: in [2][in_ell][N], out [2][out_ell][N] with out_ell <= in_ell (device table entry)
+struct RerandItem {
+    const u64* in;
+    u64* out;
+    int32_t in_ell;
+    int32_t pad_ = 0;
+};
+static_assert(sizeof(RerandItem) == 24, "RerandItem is 24 bytes");
+// out_b = first out_ell limbs of in_b + (pk_b u_b + w_b, pk_a u_b + e1_b) for b < n_ct (<= 65535) in one launch; tab [n_ct] on the
+// device; u, w, e1 [n_ct][out_ell][N] and pk [2][L1][N] in NTT form
+void launch_rerandomize_combine(const DeviceTables& t, const RerandItem* tab, const u64* pk, const u64* u, const u64* w, const u64* e1,
+                                int out_ell, int L1, int n_ct, hipStream_t s);
+
 
 // ---- client-side ingestion of one sample (reference src/python/dimReduce.py:141-160 and the read_expanded_input packing,
 // src/FHEController.cpp:623-650), all in fp64 with the operation order of the NumPy statement and FMA contraction off:

@@ -13,6 +13,10 @@
 //  * sample_small_kernel          : ChaCha20 (RFC 8439 block function) keyed per call; ternary {-1,0,1} or rounded
 //    Gaussian (sigma 3.19, Box-Muller) coefficients written as residues of every limb.
 //  * encrypt_combine_kernel       : c0 = b*u + e0 + m, c1 = a*u + e1 (NTT form) for a batch.
+//  * sample_flood_kernel          : uniform coefficients on [-2^B, 2^B) (noise flooding), optionally plus the rounded Gaussian,
+//    as residues of every limb (|f| may exceed q_l: reduced with the limb's Barrett constants).
+//  * rerandomize_combine_kernel   : out = in + (b*u + w, a*u + e1) on the first out_ell limbs of a batch of ciphertexts of any limb
+//    counts (a fresh encryption of zero added, the level drop part of the same pass).
 // All HBM-bound or trivially small; no MFMA.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
@@ -29,6 +33,19 @@ __device__ __forceinline__ Barrett load_barrett(const DeviceTables& t, int limb)
     b.q = t.moduli[limb];
     b.r0 = t.barrett[2 * limb];
     b.r1 = t.barrett[2 * limb + 1];
+    return b;
+}
+
+// the same for a limb index that is uniform but a loop counter, in a kernel that stores between the loads: the constants are vector
+// loads then, and this brings them back to scalar registers
+__device__ __forceinline__ u64 uniform64(u64 x) {
+    return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(x >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)x);
+}
+__device__ __forceinline__ Barrett load_barrett_uniform(const DeviceTables& t, int limb) {
+    Barrett b = load_barrett(t, limb);
+    b.q = uniform64(b.q);
+    b.r0 = uniform64(b.r0);
+    b.r1 = uniform64(b.r1);
     return b;
 }
 
@@ -209,6 +226,92 @@ __global__ __launch_bounds__(256) void encrypt_combine_kernel(DeviceTables t, u6
     C[((size_t)(2 * b + 1) * ell + l) * row + n2] = c1;
 }
 
+// grid (N/8/256, n_poly): one ChaCha20 block = 8 coefficients per thread, as sample_small_kernel.  Coefficient i of polynomial p is
+// f_i = (W >> (63 - B)) - 2^B with W word i % 8 of block i / 8 of stream stream_base + p: uniform on [-2^B, 2^B), 1 <= B <= 62.
+// gauss: plus the rounded Gaussian of sample_small_kernel kind 0 drawn from the block of stream gauss_stream_base + p (e0 + f as one
+// polynomial).  out [n_poly][ell][N] residues f_i mod q_l in [0, q_l) (coefficient form)
+__global__ __launch_bounds__(256, 8) void sample_flood_kernel(DeviceTables t, u64* __restrict__ out, SamplerKey key, u64 stream_base,
+                                                           u64 gauss_stream_base, int flood_bits, int gauss, int ell) {
+    const size_t N = (size_t)1 << t.log_n;
+    const size_t blk = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (blk >= N / 8) return;
+    u64 r[8];
+    u32 g[2] = {0, 0};   // the Gaussian terms (|e| <= 28: sigma 3.19 times the radius of a 53-bit uniform) packed as eight int8
+    if (gauss) {   // first, and one pair at a time: the double-precision pairs are what the register count is made of
+        chacha20_block(key, blk, gauss_stream_base + blockIdx.y, r);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const double u1 = ((double)(r[2 * i] >> 11) + 1.0) * (1.0 / 9007199254740992.0);   // (0, 1]
+            const double u2 = (double)(r[2 * i + 1] >> 11) * (1.0 / 9007199254740992.0);       // [0, 1)
+            const double rad = sqrt(-2.0 * log(u1)) * 3.19, th = 6.283185307179586476925 * u2;
+            double sn, cs;
+            sincos(th, &sn, &cs);
+            g[i >> 1] |= (((u32)(int)llrint(rad * cs) & 0xFFu) | (((u32)(int)llrint(rad * sn) & 0xFFu) << 8)) << (16 * (i & 1));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // the thread's position formed again from an opaque copy of its index: nothing but the packed Gaussian terms lives across the
+    // double-precision code above (what the compiler otherwise keeps there, it spills)
+    u32 tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const size_t pos = (size_t)blockIdx.x * 256 + tid;
+    chacha20_block(key, pos, stream_base + blockIdx.y, r);
+    const int sh = 63 - flood_bits;
+    const long long off = 1ll << flood_bits;
+    u32 neg = 0;   // bit i: coefficient i is negative; r[i] becomes its magnitude (|f + e| < 2^62 + 2^5)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const long long v = (long long)(r[i] >> sh) - off + (int)(signed char)(g[i >> 2] >> (8 * (i & 3)));
+        neg |= (v < 0 ? 1u : 0u) << i;
+        r[i] = v < 0 ? (u64)(-v) : (u64)v;
+    }
+    u64* o = out + (size_t)blockIdx.y * ell * N + pos * 8;
+    for (int l = 0; l < ell; ++l) {
+        const Barrett br = load_barrett_uniform(t, l);
+        u64x2* dst = reinterpret_cast<u64x2*>(o + (size_t)l * N);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            // one reduction at a time: interleaved, the eight cost 128 registers
+            const u64 ra = barrett_reduce128(r[2 * i], 0, br);
+            u64x2 w;
+            w.x = (neg >> (2 * i)) & 1 ? neg_mod(ra, br.q) : ra;
+            __builtin_amdgcn_sched_barrier(0);
+            const u64 rb = barrett_reduce128(r[2 * i + 1], 0, br);
+            w.y = (neg >> (2 * i + 1)) & 1 ? neg_mod(rb, br.q) : rb;
+            dst[i] = w;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+// grid (N/512, out_ell, n_ct): item b = tab[blockIdx.z] is a ciphertext in [2][in_ell][N] with in_ell >= out_ell; its first out_ell
+// limbs plus a fresh public-key encryption of zero go to out [2][out_ell][N]:
+//   out0[l] = in0[l] + pk_b[l] u + w,  out1[l] = in1[l] + pk_a[l] u + e1      u, w, e1 [n_ct][out_ell][N], pk [2][L1][N], all NTT form
+__global__ __launch_bounds__(256) void rerandomize_combine_kernel(DeviceTables t, const RerandItem* __restrict__ tab, const u64* __restrict__ pk,
+                                                                  const u64* __restrict__ u, const u64* __restrict__ w,
+                                                                  const u64* __restrict__ e1, int out_ell, int L1) {
+    const int b = blockIdx.z, l = blockIdx.y;
+    const RerandItem it = tab[b];
+    const Barrett br = load_barrett(t, l);
+    const size_t row = ((size_t)1 << t.log_n) >> 1;
+    const size_t n2 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t rnd = ((size_t)b * out_ell + l) * row + n2;
+    const u64x2 uu = reinterpret_cast<const u64x2*>(u)[rnd];
+    const u64x2 a0 = reinterpret_cast<const u64x2*>(w)[rnd], a1 = reinterpret_cast<const u64x2*>(e1)[rnd];
+    const u64x2 kb = reinterpret_cast<const u64x2*>(pk)[(size_t)l * row + n2];
+    const u64x2 ka = reinterpret_cast<const u64x2*>(pk)[((size_t)L1 + l) * row + n2];
+    const u64x2* I = reinterpret_cast<const u64x2*>(it.in);
+    const u64x2 i0 = I[(size_t)l * row + n2], i1 = I[((size_t)it.in_ell + l) * row + n2];
+    u64x2 c0, c1;
+    c0.x = add_mod(add_mod(mul_mod(kb.x, uu.x, br), a0.x, br.q), i0.x, br.q);
+    c0.y = add_mod(add_mod(mul_mod(kb.y, uu.y, br), a0.y, br.q), i0.y, br.q);
+    c1.x = add_mod(add_mod(mul_mod(ka.x, uu.x, br), a1.x, br.q), i1.x, br.q);
+    c1.y = add_mod(add_mod(mul_mod(ka.y, uu.y, br), a1.y, br.q), i1.y, br.q);
+    u64x2* O = reinterpret_cast<u64x2*>(it.out);
+    O[(size_t)l * row + n2] = c0;
+    O[((size_t)out_ell + l) * row + n2] = c1;
+}
+
 }  // namespace
 
 void launch_fft_special_inv(double* data, const u32* rot, const double* ksi, int slots, int n_vec, hipStream_t s) {
@@ -232,6 +335,17 @@ void launch_encrypt_combine(const DeviceTables& t, u64* ct, const u64* pk, const
                             int L1, size_t m_stride, int n_vec, hipStream_t s) {
     hipLaunchKernelGGL(encrypt_combine_kernel, dim3((1u << t.log_n) / 512, (unsigned)(n_vec * ell)), dim3(256), 0, s, t, ct, pk, u, e0, e1, m,
                        ell, L1, m_stride);
+}
+void launch_sample_flood(const DeviceTables& t, u64* out, const SamplerKey& key, u64 stream_base, u64 gauss_stream_base, int flood_bits,
+                         bool gauss, int ell, int n_poly, hipStream_t s) {
+    const unsigned bx = (unsigned)(((1u << t.log_n) / 8 + 255) / 256);
+    hipLaunchKernelGGL(sample_flood_kernel, dim3(bx, (unsigned)n_poly), dim3(256), 0, s, t, out, key, stream_base, gauss_stream_base, flood_bits,
+                       gauss ? 1 : 0, ell);
+}
+void launch_rerandomize_combine(const DeviceTables& t, const RerandItem* tab, const u64* pk, const u64* u, const u64* w, const u64* e1,
+                                int out_ell, int L1, int n_ct, hipStream_t s) {
+    hipLaunchKernelGGL(rerandomize_combine_kernel, dim3((1u << t.log_n) / 512, (unsigned)out_ell, (unsigned)n_ct), dim3(256), 0, s, t, tab, pk,
+                       u, w, e1, out_ell, L1);
 }
 
 

@@ -45,6 +45,17 @@ def cheb_coeffs(f, a, b, degree):
     return np.array([2.0 / n * np.sum(fx * np.cos(np.pi * k * (j + 0.5) / n)) for k in range(n)])
 
 
+LOGIT_SLOTS = tuple(int(i) * 128 for i in range(20))           # where the classifier leaves the answer (main.cpp:105-123)
+
+
+def _keep_mask(keep_slots):
+    if keep_slots is None:
+        return None
+    m = np.zeros(SLOTS)
+    m[np.asarray(list(keep_slots), dtype=np.int64)] = 1.0
+    return m
+
+
 class GpuController:
     """The reference's FHEController surface on top of fhe_linformer_amd.Engine."""
 
@@ -71,6 +82,11 @@ class GpuController:
 
     def decrypt(self, c):
         return self.e.decrypt(c, SLOTS)
+
+    def sanitize(self, c, keep_slots=None, flood_bits=0, out_ell=2):
+        """the reply form of a result (include/fhelin.h "Sanitised replies"): only keep_slots survive (None: no mask), out_ell limbs,
+        re-randomised, flooded with flood_bits bits; the server's last step, off unless the driver is asked for it"""
+        return self.e.sanitize(c, _keep_mask(keep_slots), flood_bits, out_ell)
 
     def read_expanded_input(self, v, scale=1.0):
         return self.encrypt(expanded(np.asarray(v) * scale), 0)
@@ -322,6 +338,10 @@ class BatchedController:
 
     def decrypt(self, c):
         return [self.e.decrypt(h, SLOTS) for h in c]
+
+    def sanitize(self, c, keep_slots=None, flood_bits=0, out_ell=2):
+        """GpuController.sanitize for every sample's result in ONE call: one mask, one fused launch for the batch"""
+        return Batch(self.e.sanitize(list(c), _keep_mask(keep_slots), flood_bits, out_ell))
 
     def read_expanded_inputs_batch(self, rows_per_sample, scale=1.0):
         """per sample the rows of read_expanded_inputs -> list of Batches (row-major)"""
@@ -690,14 +710,18 @@ def classifier(ctl, w, x, encrypted_mask=True):                                 
     return ctl.mult(out, ctl.encode(mask, ctl.level(out)))                                  # main_2.cpp:427: plaintext mask
 
 
-def forward_encrypted(ctl, w, enc, trace=None, variant="main"):
+def forward_encrypted(ctl, w, enc, trace=None, variant="main", reply=None):
     """server side of one sample: encoder1 -> pooler -> classifier -> logits at slots {0,128,...,19*128} (main.cpp:105-123).
     variant "main" = src/main.cpp as built (CLS-query attention); "main_2" = src/main_2.cpp (full attention,
-    tanh scale 1/18, plaintext output mask)."""
+    tanh scale 1/18, plaintext output mask).  reply (off by default): dict(flood_bits=..., out_ell=...) - the result is handed back in
+    its reply form, only the logit slots kept (ctl.sanitize; include/fhelin.h "Sanitised replies")."""
     full = variant == "main_2"
     out = encoder1(ctl, w, enc, trace, full_attention=full)
     pooled = pooler(ctl, w, out, trace, tanh_scale=1.0 / 18 if full else 1.0 / 50)
-    return classifier(ctl, w, pooled, encrypted_mask=not full)
+    res = classifier(ctl, w, pooled, encrypted_mask=not full)
+    if reply is not None:
+        res = ctl.sanitize(res, keep_slots=LOGIT_SLOTS, **reply)
+    return res
 
 
 def forward(ctl, w, x_in, X_E, X_F, trace=None, variant="main"):

@@ -402,6 +402,36 @@ public:
         fhelin_shim::check(fhelin_decrypt(context, c->h, v.data(), slots), "Decrypt");
         return v;
     }
+    /* noise-flooding decryption (fhelin.h "Sanitised replies"): a uniform term on [-2^flood_bits, 2^flood_bits) per coefficient is added
+     * to the phase before it leaves the device, so that values the client shares do not expose the exact noise.  flood_bits = 0:
+     * decrypt_tovector. */
+    vector<double> decrypt_tovector_flooded(const Ctxt& c, int slots, int flood_bits) {
+        if (slots == 0) slots = num_slots;
+        vector<double> v(slots);
+        fhelin_shim::check(fhelin_decrypt_flooded(context, c->h, flood_bits, v.data(), slots), "Decrypt (flooded)");
+        return v;
+    }
+    /* The reply form of a result (fhelin.h "Sanitised replies"): only keep_slots survive (every other slot is masked out; empty = no
+     * mask), out_ell limbs remain, a fresh public-key encryption of zero and a flood term of flood_bits bits are added.  Runs on a
+     * server without the secret key; nothing else in this class calls it. */
+    Ctxt sanitize(const Ctxt& c, const vector<int>& keep_slots, int flood_bits, int out_ell = 2) {
+        fhelin_pt* m = nullptr;
+        Ptxt mask;
+        if (!keep_slots.empty()) {
+            const int slots = c->GetSlots() ? (int)c->GetSlots() : num_slots;
+            vector<double> v(slots, 0.0);
+            for (int k : keep_slots) {
+                if (k < 0 || k >= slots) throw std::runtime_error("sanitize: slot index outside the ciphertext's slots");
+                v[k] = 1.0;
+            }
+            mask = encode(v, 0, slots);
+            m = mask->h;
+        }
+        const fhelin_ct* in = c->h;
+        fhelin_ct* o = nullptr;
+        fhelin_shim::check(fhelin_sanitize(context, &in, 1, m, flood_bits, out_ell, &o), "Sanitize");
+        return wrap(o);
+    }
 
     /* homomorphic operations (reference :409-469) */
     Ctxt add(const Ctxt& c1, const Ctxt& c2) { return bin(fhelin_add, c1, c2, "EvalAdd"); }

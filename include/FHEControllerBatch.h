@@ -73,6 +73,27 @@ public:
         for (auto& h : c->v) out.push_back(c_.decrypt_tovector(h, slots));
         return out;
     }
+    vector<vector<double>> decrypt_tovector_flooded(const CtxtBatch& c, int slots, int flood_bits) {
+        vector<vector<double>> out;
+        for (auto& h : c->v) out.push_back(c_.decrypt_tovector_flooded(h, slots, flood_bits));
+        return out;
+    }
+    /* the reply form of every sample's result in ONE call (FHEController::sanitize; fhelin.h "Sanitised replies"): one mask for the
+     * batch, the randomness of all samples sampled and transformed together, one fused launch */
+    CtxtBatch sanitize(const CtxtBatch& c, const vector<int>& keep_slots, int flood_bits, int out_ell = 2) {
+        Ptxt mask;
+        if (!keep_slots.empty()) {
+            const int slots = c->v.at(0)->GetSlots() ? (int)c->v.at(0)->GetSlots() : num_slots;
+            vector<double> v(slots, 0.0);
+            for (int k : keep_slots) {
+                if (k < 0 || k >= slots) throw std::runtime_error("sanitize: slot index outside the ciphertext's slots");
+                v[k] = 1.0;
+            }
+            mask = c_.encode(v, 0, slots);
+        }
+        return rows1(c, [&](const fhelin_ct* const* hs, int32_t n, fhelin_ct** outs) {
+            return fhelin_sanitize(ctx(), hs, n, mask ? mask->h : nullptr, flood_bits, out_ell, outs); }, "Sanitize");
+    }
 
     /* leaf operations (reference :409-436) */
     CtxtBatch add(const CtxtBatch& a, const CtxtBatch& b) {

@@ -611,6 +611,39 @@ int fhelin_wrapped_info(const fhelin_ct* ct, int32_t* count, int32_t* total, int
  * planned output.  Works on an evaluation context that holds the circuit's rotation keys. */
 int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t n, fhelin_ct** outs);
 
+/* ---- sanitised replies: mask, shrink, re-randomise and flood what a server hands back -------------------------------------
+ * The ciphertext a circuit ends with is no fit reply as it stands: only some slots are the answer (the others hold intermediate
+ * values of the model), (c0, c1) is a deterministic function of inputs, keys and model whose limb count, roundings and noise depend on
+ * the circuit that ran, and decryption reads two limbs of it.  fhelin_sanitize makes the reply, in this order:
+ *   1. degree-2 inputs are rescaled (as fhelin_decrypt does);
+ *   2. with a mask - an ordinary plaintext of 0/1 slot values - product and rescale (fhelin_mult_plain_batch, fhelin_rescale_batch):
+ *      one limb, the masked-out slots hold rounding noise only;
+ *   3. out0 = in0 + pk_b u + NTT(e0 + f), out1 = in1 + pk_a u + e1 on the FIRST out_ell limbs (the level drop is part of the same
+ *      pass): u uniform ternary, e0 and e1 rounded Gaussians (sigma 3.19) - a fresh public-key encryption of zero - and f the
+ *      flooding term, uniform on [-2^flood_bits, 2^flood_bits) per coefficient.  One fused launch for the whole batch; the
+ *      randomness is sampled on the device, transformed by one forward NTT and wiped afterwards.
+ * flood_bits = 0: re-randomisation only.  out_ell <= 0: 2.  Outputs: 2 components, out_ell limbs, degree 1, the (masked) input's
+ * scale and slots; never seeded.  Needs the public key only: works on an evaluation context (FHELIN_ERR_KEY without a public key).
+ * Randomness: a ChaCha20 key per sampler call drawn from the CONTEXT'S OWN generator, exactly as public-key encryption draws it - a
+ * server creates its context with a seed of its own (fhelin_ctx_create: OS entropy), never with the client's.
+ * FHELIN_ERR_ARG: flood_bits outside [0, 62]; 2^(flood_bits + 2) not below q_0 .. q_{out_ell-1}; fewer limbs than the rescales, the
+ * mask and out_ell need; a 3-component input; a wrapped input; n < 1.  FHELIN_ERR_NO_DEVICE on a host-only context.  Nothing is
+ * launched when a call is refused.
+ * What flooding hides: the noise the circuit left (key-switch and rescale roundings, whose distribution depends on the model) under
+ * a term 2^flood_bits / that noise times larger.  What it does not: the approximation error of the circuit is part of the MESSAGE,
+ * and the kept slots carry it.  flood_bits is the caller's trade: the slot error it adds is about 2^flood_bits sqrt(N/3) / scale.
+ * The wide sampler, exactly: coefficient i of polynomial p uses the little-endian u64 word W = word (i mod 8) of ChaCha20 block
+ * (key, counter = i / 8, stream + p); f_i = (W >> (63 - B)) - 2^B for 1 <= B <= 62; the residue on limb l is f_i mod q_l in [0, q_l). */
+int fhelin_sanitize(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, const fhelin_pt* mask /* may be NULL */, int32_t flood_bits,
+                    int32_t out_ell, fhelin_ct** outs);
+/* test hook: the flood term alone for an explicit key (32 bytes) and stream, residues [ell][N] in coefficient form; 1 <= flood_bits <= 62 */
+int fhelin_debug_flood(fhelin_ctx* c, const uint8_t* key, uint64_t stream, int32_t flood_bits, int32_t ell, uint64_t* out, size_t cap_words);
+/* noise-flooding decryption: fhelin_decrypt with one flood polynomial (uniform on [-2^flood_bits, 2^flood_bits), the wide sampler,
+ * keyed from the context's generator) added to the phase after the inverse NTT and before the download, on the one or two limbs
+ * decryption reads - values a client shares then do not expose the exact noise.  flood_bits = 0: exactly fhelin_decrypt.
+ * FHELIN_ERR_ARG: flood_bits outside [0, 62] or 2^(flood_bits + 2) not below the modulus of the limbs read. */
+int fhelin_decrypt_flooded(fhelin_ctx* c, const fhelin_ct* ct, int32_t flood_bits, double* out, int32_t slots);
+
 #ifdef __cplusplus
 }
 #endif
