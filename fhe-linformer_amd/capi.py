@@ -225,6 +225,7 @@ def load_library():
         "fhelin_sanitize": (i32, [vp, C.POINTER(vp), i32, vp, i32, i32, C.POINTER(vp)]),
         "fhelin_debug_flood": (i32, [vp, vp, C.c_uint64, i32, i32, vp, C.c_size_t]),
         "fhelin_decrypt_flooded": (i32, [vp, vp, i32, C.POINTER(C.c_double), i32]),
+        "fhelin_debug_sampler_peek": (i32, [vp, i32, vp, u64p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -686,6 +687,15 @@ class Engine:
         out = np.empty((max(ell, 0), self.N), dtype=np.uint64)
         self._ck(self.lib.fhelin_debug_flood(self.h, kb, int(stream), int(flood_bits), ell, out.ctypes.data_as(C.c_void_p), out.size))
         return out
+
+    def debug_sampler_peek(self, n_keys=1):
+        """test hook (include/fhelin.h "Sampler streams"): (keys uint32 [n_keys][8] that the next n_keys sampler-key draws will give,
+        the current sampler call counter); consumes nothing; host-only"""
+        keys = np.zeros((int(n_keys), 8), dtype=np.uint32)
+        calls = C.c_uint64()
+        self._ck(self.lib.fhelin_debug_sampler_peek(self.h, int(n_keys), keys.ctypes.data_as(C.c_void_p) if keys.size else None,
+                                                    C.byref(calls)))
+        return keys, int(calls.value)
 
     def decrypt_flooded(self, ct, flood_bits, slots=0):
         """noise-flooding decryption: decrypt with one flood polynomial added to the phase before the download; flood_bits=0 is decrypt"""

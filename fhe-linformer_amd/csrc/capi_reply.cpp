@@ -38,6 +38,14 @@ int fhelin_debug_flood(fhelin_ctx* c, const uint8_t* key, uint64_t stream, int32
     FHELIN_CATCH
 }
 
+int fhelin_debug_sampler_peek(const fhelin_ctx* c, int32_t n_keys, uint32_t* key_words, uint64_t* sample_calls) {
+    NEED(c && (key_words || n_keys == 0));
+    FHELIN_TRY
+    if (n_keys < 0 || n_keys > 4096) throw Error(FHELIN_ERR_ARG, "debug_sampler_peek: n_keys must lie in [0, 4096]");
+    c->cl.debug_sampler_peek(n_keys, key_words, sample_calls);
+    FHELIN_CATCH
+}
+
 int fhelin_decrypt_flooded(fhelin_ctx* c, const fhelin_ct* ct, int32_t flood_bits, double* out, int32_t slots) {
     NEED(c && ct && out);
     FHELIN_TRY

@@ -606,6 +606,17 @@ SamplerKey Client::draw_sampler_key() {
     return key;
 }
 
+void Client::debug_sampler_peek(int n_keys, u32* key_words, u64* sample_calls) const {
+    Prng copy = rng_;   // the draws below advance the copy only
+    for (int k = 0; k < n_keys; ++k)
+        for (int i = 0; i < 4; ++i) {   // as draw_sampler_key
+            const u64 w = copy.next();
+            key_words[8 * k + 2 * i] = (u32)w;
+            key_words[8 * k + 2 * i + 1] = (u32)(w >> 32);
+        }
+    if (sample_calls) *sample_calls = sample_calls_;
+}
+
 void Client::sample_flood_device(u64* dst, int n_poly, int ell, int flood_bits, bool gauss) {
     const SamplerKey key = draw_sampler_key();
     const u64 flood_stream = (sample_calls_++) << 32, gauss_stream = (sample_calls_++) << 32;   // two distinct stream ranges

@@ -83,6 +83,10 @@ public:
     std::vector<CtPtr> sanitize(const std::vector<CtPtr>& v, const PtPtr& mask, int flood_bits, int out_ell);
     // test hook: the flood sampler alone for an explicit ChaCha20 key and stream, residues [ell][N] (coefficient form)
     std::vector<u64> debug_flood(const uint8_t key[32], u64 stream, int flood_bits, int ell);
+    // test hook (include/fhelin.h "Sampler streams"): the keys the next n_keys sampler-key draws (sample_small_device,
+    // draw_sampler_key) will return, key_words [n_keys][8], computed on a COPY of the generator - nothing is consumed - and the
+    // current sampler call counter.  No device work.
+    void debug_sampler_peek(int n_keys, u32* key_words, u64* sample_calls) const;
     CtPtr phase(const CtPtr& c, int nlimbs);   // c0 + c1 s (+ c2 s^2) on the first nlimbs limbs, NTT form, 1 component
 
     // raw import/export of key material (parity tests feed identical arrays to the oracle)

@@ -638,6 +638,42 @@ int fhelin_sanitize(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, const f
                     int32_t out_ell, fhelin_ct** outs);
 /* test hook: the flood term alone for an explicit key (32 bytes) and stream, residues [ell][N] in coefficient form; 1 <= flood_bits <= 62 */
 int fhelin_debug_flood(fhelin_ctx* c, const uint8_t* key, uint64_t stream, int32_t flood_bits, int32_t ell, uint64_t* out, size_t cap_words);
+/* ---- sampler streams: which ChaCha20 key and stream every random polynomial comes from ---------------------------------------
+ * The context's generator G is the ChaCha20 stream (key = the secret seed, stream 0, block counter 0, 1, ...) read as little-endian
+ * u64 words in order (8 per block).  A KEY DRAW takes the next four words w0..w3 of G: sampler key words k[2i] = low 32 bits of w_i,
+ * k[2i+1] = high 32 bits.  The context also keeps a counter C of sampler calls (0 at creation).  Polynomial p of a sampler call made
+ * with key K at counter value c uses the blocks ChaCha20(K, block counter = i / 8, stream = (c << 32) + p); W_j is u64 word j of it:
+ *   ternary : coefficient 8 b + j = ((W_j * 3) >> 64) - 1                                                   (block b, j = 0..7)
+ *   Gaussian: u1 = ((W_2j >> 11) + 1) 2^-53, u2 = (W_2j+1 >> 11) 2^-53, r = 3.19 sqrt(-2 ln u1);
+ *             coefficient 8 b + 2 j = round(r cos 2 pi u2), coefficient 8 b + 2 j + 1 = round(r sin 2 pi u2)   (j = 0..3), |e| <= 28
+ *   flood   : coefficient 8 b + j = (W_j >> (63 - B)) - 2^B                                                  (as fhelin_sanitize)
+ * and the same integer polynomial is written to every limb as its residue in [0, q_l).  Callers, in the order they draw:
+ *   fhelin_debug_sample(kind, n)  : one key draw; polynomial p at stream (C << 32) + p; C += 1.
+ *   public-key encryption of n <= 32 vectors (fhelin_encrypt: n = 1; fhelin_encrypt_batch and fhelin_client_ingest: once per chunk of
+ *     at most 32 vectors of one level, chunks in order): key draw 1, u_b (ternary) at (C << 32) + b; key draw 2, e0_b (Gaussian) at
+ *     ((C + 1) << 32) + b and e1_b at ((C + 1) << 32) + n + b - one call of 2 n polynomials; C += 2.
+ *     c0_b = pk_b NTT(u_b) + NTT(e0_b) + m_b, c1_b = pk_a NTT(u_b) + NTT(e1_b).
+ *   seeded secret-key encryption: the call's 32-byte public seed is the next four words of G (little-endian bytes), drawn once per
+ *     fhelin_encrypt / fhelin_encrypt_batch / ingest call; then per chunk of at most 32 vectors one key draw, e_b (Gaussian) at
+ *     (C << 32) + b; C += 1.  c0_b = m_b - a_b s + NTT(e_b).
+ *   fhelin_sanitize, per chunk of at most 32 ciphertexts (chunks in order; the mask and the rescales draw nothing):
+ *     flood_bits = 0: key draw 1, u_b at (C << 32) + b; key draw 2, e0_b at ((C + 1) << 32) + b; key draw 3, e1_b at
+ *       ((C + 2) << 32) + b; C += 3.
+ *     flood_bits > 0: key draw 1, u_b at (C << 32) + b; key draw 2 serves two stream ranges, f_b (flood) at ((C + 1) << 32) + b and
+ *       e0_b (Gaussian) at ((C + 2) << 32) + b; key draw 3, e1_b at ((C + 3) << 32) + b; C += 4.
+ *     out0_b = in0_b + pk_b NTT(u_b) + NTT(e0_b + f_b), out1_b = in1_b + pk_a NTT(u_b) + NTT(e1_b) on the first out_ell limbs.
+ *   fhelin_decrypt_flooded (flood_bits > 0): one key draw, f (flood, no Gaussian) at (C << 32); C += 2 (the unused Gaussian range
+ *     is skipped).
+ *   seeded fhelin_keygen: the secret's draws from G, then the key-set seed (the next four words of G), then one key draw: the public
+ *     key's e (Gaussian, one polynomial over the Q limbs) at (C << 32); C += 1.  pk_b = NTT(e) - pk_a s.
+ *   seeded switching keys (fhelin_gen_relin_key, each rotation key, fhelin_gen_conj_key): one key draw per key; digit j's e_j
+ *     (Gaussian, one polynomial over the Q and P limbs) at (C << 32) + j; C += 1.
+ * Key generation without seeded keys samples on the host, straight from G.
+ * Test hook: the keys the next n_keys key draws will give (key_words [n_keys][8]; computed on a copy of G, nothing is consumed) and
+ * the current C.  Works on client and evaluation contexts and without a device.  It reveals nothing the owner of the context cannot
+ * derive from fhelin_ctx_secret_seed (an evaluation context: from the seed it was created with).  FHELIN_ERR_ARG: n_keys outside
+ * [0, 4096].  key_words may be NULL when n_keys = 0; sample_calls may be NULL. */
+int fhelin_debug_sampler_peek(const fhelin_ctx* c, int32_t n_keys, uint32_t* key_words /* [n_keys][8] */, uint64_t* sample_calls);
 /* noise-flooding decryption: fhelin_decrypt with one flood polynomial (uniform on [-2^flood_bits, 2^flood_bits), the wide sampler,
  * keyed from the context's generator) added to the phase after the inverse NTT and before the download, on the one or two limbs
  * decryption reads - values a client shares then do not expose the exact noise.  flood_bits = 0: exactly fhelin_decrypt.

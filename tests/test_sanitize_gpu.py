@@ -14,48 +14,12 @@ import struct
 import numpy as np
 import pytest
 
+from sampler_model import chacha20_words, flood_values  # noqa: F401  (the restatement lives with the sampler model)
+
 pytestmark = pytest.mark.gpu
 
 ERR_ARG, ERR_NO_DEVICE, ERR_KEY = 1, 2, 5
 SIGMA = 3.19
-
-
-def chacha20_words(seed, counter, stream):
-    """ChaCha20 blocks (RFC 8439) for 64-bit counters (array), one 64-bit stream -> uint64 [len(counter)][8], little-endian
-    (the helper of tests/test_compact_gpu.py; pinned to the RFC's vector in tests/test_sanitize_host.py)"""
-    ctr = np.atleast_1d(np.asarray(counter, dtype=np.uint64))
-    key = np.frombuffer(bytes(seed), dtype="<u4")
-    init = np.empty((16, ctr.size), dtype=np.uint32)
-    init[0:4] = np.array([0x61707865, 0x3320646E, 0x79622D32, 0x6B206574], dtype=np.uint32)[:, None]
-    init[4:12] = key[:, None]
-    init[12] = (ctr & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    init[13] = (ctr >> np.uint64(32)).astype(np.uint32)
-    init[14] = np.uint32(stream & 0xFFFFFFFF)
-    init[15] = np.uint32(stream >> 32)
-    x = init.copy()
-
-    def rotl(v, k):
-        return (v << np.uint32(k)) | (v >> np.uint32(32 - k))
-
-    def qr(a, b, c, d):
-        x[a] += x[b]; x[d] ^= x[a]; x[d] = rotl(x[d], 16)
-        x[c] += x[d]; x[b] ^= x[c]; x[b] = rotl(x[b], 12)
-        x[a] += x[b]; x[d] ^= x[a]; x[d] = rotl(x[d], 8)
-        x[c] += x[d]; x[b] ^= x[c]; x[b] = rotl(x[b], 7)
-
-    with np.errstate(over="ignore"):
-        for _ in range(10):
-            qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15)
-            qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14)
-        x += init
-    w = x.astype(np.uint64)
-    return (w[0::2] | (w[1::2] << np.uint64(32))).T
-
-
-def flood_values(key, stream, bits, n):
-    """coefficient i = (W >> (63 - B)) - 2^B, W = word i % 8 of block i / 8 (Python integers)"""
-    W = chacha20_words(key, np.arange(n // 8, dtype=np.uint64), stream).reshape(-1)
-    return [(int(w) >> (63 - bits)) - (1 << bits) for w in W]
 
 
 def sigma_v(eng, bits):

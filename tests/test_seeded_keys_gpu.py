@@ -128,6 +128,20 @@ def _small(fa, v, moduli, roots):
     return cent[0]
 
 
+def key_noise(fa, key, s_from, s_to, m, roots, n_q, alpha, P):
+    """per digit j of a switching key [digits][2][nl][N]: b_j + a_j s_to - (P mod q_t) s_from on the digit's limbs, as the centred integer
+    polynomial it is on all Q and P limbs (tests/test_client_randomness_gpu.py compares it with the sampler model)"""
+    import oracle as orc
+    out = []
+    for j in range(key.shape[0]):
+        v = orc.add(key[j, 0], orc.mul(key[j, 1], s_to, m), m)
+        for t in range(j * alpha, min((j + 1) * alpha, n_q)):
+            pm = P % m[t]
+            v[t] = (v[t].astype(object) - pm * s_from[t].astype(object)) % m[t]
+        out.append(_small(fa, v.astype(np.uint64), m, roots))
+    return out
+
+
 def test_keys_are_valid_keys_of_the_secret(fa, tmp_path):
     import oracle as orc
     rot = (1, -1, 5)
@@ -147,12 +161,7 @@ def test_keys_are_valid_keys_of_the_secret(fa, tmp_path):
             else:
                 gi = pow(g, -1, 2 * N)
                 s_from, s_to = s, np.stack([orc.automorph_ntt(s[l], gi) for l in range(nl)])
-            for j in range(cl.dnum_digits):
-                v = orc.add(key[j, 0], orc.mul(key[j, 1], s_to, m), m)
-                for t in range(j * alpha, min((j + 1) * alpha, n_q)):
-                    pm = P % m[t]
-                    v[t] = (v[t].astype(object) - pm * s_from[t].astype(object)) % m[t]
-                e = _small(fa, v.astype(np.uint64), m, roots)
+            for j, e in enumerate(key_noise(fa, key, s_from, s_to, m, roots, n_q, alpha, P)):
                 assert np.abs(e).max() <= 10 * SIGMA, (kind, g, j)
                 assert np.abs(e).max() > 0
         cl.save_eval_keys(path)
