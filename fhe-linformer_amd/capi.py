@@ -226,6 +226,11 @@ def load_library():
         "fhelin_debug_flood": (i32, [vp, vp, C.c_uint64, i32, i32, vp, C.c_size_t]),
         "fhelin_decrypt_flooded": (i32, [vp, vp, i32, C.POINTER(C.c_double), i32]),
         "fhelin_debug_sampler_peek": (i32, [vp, i32, vp, u64p]),
+        "fhelin_debug_pt_from_residues": (i32, [vp, vp, i32, C.POINTER(vp)]),
+        "fhelin_debug_dot_plain": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp)]),
+        "fhelin_debug_dot_groups": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp), i32, C.POINTER(vp)]),
+        "fhelin_debug_dot_cyclic": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
+        "fhelin_debug_dot_window": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -851,6 +856,50 @@ class Engine:
 
     def raw_mult_relin(self, a, b):
         return self._un(self.lib.fhelin_raw_mult_relin, a, b.h)
+
+    # ---- test hooks: the plaintext inner-sum kernels on chosen residues (include/fhelin.h "test hooks")
+    @staticmethod
+    def _harr_opt(objs):
+        return (C.c_void_p * len(objs))(*[(o.h if o is not None else None) for o in objs])
+
+    def debug_pt_from_residues(self, residues):
+        """a plaintext whose only encoding is residues [ell][N] (NTT form) at ell limbs and that limb count's own scale"""
+        r = np.ascontiguousarray(residues, dtype=np.uint64)
+        ell, n = r.shape
+        assert n == self.N
+        h = C.c_void_p()
+        self._ck(self.lib.fhelin_debug_pt_from_residues(self.h, r.ctypes.data_as(C.c_void_p), ell, C.byref(h)))
+        return Pt(self, h)
+
+    def debug_dot_plain(self, cts, pts):
+        """sum_i cts[i] * pts[i] (Evaluator::dot_plain)"""
+        assert len(cts) == len(pts)
+        h = C.c_void_p()
+        self._ck(self.lib.fhelin_debug_dot_plain(self.h, self._harr(cts), self._harr(pts), len(cts), C.byref(h)))
+        return Ct(self, h)
+
+    def debug_dot_groups(self, cts, pts):
+        """cts [nb][na], pts [ng][na] (None = term absent) -> outs [nb][ng], outs[x][g] = sum_b cts[x][b] * pts[g][b] in one launch"""
+        nb, na, ng = len(cts), len(cts[0]), len(pts)
+        assert all(len(r) == na for r in cts) and all(len(r) == na for r in pts)
+        outs = self._outs(nb * ng)
+        self._ck(self.lib.fhelin_debug_dot_groups(self.h, self._harr([c for r in cts for c in r]), nb, na,
+                                                  self._harr_opt([p for r in pts for p in r]), ng, outs))
+        flat = self._cts(outs, nb * ng)
+        return [flat[x * ng:(x + 1) * ng] for x in range(nb)]
+
+    def debug_dot_cyclic(self, cts, pts):
+        """outs[k] = sum_i cts[i] * pts[(i + k) mod 32], k < 32 (Evaluator::dot_plain_cyclic)"""
+        assert len(pts) == 32
+        outs = self._outs(32)
+        self._ck(self.lib.fhelin_debug_dot_cyclic(self.h, self._harr(cts), len(cts), self._harr(pts), outs))
+        return self._cts(outs, 32)
+
+    def debug_dot_window(self, cur, prev, pts, dest, accumulate=False):
+        """dest[t] (+)= sum_j (j <= t ? cur[j] : prev[j]) * pts[(t - j) mod 32]; cur / prev entries may be None; dest is written in place"""
+        assert len(cur) == len(prev) == len(pts) == len(dest) == 32
+        self._ck(self.lib.fhelin_debug_dot_window(self.h, self._harr_opt(cur), self._harr_opt(prev), self._harr(pts), self._harr(dest),
+                                                  int(bool(accumulate))))
 
     # ---- FHEController composites (names follow the reference methods)
     @staticmethod

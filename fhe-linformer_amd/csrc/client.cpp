@@ -319,6 +319,7 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
         hip_check(hipStreamSynchronize(ctx->main_stream), "encoding eviction sync");
         for (int k = 1; k <= ctx->n_lanes; ++k) hip_check(hipStreamSynchronize(ctx->lane_stream[k]), "encoding eviction sync (lane)");
     };
+    if (fixed) throw Error(FHELIN_ERR_STATE, "a plaintext made from residues holds one encoding only: asked for another limb count or scale");
     std::shared_ptr<Encoding> e;
     if (shared)   // an earlier handle of the same values has made exactly this encoding: nothing to launch
         for (size_t i = 0; i < shared->cache.size() && !e; ++i)

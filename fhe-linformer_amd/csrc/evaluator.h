@@ -83,6 +83,9 @@ struct Plaintext {
     // list, and with it which of two nearly equal scales an operation gets, is what it would be without the cache.
     std::shared_ptr<Plaintext> shared;
     static constexpr size_t MAX_SHARED_ENCODINGS = 64;
+    // set on a handle made from residues (fhelin_debug_pt_from_residues): it has no slot values, its one encoding is all it holds, and a
+    // request at any other (limb count, scale) is an error (FHELIN_ERR_STATE) instead of an encoding of nothing
+    bool fixed = false;
 };
 typedef std::shared_ptr<Plaintext> PtPtr;
 

@@ -101,7 +101,9 @@ struct EwScalarItems {
 void launch_ew_scalar_items(const DeviceTables& t, const EwScalarItems& d, u64* out, const u64* consts, hipStream_t s);
 // out[v] = sum_i a_i[v] * b_i[v % b_vecs] over the n items (n <= MAX_ITEMS): an inner product of ciphertexts with plaintexts in
 // one pass (the diagonal sums of the bootstrapping linear transforms, wrapUpRepeated, matmulCRlarge) instead of n product
-// launches and a tree of additions.  128-bit accumulation, one reduction: the canonical residue of the sum.
+// launches and a tree of additions.  128-bit accumulation, one reduction: the canonical residue of the sum - 32 products below 2^120 each
+// stay below 2^125, and barrett_reduce128 takes any 128-bit value (a high word at or above q included), so the sum of MAX_ITEMS maximal
+// products on a 60-bit limb is reduced exactly.
 void launch_ew_dot(const DeviceTables& t, u64* out, const EwItems& it, int limb_count, hipStream_t s);
 // Several such inner products over the SAME ciphertexts in one pass: out_g = sum_b a_b * p_{g,b} for g < ng (the inner sums of
 // all giant steps of a baby-step/giant-step linear transform: every rotated ciphertext is read once instead of once per

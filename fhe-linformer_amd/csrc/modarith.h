@@ -116,7 +116,9 @@ FHE_HD u64 mul_mod(u64 a, u64 c, const Barrett& b) {
     return barrett_reduce128(a * c, mulhi64(a, c), b);
 }
 
-// 128-bit accumulator for sums of up to 16 products of 60-bit numbers.
+// 128-bit accumulator for sums of up to 32 products of residues below 2^60 (EwItems::MAX_ITEMS terms in ew_dot_kernel): every product
+// is below 2^120, the sum below 2^125 - no carry is lost - and one barrett_reduce128 gives its canonical residue although the high
+// word is then not below q: the reduction takes any 128-bit value (tests/test_dot_kernels_gpu.py, tests/test_dot_kernels_host.py).
 struct Acc128 {
     u64 lo, hi;
 };

@@ -289,6 +289,29 @@ int fhelin_raw_modraise(fhelin_ctx* c, const fhelin_ct* a, int32_t new_ell, fhel
  * decoding; client side: needs the secret key) */
 int fhelin_raw_phase(fhelin_ctx* c, const fhelin_ct* a, fhelin_ct** out);
 
+/* ---- test hooks: the ciphertext x plaintext inner-sum kernels on operands chosen residue by residue --------
+ * No driver calls these.  Ciphertexts arrive through fhelin_ct_import (degree 1, two components, one limb count and scale per call),
+ * plaintexts through fhelin_debug_pt_from_residues, results leave through fhelin_ct_export (noise degree 2).
+ *
+ * A plaintext whose ONLY encoding is `residues` [ell][N] (NTT form, every word below its limb's modulus, else FHELIN_ERR_ARG) at ell limbs
+ * and the scale the inner sums ask for at that limb count (Delta of level n_q - ell).  It has no slot values: used at any other (limb
+ * count, scale) it fails with FHELIN_ERR_STATE.  It never enters the content-keyed plaintext cache of fhelin_encode. */
+int fhelin_debug_pt_from_residues(fhelin_ctx* c, const uint64_t* residues, int32_t ell, fhelin_pt** out);
+/* out = sum_i cts[i] * pts[i]: one launch per 32 terms */
+int fhelin_debug_dot_plain(fhelin_ctx* c, const fhelin_ct* const* cts, const fhelin_pt* const* pts, int32_t n, fhelin_ct** out);
+/* outs[x][g] = sum_b cts[x][b] * pts[g][b] for x < nb, g < ng (na <= 16 columns, ng <= 8 groups; pts[g][b] NULL = term absent) in ONE
+ * launch.  nb >= 2: the same plaintexts over nb sets of ciphertexts, which are first copied into equally spaced views of one block.
+ * Operands the kernel does not take are an error (FHELIN_ERR_STATE), never another path. */
+int fhelin_debug_dot_groups(fhelin_ctx* c, const fhelin_ct* const* cts /* [nb][na] */, int32_t nb, int32_t na,
+                            const fhelin_pt* const* pts /* [ng][na] */, int32_t ng, fhelin_ct** outs /* [nb][ng] */);
+/* outs[k] = sum_{i<n} cts[i] * pts[(i + k) mod 32] for k < 32, n <= 32 */
+int fhelin_debug_dot_cyclic(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n, const fhelin_pt* const* pts /* [32] */,
+                            fhelin_ct** outs /* [32] */);
+/* dest[t] (+)= sum_{j<32} (j <= t ? cur[j] : prev[j]) * pts[(t - j) mod 32] for t < 32; cur[j], prev[j] NULL = zero (at least one entry
+ * present).  dest is in/out: 32 imported ciphertexts of the operands' shape, overwritten - accumulate != 0: added to. */
+int fhelin_debug_dot_window(fhelin_ctx* c, const fhelin_ct* const* cur /* [32] */, const fhelin_ct* const* prev /* [32] */,
+                            const fhelin_pt* const* pts /* [32] */, fhelin_ct* const* dest /* [32] */, int32_t accumulate);
+
 /* ---- FHEController composite circuit ops (callers of the hot path) --------
  * One entry point per reference method; `vector<Ctxt>` travels as (array of handles, count); outputs are
  * written to caller-provided handle arrays.  A NULL bias means `bias == nullptr` in the reference. */

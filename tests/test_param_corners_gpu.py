@@ -353,8 +353,11 @@ def test_extreme_operands(corner_engine, orc, corner, form):
 
 def test_sixty_bit_reference_ring_slot_kernels(fa, orc):
     """the kernels that need a slot layout, on a 60-bit chain at the reference ring (N = 2^15, 16384 slots): wrapUpRepeated over 32
-    ciphertexts at q - 1 (ew_dot_kernel: 32 products of up to (q - 1)^2 before one reduction) and matmulRElarge with rows at q - 1,
-    read directly and through generate_containers (ew_cyclic_dot_kernel, 30-bit split with a fold every 16 products)"""
+    ciphertexts at q - 1 (ew_dot_kernel: 32 products before one reduction, q - 1 on the ciphertext side, the encoder's block masks on
+    the plaintext side) and matmulRElarge with rows at q - 1, read directly and through generate_containers (ew_cyclic_dot_kernel on its
+    30-bit split path with NINE of its 32 columns live: no output sums more than nine products, so neither a second flush of eight nor
+    the fold after sixteen carries anything here).  The full sums - 32 live columns, plaintext residues at their extremes too - are in
+    tests/test_dot_kernels_gpu.py"""
     eng = fa.Engine("reference", seed=3, n_q=6, n_p=2, dnum=3, first_bits=60, scale_bits=59)
     try:
         assert int(eng.q[0]).bit_length() == 60
