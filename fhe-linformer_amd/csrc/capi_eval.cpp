@@ -5,12 +5,26 @@
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
+#include <memory>
 #include "capi_internal.h"
 
 using namespace fhelin;
 
 #define NEED(x) if (!(x)) return capi_fail(FHELIN_ERR_ARG, "null argument")
 
+
+// a call that fails (the encoder's domain, a missing key) has made no source: the level plan's source counter goes back to where the call
+// found it, so that a refused call does not shift the targets of the sources after it
+namespace {
+struct PlanRewind {
+    LevelPlan& plan;
+    int at;
+    bool keep = false;
+    ~PlanRewind() {
+        if (!keep) plan.next_ordinal = at;
+    }
+};
+}  // namespace
 
 static KeyPtr& key_slot(fhelin_ctx* c, int kind, int index) {
     if (kind == 0) return c->ev.relin_key;
@@ -72,6 +86,7 @@ static PtPtr handle_on(const PtPtr& master) {
     p->values = master->values;
     p->slots = master->slots;
     p->level = master->level;
+    p->max_abs = master->max_abs;
     p->shared = master;
     return p;
 }
@@ -167,9 +182,9 @@ int fhelin_key_import(fhelin_ctx* c, int32_t kind, int32_t index, const uint64_t
 int fhelin_encode(fhelin_ctx* c, const double* vals, int32_t n, int32_t level, int32_t slots, fhelin_pt** out) {
     NEED(c && out && (vals || n == 0));
     FHELIN_TRY
-    auto* h = new fhelin_pt;
+    std::unique_ptr<fhelin_pt> h(new fhelin_pt);   // a refusal (a NaN among the values) leaves no handle behind
     h->p = c->pt_cache.encode(c->cl, 1 << c->ctx.prm.log_slots, vals, n, level, slots);
-    *out = h;
+    *out = h.release();
     FHELIN_CATCH
 }
 void fhelin_pt_free(fhelin_pt* p) { delete p; }
@@ -191,8 +206,10 @@ int fhelin_pt_export(fhelin_ctx* c, const fhelin_pt* p, int32_t ell, double scal
 int fhelin_encrypt(fhelin_ctx* c, const fhelin_pt* p, fhelin_ct** out) {
     NEED(c && p && out);
     FHELIN_TRY
+    PlanRewind rewind{c->plan, c->plan.next_ordinal};
     *out = wrap(c, c->cl.encrypt(p->p, c->plan.next_drop(c->ctx.L + 1 - p->p->level)));
     if (c->plan.live((*out)->node, (*out)->node_epoch)) c->plan.nodes[(*out)->node].ordinal = c->plan.next_ordinal - 1;
+    rewind.keep = true;
     FHELIN_CATCH
 }
 int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32_t n_per, int32_t level, int32_t slots, fhelin_ct** outs) {
@@ -202,6 +219,7 @@ int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32
     // the batched encryptor together
     if (n_vec < 0 || n_per < 0) throw Error(FHELIN_ERR_ARG, "encrypt_batch: negative count");
     if (level < 0 || level > c->ctx.L) throw Error(FHELIN_ERR_ARG, "encrypt_batch: level out of range");
+    PlanRewind rewind{c->plan, c->plan.next_ordinal};
     std::vector<int> drop(n_vec);
     for (int i = 0; i < n_vec; ++i)
         drop[i] = std::max(0, std::min(c->ctx.L - level, c->plan.next_drop(c->ctx.L + 1 - level)));
@@ -231,6 +249,7 @@ int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32
         outs[i] = wrap(c, r[i]);
         if (c->plan.live(outs[i]->node, outs[i]->node_epoch)) c->plan.nodes[outs[i]->node].ordinal = first_ordinal + i;
     }
+    rewind.keep = true;
     FHELIN_CATCH
 }
 int fhelin_client_ingest(fhelin_ctx* c, const double* emb, const int32_t* tokens, const double* table, int32_t vocab, int32_t S,

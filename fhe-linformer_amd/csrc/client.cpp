@@ -218,6 +218,18 @@ static const Context::FftDev& fft_dev_tables(Context& c, int slots) {
     return c.fft_dev.emplace(slots, d).first->second;
 }
 
+// The encoder's domain (include/fhelin.h fhelin_encode): finite slot values, and max|v| * scale below 2^125 - tested on the exponents
+// alone: floor(log2 max|v|) + floor(log2 scale) <= 123 guarantees it (each factor is below twice its power of two), needs no product
+// that could round, and refuses everything that reaches 2^125.  reduce_i128_kernel takes |x| < 2^126 and x87_mul_round < 2^127; a
+// coefficient is an average of slot values, so max|v| bounds it up to the FFT's rounding.  A NaN or an infinity would reach the
+// rounding code as exponent 0x7FF (device) or as (u64)floorl(NaN) (host) and leave arbitrary residues.
+void encode_domain_check(double max_abs, long double scale) {
+    if (!std::isfinite(max_abs)) throw Error(FHELIN_ERR_ARG, "encode: a slot value is NaN or infinite");
+    if (!(scale > 0) || !std::isfinite(scale)) throw Error(FHELIN_ERR_ARG, "encode: the scale must be positive and finite");
+    if (max_abs != 0.0 && std::ilogb(max_abs) + std::ilogb(scale) > 123)
+        throw Error(FHELIN_ERR_ARG, "encode: max|value| * scale may reach 2^125 (floor(log2 max|value|) + floor(log2 scale) > 123)");
+}
+
 void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale) {
     c.require_device();
     if (slots < 2 || (slots & (slots - 1)) || slots > c.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots must be a power of two in [2, N/2]");
@@ -230,10 +242,17 @@ void encode_batch_device(Context& c, u64* dst, const double* re, const double* i
     std::vector<u64> host(words);
     for (int b = 0; b < n_vec; ++b) {                       // through the pinned staging ring: no stream drain
         double* h = reinterpret_cast<double*>(host.data());
+        double mx = 0.0;                                    // the encoder's domain (encode_domain_check), on the values as they pass
         for (int i = 0; i < slots; ++i) {
-            h[2 * i] = i < n_per ? re[(size_t)b * n_per + i] : 0.0;
-            h[2 * i + 1] = (im && i < n_per) ? im[(size_t)b * n_per + i] : 0.0;
+            const double x = i < n_per ? re[(size_t)b * n_per + i] : 0.0;
+            const double y = (im && i < n_per) ? im[(size_t)b * n_per + i] : 0.0;
+            h[2 * i] = x;
+            h[2 * i + 1] = y;
+            const double ax = std::fabs(x), ay = std::fabs(y);
+            if (ax > mx || ax != ax) mx = ax;               // a NaN takes over mx and stays: nothing compares greater than it
+            if (ay > mx || ay != ay) mx = ay;
         }
+        encode_domain_check(mx, scale);
         c.upload_async(reinterpret_cast<u64*>(dv.get()) + words * b, host.data(), words);
     }
     encode_complex_on_device(c, dst, dv, n_vec, slots, ell, scale);
@@ -329,6 +348,7 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
                 order(e);
             }
     if (!e) {
+        encode_domain_check(max_abs, scale);   // before anything is launched: a refused encoding leaves the plaintext and its cache as they were
         e = encode_to_device(*ctx, values, imag, slots, ell, scale);
         e->made_lane = ctx->pool.cur_lane;
         e->lanes_ordered = 1u << e->made_lane;
@@ -583,7 +603,14 @@ PtPtr Client::encode(const double* vals, int n, int level, int slots) {
     p->slots = slots;
     p->level = level;
     p->values.assign(slots, 0.0);
-    for (int i = 0; i < n && i < slots; ++i) p->values[i] = vals[i];
+    double mx = 0.0;
+    for (int i = 0; i < n && i < slots; ++i) {
+        p->values[i] = vals[i];
+        const double a = std::fabs(vals[i]);
+        if (a > mx || a != a) mx = a;                       // a NaN takes over mx and stays: nothing compares greater than it
+    }
+    if (!std::isfinite(mx)) throw Error(FHELIN_ERR_ARG, "encode: a slot value is NaN or infinite");
+    p->max_abs = mx;
     return p;
 }
 

@@ -131,6 +131,8 @@ void ckks_fft_special(std::vector<std::pair<double, double>>& v, bool inverse);
 void ckks_fft_tables(int slots, std::vector<u32>& rot, std::vector<std::pair<double, double>>& ksi);
 std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>& values, const std::vector<double>& imag, int slots,
                                            int ell, long double scale);
+// the encoder's domain: throws FHELIN_ERR_ARG for a non-finite max_abs, or when the two exponents allow max_abs * scale >= 2^125
+void encode_domain_check(double max_abs, long double scale);
 // device encoder for n_vec vectors: re / im [n_vec][n_per] (im may be null) -> dst [n_vec][ell][N] NTT form
 void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale);
 void encode_complex_on_device(Context& c, u64* dst, double* dv, int n_vec, int slots, int ell, long double scale);

@@ -74,6 +74,11 @@ struct Plaintext {
     std::vector<double> imag;    // optional imaginary parts (bootstrapping's DFT diagonals); empty = real vector
     int slots = 0;
     int level = 0;               // level requested at encode time (reference encode(vec, level, slots))
+    // max |values[i]|, kept by Client::encode (finite there): at() refuses an encoding whose max_abs * scale may reach 2^125
+    // (encode_domain_check) without a second pass over the values (every coefficient is an average of slot values, so max_abs bounds
+    // it).  0 on plaintexts the library fills in itself (bootstrapping's diagonals, the unwrap mask): bounded by construction, and
+    // the device encoder's staging walk sees their values anyway
+    double max_abs = 0.0;
     static constexpr size_t MAX_ENCODINGS = 16;
     std::vector<std::shared_ptr<Encoding>> cache;   // most recently used first (Plaintext::at)
     std::shared_ptr<Encoding> at(int ell, long double scale);

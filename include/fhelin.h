@@ -182,7 +182,15 @@ int fhelin_key_import(fhelin_ctx* c, int32_t kind, int32_t index, const uint64_t
 /* Plaintexts are cached per context BY CONTENT: a second encode of the same (n, slots, level, value bytes) gives a handle that shares the
  * first one's device encodings at exactly equal (limbs, scale) (a model's weights and masks are encoded once, not once per pass).  `vals` is copied: changing the array
  * afterwards changes nothing.  fhelin_pt_free drops the handle's reference only; the cache itself is bounded (FHELIN_PT_CACHE_MB, default
- * 1024, least recently used plaintext first) and emptied by fhelin_ctx_trim and fhelin_ctx_destroy.  FHELIN_PT_CACHE=0: no cache. */
+ * 1024, least recently used plaintext first) and emptied by fhelin_ctx_trim and fhelin_ctx_destroy.  FHELIN_PT_CACHE=0: no cache.
+ * DOMAIN of the encoder: every value that becomes part of the plaintext (the first min(n, slots)) must be finite - a NaN or an infinity
+ * is refused here with FHELIN_ERR_ARG (no device needed), no handle is made.  A plaintext is encoded when an operation first needs it at
+ * some (limbs, scale); an encoding is refused there with FHELIN_ERR_ARG (fhelin_pt_export, fhelin_encrypt, every ct x pt / ct + pt
+ * operation) unless floor(log2 max|vals[i]|) + floor(log2 scale) <= 123.  The test reads the two exponents only: it guarantees
+ * max|vals[i]| * scale < 2^125, so everything that reaches 2^125 is refused (and some products from 2^123 on: at a Delta just below 2^52
+ * values below 2^73 are accepted, at one just above 2^52 values below 2^72).  The rounding code takes integers below 2^126, and every
+ * coefficient of an encoding is an average of slot values.  A refusal launches nothing and leaves the plaintext, the cache and the context as they were;
+ * neither check changes a residue of an accepted input. */
 int fhelin_encode(fhelin_ctx* c, const double* vals, int32_t n, int32_t level, int32_t slots, fhelin_pt** out);
 void fhelin_pt_free(fhelin_pt* p);
 /* the residues [ell][N] (NTT form) this plaintext multiplies / adds with at `ell` live limbs and real scaling factor
@@ -198,7 +206,13 @@ int fhelin_encrypt(fhelin_ctx* c, const fhelin_pt* p, fhelin_ct** out);         
 /* n_vec inputs at once (the driver's 194 read_expanded_input calls per sample, src/main.cpp:159-173; FHEController.cpp:623-650):
  * vals [n_vec][n_per] real slot values -> n_vec fresh ciphertexts at `level`.  Encoding (special FFT in fp64, scaling,
  * rounding), the sampling of the encryption randomness (ChaCha20 on the GPU, keyed from the client's generator) and the
- * dyadic combination run as batched kernels. */
+ * dyadic combination run as batched kernels.
+ * The same DOMAIN as fhelin_encode: a NaN or an infinity among the values read (the first min(n_per, slots) of every vector), or
+ * floor(log2 max|vals|) + floor(log2 Delta) > 123 with Delta the scale of the level a vector starts at (`level`, lower by what an
+ * applied level plan takes off), fails the whole call with FHELIN_ERR_ARG and gives no handle.  The values are checked as they are
+ * staged, one chunk of 32 vectors after the other: the context's generator may have advanced by the draws of the chunks before the
+ * refused one.  The level plan does not move: a failed fhelin_encrypt or fhelin_encrypt_batch has made no source, and the plan's
+ * source counter is where the call found it. */
 int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32_t n_per, int32_t level, int32_t slots, fhelin_ct** outs);
 /* The client side of ONE sample on the device: what the reference does in NumPy before the server sees anything
  * (src/python/dimReduce.py:141-160: x_in = [cls; emb + pos/3], X_E = E[:, :S+1] x_in + b_E, X_F likewise) followed by the 64 + S + 1
@@ -207,7 +221,9 @@ int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32
  * Give the S token embeddings as emb [S][128], or token ids tokens [S] into table [vocab][128].  pos [>= S][128], cls [128],
  * E_w / F_w [32][w_cols] row-major (w_cols >= S + 1), E_b / F_b [32].  outs: 64 + S + 1 handles in the order of the driver's reads:
  * the 32 E-projected rows, the 32 F-projected rows, then the S + 1 tokens (CLS first).  Every output is a source of the level plan.
- * proj_out (optional, (S + 1 + 64) * 128 doubles): x_in rows then the projected rows as the device computed them (parity tests). */
+ * proj_out (optional, (S + 1 + 64) * 128 doubles): x_in rows then the projected rows as the device computed them (parity tests).
+ * The rows that are encoded are computed on the device: the encoder's DOMAIN (fhelin_encode) is NOT checked here - finite inputs whose
+ * sums stay far below 2^125 / Delta are the caller's to give. */
 int fhelin_client_ingest(fhelin_ctx* c, const double* emb, const int32_t* tokens, const double* table, int32_t vocab, int32_t S,
                          const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
                          int32_t w_cols, int32_t level, fhelin_ct** outs, double* proj_out);
