@@ -231,6 +231,13 @@ def load_library():
         "fhelin_debug_dot_groups": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp), i32, C.POINTER(vp)]),
         "fhelin_debug_dot_cyclic": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
         "fhelin_debug_dot_window": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32]),
+        "fhelin_ctx_set_interleave": (i32, [vp, i32]),
+        "fhelin_ctx_interleave": (i32, [vp, C.POINTER(i32)]),
+        "fhelin_evalkeys_interleave": (i32, [C.c_char_p, C.POINTER(i32)]),
+        "fhelin_encrypt_interleaved_batch": (i32, [vp, C.POINTER(C.c_double), i32, i32, i32, i32, C.POINTER(vp)]),
+        "fhelin_decrypt_interleaved": (i32, [vp, vp, i32, C.POINTER(C.c_double), i32]),
+        "fhelin_client_ingest_interleaved": (i32, [vp, i32, C.POINTER(vp), C.POINTER(vp), vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32,
+                                                   C.POINTER(vp), C.POINTER(vp)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -250,6 +257,21 @@ def compact_info(blob):
     if rc != 0:
         raise FhelinError(rc, lib.fhelin_last_error().decode())
     return dict(zip(("log_n", "ell", "deg", "slots"), (x.value for x in v)))
+
+
+def interleave(vectors):
+    """`stride` sample vectors [stride][n] -> the physical slot vector [n * stride] of an interleaved ciphertext (include/fhelin.h
+    "Interleaved samples"): slot stride * k + i = vectors[i][k]"""
+    v = np.asarray(vectors)
+    assert v.ndim == 2
+    return np.ascontiguousarray(v.T).reshape(-1)
+
+
+def deinterleave(physical, stride):
+    """the inverse of interleave: a physical slot vector [n * stride] -> [stride][n]"""
+    w = np.asarray(physical)
+    assert w.ndim == 1 and w.size % stride == 0
+    return np.ascontiguousarray(w.reshape(-1, stride).T)
 
 
 def _np_u64(a):
@@ -287,9 +309,10 @@ class DevBuf:
 class Engine:
     """One fhelin context (one GPU, one stream)."""
 
-    def __init__(self, preset="bench", device=0, seed=0, seed_bytes=None, **overrides):
+    def __init__(self, preset="bench", device=0, seed=0, seed_bytes=None, interleave=1, **overrides):
         """seed=0 (default): keys from 256 bits of OS entropy.  seed != 0: deterministic TEST seed.  seed_bytes: an explicit
-        32-byte secret seed (re-creating a client's keys)."""
+        32-byte secret seed (re-creating a client's keys).  interleave: the slot stride (include/fhelin.h "Interleaved samples"): that
+        many samples per ciphertext; 1 (default) leaves the context as it is (set_interleave(1) sets it explicitly)."""
         self.lib = load_library()
         cfg = dict(PRESETS[preset]) if isinstance(preset, str) else dict(preset)
         cfg.update(overrides)
@@ -326,10 +349,88 @@ class Engine:
         self.alpha, self.has_device = a.value, bool(d.value)
         self.lazy_heavy = os.environ.get("FHELIN_LAZY_HEAVY", "1") != "0"
         self.lazy_rows_on = os.environ.get("FHELIN_LAZY_ROWS", "1") != "0"   # the library reads the same knob (capi.cpp)
+        if interleave != 1:
+            try:
+                self.set_interleave(interleave)
+            except Exception:
+                self.close()
+                raise
 
     def _ck(self, rc):
         if rc != 0:
             raise FhelinError(rc, self.lib.fhelin_last_error().decode())
+
+    # ---- interleaved samples (include/fhelin.h "Interleaved samples")
+    def set_interleave(self, stride):
+        """the slot stride: `stride` samples per ciphertext; before the first key, plaintext, ciphertext or bootstrap set-up"""
+        self._ck(self.lib.fhelin_ctx_set_interleave(self.h, int(stride)))
+
+    @property
+    def interleave(self):
+        s = C.c_int32()
+        self._ck(self.lib.fhelin_ctx_interleave(self.h, C.byref(s)))
+        return s.value
+
+    @staticmethod
+    def eval_keys_interleave(path):
+        """the stride a key set was written at; host-only"""
+        lib = load_library()
+        s = C.c_int32()
+        rc = lib.fhelin_evalkeys_interleave(os.fsencode(path), C.byref(s))
+        if rc != 0:
+            raise FhelinError(rc, lib.fhelin_last_error().decode())
+        return s.value
+
+    def encrypt_interleaved_batch(self, rows, level=0, slots=0):
+        """rows [n_vec][stride][n_per] -> n_vec fresh ciphertexts, sample i of a row in the physical slots = i mod stride"""
+        a = np.ascontiguousarray(rows, dtype=np.float64)
+        assert a.ndim == 3 and a.shape[1] == self.interleave
+        outs = self._outs(a.shape[0])
+        self._ck(self.lib.fhelin_encrypt_interleaved_batch(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[0], a.shape[2], level,
+                                                           slots, outs))
+        return self._cts(outs, a.shape[0])
+
+    def decrypt_interleaved(self, ct, slots=0, flood_bits=0):
+        """every sample of a ciphertext: [stride][slots]"""
+        n = slots or ct.slots or (1 << self.params.log_slots)
+        out = np.empty((self.interleave, n), dtype=np.float64)
+        self._ck(self.lib.fhelin_decrypt_interleaved(self.h, ct.h, int(flood_bits), out.ctypes.data_as(C.POINTER(C.c_double)), n))
+        return out
+
+    def client_ingest_interleaved(self, cls, pos, E_w, E_b, F_w, F_b, embs=None, tokens=None, table=None, level=0, want_proj=False):
+        """client_ingest for `stride` samples of one length that share every ciphertext: embs (or tokens) is the list of the samples'
+        embeddings (token ids).  Returns the group's {"inputs_E", "inputs_F", "inputs"} (+ per-sample lists x_in, proj if want_proj)"""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        cls, pos, E_w, E_b, F_w, F_b = f(cls), f(pos), f(E_w), f(E_b), f(F_w), f(F_b)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        if embs is not None:
+            xs = [f(e) for e in embs]
+            S, tab, vocab = xs[0].shape[0], None, 0
+            if any(x.shape != (S, 128) for x in xs):
+                raise FhelinError(1, "client_ingest_interleaved: the samples of a group have one length, rows of 128")
+        else:
+            xs = [np.ascontiguousarray(t, dtype=np.int32) for t in tokens]
+            tab = f(table)
+            S, vocab = xs[0].shape[0], tab.shape[0]
+            if any(x.shape != (S,) for x in xs):
+                raise FhelinError(1, "client_ingest_interleaved: the samples of a group have one length")
+        if pos.shape[0] < S or pos.shape[1] != 128 or E_w.shape != F_w.shape or E_w.shape[0] != 32 or E_w.shape[1] < S + 1 or cls.size != 128 \
+                or E_b.size != 32 or F_b.size != 32:
+            raise FhelinError(1, "client_ingest_interleaved: pos needs >= S rows of 128, E_w / F_w [32][>= S + 1], E_b / F_b [32], cls [128]")
+        ns = len(xs)
+        ptrs = (C.c_void_p * ns)(*[x.ctypes.data for x in xs])
+        n = 64 + S + 1
+        outs = self._outs(n)
+        proj = [np.empty((S + 1 + 64, 128)) for _ in range(ns)] if want_proj else None
+        pp = (C.c_void_p * ns)(*[a.ctypes.data for a in proj]) if want_proj else None
+        self._ck(self.lib.fhelin_client_ingest_interleaved(self.h, ns, ptrs if embs is not None else None, ptrs if embs is None else None,
+                                                           p(tab), vocab, S, p(cls), p(pos), p(E_w), p(E_b), p(F_w), p(F_b), E_w.shape[1],
+                                                           level, outs, pp))
+        cts = self._cts(outs, n)
+        res = {"inputs_E": cts[:32], "inputs_F": cts[32:64], "inputs": cts[64:]}
+        if want_proj:
+            res["x_in"], res["proj"] = [a[:S + 1] for a in proj], [a[S + 1:] for a in proj]
+        return res
 
     def set_lazy_rows(self, on):
         """deferred evaluation of the rows of matmul_pt / unwrapExpanded (default on)"""

@@ -154,15 +154,27 @@ LinStage Bootstrapper::prepare(const DiagMap& m, int n) {
     return st;
 }
 
+// Interleaved samples (context.h Context::stride): `slots` is logical; the stages, their diagonals and every rotation of the bootstrap
+// (baby and giant steps, SubSum, conjugation) belong to the PHYSICAL packing of slots * stride slots, so the public entry points run
+// under a Context::PhysicalScope and nothing below multiplies an index by the stride.
 void Bootstrapper::setup(int budget_enc, int budget_dec, int slots) {
     Context& c = ev_.ctx();
     c.require_device();
+    if (slots <= 0) slots = 1 << c.prm.log_slots;
+    const int logical = slots;
+    if (c.stride > 1) {
+        if ((long)slots * c.stride > c.N / 2) throw Error(FHELIN_ERR_ARG, "bootstrap: slots x interleave stride must be <= N/2");
+        slots *= c.stride;
+    }
+    c.stride_locked = true;
+    Context::PhysicalScope physical(c);
     // an evaluation context (no secret) builds its stages from the imported keys: a missing one is named below (FHELIN_ERR_KEY)
     if (!cl_.has_keys() && !cl_.eval_only()) throw Error(FHELIN_ERR_KEY, "bootstrap setup needs the secret key (keygen first)");
     if (slots <= 0) slots = 1 << c.prm.log_slots;
     if (slots & (slots - 1) || slots > c.N / 2 || slots < 4) throw Error(FHELIN_ERR_ARG, "bootstrap: slots must be a power of two in [4, N/2]");
     if (budget_enc < 1 || budget_dec < 1) throw Error(FHELIN_ERR_ARG, "bootstrap: level budget must be >= 1");
     slots_ = slots;
+    logical_slots_ = logical;
     budget_enc_ = budget_enc;
     budget_dec_ = budget_dec;
     const int n = slots;
@@ -402,7 +414,7 @@ CtPtr Bootstrapper::run(const CtPtr& ct, int stop_after, int drop) {
     v = ev_.mult_int(v, 1ull << correction, false, v->scale);
     v->scale = v->scale * rho;
     if (v->deg >= 2) v = ev_.rescale(v);
-    v->slots = ct->slots > 0 ? ct->slots : slots_;
+    v->slots = ct->slots > 0 ? ct->slots : logical_slots_;
     return v;
 }
 
@@ -559,12 +571,13 @@ std::vector<CtPtr> Bootstrapper::run_batch(const std::vector<CtPtr>& cts, int dr
         out[i]->scale = out[i]->scale * rho[i];
     }
     if (out[0]->deg >= 2) out = ev_.rescale_batch(out);
-    for (size_t i = 0; i < B; ++i) out[i]->slots = cts[i]->slots > 0 ? cts[i]->slots : slots_;
+    for (size_t i = 0; i < B; ++i) out[i]->slots = cts[i]->slots > 0 ? cts[i]->slots : logical_slots_;
     return out;
 }
 
 std::vector<CtPtr> Bootstrapper::bootstrap_batch(const std::vector<CtPtr>& cts, int drop) {
     if (cts.empty()) return {};
+    Context::PhysicalScope physical(ev_.ctx());
     if (cts.size() == 1) return {run(cts[0], 0, drop)};
     return run_batch(cts, drop);
 }
@@ -579,6 +592,7 @@ std::vector<CtPtr> Bootstrapper::bootstrap_iter_batch(const std::vector<CtPtr>& 
     if (ell_y < 3) throw Error(FHELIN_ERR_STATE, "bootstrap_iter: the first bootstrap must leave at least three limbs (one for the final scaling)");
     const size_t B = cts.size();
     if (B == 0) return {};
+    Context::PhysicalScope physical(c);
     // x2: exactly what ModRaise reads (rescaled if degree 2, two limbs); bootstrapping it gives the residues of bootstrapping x
     std::vector<CtPtr> x2(B);
     {
@@ -630,7 +644,13 @@ std::vector<CtPtr> Bootstrapper::bootstrap_iter_batch(const std::vector<CtPtr>& 
 
 CtPtr Bootstrapper::bootstrap_iter(const CtPtr& ct, int p, int drop) { return bootstrap_iter_batch({ct}, p, drop)[0]; }
 
-CtPtr Bootstrapper::bootstrap(const CtPtr& ct, int drop) { return run(ct, 0, drop); }
-CtPtr Bootstrapper::partial(const CtPtr& ct, int stage) { return run(ct, stage); }
+CtPtr Bootstrapper::bootstrap(const CtPtr& ct, int drop) {
+    Context::PhysicalScope physical(ev_.ctx());
+    return run(ct, 0, drop);
+}
+CtPtr Bootstrapper::partial(const CtPtr& ct, int stage) {
+    Context::PhysicalScope physical(ev_.ctx());
+    return run(ct, stage);
+}
 
 }  // namespace fhelin

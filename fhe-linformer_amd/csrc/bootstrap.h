@@ -57,7 +57,8 @@ public:
     const std::vector<LinStage>& stages(bool s2c) const { return s2c ? s2c_ : c2s_; }
     const std::vector<double>& cheb() const { return cheb_; }
     bool packed() const { return packed_; }
-    int slots() const { return slots_; }
+    int slots() const { return slots_; }                   // of the physical packing the stages are built for
+    int logical_slots() const { return logical_slots_; }   // as setup() was asked: slots() / the interleave stride
     int budget_enc() const { return budget_enc_; }   // as setup() was called (evaluation-key sets record them)
     int budget_dec() const { return budget_dec_; }
 
@@ -70,7 +71,7 @@ public:
 private:
     Evaluator& ev_;
     Client& cl_;
-    int slots_ = 0;
+    int slots_ = 0, logical_slots_ = 0;
     int budget_enc_ = 0, budget_dec_ = 0;
     bool stage_order_legacy_ = false;   // FHELIN_BOOT_STAGES_LEGACY=1: larger stages first (round-1 split 5+5+4)
     bool packed_ = false;   // sparse packing: real and imaginary halves share one ciphertext through EvalMod (bootstrap.cpp)

@@ -28,7 +28,7 @@ struct PlanRewind {
 
 static KeyPtr& key_slot(fhelin_ctx* c, int kind, int index) {
     if (kind == 0) return c->ev.relin_key;
-    if (kind == 1) return c->ev.rot_keys[c->ctx.galois_element(index)];
+    if (kind == 1) return c->ev.rot_keys[c->ctx.rot_element(index)];
     if (kind == 2) return c->ev.conj_key;
     throw Error(FHELIN_ERR_ARG, "unknown key kind");
 }
@@ -85,6 +85,7 @@ static PtPtr handle_on(const PtPtr& master) {
     p->ctx = master->ctx;
     p->values = master->values;
     p->slots = master->slots;
+    p->stride = master->stride;
     p->level = master->level;
     p->max_abs = master->max_abs;
     p->shared = master;
@@ -212,9 +213,12 @@ int fhelin_encrypt(fhelin_ctx* c, const fhelin_pt* p, fhelin_ct** out) {
     rewind.keep = true;
     FHELIN_CATCH
 }
-int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32_t n_per, int32_t level, int32_t slots, fhelin_ct** outs) {
+// fhelin_encrypt_batch, and fhelin_encrypt_interleaved_batch (per_lane: vals [n_vec][stride][n_per], a row = one ciphertext's samples)
+static int encrypt_batch_rows(fhelin_ctx* c, const double* vals, int32_t n_vec, int32_t n_per, int32_t level, int32_t slots, fhelin_ct** outs,
+                              bool per_lane) {
     NEED(c && (vals || n_vec == 0) && outs);
     FHELIN_TRY
+    const size_t row = (size_t)std::max(0, n_per) * (per_lane ? c->ctx.stride : 1);
     // every vector is a source of the level plan of its own: vectors that the plan starts at the same level go through
     // the batched encryptor together
     if (n_vec < 0 || n_per < 0) throw Error(FHELIN_ERR_ARG, "encrypt_batch: negative count");
@@ -236,13 +240,12 @@ int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32
                 seen[j] = 1;
             }
         if ((int)pick.size() == n_vec) {
-            r = c->cl.encrypt_batch(vals, n_vec, n_per, level + drop[i], slots, pick.data());
+            r = c->cl.encrypt_batch(vals, n_vec, n_per, level + drop[i], slots, pick.data(), per_lane);
             break;
         }
-        std::vector<double> sub((size_t)pick.size() * n_per);
-        for (size_t k = 0; k < pick.size(); ++k)
-            std::memcpy(sub.data() + k * n_per, vals + (size_t)pick[k] * n_per, (size_t)n_per * sizeof(double));
-        std::vector<CtPtr> part = c->cl.encrypt_batch(sub.data(), (int)pick.size(), n_per, level + drop[i], slots, pick.data());
+        std::vector<double> sub((size_t)pick.size() * row);
+        for (size_t k = 0; k < pick.size(); ++k) std::memcpy(sub.data() + k * row, vals + (size_t)pick[k] * row, row * sizeof(double));
+        std::vector<CtPtr> part = c->cl.encrypt_batch(sub.data(), (int)pick.size(), n_per, level + drop[i], slots, pick.data(), per_lane);
         for (size_t k = 0; k < pick.size(); ++k) r[pick[k]] = part[k];
     }
     for (int i = 0; i < n_vec; ++i) {
@@ -251,6 +254,13 @@ int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32
     }
     rewind.keep = true;
     FHELIN_CATCH
+}
+int fhelin_encrypt_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32_t n_per, int32_t level, int32_t slots, fhelin_ct** outs) {
+    return encrypt_batch_rows(c, vals, n_vec, n_per, level, slots, outs, false);
+}
+int fhelin_encrypt_interleaved_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32_t n_per, int32_t level, int32_t slots,
+                                     fhelin_ct** outs) {
+    return encrypt_batch_rows(c, vals, n_vec, n_per, level, slots, outs, true);
 }
 int fhelin_client_ingest(fhelin_ctx* c, const double* emb, const int32_t* tokens, const double* table, int32_t vocab, int32_t S,
                          const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
@@ -534,7 +544,7 @@ int fhelin_raw_rescale(fhelin_ctx* c, const fhelin_ct* a, fhelin_ct** out) {
 int fhelin_raw_rotate(fhelin_ctx* c, const fhelin_ct* a, int32_t index, fhelin_ct** out) {
     NEED(c && a && out);
     FHELIN_TRY
-    const u64 g = c->ctx.galois_element(index);
+    const u64 g = c->ctx.rot_element(index);
     auto it = c->ev.rot_keys.find(g);
     if (it == c->ev.rot_keys.end() || !it->second) throw Error(FHELIN_ERR_KEY, "no rotation key for this index");
     *out = wrap(c, c->ev.raw_rotate(ct_in(c, a), g, *it->second));

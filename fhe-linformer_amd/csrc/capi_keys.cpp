@@ -36,6 +36,7 @@ struct EkFile {
     std::vector<uint64_t> moduli;
     std::vector<EkEntry> keys;
     uint64_t data_offset = 0;
+    int32_t stride = 1;       // interleave stride (header word 88: 0 = 1)
     bool compact = false;     // "FHELINEC": b halves only, a expanded from `seed`
     uint8_t seed[32] = {};
 };
@@ -94,8 +95,13 @@ EkFile read_header(const char* path) {
     for (int i = 0; i < 7; ++i) e.boot[i] = get<int32_t>(h, 52 + 4 * i);
     e.data_offset = get<uint64_t>(h, 80);
     const int log_n = e.prm[0], n_q = e.prm[1], n_p = e.prm[4];
-    if (log_n < 12 || log_n > 17 || n_q < 1 || n_q > 64 || n_p < 0 || n_p > 64 || e.prm[6] < 1 || get<uint64_t>(h, 88) != 0)
+    if (log_n < 12 || log_n > 17 || n_q < 1 || n_q > 64 || n_p < 0 || n_p > 64 || e.prm[6] < 1)
         throw Error(FHELIN_ERR_ARG, "evaluation-key set: parameters out of range");
+    // the interleave stride: 0 (a set written at stride 1), or a power of two >= 2 whose physical packing fits the ring
+    const uint64_t sw = get<uint64_t>(h, 88);
+    if (sw == 1 || (sw & (sw - 1)) || e.prm[7] < 1 || e.prm[7] > log_n - 1 || (sw << e.prm[7]) > (1ull << (log_n - 1)))
+        throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad interleave stride");
+    e.stride = sw ? (int32_t)sw : 1;
     const int32_t* b = e.boot;
     const bool boot_ok = b[2] == 0 ? (b[0] | b[1] | b[3] | b[4] | b[5] | b[6]) == 0
                                    : b[0] >= 1 && b[1] >= 1 && b[2] >= 4 && !(b[2] & (b[2] - 1)) && b[3] >= 1 && b[4] >= 0 && b[4] <= 8 &&
@@ -304,11 +310,12 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
     from_params(x.prm, prm);
     std::memcpy(h.data() + 16, prm, sizeof(prm));
     if (c->boot.ready()) {
-        const int32_t b[7] = {c->boot.budget_enc(), c->boot.budget_dec(), c->boot.slots(), c->boot.K, c->boot.R, c->boot.cheb_degree,
+        const int32_t b[7] = {c->boot.budget_enc(), c->boot.budget_dec(), c->boot.logical_slots(), c->boot.K, c->boot.R, c->boot.cheb_degree,
                               c->boot.correction};
         std::memcpy(h.data() + 52, b, sizeof(b));
     }
     put<uint64_t>(h.data(), 80, data_offset);
+    if (x.stride != 1) put<uint64_t>(h.data(), 88, (uint64_t)x.stride);   // a set written at stride 1 keeps 0 here
     if (compact) std::memcpy(h.data() + EK_HEADER, c->cl.key_seed(), 32);
     std::memcpy(h.data() + head, x.moduli.data(), 8 * nm);
     uint64_t at = data_offset;
@@ -388,6 +395,13 @@ int fhelin_evalkeys_info(const char* path, int32_t* boot7, int32_t* n_keys) {
     FHELIN_CATCH
 }
 
+int fhelin_evalkeys_interleave(const char* path, int32_t* stride) {
+    if (!path || !stride) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    *stride = read_header(path).stride;
+    FHELIN_CATCH
+}
+
 int fhelin_evalkeys_save(fhelin_ctx* c, const char* path) {
     if (!c || !path) return capi_fail(FHELIN_ERR_ARG, "null argument");
     FHELIN_TRY
@@ -429,6 +443,12 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
     from_params(x.prm, prm);
     if (std::memcmp(prm, e.prm, sizeof(prm)) != 0) throw Error(FHELIN_ERR_STATE, "evalkeys_load: the set was made for other parameters");
     check_moduli(e, x.moduli);
+    // the set's interleave stride: adopted, unless this context was told another one
+    if (e.stride != x.stride) {
+        if (x.stride_explicit) throw Error(FHELIN_ERR_STATE, "evalkeys_load: the set was written at interleave stride " + std::to_string(e.stride) +
+                                                                 ", the context was set to " + std::to_string(x.stride));
+        if (x.stride_locked) throw Error(FHELIN_ERR_STATE, "evalkeys_load: the set has another interleave stride than the plaintexts or ciphertexts the context already holds");
+    }
     const int digits = x.digits_at(x.L + 1);
     for (const auto& k : e.keys)
         if (k.kind != EK_PUBLIC && (int)k.digits != digits)
@@ -512,6 +532,7 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
     }
 
     // install
+    x.stride = e.stride;
     for (size_t k = 0; k < e.keys.size(); ++k) {
         if (sw[k]) sw[k]->seeded = e.compact;
         switch (e.keys[k].kind) {

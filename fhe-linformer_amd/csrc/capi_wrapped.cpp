@@ -47,6 +47,7 @@ const PtPtr& mask_of(fhelin_ctx* c) {
         auto p = std::make_shared<Plaintext>();
         p->ctx = &c->ctx;
         p->slots = 1 << c->ctx.prm.log_slots;
+        p->stride = c->ctx.stride;   // interleaved samples: the same columns in every lane
         p->level = 0;
         p->values.assign(p->slots, 0.0);
         for (int i = 0; i < p->slots; i += 128) p->values[i] = 1.0;
@@ -81,6 +82,8 @@ int fhelin_client_ingest_wrapped(fhelin_ctx* c, const double* emb, const int32_t
     NEED(c && (emb || (tokens && table)) && cls && pos && E_w && E_b && F_w && F_b && outs && n_out);
     FHELIN_TRY
     *n_out = 0;
+    if (c->ctx.stride > 1)
+        throw Error(FHELIN_ERR_STATE, "client_ingest_wrapped: wrapped inputs of interleaved samples are not supported (interleave stride > 1)");
     if (S < 1) throw Error(FHELIN_ERR_ARG, "ingest: need at least one token");
     if (level < 0 || level > c->ctx.L) throw Error(FHELIN_ERR_ARG, "ingest: level out of range");
     if (c->ctx.K < 1) throw Error(FHELIN_ERR_STATE, "wrapped inputs: a chain without special primes has no p_0 limb");
@@ -159,7 +162,7 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
         for (int step = 0; step < 3; ++step)
             for (int k : unwrap_offsets(step, r.t)) need.insert(k);
     for (int k : need)
-        if (!c->ev.rot_keys.count(x.galois_element(k)))
+        if (!c->ev.rot_keys.count(x.rot_element(k)))
             throw Error(FHELIN_ERR_KEY, "unwrap: no rotation key for index " + std::to_string(k) + " (EvalRotateKeyGen list)");
     const size_t N = x.N;
     const int R = (int)rows.size();
@@ -200,7 +203,7 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
                 const long double q = (long double)x.moduli[tau];
                 enc = mask->at(ell1, tau == ell ? q : x.sf_real[x.L + 1 - tau] * q / x.sf_real[x.L + 1 - ell]);
             }
-            tab[g.second[k]] = WrapMaskRow{w[r.w]->d, d + k * 2 * (size_t)ell1 * N, enc->d, x.automorph_map(x.galois_element(-r.t)), ell1,
+            tab[g.second[k]] = WrapMaskRow{w[r.w]->d, d + k * 2 * (size_t)ell1 * N, enc->d, x.automorph_map(x.rot_element(-r.t)), ell1,
                                            w[r.w]->ell};
         }
         max_ell = std::max(max_ell, ell1);

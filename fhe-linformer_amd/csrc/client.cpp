@@ -230,17 +230,21 @@ void encode_domain_check(double max_abs, long double scale) {
         throw Error(FHELIN_ERR_ARG, "encode: max|value| * scale may reach 2^125 (floor(log2 max|value|) + floor(log2 scale) > 123)");
 }
 
-void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale) {
+void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale,
+                         int stride, int lanes) {
     c.require_device();
     if (slots < 2 || (slots & (slots - 1)) || slots > c.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots must be a power of two in [2, N/2]");
+    if (stride < 1 || (stride & (stride - 1)) || (long)slots * stride > c.N / 2 || (lanes != 1 && lanes != stride))
+        throw Error(FHELIN_ERR_ARG, "encode: the interleaved packing (slots x stride) must be a power of two <= N/2");
     // ell = L + 1 + k: the encoding over the FULL key basis (limb ids 0..L+k: Q limbs, then the special limbs), for plaintexts
     // folded into rotation keys (Evaluator::folded_key); the leveled operations only ever ask for ell <= L + 1
     if (ell < 1 || ell > c.L + 1 + c.K) throw Error(FHELIN_ERR_ARG, "encode: level out of range");
     if (n_vec < 1) return;
     const size_t words = (size_t)2 * slots;                 // one complex vector, in doubles
-    Scratch<double> dv = c.scratch<double>(words * n_vec);
+    const int n_staged = n_vec * lanes;                     // interleaved samples: re / im [n_vec][lanes][n_per], uploads at logical size
+    Scratch<double> dv = c.scratch<double>(words * n_staged);
     std::vector<u64> host(words);
-    for (int b = 0; b < n_vec; ++b) {                       // through the pinned staging ring: no stream drain
+    for (int b = 0; b < n_staged; ++b) {                    // through the pinned staging ring: no stream drain
         double* h = reinterpret_cast<double*>(host.data());
         double mx = 0.0;                                    // the encoder's domain (encode_domain_check), on the values as they pass
         for (int i = 0; i < slots; ++i) {
@@ -254,6 +258,12 @@ void encode_batch_device(Context& c, u64* dst, const double* re, const double* i
         }
         encode_domain_check(mx, scale);
         c.upload_async(reinterpret_cast<u64*>(dv.get()) + words * b, host.data(), words);
+    }
+    if (stride > 1) {   // the staged vectors are logical: the physical ones are made on the device, in front of the FFT
+        Scratch<double> phys = c.scratch<double>(words * stride * n_vec);
+        launch_interleave_slots(phys, dv, slots, stride, lanes, n_vec, c.stream);
+        encode_complex_on_device(c, dst, phys, n_vec, slots * stride, ell, scale);
+        return;
     }
     encode_complex_on_device(c, dst, dv, n_vec, slots, ell, scale);
 }
@@ -273,8 +283,17 @@ void encode_complex_on_device(Context& c, u64* dst, double* dv, int n_vec, int s
 }
 
 std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>& values, const std::vector<double>& imag, int slots,
-                                           int ell, long double scale) {
+                                           int ell, long double scale, int stride) {
     c.require_device();
+    if (stride > 1 && (c.host_encode || slots < 2)) {   // the host encoder takes the physical vector: every value in all of its lanes
+        if ((long)slots * stride > c.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots x stride must be <= N/2");
+        std::vector<double> re((size_t)slots * stride, 0.0), im(imag.empty() ? 0 : (size_t)slots * stride, 0.0);
+        for (int i = 0; i < slots && i < (int)values.size(); ++i)
+            for (int k = 0; k < stride; ++k) re[(size_t)i * stride + k] = values[i];
+        for (int i = 0; i < slots && i < (int)imag.size(); ++i)
+            for (int k = 0; k < stride; ++k) im[(size_t)i * stride + k] = imag[i];
+        return encode_to_device(c, re, im, slots * stride, ell, scale, 1);
+    }
     if (slots < 1 || (slots & (slots - 1)) || slots > c.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots must be a power of two <= N/2");
     if (ell < 1 || ell > c.L + 1 + c.K) throw Error(FHELIN_ERR_ARG, "encode: level out of range");   // L + 1 + k: full key basis (see above)
     if (!c.host_encode && slots >= 2) {
@@ -286,7 +305,7 @@ std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>
         std::vector<double> re(slots, 0.0), im(slots, 0.0);
         for (int i = 0; i < slots && i < (int)values.size(); ++i) re[i] = values[i];
         for (int i = 0; i < slots && i < (int)imag.size(); ++i) im[i] = imag[i];
-        encode_batch_device(c, e->d, re.data(), imag.empty() ? nullptr : im.data(), 1, slots, slots, ell, scale);
+        encode_batch_device(c, e->d, re.data(), imag.empty() ? nullptr : im.data(), 1, slots, slots, ell, scale, stride, 1);
         return e;
     }
     std::vector<std::pair<double, double>> v(slots, {0.0, 0.0});
@@ -349,7 +368,7 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
             }
     if (!e) {
         encode_domain_check(max_abs, scale);   // before anything is launched: a refused encoding leaves the plaintext and its cache as they were
-        e = encode_to_device(*ctx, values, imag, slots, ell, scale);
+        e = encode_to_device(*ctx, values, imag, slots, ell, scale, stride);
         e->made_lane = ctx->pool.cur_lane;
         e->lanes_ordered = 1u << e->made_lane;
         if (ctx->n_lanes > 0) {
@@ -414,12 +433,14 @@ void Client::install_public_key(u64* d_pk, bool seeded) {
     pk = d_pk;
     pk_seeded_ = seeded;
     eval_only_ = true;
+    c_.stride_locked = true;
 }
 
 void Client::keygen() {
     if (eval_only_) throw Error(FHELIN_ERR_KEY, "keygen: an evaluation context holds no secret and cannot make one");
     c_.require_device();
     keygen_run_ = true;
+    c_.stride_locked = true;
     const size_t N = c_.N;
     const int L1 = c_.L + 1, nl = L1 + c_.K;
     // sparse ternary secret of Hamming weight h (reference SetSecretKeyDist(SPARSE_TERNARY), :8)
@@ -565,7 +586,7 @@ void Client::gen_relin_key() {
 }
 
 void Client::gen_rotation_key(int index) {
-    const u64 g = c_.galois_element(index);
+    const u64 g = c_.rot_element(index);   // a logical index (bootstrapping asks for its physical ones under a PhysicalScope)
     if (!s_all) {
         auto it = ev_.rot_keys.find(g);
         if (it != ev_.rot_keys.end() && it->second) return;
@@ -575,7 +596,7 @@ void Client::gen_rotation_key(int index) {
     if (ev_.rot_keys.count(g)) return;
     const int nl = c_.L + 1 + c_.K;
     // key switches from s to sigma_{g^-1}(s); applying sigma_g afterwards restores s (oracle orc_rotate)
-    const u64 ginv = c_.galois_element(-index);
+    const u64 ginv = c_.rot_element(-index);
     Scratch<u64> sp = c_.scratch<u64>((size_t)nl * c_.N);
     launch_automorph(c_.dt, sp, s_all, c_.automorph_map(ginv), nl, c_.stream);
     ev_.rot_keys[g] = make_switch_key(s_all, sp, 2, g);
@@ -597,10 +618,13 @@ void Client::gen_conj_key() {
 PtPtr Client::encode(const double* vals, int n, int level, int slots) {
     if (slots <= 0) slots = 1 << c_.prm.log_slots;
     if (slots & (slots - 1)) throw Error(FHELIN_ERR_ARG, "encode: slots must be a power of two");
+    if (c_.stride > 1 && (long)slots * c_.stride > c_.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots x interleave stride must be <= N/2");
     if (level < 0 || level > c_.L) throw Error(FHELIN_ERR_ARG, "encode: level out of range");
     auto p = std::make_shared<Plaintext>();
     p->ctx = &c_;
     p->slots = slots;
+    p->stride = c_.stride;
+    c_.stride_locked = true;
     p->level = level;
     p->values.assign(slots, 0.0);
     double mx = 0.0;
@@ -827,9 +851,11 @@ CtPtr Client::encrypt(const PtPtr& p, int drop) {
     return out[0];
 }
 
-std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots, const int* nonce_of) {
+std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots, const int* nonce_of, bool per_lane) {
     if (seeded_ ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     if (slots <= 0) slots = 1 << c_.prm.log_slots;
+    // interleaved samples: every vector replicated into all lanes, or (per_lane) vals [n_vec][stride][n_per], one vector per sample
+    const int lanes = per_lane ? c_.stride : 1;
     if (level < 0 || level > c_.L) throw Error(FHELIN_ERR_ARG, "encrypt: level out of range");
     if (n_vec < 0 || n_per < 0) throw Error(FHELIN_ERR_ARG, "encrypt_batch: negative count");
     const int ell = c_.L + 1 - level;
@@ -841,7 +867,7 @@ std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_pe
     for (int lo = 0; lo < n_vec; lo += CHUNK) {
         const int n = std::min(CHUNK, n_vec - lo);
         Scratch<u64> enc = c_.scratch<u64>((size_t)n * pn);
-        encode_batch_device(c_, enc, vals + (size_t)lo * n_per, nullptr, n, n_per, slots, ell, scale);
+        encode_batch_device(c_, enc, vals + (size_t)lo * lanes * n_per, nullptr, n, n_per, slots, ell, scale, c_.stride, lanes);
         u64 nonces[CHUNK];
         for (int k = 0; k < n; ++k) nonces[k] = nonce_of ? (u64)nonce_of[lo + k] : (u64)(lo + k);
         encrypt_encoded(enc, pn, n, ell, scale, slots, out, nonces);
@@ -859,6 +885,7 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
     if (wrap_ell && eval_only_) throw Error(FHELIN_ERR_KEY, "wrapped inputs are secret-key encryptions: an evaluation context holds no secret");
     if ((seeded_ || wrap_ell) ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     const int slots = 1 << c_.prm.log_slots, S1 = S + 1, n_vec = 64 + S1;
+    if (c_.stride > 1) throw Error(FHELIN_ERR_STATE, "ingest: a context with interleaved samples takes its samples through ingest_interleaved");
     if (slots != 16384) throw Error(FHELIN_ERR_ARG, "ingest: the expanded layout needs 16384 slots (128 x 128)");
     if (S < 1 || S1 > w_cols || (!emb && !(tokens && table && vocab > 0))) throw Error(FHELIN_ERR_ARG, "ingest: bad token count / inputs");
     if (level < 0 || level > c_.L || (int)drop.size() != n_vec) throw Error(FHELIN_ERR_ARG, "ingest: level out of range");
@@ -1005,6 +1032,107 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
     return out;   // ~Temps wipes and frees
 }
 
+// ingest_sample for `stride` samples of one length S that share a ciphertext (include/fhelin.h "Interleaved samples"): x_in and the
+// projections run per sample with ingest_sample's own kernels (so proj_out[i] is ingest_sample's, bit for bit), the expand step writes
+// sample i into lane i of the shared [n_vec][slots * stride] buffer, and the 64 + S + 1 vectors are encoded and encrypted once for the
+// group: the sampler draws of ONE ingest_sample.
+std::vector<CtPtr> Client::ingest_interleaved(const double* const* emb, const int* const* tokens, const double* table, int vocab, int S,
+                                              const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w,
+                                              const double* F_b, int w_cols, int level, const std::vector<int>& drop,
+                                              std::vector<std::vector<double>>* proj_out) {
+    if (seeded_ ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+    const int st = c_.stride, slots = 1 << c_.prm.log_slots, S1 = S + 1, n_vec = 64 + S1, phys = slots * st;
+    if (slots != 16384) throw Error(FHELIN_ERR_ARG, "ingest: the expanded layout needs 16384 slots (128 x 128)");
+    if ((long)slots * st > c_.N / 2) throw Error(FHELIN_ERR_ARG, "ingest: slots x interleave stride must be <= N/2");
+    if (S < 1 || S1 > w_cols || (!emb && !(tokens && table && vocab > 0))) throw Error(FHELIN_ERR_ARG, "ingest: bad token count / inputs");
+    if (level < 0 || level > c_.L || (int)drop.size() != n_vec) throw Error(FHELIN_ERR_ARG, "ingest: level out of range");
+    for (int i = 0; i < st; ++i) {
+        if (emb ? !emb[i] : !tokens[i]) throw Error(FHELIN_ERR_ARG, "ingest: a sample of the group has no input");
+        if (!emb)
+            for (int t = 0; t < S; ++t)
+                if (tokens[i][t] < 0 || tokens[i][t] >= vocab) throw Error(FHELIN_ERR_ARG, "ingest: token id outside the embedding table");
+    }
+    hipStream_t s = c_.stream;
+    // as ingest_sample: every temporary is the client's plaintext - wiped, then freed, on every path out
+    struct Temps {
+        Context& c;
+        hipStream_t s;
+        std::vector<std::pair<Scratch<char>, size_t>> blocks;
+        void* get(size_t bytes) {
+            blocks.emplace_back(c.scratch<char>(bytes), bytes);
+            return blocks.back().first.get();
+        }
+        ~Temps() {
+            for (auto& b : blocks) (void)hipMemsetAsync(b.first.get(), 0, b.second, s);
+        }
+    } tmp{c_, s, {}};
+    auto up = [&](const void* h, size_t bytes) {
+        void* d = tmp.get(bytes);
+        hip_check(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s), "ingest upload");
+        return d;
+    };
+    double* d_tab = emb ? nullptr : (double*)up(table, (size_t)vocab * 128 * 8);
+    double* d_cls = (double*)up(cls, 128 * 8);
+    double* d_pos = (double*)up(pos, (size_t)S * 128 * 8);
+    double* d_Ew = (double*)up(E_w, (size_t)32 * w_cols * 8);
+    double* d_Fw = (double*)up(F_w, (size_t)32 * w_cols * 8);
+    double* d_Eb = (double*)up(E_b, 32 * 8);
+    double* d_Fb = (double*)up(F_b, 32 * 8);
+    double* x_in = (double*)tmp.get((size_t)st * S1 * 128 * 8);     // [stride][S1][128]
+    double* proj = (double*)tmp.get((size_t)st * 64 * 128 * 8);     // [stride][64][128]
+    for (int i = 0; i < st; ++i) {
+        double* d_emb = emb ? (double*)up(emb[i], (size_t)S * 128 * 8) : nullptr;
+        int* d_tok = emb ? nullptr : (int*)up(tokens[i], (size_t)S * 4);
+        launch_ingest_xin(x_in + (size_t)i * S1 * 128, d_emb, d_tok, d_tab, d_cls, d_pos, S, s);
+        launch_ingest_project(proj + (size_t)i * 64 * 128, x_in + (size_t)i * S1 * 128, d_Ew, d_Eb, d_Fw, d_Fb, w_cols, S1, s);
+    }
+    double* dv = (double*)tmp.get((size_t)n_vec * phys * 16);
+    launch_ingest_expand_interleaved(dv, proj, x_in, S1, slots, st, s);
+    hip_check(hipGetLastError(), "ingest kernels");
+    if (proj_out) {   // per sample: x_in rows then the 64 projected rows, as ingest_sample reports them
+        proj_out->assign(st, std::vector<double>((size_t)(S1 + 64) * 128));
+        for (int i = 0; i < st; ++i) {
+            double* h = (*proj_out)[i].data();
+            hip_check(hipMemcpyAsync(h, x_in + (size_t)i * S1 * 128, (size_t)S1 * 128 * 8, hipMemcpyDeviceToHost, s), "ingest download");
+            hip_check(hipMemcpyAsync(h + (size_t)S1 * 128, proj + (size_t)i * 64 * 128, (size_t)64 * 128 * 8, hipMemcpyDeviceToHost, s),
+                      "ingest download");
+        }
+    }
+    hip_check(hipStreamSynchronize(s), "ingest sync");   // the host buffers are the caller's: done with them
+    begin_call();
+    std::vector<CtPtr> out(n_vec);
+    std::vector<char> seen(n_vec, 0);
+    for (int i = 0; i < n_vec; ++i) {   // runs of one level in chunks of 32, exactly as ingest_sample forms them
+        if (seen[i]) continue;
+        const int lvl = std::min(c_.L, level + std::max(0, drop[i]));
+        const int ell = c_.L + 1 - lvl;
+        const size_t pn = (size_t)ell * c_.N;
+        const long double scale = c_.sf_real[lvl];
+        int j = i;
+        while (j < n_vec) {
+            if (seen[j] || std::min(c_.L, level + std::max(0, drop[j])) != lvl) {
+                ++j;
+                continue;
+            }
+            int hi = j;
+            while (hi < n_vec && hi - j < 32 && !seen[hi] && std::min(c_.L, level + std::max(0, drop[hi])) == lvl) ++hi;
+            const int n = hi - j;
+            u64* enc = (u64*)tmp.get((size_t)n * pn * sizeof(u64));
+            encode_complex_on_device(c_, enc, dv + (size_t)j * phys * 2, n, phys, ell, scale);
+            std::vector<CtPtr> part;
+            u64 nonces[32];
+            for (int k = 0; k < n; ++k) nonces[k] = (u64)(j + k);
+            encrypt_encoded(enc, pn, n, ell, scale, slots, part, nonces);
+            for (int k = 0; k < n; ++k) {
+                out[j + k] = part[k];
+                seen[j + k] = 1;
+            }
+            j = hi;
+        }
+    }
+    return out;   // ~Temps wipes and frees
+}
+
 CtPtr Client::phase(const CtPtr& ct, int nl) {
     if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     if (nl < 1 || nl > ct->ell || ct->npoly < 2) throw Error(FHELIN_ERR_ARG, "phase: bad limb count / component count");
@@ -1023,11 +1151,34 @@ CtPtr Client::phase(const CtPtr& ct, int nl) {
 }
 
 std::vector<double> Client::decrypt(const CtPtr& cin, int slots, int flood_bits) {
+    if (c_.stride == 1) return decrypt_physical(cin, slots, flood_bits, 1);
+    const std::vector<double> v = decrypt_physical(cin, slots, flood_bits, c_.stride);   // lane 0 of the physical vector
+    std::vector<double> out(v.size() / c_.stride);
+    for (size_t k = 0; k < out.size(); ++k) out[k] = v[k * c_.stride];
+    return out;
+}
+
+std::vector<double> Client::decrypt_interleaved(const CtPtr& cin, int slots, int flood_bits) {
+    const int s = c_.stride;
+    const std::vector<double> v = decrypt_physical(cin, slots, flood_bits, s);
+    const size_t n = v.size() / s;
+    std::vector<double> out(v.size());
+    for (int i = 0; i < s; ++i)
+        for (size_t k = 0; k < n; ++k) out[(size_t)i * n + k] = v[k * s + i];
+    return out;
+}
+
+// slots: logical (<= 0: the ciphertext's); the decoded packing has slots * mult physical slots
+std::vector<double> Client::decrypt_physical(const CtPtr& cin, int slots, int flood_bits, int mult) {
     if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     if (flood_bits < 0 || flood_bits > 62) throw Error(FHELIN_ERR_ARG, "decrypt_flooded: flood_bits must lie in [0, 62]");
     CtPtr ct = cin;
     while (ct->deg > 1 && ct->ell > 2) ct = ev_.rescale(ct);
     if (slots <= 0) slots = ct->slots > 0 ? ct->slots : (1 << c_.prm.log_slots);
+    if (mult > 1) {
+        if ((slots & (slots - 1)) || (long)slots * mult > c_.N / 2) throw Error(FHELIN_ERR_ARG, "decrypt: slots x interleave stride must be a power of two <= N/2");
+        slots *= mult;
+    }
     const size_t N = c_.N;
     const int ell = ct->ell - (ct->wrapped() ? 1 : 0), nl = std::min(ell, 2);   // a wrapped input's extra limb is left out
     CtPtr ph = phase(ct, nl);
@@ -1086,6 +1237,7 @@ void Client::import_secret(const u64* in) {
     if (eval_only_) throw Error(FHELIN_ERR_KEY, "import_secret: an evaluation context holds no secret");
     c_.require_device();
     keygen_run_ = true;
+    c_.stride_locked = true;
     const size_t n = (size_t)(c_.L + 1 + c_.K) * c_.N;
     if (!s_all) s_all = c_.dalloc<u64>(n);
     hip_check(hipMemcpyAsync(s_all, in, n * 8, hipMemcpyHostToDevice, c_.stream), "import secret");

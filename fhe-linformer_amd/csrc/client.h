@@ -65,18 +65,28 @@ public:
     // rounding), sampling of (u, e0, e1) and the dyadic combination all on the GPU, in batched launches
     // nonce_of (seeded mode): null = a call of its own (a fresh seed, nonce = vector index); else the output index of every vector
     // within a call whose seed the caller drew with begin_call()
-    std::vector<CtPtr> encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots, const int* nonce_of = nullptr);
+    // per_lane (interleaved samples): vals [n_vec][stride][n_per], sample i of a vector in the physical slots = i mod stride; otherwise every
+    // vector is replicated into all lanes.  The interleaving happens in front of the encoder and draws nothing.
+    std::vector<CtPtr> encrypt_batch(const double* vals, int n_vec, int n_per, int level, int slots, const int* nonce_of = nullptr,
+                                     bool per_lane = false);
     std::vector<CtPtr> ingest_sample(const double* emb, const int* tokens, const double* table, int vocab, int S, const double* cls,
                                      const double* pos, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
                                      int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out = nullptr,
                                      const std::vector<int>* wrap_ell = nullptr);
+    // `stride` samples of one length S in one group of 64 + S + 1 ciphertexts (interleaved samples): emb / tokens [stride] pointers (emb
+    // null: token ids), everything else shared; proj_out [stride] as ingest_sample's
+    std::vector<CtPtr> ingest_interleaved(const double* const* emb, const int* const* tokens, const double* table, int vocab, int S,
+                                          const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w,
+                                          const double* F_b, int w_cols, int level, const std::vector<int>& drop,
+                                          std::vector<std::vector<double>>* proj_out = nullptr);
     // wrap_ell (include/fhelin.h "Wrapped inputs"): the limbs every input is wanted at; the result is then the WRAPPED ciphertexts (runs
     // of inputs of one target in read order, <= 128 each, over ell + 1 limbs), always seeded secret-key encryptions; drop is ignored
     // test hook: the sampler's raw output, n_poly polynomials of N centred coefficients (kind 0 Gaussian, 1 ternary)
     std::vector<long> debug_sample(int kind, int n_poly);
     // flood_bits > 0 (include/fhelin.h "Sanitised replies"): one uniform polynomial on [-2^flood_bits, 2^flood_bits) is added to the phase
     // on the device, after the inverse NTT and before the download; 0: the plain decryption, unchanged
-    std::vector<double> decrypt(const CtPtr& c, int slots, int flood_bits = 0);
+    std::vector<double> decrypt(const CtPtr& c, int slots, int flood_bits = 0);   // interleaved samples: lane 0
+    std::vector<double> decrypt_interleaved(const CtPtr& c, int slots, int flood_bits = 0);   // [stride][slots]: every lane
     // Reply sanitisation (include/fhelin.h "Sanitised replies"): degree-2 inputs rescaled, the optional 0/1 mask applied (product +
     // rescale), then out_b = first out_ell limbs of x_b + Enc_pk(0) + flood in ONE fused launch for the whole batch; the randomness
     // scratch is wiped.  Needs the public key only (works on an evaluation context).
@@ -116,6 +126,7 @@ private:
     // seeded mode: c0 = m - a s + e, c1 = a instead; nonces [n_vec] are the vectors' output indices within the current call
     void encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out,
                          const u64* nonces);
+    std::vector<double> decrypt_physical(const CtPtr& c, int slots, int flood_bits, int mult);
     u64 sample_calls_ = 0;
     bool eval_only_ = false, keygen_run_ = false;
     bool seeded_ = false;
@@ -129,12 +140,16 @@ private:
 void ckks_fft_special(std::vector<std::pair<double, double>>& v, bool inverse);
 // tables of the special FFT for `slots` slots: rot[j] = 5^j mod 4*slots, ksi[k] = exp(2 pi i k / (4*slots))
 void ckks_fft_tables(int slots, std::vector<u32>& rot, std::vector<std::pair<double, double>>& ksi);
+// stride > 1 (interleaved samples): slots logical values, each replicated into the stride lanes of the slots * stride physical slots
 std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>& values, const std::vector<double>& imag, int slots,
-                                           int ell, long double scale);
+                                           int ell, long double scale, int stride = 1);
 // the encoder's domain: throws FHELIN_ERR_ARG for a non-finite max_abs, or when the two exponents allow max_abs * scale >= 2^125
 void encode_domain_check(double max_abs, long double scale);
 // device encoder for n_vec vectors: re / im [n_vec][n_per] (im may be null) -> dst [n_vec][ell][N] NTT form
-void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale);
+// stride > 1: re / im [n_vec][lanes][n_per] with lanes = stride (lane i = sample i) or 1 (the vector replicated); the staged uploads stay at
+// logical size and launch_interleave_slots makes the physical vectors in front of the inverse FFT
+void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale,
+                         int stride = 1, int lanes = 1);
 void encode_complex_on_device(Context& c, u64* dst, double* dv, int n_vec, int slots, int ell, long double scale);
 
 }  // namespace fhelin

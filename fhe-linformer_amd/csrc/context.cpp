@@ -669,7 +669,7 @@ void Context::join_lanes() {
     }
 }
 
-u64 Context::galois_element(int r) const {
+u64 Context::galois_element(long r) const {
     const u64 M = 2ull * N;
     const u64 order = N / 2;  // order of 5 in Z_{2N}^*
     long rr = r % (long)order;

@@ -275,7 +275,21 @@ struct Context {
     int limb_id_q(int i) const { return i; }
     int limb_id_p(int j) const { return L + 1 + j; }
     int digits_at(int ell) const { return (ell + alpha - 1) / alpha; }
-    u64 galois_element(int rot_index) const;       // 5^r mod 2N (r may be negative)
+    u64 galois_element(long rot_index) const;      // 5^r mod 2N (r may be negative): a rotation of the PHYSICAL slot vector
+    // Interleaved samples (include/fhelin.h "Interleaved samples"): `stride` sample vectors of n logical slots share the n * stride
+    // physical slots of a packing, sample i in the slots = i mod stride.  Every rotation index the evaluator, the composites and the
+    // C ABI take is LOGICAL and goes through rot_element: a physical rotation by stride * r rotates every sample by r.  Bootstrapping
+    // works on the physical packing and is the one caller that bypasses the mapping (PhysicalScope).  stride == 1: nothing changes.
+    int stride = 1;
+    bool stride_explicit = false;   // set by fhelin_ctx_set_interleave (an evaluation-key set of another stride is then refused)
+    bool stride_locked = false;     // a key, plaintext, ciphertext or bootstrap set-up exists: the stride can no longer change
+    u64 rot_element(int rot_index) const { return stride == 1 ? galois_element(rot_index) : galois_element((long)stride * rot_index); }
+    struct PhysicalScope {          // host-side: indices and slot counts are physical until destruction
+        Context& c;
+        int was;
+        explicit PhysicalScope(Context& ctx) : c(ctx), was(ctx.stride) { c.stride = 1; }
+        ~PhysicalScope() { c.stride = was; }
+    };
     const u32* automorph_map(u64 galois);          // device map for the NTT-domain permutation
     const u32* automorph_inverse_of(const u32* map);  // the map of the inverse automorphism (built together with `map`)
     std::map<const u32*, const u32*> automorph_inverse;

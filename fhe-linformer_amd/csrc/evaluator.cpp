@@ -45,6 +45,7 @@ CtPtr Evaluator::new_ct(int npoly, int ell, int deg, long double scale, int slot
     ct->scale = scale;
     ct->slots = slots;
     ct->d = c_.dalloc<u64>(ct->words());
+    c_.stride_locked = true;
     return ct;
 }
 
@@ -62,6 +63,7 @@ std::vector<CtPtr> Evaluator::new_ct_batch(int count, int npoly, int ell, int de
     blk->ctx = &c_;
     const size_t words = (size_t)npoly * ell * c_.N;
     blk->d = c_.dalloc<u64>(words * count);
+    c_.stride_locked = true;
     std::vector<CtPtr> v;
     for (int i = 0; i < count; ++i) {
         auto ct = std::make_shared<Ciphertext>();
@@ -113,6 +115,7 @@ KeyPtr Evaluator::new_key() {
     k->ctx = &c_;
     k->digits = c_.digits_at(c_.L + 1);
     k->d = c_.dalloc<u64>(k->words());
+    c_.stride_locked = true;
     return k;
 }
 
@@ -333,7 +336,7 @@ bool Evaluator::have_rotation_keys(const std::vector<int>& indices, int slots) c
     const int ns = slots > 0 ? slots : (1 << c_.prm.log_slots);
     for (int r : indices) {
         if (r % ns == 0) return false;
-        if (!rot_keys.count(c_.galois_element(r))) return false;
+        if (!rot_keys.count(c_.rot_element(r))) return false;
     }
     return !indices.empty();
 }
@@ -358,7 +361,7 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
     std::vector<const EvalKey*> keys;
     std::vector<const u32*> maps;
     for (int r : indices) {
-        const u64 g = c_.galois_element(r);
+        const u64 g = c_.rot_element(r);
         keys.push_back(rot_keys.at(g).get());
         maps.push_back(c_.automorph_map(g));
     }
@@ -392,7 +395,7 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
             sh.map_rot[r] = maps[r];
             // the automorphism of g keeps every 512-coefficient tile in place iff g = 1 mod N/256 (index bits above the tile
             // correspond to the low bits of the odd exponent 2 bitrev(j) + 1, which multiplication by such a g leaves alone)
-            if (c_.galois_element(indices[r]) % (u64)(c_.N / 256) != 1) sh.lds_digits = 0;
+            if (c_.rot_element(indices[r]) % (u64)(c_.N / 256) != 1) sh.lds_digits = 0;
         }
         // accounting in units of the reference's rotations: R = 2^k - 1 merged terms stand for k tree steps
         int steps = 0;
@@ -432,7 +435,7 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
 Evaluator::FoldedKey Evaluator::folded_key(const PtPtr& p, int index, long double scale) {
     // the scale must match exactly: the scaling factors of neighbouring levels can lie within 1e-12 of each other (always for
     // ~60-bit scaling primes, whose spacing is 2N / 2^60), and a key folded at another level's scale is a different encoding
-    const u64 g = c_.galois_element(index);
+    const u64 g = c_.rot_element(index);
     auto kit = rot_keys.find(g);
     if (kit == rot_keys.end()) throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
     for (size_t i = 0; i < folded_keys.size(); ++i) {
@@ -498,7 +501,7 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
         }
     }
     std::vector<const u32*> maps;
-    for (int r : indices) maps.push_back(c_.automorph_map(c_.galois_element(r)));
+    for (int r : indices) maps.push_back(c_.automorph_map(c_.rot_element(r)));
     const size_t N = c_.N;
     const int K = c_.K, L1 = c_.L + 1;
     hipStream_t s = c_.stream;
@@ -538,7 +541,7 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
             sh.map_rot[r] = maps[r];
             h.v[r + 1] = hold.back().enc->d;
             h.map[r] = maps[r];
-            if (c_.galois_element(indices[r]) % (u64)(c_.N / 256) != 1) sh.lds_digits = 0;
+            if (c_.rot_element(indices[r]) % (u64)(c_.N / 256) != 1) sh.lds_digits = 0;
         }
         c_.stats.keyswitch += (u64)B * R;
         c_.stats.keyswitch_limbs += (u64)B * R * ell;
@@ -624,7 +627,7 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
             sh.rot_ext_stride = (size_t)lt.beta * nt * N;
             sh.rot_input_stride = ctw;
             for (int r = 0; r < R; ++r) {
-                const u64 g = c_.galois_element(ridx[first + r]);
+                const u64 g = c_.rot_element(ridx[first + r]);
                 sh.map_rot[r] = c_.automorph_map(g);
                 sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
             }
@@ -722,7 +725,7 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
             sh.rot_input_stride = ctw;
             sh.ext_batch_stride = (size_t)R * lt.beta * nt * N;
             for (int r = 0; r < R; ++r) {
-                const u64 g = c_.galois_element(ridx[r]);
+                const u64 g = c_.rot_element(ridx[r]);
                 sh.map_rot[r] = c_.automorph_map(g);
                 sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
             }
@@ -777,7 +780,7 @@ std::vector<CtPtr> Evaluator::rotate_many(const CtPtr& a, const std::vector<int>
         rows.shared_input = true;
         for (int b = 0; b < B; ++b) {
             const int index = indices[todo[first + b]];
-            const u64 g = c_.galois_element(index);
+            const u64 g = c_.rot_element(index);
             auto it = rot_keys.find(g);
             if (it == rot_keys.end())
                 throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
@@ -821,7 +824,7 @@ std::vector<CtPtr> Evaluator::rotate_each(const std::vector<CtPtr>& vin, const s
         KsRows rows;
         for (size_t i : idx) {
             chunk.push_back(vin[i]);
-            const u64 g = c_.galois_element(indices[i]);
+            const u64 g = c_.rot_element(indices[i]);
             auto it = rot_keys.find(g);
             if (it == rot_keys.end())
                 throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(indices[i]) + " (EvalRotateKeyGen list)");
@@ -928,7 +931,7 @@ std::vector<CtPtr> Evaluator::rotate_batch_impl(const std::vector<CtPtr>& vin, i
         for (size_t i = 0; i < vin.size(); ++i) out[i] = accumulate ? rotate_add(vin[i], index) : rotate(vin[i], index);
         return out;
     }
-    const u64 g = c_.galois_element(index);
+    const u64 g = c_.rot_element(index);
     auto it = rot_keys.find(g);
     if (it == rot_keys.end())
         throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
@@ -1003,7 +1006,7 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
     std::vector<const EvalKey*> keys;
     std::vector<const u32*> maps;
     for (size_t k : todo) {
-        const u64 g = c_.galois_element(indices[k]);
+        const u64 g = c_.rot_element(indices[k]);
         auto it = rot_keys.find(g);
         if (it == rot_keys.end())
             throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(indices[k]) + " (EvalRotateKeyGen list)");
@@ -1842,7 +1845,7 @@ std::vector<CtPtr> Evaluator::add_plain_batch(const std::vector<CtPtr>& v, const
 CtPtr Evaluator::rotate_add(const CtPtr& a, int index) {
     const int ns = a->slots > 0 ? a->slots : (1 << c_.prm.log_slots);
     if (index % ns == 0) return add(a, a);
-    const u64 g = c_.galois_element(index);
+    const u64 g = c_.rot_element(index);
     auto it = rot_keys.find(g);
     if (it == rot_keys.end())
         throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
@@ -2210,7 +2213,7 @@ CtPtr Evaluator::rotate(const CtPtr& a, int index) {
     const int ns = a->slots > 0 ? a->slots : (1 << c_.prm.log_slots);
     int r = index % ns;
     if (r == 0) return clone(a);
-    const u64 g = c_.galois_element(index);
+    const u64 g = c_.rot_element(index);
     auto it = rot_keys.find(g);
     if (it == rot_keys.end())
         throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");

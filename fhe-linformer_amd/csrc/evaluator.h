@@ -73,6 +73,9 @@ struct Plaintext {
     std::vector<double> values;  // real slot values, size == slots
     std::vector<double> imag;    // optional imaginary parts (bootstrapping's DFT diagonals); empty = real vector
     int slots = 0;
+    // interleaved samples (context.h Context::stride) as the plaintext was made: `values` stay logical and at() encodes each into all
+    // `stride` lanes of the slots * stride physical slots.  1 on bootstrapping's diagonals, which are written over the physical packing.
+    int stride = 1;
     int level = 0;               // level requested at encode time (reference encode(vec, level, slots))
     // max |values[i]|, kept by Client::encode (finite there): at() refuses an encoding whose max_abs * scale may reach 2^125
     // (encode_domain_check) without a second pass over the values (every coefficient is an average of slot values, so max_abs bounds

@@ -8,6 +8,9 @@ struct SamplerKey {
     u32 w[8];  // ChaCha20 key words of one sampling call (drawn from the client's generator)
 };
 
+// Interleaved samples (include/fhelin.h): out [n_vec][slots * stride] complex, physical slot stride * k + i = in [b][lanes == 1 ? 0 : i][k];
+// in [n_vec][lanes][slots] with lanes = stride (one staged vector per sample) or 1 (one vector replicated).  stride a power of two >= 2
+void launch_interleave_slots(double* out, const double* in, int slots, int stride, int lanes, int n_vec, hipStream_t s);
 // data [n_vec][slots] complex (re, im): all stages of the inverse special FFT (without the bit reversal and the 1/n scaling,
 // which launch_encode_round_reduce applies while reading).  rot [slots] = 5^j mod 4 slots, ksi [4 slots + 1] = e^{2 pi i k / (4 slots)}
 void launch_fft_special_inv(double* data, const u32* rot, const double* ksi, int slots, int n_vec, hipStream_t s);
@@ -51,6 +54,9 @@ void launch_ingest_xin(double* x_in, const double* emb, const int* tokens, const
 void launch_ingest_project(double* proj, const double* x_in, const double* E_w, const double* E_b, const double* F_w, const double* F_b,
                            int w_cols, int S1, hipStream_t s);
 void launch_ingest_expand(double* out, const double* proj, const double* x_in, int S1, int slots, hipStream_t s);
+// `stride` samples of one length S1 - 1: proj [stride][64][128], x_in [stride][S1][128]; out [(64 + S1)][slots * stride][2], sample i in
+// the physical slots = i mod stride
+void launch_ingest_expand_interleaved(double* out, const double* proj, const double* x_in, int S1, int slots, int stride, hipStream_t s);
 // the wrapped layout (include/fhelin.h "Wrapped inputs"): out [n_w][slots][2], slot j*128 + t of vector w = input pos[w][t] [j]
 // (inputs numbered as in launch_ingest_expand: E rows, F rows, tokens); pos [n_w][128] on the device, -1 = empty column
 void launch_ingest_wrap(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int slots, hipStream_t s);

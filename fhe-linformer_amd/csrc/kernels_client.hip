@@ -49,6 +49,19 @@ __device__ __forceinline__ Barrett load_barrett_uniform(const DeviceTables& t, i
     return b;
 }
 
+// ---- interleaved samples (include/fhelin.h "Interleaved samples"): the PHYSICAL slot vectors of a chunk from staged logical ones, in
+// front of the inverse special FFT.  out [n_vec][slots << log_stride]: physical slot p holds logical slot p >> log_stride of lane
+// p & (stride - 1); in [n_vec][lanes][slots] with lanes = stride (one vector per sample) or 1 (one vector replicated into every lane:
+// model plaintexts, masks).  grid ((slots << log_stride) / 256 rounded up, n_vec): consecutive threads write consecutive physical slots.
+__global__ __launch_bounds__(256) void interleave_slots_kernel(double2* __restrict__ out, const double2* __restrict__ in, int slots,
+                                                               int log_stride, int lanes) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int phys = slots << log_stride;
+    if (p >= phys) return;
+    const int lane = lanes == 1 ? 0 : p & ((1 << log_stride) - 1);
+    out[(size_t)blockIdx.y * phys + p] = in[((size_t)blockIdx.y * lanes + lane) * slots + (p >> log_stride)];
+}
+
 // ---- inverse special FFT, one stage.  data [n_vec][size] (re, im) pairs; grid (size/2 / 256, n_vec)
 #pragma clang fp contract(off)
 __global__ __launch_bounds__(256) void fft_special_inv_stage_kernel(double2* data, const u32* rot, const double2* ksi, int size, int len) {
@@ -314,6 +327,13 @@ __global__ __launch_bounds__(256) void rerandomize_combine_kernel(DeviceTables t
 
 }  // namespace
 
+void launch_interleave_slots(double* out, const double* in, int slots, int stride, int lanes, int n_vec, hipStream_t s) {
+    if (n_vec < 1) return;
+    int log_stride = 0;
+    while ((1 << log_stride) < stride) ++log_stride;
+    hipLaunchKernelGGL(interleave_slots_kernel, dim3((unsigned)((((size_t)slots << log_stride) + 255) / 256), (unsigned)n_vec), dim3(256), 0, s,
+                       reinterpret_cast<double2*>(out), reinterpret_cast<const double2*>(in), slots, log_stride, lanes);
+}
 void launch_fft_special_inv(double* data, const u32* rot, const double* ksi, int slots, int n_vec, hipStream_t s) {
     const dim3 g((unsigned)((slots / 2 + 255) / 256), (unsigned)n_vec);
     for (int len = slots; len >= 2; len >>= 1)
@@ -393,6 +413,23 @@ __global__ void ingest_expand_kernel(double* __restrict__ out, const double* __r
     o.y = 0.0;
     reinterpret_cast<double2*>(out)[(size_t)v * slots + slot] = o;
 }
+// The expanded layout of `stride` samples of one length interleaved: physical slot p of vector v holds slot p >> log_stride of sample
+// p & (stride - 1), whose rows are proj + sample * 64 * 128 and x_in + sample * S1 * 128.  Same sources and values as
+// ingest_expand_kernel per sample; consecutive threads write consecutive physical slots.
+__global__ void ingest_expand_interleaved_kernel(double* __restrict__ out, const double* __restrict__ proj, const double* __restrict__ x_in,
+                                                 int S1, int slots, int log_stride) {
+    const int v = blockIdx.y;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const int phys = slots << log_stride;
+    if (p >= phys) return;
+    const int sample = p & ((1 << log_stride) - 1), slot = p >> log_stride;
+    const double* src = v < 64 ? proj + ((size_t)sample * 64 + v) * 128 : x_in + ((size_t)sample * S1 + (v - 64)) * 128;
+    const int j = slot >> 7;
+    double2 o;
+    o.x = j < 128 ? src[j] : 0.0;
+    o.y = 0.0;
+    reinterpret_cast<double2*>(out)[(size_t)v * phys + p] = o;
+}
 // Wrapped layout (include/fhelin.h "Wrapped inputs"): vector w holds up to 128 inputs, slot j*128 + t = row pos[w][t] [j];
 // pos [n_w][128] (-1: no input, the slot column stays 0).  Same sources and order as ingest_expand_kernel.
 __global__ void ingest_wrap_kernel(double* __restrict__ out, const double* __restrict__ proj, const double* __restrict__ x_in,
@@ -409,6 +446,12 @@ __global__ void ingest_wrap_kernel(double* __restrict__ out, const double* __res
     reinterpret_cast<double2*>(out)[(size_t)w * slots + slot] = o;
 }
 }  // namespace
+void launch_ingest_expand_interleaved(double* out, const double* proj, const double* x_in, int S1, int slots, int stride, hipStream_t s) {
+    int log_stride = 0;
+    while ((1 << log_stride) < stride) ++log_stride;
+    hipLaunchKernelGGL(ingest_expand_interleaved_kernel, dim3((unsigned)((((size_t)slots << log_stride) + 255) / 256), 64 + S1), dim3(256), 0, s,
+                       out, proj, x_in, S1, slots, log_stride);
+}
 void launch_ingest_wrap(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int slots, hipStream_t s) {
     if (n_w < 1) return;
     hipLaunchKernelGGL(ingest_wrap_kernel, dim3((slots + 255) / 256, n_w), dim3(256), 0, s, out, proj, x_in, pos, slots);

@@ -83,6 +83,10 @@ class GpuController:
     def decrypt(self, c):
         return self.e.decrypt(c, SLOTS)
 
+    def decrypt_lanes(self, c):
+        """interleaved samples (Engine(interleave=s)): every sample's slots, [s][SLOTS]; decrypt gives sample 0"""
+        return self.e.decrypt_interleaved(c, SLOTS)
+
     def sanitize(self, c, keep_slots=None, flood_bits=0, out_ell=2):
         """the reply form of a result (include/fhelin.h "Sanitised replies"): only keep_slots survive (None: no mask), out_ell limbs,
         re-randomised, flooded with flood_bits bits; the server's last step, off unless the driver is asked for it"""
@@ -100,6 +104,8 @@ class GpuController:
             cts = self.e.unwrap_inputs(self.e.client_ingest_wrapped(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"],
                                                                     emb=x_emb))
             return {"inputs_E": cts[:32], "inputs_F": cts[32:64], "inputs": cts[64:]}
+        if self.e.interleave > 1:   # x_emb: the list of the samples that share every ciphertext (one length)
+            return self.e.client_ingest_interleaved(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], embs=x_emb)
         return self.e.client_ingest(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], emb=x_emb)
 
     def read_plain_input(self, m, level=0, scale=1.0):
@@ -339,6 +345,10 @@ class BatchedController:
     def decrypt(self, c):
         return [self.e.decrypt(h, SLOTS) for h in c]
 
+    def decrypt_lanes(self, c):
+        """interleaved samples: per batch entry every sample's slots, [B][s][SLOTS]"""
+        return [self.e.decrypt_interleaved(h, SLOTS) for h in c]
+
     def sanitize(self, c, keep_slots=None, flood_bits=0, out_ell=2):
         """GpuController.sanitize for every sample's result in ONE call: one mask, one fused launch for the batch"""
         return Batch(self.e.sanitize(list(c), _keep_mask(keep_slots), flood_bits, out_ell))
@@ -355,6 +365,9 @@ class BatchedController:
             n = len(cts) // len(ws)
             encs = [{"inputs_E": cts[x * n:x * n + 32], "inputs_F": cts[x * n + 32:x * n + 64], "inputs": cts[x * n + 64:(x + 1) * n]}
                     for x in range(len(ws))]
+            return batch_inputs(encs)
+        if self.e.interleave > 1:   # x_embs: per batch entry the list of the samples that share its ciphertexts
+            encs = [self.e.client_ingest_interleaved(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], embs=x) for x in x_embs]
             return batch_inputs(encs)
         encs = [self.e.client_ingest(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], emb=x) for x in x_embs]
         return batch_inputs(encs)
@@ -557,7 +570,9 @@ def ingest_sample(ctl, w, x_emb, wrapped=False):
     with `client_ingest` (the GPU engine: fhelin_client_ingest) does positional embedding, both Linformer projections, packing,
     encoding and encryption on the device; any other controller gets the NumPy statement of the same lines.
     wrapped: the sample travels as a few wrapped ciphertexts that the server unwraps (include/fhelin.h "Wrapped inputs"); a
-    BatchedController then takes x_emb as the list of its B samples' embeddings."""
+    BatchedController then takes x_emb as the list of its B samples' embeddings.
+    On an engine with interleaved samples (Engine(interleave=s)) x_emb is the list [x_0 .. x_{s-1}] of the samples that share every
+    ciphertext, all of one length."""
     if wrapped:
         if hasattr(ctl, "client_ingest_batch"):
             return ctl.client_ingest_batch(w, x_emb, wrapped=True)

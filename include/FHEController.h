@@ -279,6 +279,38 @@ public:
      * every key's uniform half the expansion of a public key-set seed; save_evaluation_keys(filename, true) then writes the compact
      * set (b halves and the seed, half the bytes), which load_evaluation_context reads as it reads the full one. */
     void set_seeded_keys(bool on) { seeded_keys = on; }
+    /* Interleaved samples (include/fhelin.h "Interleaved samples"): set_interleave(s) before generate_context / load_context /
+     * load_evaluation_context makes every ciphertext carry s samples (s = 2, 4, ... with num_slots * s <= N/2).  The circuit, its
+     * rotation indices and num_slots stay as they are (logical); encode / encrypt replicate their values into every sample (model
+     * plaintexts, masks), encrypt_interleaved packs one vector per sample and decrypt_tovector_lanes returns every sample's slots
+     * (decrypt_tovector: sample 0).  An evaluation-key set records the stride; load_evaluation_context adopts it. */
+    void set_interleave(int stride) { interleave_stride = stride; }
+    int interleave() const {
+        int32_t s = interleave_stride > 0 ? interleave_stride : 1;
+        if (context) fhelin_shim::check(fhelin_ctx_interleave(context, &s), "GetInterleave");
+        return s;
+    }
+    Ctxt encrypt_interleaved(const vector<vector<double>>& samples, int level = 0, int plaintext_num_slots = 0) {
+        if (plaintext_num_slots == 0) plaintext_num_slots = num_slots;
+        if ((int)samples.size() != interleave()) throw std::runtime_error("encrypt_interleaved: one vector per sample (the interleave stride)");
+        size_t n_per = 0;
+        for (const auto& v : samples) n_per = std::max(n_per, v.size());
+        vector<double> flat(samples.size() * n_per, 0.0);
+        for (size_t i = 0; i < samples.size(); i++) std::copy(samples[i].begin(), samples[i].end(), flat.begin() + i * n_per);
+        fhelin_ct* o = nullptr;
+        fhelin_shim::check(fhelin_encrypt_interleaved_batch(context, flat.data(), 1, (int32_t)n_per, level, plaintext_num_slots, &o),
+                           "Encrypt (interleaved)");
+        return wrap(o);
+    }
+    vector<vector<double>> decrypt_tovector_lanes(const Ctxt& c, int slots = 0) {
+        if (slots == 0) slots = num_slots;
+        const int s = interleave();
+        vector<double> flat((size_t)s * slots);
+        fhelin_shim::check(fhelin_decrypt_interleaved(context, c->h, 0, flat.data(), slots), "Decrypt (interleaved)");
+        vector<vector<double>> out;
+        for (int i = 0; i < s; i++) out.emplace_back(flat.begin() + (size_t)i * slots, flat.begin() + (size_t)(i + 1) * slots);
+        return out;
+    }
     void save_evaluation_keys(const string& filename, bool compact = false) {
         const string path = "../" + parameters_folder + "/" + filename;
         fhelin_shim::check(compact ? fhelin_evalkeys_save_compact(context, path.c_str()) : fhelin_evalkeys_save(context, path.c_str()),
@@ -290,6 +322,7 @@ public:
         level_budget = {3, 3};
         circuit_depth = 12 + 14;  // as load_context
         create(p);                // this context's own generator (public-key encryption randomness): OS entropy
+        apply_interleave();       // only when set_interleave was called: the set's own stride is adopted otherwise
         const string path = "../" + parameters_folder + "/" + filename;
         fhelin_shim::check(fhelin_evalkeys_load(context, path.c_str()), "Deserialize(evaluation keys)");
         if (verbose) cout << "Evaluation keys loaded from " << path << "; CtoS: " << level_budget[0] << ", StoC: " << level_budget[1] << endl;
@@ -868,8 +901,13 @@ private:
         return p;
     }
     bool seeded_keys = false;   // set_seeded_keys: applied between context creation and keygen
-    void apply_seeded_keys() {
+    int interleave_stride = 0;  // set_interleave: applied there too (0: not set, the context's default of 1 or a key set's own)
+    void apply_seeded_keys() {   // the settings a fresh context takes before its first key: seeded keys, interleaved samples
         if (seeded_keys) fhelin_shim::check(fhelin_ctx_set_seeded_keys(context, 1), "SetSeededKeys");
+        apply_interleave();
+    }
+    void apply_interleave() {
+        if (interleave_stride > 0) fhelin_shim::check(fhelin_ctx_set_interleave(context, interleave_stride), "SetInterleave");
     }
     void create(const fhelin_params& p) {
         fhelin_ctx_destroy(context);

@@ -73,6 +73,20 @@ public:
         for (auto& h : c->v) out.push_back(c_.decrypt_tovector(h, slots));
         return out;
     }
+    /* interleaved samples (FHEController::set_interleave on the single controller before its context exists): every batch entry carries
+     * `stride` samples.  encrypt_interleaved: per batch entry one vector per sample; decrypt_tovector_lanes: [entry][sample][slots] */
+    void set_interleave(int stride) { c_.set_interleave(stride); }
+    CtxtBatch encrypt_interleaved(const vector<vector<vector<double>>>& samples_per_entry, int level = 0, int plaintext_num_slots = 0) {
+        need_B(samples_per_entry.size());
+        vector<Ctxt> v;
+        for (const auto& s : samples_per_entry) v.push_back(c_.encrypt_interleaved(s, level, plaintext_num_slots));
+        return make(std::move(v));
+    }
+    vector<vector<vector<double>>> decrypt_tovector_lanes(const CtxtBatch& c, int slots = 0) {
+        vector<vector<vector<double>>> out;
+        for (auto& h : c->v) out.push_back(c_.decrypt_tovector_lanes(h, slots));
+        return out;
+    }
     vector<vector<double>> decrypt_tovector_flooded(const CtxtBatch& c, int slots, int flood_bits) {
         vector<vector<double>> out;
         for (auto& h : c->v) out.push_back(c_.decrypt_tovector_flooded(h, slots, flood_bits));

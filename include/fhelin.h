@@ -464,7 +464,8 @@ int fhelin_bootstrap_cheb(fhelin_ctx* c, double* out, int32_t cap, int32_t* n);
  *          52  i32[7]   bootstrapping as the client set it up: budget_enc, budget_dec, slots, K, R, cheb_degree, correction
  *                       (fhelin_bootstrap_setup / _config); all zero when it was not set up
  *          80  u64      data_offset: first payload byte = (end of the key table) rounded up to a multiple of 4096
- *          88  u64      0 (reserved)
+ *          88  u64      0, or the interleave stride when it is not 1 ("Interleaved samples": 2, 4, ...; log_slots and the
+ *                       bootstrap's slots above stay LOGICAL).  A set written at stride 1 keeps 0 here.
  *          96  u64[n_q + n_p]  the moduli, Q then P: a set whose moduli differ from the chain its parameters give is refused
  *   then the key table, n_keys entries of 40 bytes:
  *           0  u32 kind     0 public key, 1 relinearisation key, 2 rotation key, 3 conjugation key (at most one each of 0, 1, 3)
@@ -649,6 +650,51 @@ int fhelin_wrapped_info(const fhelin_ct* ct, int32_t* count, int32_t* total, int
  * limbs, with the mask encoded at Delta_tau q_tau / Delta_ell, and the output has the fresh scale Delta_tau, as fhelin_client_ingest's
  * planned output.  Works on an evaluation context that holds the circuit's rotation keys. */
 int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t n, fhelin_ct** outs);
+
+/* ---- interleaved samples: several samples in the idle slots of one ciphertext (slot stride) -------------------------------
+ * A ring of dimension N has N/2 slots; a circuit written for n = 2^log_slots slots leaves the rest idle when n < N/2.  With the
+ * SLOT STRIDE s (1, 2, 4, ... with n * s <= N/2) a ciphertext carries s sample vectors z_0 .. z_{s-1} of n LOGICAL slots in its
+ * n * s PHYSICAL slots, w[s k + i] = z_i[k].  A physical rotation by s r rotates every z_i by r with the cyclic wrap of n, and
+ * every slot-wise operation acts sample by sample, so one pass of an unchanged circuit serves s samples.  The client packs
+ * (merging separately encrypted samples on the server would be a full linear transform).
+ * With the stride set, every entry point keeps its signature and speaks LOGICAL slots and LOGICAL rotation indices:
+ *   - fhelin_rotate*, fhelin_hoisted_dot, fhelin_gen_rotation_keys, fhelin_key_export / _import (kind 1), fhelin_raw_rotate, every
+ *     fhelin_fc_* / fhelin_fcb_* composite and fhelin_unwrap_inputs use the Galois element 5^(s r) for the index r.  As at stride 1
+ *     the index is not reduced modulo n first: r and r + n rotate the samples alike and are different Galois elements (and keys)
+ *     unless n * s = N/2.
+ *   - fhelin_ct_info and fhelin_compact_info report logical slots.
+ *   - fhelin_encode, fhelin_encrypt and fhelin_encrypt_batch REPLICATE their values into all s samples (model weights, masks, the
+ *     mask of fhelin_sanitize, a driver's own server-side encryptions).
+ *   - fhelin_decrypt and fhelin_decrypt_flooded return sample 0.
+ *   - fhelin_bootstrap_setup takes logical slots and sets bootstrapping up for slots * s physical slots; the bootstrap's own
+ *     rotations, diagonals and keys belong to the physical packing, and fhelin_bootstrap_describe / _diag describe the PHYSICAL
+ *     stages (slot counts, giant and baby shifts of the slots * s packing).
+ *   - fhelin_client_ingest and fhelin_client_ingest_wrapped return FHELIN_ERR_STATE (wrapped interleaved ingest is not supported);
+ *     fhelin_client_ingest_interleaved below takes their place.
+ * Evaluation-key sets record the stride (header offset 88): fhelin_evalkeys_load into a fresh context adopts it; a context whose
+ * stride was set explicitly (fhelin_ctx_set_interleave) to another value gets FHELIN_ERR_STATE.  stride 1, the default, changes
+ * nothing: no launch, byte, residue or file. */
+/* set the stride: before the first key, plaintext, ciphertext or bootstrap set-up exists on the context (FHELIN_ERR_STATE later);
+ * FHELIN_ERR_ARG for a stride that is no power of two or with 2^log_slots * stride > N/2.  Works on a host-only context. */
+int fhelin_ctx_set_interleave(fhelin_ctx* c, int32_t stride);
+int fhelin_ctx_interleave(const fhelin_ctx* c, int32_t* stride);
+/* the stride an evaluation-key set (full or compact) was written at; host-only */
+int fhelin_evalkeys_interleave(const char* path, int32_t* stride);
+/* fhelin_encrypt_batch for n_vec ciphertexts of `stride` samples each: vals [n_vec][stride][n_per].  Domain checks, chunking,
+ * level-plan sources and sampler draws of fhelin_encrypt_batch with n_vec vectors; the interleaving happens in front of the encoder
+ * and draws nothing. */
+int fhelin_encrypt_interleaved_batch(fhelin_ctx* c, const double* vals, int32_t n_vec, int32_t n_per, int32_t level, int32_t slots,
+                                     fhelin_ct** outs);
+/* every sample of a ciphertext: out [stride][slots] (slots <= 0: the ciphertext's); flood_bits as fhelin_decrypt_flooded, 0 = plain */
+int fhelin_decrypt_interleaved(fhelin_ctx* c, const fhelin_ct* ct, int32_t flood_bits, double* out, int32_t slots);
+/* fhelin_client_ingest for n_samples == stride samples of one length S: emb / tokens are arrays of n_samples pointers (emb NULL:
+ * token ids into the shared table), cls / pos / E / F are shared.  outs: the 64 + S + 1 handles of the GROUP, sample i in the
+ * physical slots = i mod stride; proj_out (NULL, or n_samples pointers to [(S + 1 + 64)][128]): per sample exactly what
+ * fhelin_client_ingest reports for it.  The sampler draws are those of ONE fhelin_client_ingest. */
+int fhelin_client_ingest_interleaved(fhelin_ctx* c, int32_t n_samples, const double* const* emb, const int32_t* const* tokens,
+                                     const double* table, int32_t vocab, int32_t S, const double* cls, const double* pos,
+                                     const double* E_w, const double* E_b, const double* F_w, const double* F_b, int32_t w_cols,
+                                     int32_t level, fhelin_ct** outs, double* const* proj_out);
 
 /* ---- sanitised replies: mask, shrink, re-randomise and flood what a server hands back -------------------------------------
  * The ciphertext a circuit ends with is no fit reply as it stands: only some slots are the answer (the others hold intermediate
