@@ -491,7 +491,7 @@ std::vector<CtVec> Composite::relarge_containers_multi(const std::vector<CtVec>&
             CtVec ug(u.begin() + x * total + lo, u.begin() + x * total + lo + q);
             bool uniform = q >= RELARGE_FUSE_MIN;
             for (const CtPtr& c : ug)
-                uniform = uniform && c->npoly == 2 && c->ell == ug[0]->ell && c->deg == ug[0]->deg && fabsl(c->scale / ug[0]->scale - 1.0L) < 1e-9L;
+                uniform = uniform && same_shape(*ug[0], *c);
             if (uniform) {
                 fused[q].push_back({x, i});
                 fused_w[q].push_back(relarge_w(ug, mask_val));

@@ -305,9 +305,6 @@ struct Context {
     // FHELIN_HOST_ENCODE=1 / fhelin_ctx_set_host_encode: the special FFT of CKKS encoding on the host (the original path, kept
     // as the reference the device encoder is compared with bit for bit); default: on the GPU (kernels_client.hip)
     bool host_encode = false;
-    // FHELIN_FUSE_GATHER=0: the rotated c0 parts of a merged rotation sum go through their own gather-and-sum kernel instead of
-    // the ModDown epilogue (bit-identical; kept for A/B measurements)
-    bool fuse_gather = true;
     // Rotations gather at the inner product, so that every ModDown is the identity one that the row pass of NTT(conv) finishes
     // (needs fuse_finish).  A merged rotation sum: launch_ks_inner_multi adds P * sum_r sigma_r(c0) to the
     // accumulator's Q part while it has the maps in hand.  A plain rotation: launch_ks_inner reads digits, own limb and c0 through

@@ -34,6 +34,49 @@ EvalKey::~EvalKey() {
 
 static void launch_ok(const char* what) { hip_check(hipGetLastError(), what); }
 
+namespace {
+// consecutive runs of operands with the same (components, limbs): one output block and one launch per <= 32 of them
+template <class SameShape, class Emit>
+void for_runs(size_t n, SameShape same, Emit emit) {
+    size_t lo = 0;
+    while (lo < n) {
+        size_t hi = lo + 1;
+        while (hi < n && hi - lo < (size_t)EwItems::MAX_ITEMS && same(lo, hi)) ++hi;
+        emit(lo, hi);
+        lo = hi;
+    }
+}
+
+// groups of operands that share one launch set, wherever they stand in the list: the leader of a group is the first index not yet
+// done, its members the leader and the later indices not yet done for which same(leader, i) holds, in ascending order, until `limit`
+// are collected - each is compared with the leader, never with another member.  run(idx) returns one output per member, in the
+// order of idx; output k goes to out[idx[k]].
+template <class Same, class Run>
+std::vector<CtPtr> for_groups(size_t n, int limit, Same same, Run run) {
+    std::vector<CtPtr> out(n);
+    std::vector<char> done(n, 0);
+    for (size_t first = 0; first < n; ++first) {
+        if (done[first]) continue;
+        std::vector<size_t> idx{first};
+        for (size_t i = first + 1; i < n && (int)idx.size() < limit; ++i)
+            if (!done[i] && same(first, i)) idx.push_back(i);
+        std::vector<CtPtr> o = run(idx);
+        for (size_t k = 0; k < idx.size(); ++k) {
+            out[idx[k]] = std::move(o[k]);
+            done[idx[k]] = 1;
+        }
+    }
+    return out;
+}
+
+std::vector<CtPtr> pick(const std::vector<CtPtr>& v, const std::vector<size_t>& idx) {
+    std::vector<CtPtr> o;
+    o.reserve(idx.size());
+    for (size_t i : idx) o.push_back(v[i]);
+    return o;
+}
+}  // namespace
+
 CtPtr Evaluator::new_ct(int npoly, int ell, int deg, long double scale, int slots) {
     c_.require_device();
     if (ell < 1 || ell > c_.L + 1 || npoly < 1 || npoly > 3) throw Error(FHELIN_ERR_ARG, "new_ct: bad shape");
@@ -194,8 +237,11 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
 }
 
 // ------------------------------------------------------------------------------------------------ key-switch stages
-// Every hybrid key switch of this file is ModUp -> its own inner product(s) -> one of the two tails below.  A change to the
-// pipeline (what the conversions compute, where a transform's epilogue takes over a finish) belongs HERE, once.
+// Every hybrid key switch of this file is modup -> its own inner product(s) -> one of the tails moddown / moddown_rescale /
+// moddown_rescale_exact.  A merged rotation sum is set_rotations, modup and rotation_sum, which owns the inner product and what it hands
+// to moddown.  A change to the pipeline (what the conversions compute, where a transform's epilogue takes over a finish, how a merged
+// sum feeds its ModDown) belongs HERE, once.  Which operands share a launch set is decided before that, also once: for_groups (top of
+// this file) with same_shape (evaluator.h).
 
 // ModUp of up.batch polynomials of up.ell limbs, NTT form at src, up.c_stride words apart (group2 > 0: only within runs of group2
 // polynomials; the runs lie group2_stride apart): coefficient form, basis conversion of every digit to the other limbs of QP, forward NTT
@@ -332,8 +378,60 @@ void Evaluator::moddown_rescale_finish(const KsShape& sh, u64* out, const u64* a
     launch_moddown_rescale_finish(c_.dt, sh, out, accQ, conv, minv, c_.stream);
 }
 
+Evaluator::Rotations Evaluator::rotations(const int* indices, int n) {
+    Rotations rot;
+    rot.n = n;
+    for (int r = 0; r < n; ++r) {
+        const RotKey k = rotation_key(indices[r]);
+        rot.key[r] = k.key.get();
+        rot.map[r] = k.map;
+        // the automorphism of g keeps every 512-coefficient tile in place iff g = 1 mod N/256 (index bits above the tile
+        // correspond to the low bits of the odd exponent 2 bitrev(j) + 1, which multiplication by such a g leaves alone)
+        if (k.g % (u64)(c_.N / 256) != 1) rot.tiles_in_place = false;
+    }
+    return rot;
+}
+
+// The rotations of a merged key switch (launch_ks_inner_multi) into its shape: sh.n_rot, sh.map_rot and sh.evk_rot - keys[r] where given
+// (keys in the layout of EvalKey::d_perm: folded keys), else the rotation key's permuted copy.  shared_digits: the rotations act on ONE
+// input, whose digit tiles are staged in LDS when every automorphism keeps them in place (sh.lds_digits).
+void Evaluator::set_rotations(KsShape& sh, const Rotations& rot, bool shared_digits, const u64* const* keys) {
+    sh.n_rot = rot.n;
+    for (int r = 0; r < rot.n; ++r) {
+        sh.map_rot[r] = rot.map[r];
+        sh.evk_rot[r] = keys ? keys[r] : permuted(*rot.key[r], rot.map[r]);
+    }
+    if (shared_digits) sh.lds_digits = c_.lds_digits && rot.tiles_in_place ? 1 : 0;
+}
+
+// A merged rotation sum from its digits on: out = ModDown(sum_r sigma_r(<digits_r, key_r>)) + sum_r sigma_r(c0_r) (+ post).  sh: the
+// prepared shape (strides, set_rotations, rot_ext_stride / rot_input_stride / ext_batch_stride as the caller's layout needs them); ext:
+// the digits from modup; c1 / c0: the bases of the two components, c0 of batch row b at c0 + b * c0_stride.  All rotated inner products
+// are gathered and accumulated in the extended basis, and the inner product gathers the c0 parts too: into accQ times P where the one
+// ModDown finishes in the row pass, else for moddown_finish to gather (sh.gsrc).
+void Evaluator::rotation_sum(KsShape& sh, const u64* ext, const u64* c1, const u64* c0, size_t c0_stride, u64* out, const u64* post) {
+    const size_t N = c_.N;
+    const bool rp = sum_in_row_pass();
+    sh.gsrc = c0;
+    sh.gsrc_stride = c0_stride;
+    if (rp) sh.gsrc_pmod = c_.d_pmod;
+    Scratch<u64> accQ = c_.scratch<u64>((size_t)sh.batch * 2 * sh.ell * N);
+    Scratch<u64> accP = c_.scratch<u64>((size_t)sh.batch * 2 * sh.k * N);
+    launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, c1, c_.stream);
+    moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, rp);
+}
+
+int Evaluator::slot_count(int slots) const { return slots > 0 ? slots : (1 << c_.prm.log_slots); }
+
+Evaluator::RotKey Evaluator::rotation_key(int index) {
+    const u64 g = c_.rot_element(index);
+    auto it = rot_keys.find(g);
+    if (it == rot_keys.end()) throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
+    return RotKey{it->second, c_.automorph_map(g), g};
+}
+
 bool Evaluator::have_rotation_keys(const std::vector<int>& indices, int slots) const {
-    const int ns = slots > 0 ? slots : (1 << c_.prm.log_slots);
+    const int ns = slot_count(slots);
     for (int r : indices) {
         if (r % ns == 0) return false;
         if (!rot_keys.count(c_.rot_element(r))) return false;
@@ -358,45 +456,18 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
     if (R < 1 || R > KsShape::MAX_ROT) throw Error(FHELIN_ERR_ARG, "rotate_sum_batch: 1..7 rotations");
     if (!have_rotation_keys(indices, vin[0]->slots)) throw Error(FHELIN_ERR_KEY, "rotate_sum_batch: missing rotation key");
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "hybrid key switching needs at least one special prime");
-    std::vector<const EvalKey*> keys;
-    std::vector<const u32*> maps;
-    for (int r : indices) {
-        const u64 g = c_.rot_element(r);
-        keys.push_back(rot_keys.at(g).get());
-        maps.push_back(c_.automorph_map(g));
-    }
+    const Rotations rot = rotations(indices.data(), R);
     const size_t N = c_.N;
-    const int K = c_.K, L1 = c_.L + 1;
-    hipStream_t s = c_.stream;
-    std::vector<CtPtr> out(vin.size());
-    std::vector<char> done(vin.size(), 0);
-    for (size_t first = 0; first < vin.size(); ++first) {
-        if (done[first]) continue;
-        if (vin[first]->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
-        std::vector<size_t> idx;
-        for (size_t i = first; i < vin.size() && (int)idx.size() < batch_limit; ++i) {
-            const CtPtr &a = vin[first], &b = vin[i];
-            if (!done[i] && b->npoly == 2 && b->ell == a->ell && b->deg == a->deg && fabsl(b->scale / a->scale - 1.0L) < 1e-9L)
-                idx.push_back(i);
-        }
-        std::vector<CtPtr> chunk;
-        for (size_t i : idx) chunk.push_back(vin[i]);
-        chunk = make_contiguous(chunk, 0);
+    return for_groups(vin.size(), batch_limit, [&](size_t f, size_t i) { return same_shape(*vin[f], *vin[i]); },
+                      [&](const std::vector<size_t>& idx) {
+        if (vin[idx[0]]->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
+        const std::vector<CtPtr> chunk = make_contiguous(pick(vin, idx), 0);
         const int B = (int)chunk.size(), ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
-        const LevelTables& lt = c_.lvl[ell];
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
         const u64* base = chunk[0]->d;
-        KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, ctw, ctw, pn, ctw};
-        sh.n_rot = R;
-        sh.lds_digits = c_.lds_digits ? 1 : 0;
-        for (int r = 0; r < R; ++r) {
-            sh.evk_rot[r] = permuted(*keys[r], maps[r]);
-            sh.map_rot[r] = maps[r];
-            // the automorphism of g keeps every 512-coefficient tile in place iff g = 1 mod N/256 (index bits above the tile
-            // correspond to the low bits of the odd exponent 2 bitrev(j) + 1, which multiplication by such a g leaves alone)
-            if (c_.rot_element(indices[r]) % (u64)(c_.N / 256) != 1) sh.lds_digits = 0;
-        }
+        KsShape sh{ell, c_.K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, ctw, ctw, pn, ctw};
+        set_rotations(sh, rot, true);
         // accounting in units of the reference's rotations: R = 2^k - 1 merged terms stand for k tree steps
         int steps = 0;
         while ((1 << steps) < R + 1) ++steps;
@@ -404,43 +475,21 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
         c_.stats.keyswitch_limbs += (u64)B * steps * ell;
         {
             Scratch<u64> ext = modup(sh, base + pn, false);   // of c1, once for all rotations
-            // all rotated inner products, gathered and accumulated in the extended basis; the c0 parts likewise
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
-            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-            const bool rp = sum_in_row_pass();
-            if (c_.fuse_gather) {
-                sh.gsrc = base;      // the rotated c0 parts: gathered by the inner product (times P, into accQ) or by moddown_finish
-                sh.gsrc_stride = ctw;
-                if (rp) sh.gsrc_pmod = c_.d_pmod;
-            }
-            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-            Scratch<u64> c0sum;
-            if (!c_.fuse_gather) {
-                c0sum = c_.scratch<u64>((size_t)B * ell * N);
-                launch_gather_sum(c_.dt, sh, c0sum, base, ctw, s);
-            }
-            // one ModDown; its finish adds the unrotated input (and the gathered c0 parts, where the accumulator does not hold them)
-            moddown(sh, accQ, accP, o[0]->d, c0sum, nullptr, nullptr, base, rp);
+            rotation_sum(sh, ext, base + pn, base, ctw, o[0]->d, base);   // one ModDown; its finish adds the unrotated input
             launch_ok("rotate_sum_batch");
         }
-        for (int b = 0; b < B; ++b) {
-            o[b]->scale = vin[idx[b]]->scale;
-            out[idx[b]] = o[b];
-            done[idx[b]] = 1;
-        }
-    }
-    return out;
+        for (int b = 0; b < B; ++b) o[b]->scale = vin[idx[b]]->scale;
+        return o;
+    });
 }
 
 Evaluator::FoldedKey Evaluator::folded_key(const PtPtr& p, int index, long double scale) {
     // the scale must match exactly: the scaling factors of neighbouring levels can lie within 1e-12 of each other (always for
     // ~60-bit scaling primes, whose spacing is 2N / 2^60), and a key folded at another level's scale is a different encoding
-    const u64 g = c_.rot_element(index);
-    auto kit = rot_keys.find(g);
-    if (kit == rot_keys.end()) throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
+    const RotKey rk = rotation_key(index);
     for (size_t i = 0; i < folded_keys.size(); ++i) {
         const FoldedKey& f = folded_keys[i];
-        if (f.pt.get() == p.get() && f.key.get() == kit->second.get() && f.index == index && f.scale == scale) {
+        if (f.pt.get() == p.get() && f.key.get() == rk.key.get() && f.index == index && f.scale == scale) {
             FoldedKey hit = f;
             if (i + 1 != folded_keys.size()) {   // least recently used goes first when the cache is full
                 folded_keys.erase(folded_keys.begin() + i);
@@ -451,7 +500,7 @@ Evaluator::FoldedKey Evaluator::folded_key(const PtPtr& p, int index, long doubl
     }
     FoldedKey f;
     f.pt = p;
-    f.key = kit->second;
+    f.key = rk.key;
     f.index = index;
     f.scale = scale;
     const int nl = c_.L + 1 + c_.K;
@@ -459,7 +508,7 @@ Evaluator::FoldedKey Evaluator::folded_key(const PtPtr& p, int index, long doubl
     f.d = std::make_shared<DevBlock>();
     f.d->ctx = &c_;
     f.d->d = c_.dalloc<u64>(f.key->words());
-    launch_fold_key(c_.dt, f.d->d, f.key->d, c_.automorph_map(g), f.enc->d, f.key->digits * 2 * nl, c_.stream);
+    launch_fold_key(c_.dt, f.d->d, f.key->d, rk.map, f.enc->d, f.key->digits * 2 * nl, c_.stream);
     launch_ok("fold_key");
     // built once, read from every stream afterwards: finish it before anyone else can see the pointer
     hip_check(hipStreamSynchronize(c_.stream), "fold_key sync");
@@ -481,13 +530,13 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
         throw Error(FHELIN_ERR_ARG, "hoisted_dot_rows: 1..7 rotations, one plaintext per rotation + the unrotated term's");
     if (!have_rotation_keys(indices, xin[0]->slots)) throw Error(FHELIN_ERR_KEY, "hoisted_dot_rows: missing rotation key");
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "hybrid key switching needs at least one special prime");
-    const int ns = xin[0]->slots > 0 ? xin[0]->slots : (1 << c_.prm.log_slots);
+    const int ns = slot_count(xin[0]);
     for (int r : indices)
         if (r % ns == 0) throw Error(FHELIN_ERR_ARG, "hoisted_dot_rows: a rotation by 0 is the unrotated term (pts[0])");
     if (rescale_out && c_.K + 1 > 16)   // the merged ModDown + rescale takes at most 16 sources: ModDown, then a separate rescale
         return rescale_batch(hoisted_dot_rows(xin, pts, indices, false));
     std::vector<CtPtr> x = xin;
-    {   // degree-2 operands are rescaled first (as before any product with a plaintext)
+    {   // degree-2 operands are rescaled first (as before any product with a plaintext); a ciphertext that occurs twice is rescaled twice
         std::vector<CtPtr> need;
         std::vector<size_t> pos;
         for (size_t i = 0; i < x.size(); ++i)
@@ -500,49 +549,36 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
             for (size_t k = 0; k < pos.size(); ++k) x[pos[k]] = r[k];
         }
     }
-    std::vector<const u32*> maps;
-    for (int r : indices) maps.push_back(c_.automorph_map(c_.rot_element(r)));
+    const Rotations rot = rotations(indices.data(), R);
     const size_t N = c_.N;
-    const int K = c_.K, L1 = c_.L + 1;
+    const int K = c_.K;
     hipStream_t s = c_.stream;
-    std::vector<CtPtr> out(x.size());
-    std::vector<char> done(x.size(), 0);
-    for (size_t first = 0; first < x.size(); ++first) {
-        if (done[first]) continue;
-        if (x[first]->npoly != 2) throw Error(FHELIN_ERR_STATE, "hoisted_dot_rows: ciphertext must have 2 components");
-        std::vector<size_t> idx;
-        for (size_t i = first; i < x.size() && (int)idx.size() < batch_limit; ++i) {
-            const CtPtr &a = x[first], &b = x[i];
-            if (!done[i] && b->npoly == 2 && b->ell == a->ell && b->deg == a->deg && fabsl(b->scale / a->scale - 1.0L) < 1e-9L) idx.push_back(i);
-        }
-        std::vector<CtPtr> chunk;
-        for (size_t i : idx) chunk.push_back(x[i]);
-        chunk = make_contiguous(chunk, 0);
+    return for_groups(x.size(), batch_limit, [&](size_t f, size_t i) { return same_shape(*x[f], *x[i]); },
+                      [&](const std::vector<size_t>& idx) {
+        if (x[idx[0]]->npoly != 2) throw Error(FHELIN_ERR_STATE, "hoisted_dot_rows: ciphertext must have 2 components");
+        const std::vector<CtPtr> chunk = make_contiguous(pick(x, idx), 0);
         const int B = (int)chunk.size(), ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
-        const LevelTables& lt = c_.lvl[ell];
         const long double sf = c_.sf_real[chunk[0]->level()];
         const bool merged = rescale_out && ell >= 2 && K + 1 <= 16;
         if (rescale_out && !merged) throw Error(FHELIN_ERR_STATE, "hoisted_dot_rows: no limb left to drop");
         const int oell = merged ? ell - 1 : ell;
         std::vector<CtPtr> o = new_ct_batch(B, 2, oell, merged ? chunk[0]->deg : chunk[0]->deg + 1, chunk[0]->scale * sf, chunk[0]->slots);
         const u64* base = chunk[0]->d;
-        KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, ctw, (size_t)2 * oell * N, pn, ctw};
-        sh.n_rot = R;
-        sh.lds_digits = c_.lds_digits ? 1 : 0;
+        KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, ctw, (size_t)2 * oell * N, pn, ctw};
         HoistAdd h;
         h.n_rot = R;
         std::vector<FoldedKey> hold;            // the folded keys and encodings of this launch set stay alive across a cache eviction
         const std::shared_ptr<Encoding> e0 = pts[0]->at(ell, sf);
         h.v[0] = e0->d;
+        const u64* folded[KsShape::MAX_ROT];
         for (int r = 0; r < R; ++r) {
             hold.push_back(folded_key(pts[r + 1], indices[r], sf));
-            sh.evk_rot[r] = hold.back().d->d;
-            sh.map_rot[r] = maps[r];
+            folded[r] = hold.back().d->d;
             h.v[r + 1] = hold.back().enc->d;
-            h.map[r] = maps[r];
-            if (c_.rot_element(indices[r]) % (u64)(c_.N / 256) != 1) sh.lds_digits = 0;
         }
+        set_rotations(sh, rot, true, folded);
+        for (int r = 0; r < R; ++r) h.map[r] = sh.map_rot[r];
         c_.stats.keyswitch += (u64)B * R;
         c_.stats.keyswitch_limbs += (u64)B * R * ell;
         c_.stats.ct_pt_mult += (u64)B * (R + 1);
@@ -574,16 +610,14 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
         for (int b = 0; b < B; ++b) {
             o[b]->scale = x[idx[b]]->scale * sf;
             if (merged) o[b]->scale = o[b]->scale / (long double)c_.chain.q[ell - 1];
-            out[idx[b]] = o[b];
-            done[idx[b]] = 1;
         }
-    }
-    return out;
+        return o;
+    });
 }
 
 CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vector<int>& indices) {
     if (vin.empty() || vin.size() != indices.size()) throw Error(FHELIN_ERR_ARG, "rotate_each_sum: one index per ciphertext");
-    const int ns = vin[0]->slots > 0 ? vin[0]->slots : (1 << c_.prm.log_slots);
+    const int ns = slot_count(vin[0]);
     // unrotated terms are plain additions; the rest go through the merged key switch in groups of <= 7
     std::vector<CtPtr> rot;
     std::vector<int> ridx;
@@ -599,9 +633,7 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
         const int R = (int)std::min(rot.size() - first, (size_t)KsShape::MAX_ROT);
         std::vector<CtPtr> chunk(rot.begin() + first, rot.begin() + first + R);
         bool uniform = have_rotation_keys(std::vector<int>(ridx.begin() + first, ridx.begin() + first + R), ns) && c_.K >= 1;
-        for (const CtPtr& c : chunk)
-            uniform = uniform && c->npoly == 2 && c->ell == chunk[0]->ell && c->deg == chunk[0]->deg &&
-                      fabsl(c->scale / chunk[0]->scale - 1.0L) < 1e-9L;
+        for (const CtPtr& c : chunk) uniform = uniform && same_shape(*chunk[0], *c);
         if (!uniform || R < 2) {  // fall back to separate rotations
             for (int r = 0; r < R; ++r) {
                 CtPtr t = rotate(chunk[r], ridx[first + r]);
@@ -614,8 +646,6 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
         const int K = c_.K, L1 = c_.L + 1, ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
         const LevelTables& lt = c_.lvl[ell];
-        const int nt = ell + K;
-        hipStream_t s = c_.stream;
         const u64* base = chunk[0]->d;
         CtPtr o = new_ct(2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
         {
@@ -623,31 +653,12 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
             Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, R, ctw, 0, 0, 0}, base + pn, false);
             // one accumulator for all R rotated inner products, one ModDown
             KsShape sh{ell, K, c_.alpha, lt.beta, L1, 1, 0, ctw, pn, 0};
-            sh.n_rot = R;
-            sh.rot_ext_stride = (size_t)lt.beta * nt * N;
+            sh.rot_ext_stride = (size_t)lt.beta * (ell + K) * N;
             sh.rot_input_stride = ctw;
-            for (int r = 0; r < R; ++r) {
-                const u64 g = c_.rot_element(ridx[first + r]);
-                sh.map_rot[r] = c_.automorph_map(g);
-                sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
-            }
+            set_rotations(sh, rotations(ridx.data() + first, R), false);
             c_.stats.keyswitch += (u64)R;
             c_.stats.keyswitch_limbs += (u64)R * ell;
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)2 * ell * N);
-            Scratch<u64> accP = c_.scratch<u64>((size_t)2 * K * N);
-            const bool rp = sum_in_row_pass();
-            if (c_.fuse_gather) {
-                sh.gsrc = base;
-                sh.gsrc_stride = 0;
-                if (rp) sh.gsrc_pmod = c_.d_pmod;
-            }
-            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-            Scratch<u64> c0sum;
-            if (!c_.fuse_gather) {
-                c0sum = c_.scratch<u64>((size_t)ell * N);
-                launch_gather_sum(c_.dt, sh, c0sum, base, 0, s);
-            }
-            moddown(sh, accQ, accP, o->d, c0sum, nullptr, nullptr, nullptr, rp);
+            rotation_sum(sh, ext, base + pn, base, 0, o->d, nullptr);
             launch_ok("rotate_each_sum");
         }
         acc = acc ? add(acc, o) : o;
@@ -657,7 +668,7 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
 
 std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector<CtPtr>>& rows, const std::vector<int>& indices) {
     if (rows.empty()) return {};
-    const int ns = rows[0][0]->slots > 0 ? rows[0][0]->slots : (1 << c_.prm.log_slots);
+    const int ns = slot_count(rows[0][0]);
     std::vector<int> rot_pos, plain_pos, ridx;
     for (size_t r = 0; r < indices.size(); ++r) {
         if (indices[r] % ns == 0) plain_pos.push_back((int)r);
@@ -671,8 +682,7 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
     const CtPtr& f = rows[0][0];
     for (const auto& row : rows) {
         uniform = uniform && row.size() == indices.size();
-        for (const CtPtr& c : row)
-            uniform = uniform && c->npoly == 2 && c->ell == f->ell && c->deg == f->deg && fabsl(c->scale / f->scale - 1.0L) < 1e-9L;
+        for (const CtPtr& c : row) uniform = uniform && same_shape(*f, *c);
     }
     std::vector<CtPtr> out(rows.size());
     if (!uniform) {
@@ -684,7 +694,7 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
     const size_t pn = (size_t)ell * N, ctw = 2 * pn;
     const LevelTables& lt = c_.lvl[ell];
     const int nt = ell + K;
-    hipStream_t s = c_.stream;
+    const Rotations rot = rotations(ridx.data(), R);
     const size_t chunk_rows = (size_t)std::max(1, batch_limit / 2);   // rows x R polynomials go through one ModUp
     for (size_t lo = 0; lo < rows.size(); lo += chunk_rows) {
         const size_t hi = std::min(rows.size(), lo + chunk_rows);
@@ -720,25 +730,13 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
             Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B * R, ctw, 0, 0, 0}, base + pn, false, spaced ? R : 0,
                                      spaced ? row_stride : 0);
             KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, row_stride, ctw, pn, 0};
-            sh.n_rot = R;
             sh.rot_ext_stride = (size_t)lt.beta * nt * N;
             sh.rot_input_stride = ctw;
             sh.ext_batch_stride = (size_t)R * lt.beta * nt * N;
-            for (int r = 0; r < R; ++r) {
-                const u64 g = c_.rot_element(ridx[r]);
-                sh.map_rot[r] = c_.automorph_map(g);
-                sh.evk_rot[r] = permuted(*rot_keys.at(g), sh.map_rot[r]);
-            }
-            const bool rp = sum_in_row_pass();
-            sh.gsrc = base;
-            sh.gsrc_stride = row_stride;
-            if (rp) sh.gsrc_pmod = c_.d_pmod;
+            set_rotations(sh, rot, false);
             c_.stats.keyswitch += (u64)B * R;
             c_.stats.keyswitch_limbs += (u64)B * R * ell;
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
-            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
-            moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, rp);
+            rotation_sum(sh, ext, base + pn, base, row_stride, o[0]->d, nullptr);
             launch_ok("rotate_each_sum_rows");
         }
         for (int b = 0; b < B; ++b) out[lo + b] = o[b];
@@ -762,7 +760,7 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
 // once and every index runs only its own inner product + ModDown.  Bit-identical to rotate(a, i).
 std::vector<CtPtr> Evaluator::rotate_many(const CtPtr& a, const std::vector<int>& indices) {
     if (a->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
-    const int ns = a->slots > 0 ? a->slots : (1 << c_.prm.log_slots);
+    const int ns = slot_count(a);
     std::vector<CtPtr> out(indices.size());
     std::vector<size_t> todo;
     for (size_t i = 0; i < indices.size(); ++i) {
@@ -779,13 +777,9 @@ std::vector<CtPtr> Evaluator::rotate_many(const CtPtr& a, const std::vector<int>
         KsRows rows;
         rows.shared_input = true;
         for (int b = 0; b < B; ++b) {
-            const int index = indices[todo[first + b]];
-            const u64 g = c_.rot_element(index);
-            auto it = rot_keys.find(g);
-            if (it == rot_keys.end())
-                throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
-            rows.keys.push_back(it->second.get());
-            rows.maps.push_back(c_.automorph_map(g));
+            const RotKey k = rotation_key(indices[todo[first + b]]);
+            rows.keys.push_back(k.key.get());
+            rows.maps.push_back(k.map);
         }
         std::vector<CtPtr> o = new_ct_batch(B, 2, a->ell, a->deg, a->scale, a->slots);
         keyswitch_rows(rows, a->d + pn, 0, a->ell, o[0]->d, ctw, a->d, 0);
@@ -796,53 +790,29 @@ std::vector<CtPtr> Evaluator::rotate_many(const CtPtr& a, const std::vector<int>
 
 std::vector<CtPtr> Evaluator::rotate_each(const std::vector<CtPtr>& vin, const std::vector<int>& indices) {
     if (vin.size() != indices.size()) throw Error(FHELIN_ERR_ARG, "rotate_each: one index per ciphertext");
-    std::vector<CtPtr> out(vin.size());
-    std::vector<char> done(vin.size(), 0);
-    for (size_t first = 0; first < vin.size(); ++first) {
-        if (done[first]) continue;
-        const CtPtr& a = vin[first];
+    // an operand that is not rotated is copied and joins no group
+    auto rotated = [&](size_t f, size_t i) { return indices[i] % slot_count(vin[f]) != 0; };
+    return for_groups(vin.size(), std::min(batch_limit, (int)KsShape::MAX_ROWS),
+                      [&](size_t f, size_t i) { return rotated(f, f) && rotated(f, i) && same_shape(*vin[f], *vin[i]); },
+                      [&](const std::vector<size_t>& idx) {
+        const CtPtr& a = vin[idx[0]];
         if (a->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
-        const int ns = a->slots > 0 ? a->slots : (1 << c_.prm.log_slots);
-        if (indices[first] % ns == 0) {
-            out[first] = clone(a);
-            done[first] = 1;
-            continue;
-        }
-        std::vector<size_t> idx;
-        for (size_t i = first; i < vin.size() && (int)idx.size() < std::min(batch_limit, (int)KsShape::MAX_ROWS); ++i) {
-            const CtPtr& b = vin[i];
-            if (!done[i] && indices[i] % ns != 0 && b->npoly == 2 && b->ell == a->ell && b->deg == a->deg &&
-                fabsl(b->scale / a->scale - 1.0L) < 1e-9L)
-                idx.push_back(i);
-        }
-        if (idx.size() < 2) {
-            out[first] = rotate(a, indices[first]);
-            done[first] = 1;
-            continue;
-        }
-        std::vector<CtPtr> chunk;
+        if (!rotated(idx[0], idx[0])) return std::vector<CtPtr>{clone(a)};
+        if (idx.size() < 2) return std::vector<CtPtr>{rotate(a, indices[idx[0]])};
         KsRows rows;
         for (size_t i : idx) {
-            chunk.push_back(vin[i]);
-            const u64 g = c_.rot_element(indices[i]);
-            auto it = rot_keys.find(g);
-            if (it == rot_keys.end())
-                throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(indices[i]) + " (EvalRotateKeyGen list)");
-            rows.keys.push_back(it->second.get());
-            rows.maps.push_back(c_.automorph_map(g));
+            const RotKey k = rotation_key(indices[i]);
+            rows.keys.push_back(k.key.get());
+            rows.maps.push_back(k.map);
         }
-        chunk = make_contiguous(chunk, 3);
+        const std::vector<CtPtr> chunk = make_contiguous(pick(vin, idx), 3);
         const int B = (int)chunk.size();
         const size_t pn = (size_t)a->ell * c_.N, ctw = 2 * pn;
         std::vector<CtPtr> o = new_ct_batch(B, 2, a->ell, a->deg, a->scale, a->slots);
         keyswitch_rows(rows, chunk[0]->d + pn, ctw, a->ell, o[0]->d, ctw, chunk[0]->d, ctw);
-        for (int b = 0; b < B; ++b) {
-            o[b]->scale = vin[idx[b]]->scale;
-            out[idx[b]] = o[b];
-            done[idx[b]] = 1;
-        }
-    }
-    return out;
+        for (int b = 0; b < B; ++b) o[b]->scale = vin[idx[b]]->scale;
+        return o;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ raw ops
@@ -911,12 +881,12 @@ CtPtr Evaluator::raw_rescale(const CtPtr& a) {
     return o;
 }
 
-CtPtr Evaluator::raw_rotate(const CtPtr& a, u64 g, const EvalKey& key, bool accumulate) {
+CtPtr Evaluator::raw_rotate(const CtPtr& a, u64 g, const EvalKey& key, bool accumulate, const u32* map) {
     if (a->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
     const size_t pn = (size_t)a->ell * c_.N;
     CtPtr o = new_ct(2, a->ell, a->deg, a->scale, a->slots);
     // accumulate: out = a + rot(a) — the addition of the rotate-and-sum step rides in the ModDown epilogue
-    keyswitch(a->d + pn, a->ell, key, o->d, a->d, nullptr, c_.automorph_map(g), accumulate ? a->d : nullptr);
+    keyswitch(a->d + pn, a->ell, key, o->d, a->d, nullptr, map ? map : c_.automorph_map(g), accumulate ? a->d : nullptr);
     return o;
 }
 
@@ -925,17 +895,14 @@ std::vector<CtPtr> Evaluator::rotate_add_batch(const std::vector<CtPtr>& vin, in
 
 std::vector<CtPtr> Evaluator::rotate_batch_impl(const std::vector<CtPtr>& vin, int index, bool accumulate) {
     if (vin.empty()) return {};
-    const int ns = vin[0]->slots > 0 ? vin[0]->slots : (1 << c_.prm.log_slots);
+    const int ns = slot_count(vin[0]);
     std::vector<CtPtr> out(vin.size());
     if (vin.size() == 1 || index % ns == 0) {
         for (size_t i = 0; i < vin.size(); ++i) out[i] = accumulate ? rotate_add(vin[i], index) : rotate(vin[i], index);
         return out;
     }
-    const u64 g = c_.rot_element(index);
-    auto it = rot_keys.find(g);
-    if (it == rot_keys.end())
-        throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
-    return rotate_galois_batch(vin, g, *it->second, accumulate);
+    const RotKey k = rotation_key(index);
+    return rotate_galois_batch(vin, k.g, *k.key, accumulate);
 }
 
 std::vector<CtPtr> Evaluator::conjugate_batch(const std::vector<CtPtr>& v) {
@@ -944,39 +911,22 @@ std::vector<CtPtr> Evaluator::conjugate_batch(const std::vector<CtPtr>& v) {
 }
 
 std::vector<CtPtr> Evaluator::rotate_galois_batch(const std::vector<CtPtr>& vin, u64 g, const EvalKey& key, bool accumulate) {
-    std::vector<CtPtr> out(vin.size());
-    if (vin.size() == 1) {
-        out[0] = raw_rotate(vin[0], g, key, accumulate);
-        return out;
-    }
+    if (vin.size() == 1) return {raw_rotate(vin[0], g, key, accumulate)};
     const u32* map = c_.automorph_map(g);
     // rows that share (level, degree, scale) go through one batched key switch; others form their own groups
-    std::vector<char> done(vin.size(), 0);
-    for (size_t first = 0; first < vin.size(); ++first) {
-        if (done[first]) continue;
-        if (vin[first]->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
-        std::vector<size_t> idx;
-        for (size_t i = first; i < vin.size() && (int)idx.size() < batch_limit; ++i) {
-            const CtPtr &a = vin[first], &b = vin[i];
-            if (!done[i] && b->npoly == 2 && b->ell == a->ell && b->deg == a->deg && fabsl(b->scale / a->scale - 1.0L) < 1e-9L)
-                idx.push_back(i);
-        }
-        std::vector<CtPtr> chunk;
-        for (size_t i : idx) chunk.push_back(vin[i]);
-        chunk = make_contiguous(chunk, 4);
+    return for_groups(vin.size(), batch_limit, [&](size_t f, size_t i) { return same_shape(*vin[f], *vin[i]); },
+                      [&](const std::vector<size_t>& idx) {
+        if (vin[idx[0]]->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
+        const std::vector<CtPtr> chunk = make_contiguous(pick(vin, idx), 4);
         const int B = (int)chunk.size();
         const int ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * c_.N, ctw = 2 * pn;
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
         const u64* base = chunk[0]->d;  // contiguous by construction (or a single ciphertext)
         keyswitch_batch(B, base + pn, ctw, ell, key, o[0]->d, ctw, base, nullptr, ctw, map, accumulate ? base : nullptr, ctw);
-        for (int b = 0; b < B; ++b) {
-            o[b]->scale = vin[idx[b]]->scale;
-            out[idx[b]] = o[b];
-            done[idx[b]] = 1;
-        }
-    }
-    return out;
+        for (int b = 0; b < B; ++b) o[b]->scale = vin[idx[b]]->scale;
+        return o;
+    });
 }
 
 std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<CtPtr>& xs, const std::vector<int>& indices) {
@@ -989,7 +939,7 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
         for (size_t i = 0; i < xs.size(); ++i) out[i] = rotate_many(xs[i], indices);
         return out;
     }
-    const int ns = xs[0]->slots > 0 ? xs[0]->slots : (1 << c_.prm.log_slots);
+    const int ns = slot_count(xs[0]);
     std::vector<size_t> todo;
     for (size_t i = 0; i < xs.size(); ++i) out[i].resize(indices.size());
     for (size_t k = 0; k < indices.size(); ++k) {
@@ -1006,12 +956,9 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
     std::vector<const EvalKey*> keys;
     std::vector<const u32*> maps;
     for (size_t k : todo) {
-        const u64 g = c_.rot_element(indices[k]);
-        auto it = rot_keys.find(g);
-        if (it == rot_keys.end())
-            throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(indices[k]) + " (EvalRotateKeyGen list)");
-        keys.push_back(it->second.get());
-        maps.push_back(c_.automorph_map(g));
+        const RotKey rk = rotation_key(indices[k]);
+        keys.push_back(rk.key.get());
+        maps.push_back(rk.map);
     }
     const size_t N = c_.N;
     const int K = c_.K, L1 = c_.L + 1, ell = xs[0]->ell;
@@ -1112,21 +1059,11 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
 
 // rescale of many ciphertexts of identical shape as ONE polynomial batch [2B][ell][N] (K5 kernels are per polynomial)
 std::vector<CtPtr> Evaluator::rescale_batch(const std::vector<CtPtr>& vin) {
-    std::vector<CtPtr> out(vin.size());
-    std::vector<char> done(vin.size(), 0);
-    for (size_t first = 0; first < vin.size(); ++first) {
-        if (done[first]) continue;
-        std::vector<size_t> idx;
-        for (size_t i = first; i < vin.size() && (int)idx.size() < batch_limit; ++i)
-            if (!done[i] && vin[i]->npoly == 2 && vin[first]->npoly == 2 && vin[i]->ell == vin[first]->ell) idx.push_back(i);
-        if (idx.size() < 2) {
-            out[first] = rescale(vin[first]);
-            done[first] = 1;
-            continue;
-        }
-        std::vector<CtPtr> chunk;
-        for (size_t i : idx) chunk.push_back(vin[i]);
-        chunk = make_contiguous(chunk, 5);
+    return for_groups(vin.size(), batch_limit,
+                      [&](size_t f, size_t i) { return vin[i]->npoly == 2 && vin[f]->npoly == 2 && vin[i]->ell == vin[f]->ell; },
+                      [&](const std::vector<size_t>& idx) {
+        if (idx.size() < 2) return std::vector<CtPtr>{rescale(vin[idx[0]])};
+        const std::vector<CtPtr> chunk = make_contiguous(pick(vin, idx), 5);
         const int B = (int)chunk.size(), ell = chunk[0]->ell, P = 2 * B;
         if (ell < 2) throw Error(FHELIN_ERR_STATE, "rescale: no limb left to drop");
         const size_t N = c_.N;
@@ -1146,51 +1083,22 @@ std::vector<CtPtr> Evaluator::rescale_batch(const std::vector<CtPtr>& vin) {
             const CtPtr& a = vin[idx[b]];
             o[b]->scale = a->scale / (long double)c_.chain.q[ell - 1];
             o[b]->deg = a->deg > 1 ? a->deg - 1 : 1;
-            out[idx[b]] = o[b];
-            done[idx[b]] = 1;
         }
-    }
-    return out;
+        return o;
+    });
 }
 
 std::vector<CtPtr> Evaluator::mult_plain_batch(const std::vector<CtPtr>& vin, const PtPtr& p) {
     return mult_plain_each(vin, std::vector<PtPtr>(vin.size(), p));
 }
 
-namespace {
-// consecutive runs of operands with the same (components, limbs): one output block and one launch per <= 32 of them
-template <class SameShape, class Emit>
-void for_runs(size_t n, SameShape same, Emit emit) {
-    size_t lo = 0;
-    while (lo < n) {
-        size_t hi = lo + 1;
-        while (hi < n && hi - lo < (size_t)EwItems::MAX_ITEMS && same(lo, hi)) ++hi;
-        emit(lo, hi);
-        lo = hi;
-    }
-}
-}  // namespace
-
 std::vector<CtPtr> Evaluator::mult_plain_each(const std::vector<CtPtr>& vin, const std::vector<PtPtr>& p) {
     if (vin.size() != p.size()) throw Error(FHELIN_ERR_ARG, "mult_plain_each: one plaintext per ciphertext");
     if (vin.empty()) return {};
+    // degree-2 operands are rescaled first (as in mult_plain); the same ciphertext may occur many times (one
+    // container masked 128 ways): every distinct one once
     std::vector<CtPtr> x = vin;
-    {
-        // degree-2 operands are rescaled first (as in mult_plain); the same ciphertext may occur many times (one
-        // container masked 128 ways): rescale every distinct one once
-        std::vector<CtPtr> need;
-        std::map<const Ciphertext*, size_t> slot;
-        for (size_t i = 0; i < vin.size(); ++i)
-            if (vin[i]->deg >= 2 && !slot.count(vin[i].get())) {
-                slot[vin[i].get()] = need.size();
-                need.push_back(vin[i]);
-            }
-        if (!need.empty()) {
-            std::vector<CtPtr> r = rescale_batch(need);
-            for (size_t i = 0; i < vin.size(); ++i)
-                if (vin[i]->deg >= 2) x[i] = r[slot[vin[i].get()]];
-        }
-    }
+    rescale_degree2(x);
     std::vector<CtPtr> out(x.size());
     // operands of one shape: ONE output block for all products, so that any sub-range a later batched key switch takes is
     // contiguous as it stands (no gather copies); the launches still go in runs of MAX_ITEMS
@@ -1227,23 +1135,10 @@ CtPtr Evaluator::dot_plain(const std::vector<CtPtr>& vin, const std::vector<PtPt
     if (vin.size() != p.size() || vin.empty()) throw Error(FHELIN_ERR_ARG, "dot_plain: one plaintext per ciphertext, at least one term");
     // degree-2 operands are rescaled first, every distinct ciphertext once (as mult_plain does)
     std::vector<CtPtr> x = vin;
-    {
-        std::vector<CtPtr> need;
-        std::map<const Ciphertext*, size_t> slot;
-        for (size_t i = 0; i < vin.size(); ++i)
-            if (vin[i]->deg >= 2 && !slot.count(vin[i].get())) {
-                slot[vin[i].get()] = need.size();
-                need.push_back(vin[i]);
-            }
-        if (!need.empty()) {
-            std::vector<CtPtr> r = rescale_batch(need);
-            for (size_t i = 0; i < vin.size(); ++i)
-                if (vin[i]->deg >= 2) x[i] = r[slot[vin[i].get()]];
-        }
-    }
+    rescale_degree2(x);
     bool uniform = x.size() >= 2;
-    for (const CtPtr& c : x)
-        uniform = uniform && c->npoly == x[0]->npoly && c->ell == x[0]->ell && c->deg == x[0]->deg && fabsl(c->scale / x[0]->scale - 1.0L) < 1e-9L;
+    for (const CtPtr& c : x)   // any component count, as long as it is the first operand's
+        uniform = uniform && c->npoly == x[0]->npoly && c->ell == x[0]->ell && c->deg == x[0]->deg && same_scale(*x[0], *c);
     if (!uniform) {
         if (pt_scale > 0) throw Error(FHELIN_ERR_ARG, "dot_plain: an explicit plaintext scale needs uniform operands");
         std::vector<CtPtr> prod = mult_plain_each(x, p);
@@ -1288,7 +1183,7 @@ bool Evaluator::dot_plain_groups(const std::vector<CtPtr>& cts, const std::vecto
         return false;
     const CtPtr& f = cts[0];
     for (const CtPtr& c : cts)
-        if (c->npoly != 2 || c->deg != 1 || c->ell != f->ell || fabsl(c->scale / f->scale - 1.0L) > 1e-9L) return false;
+        if (c->deg != 1 || !same_shape(*f, *c)) return false;
     for (const CtPtr& o : dest)
         if (!o || o->npoly != 2 || o->ell != f->ell) return false;
     const long double sf = pt_scale > 0 ? pt_scale : c_.sf_real[f->level()];
@@ -1327,7 +1222,7 @@ bool Evaluator::dot_plain_groups_batch(const std::vector<std::vector<CtPtr>>& ct
     for (size_t x = 0; x < nb; ++x) {
         if (cts[x].size() != na || dest[x].size() != ng) return false;
         for (const CtPtr& c : cts[x])
-            if (c->npoly != 2 || c->deg != 1 || c->ell != f->ell || fabsl(c->scale / f->scale - 1.0L) > 1e-9L) return false;
+            if (c->deg != 1 || !same_shape(*f, *c)) return false;
         for (const CtPtr& o : dest[x])
             if (!o || o->npoly != 2 || o->ell != f->ell) return false;
     }
@@ -1385,7 +1280,7 @@ bool Evaluator::dot_plain_cyclic(const std::vector<CtPtr>& cts, const std::vecto
     if (cts.empty() || (int)cts.size() > P || (int)pts.size() != P || (int)dest.size() != P) return false;
     const CtPtr& f = cts[0];
     for (const CtPtr& c : cts)
-        if (c->npoly != 2 || c->deg != 1 || c->ell != f->ell || fabsl(c->scale / f->scale - 1.0L) > 1e-9L) return false;
+        if (c->deg != 1 || !same_shape(*f, *c)) return false;
     for (const CtPtr& o : dest)
         if (!o || o->npoly != 2 || o->ell != f->ell) return false;
     const long double sf = c_.sf_real[f->level()];
@@ -1422,7 +1317,7 @@ bool Evaluator::dot_plain_window(const std::vector<CtPtr>& cur, const std::vecto
     for (const auto* v : {&cur, &prev})
         for (const CtPtr& c : *v)
             if (c) {
-                if (c->npoly != 2 || c->deg != 1 || c->ell != f->ell || fabsl(c->scale / f->scale - 1.0L) > 1e-9L) return false;
+                if (c->deg != 1 || !same_shape(*f, *c)) return false;
                 ++terms;
             }
     for (const CtPtr& o : dest)
@@ -1536,64 +1431,69 @@ std::vector<CtPtr> Evaluator::add_sub_batch(const std::vector<CtPtr>& a, const s
     return out;
 }
 
-void Evaluator::product_operands(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, std::vector<CtPtr>& x, std::vector<CtPtr>& y) {
-    const size_t n = a.size();
-    // operands of degree 2 are rescaled first (every distinct ciphertext once), then brought to a common level per pair
-    std::vector<CtPtr> in;
+void Evaluator::rescale_degree2(std::vector<CtPtr>& a, std::vector<CtPtr>* b, const char* two_components) {
+    std::vector<CtPtr> need;
     std::map<const Ciphertext*, size_t> slot;
-    for (const auto* side : {&a, &b})
-        for (const CtPtr& c : *side) {
-            if (c->npoly != 2) throw Error(FHELIN_ERR_STATE, "mult: operands must have 2 components");
+    for (const auto* side : {&a, b})
+        for (size_t i = 0; side && i < side->size(); ++i) {
+            const CtPtr& c = (*side)[i];
+            if (two_components && c->npoly != 2) throw Error(FHELIN_ERR_STATE, two_components);
             if (c->deg >= 2 && !slot.count(c.get())) {
-                slot[c.get()] = in.size();
-                in.push_back(c);
+                slot[c.get()] = need.size();
+                need.push_back(c);
             }
         }
-    std::vector<CtPtr> resc = in.empty() ? std::vector<CtPtr>() : rescale_batch(in);
-    auto ready = [&](const CtPtr& c) { return c->deg >= 2 ? resc[slot[c.get()]] : c; };
-    std::vector<CtPtr> ra(n), rb(n);
-    for (size_t i = 0; i < n; ++i) {
-        ra[i] = ready(a[i]);
-        rb[i] = ready(b[i]);
+    if (need.empty()) return;
+    const std::vector<CtPtr> r = rescale_batch(need);
+    for (auto* side : {&a, b})
+        for (size_t i = 0; side && i < side->size(); ++i) {
+            CtPtr& c = (*side)[i];
+            if (c->deg >= 2) c = r[slot[c.get()]];
+        }
+}
+
+std::vector<CtPtr> Evaluator::tensor_products(const std::vector<CtPtr>& x, const std::vector<CtPtr>& y, const std::vector<size_t>& idx) {
+    const int B = (int)idx.size(), ell = x[idx[0]]->ell;
+    std::vector<CtPtr> d = new_ct_batch(B, 3, ell, 2, 0, x[idx[0]]->slots);   // contiguous [B][3][ell][N]
+    for (int k0 = 0; k0 < B; k0 += EwItems::MAX_ITEMS) {
+        EwItems it;
+        it.n = std::min(B - k0, (int)EwItems::MAX_ITEMS);
+        for (int k = 0; k < it.n; ++k) {
+            it.out[k] = d[k0 + k]->d;
+            it.a[k] = x[idx[k0 + k]]->d;
+            it.b[k] = y[idx[k0 + k]]->d;
+        }
+        launch_tensor_items(c_.dt, it, ell, c_.stream);
     }
+    return d;
+}
+
+void Evaluator::product_operands(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, std::vector<CtPtr>& x, std::vector<CtPtr>& y) {
+    // operands of degree 2 are rescaled first (every distinct ciphertext once), then brought to a common level per pair
+    std::vector<CtPtr> ra = a, rb = b;
+    rescale_degree2(ra, &rb, "mult: operands must have 2 components");
     match_batch(ra, rb, x, y);   // the level adjustments of all pairs of a round together (one batched rescale per target level)
 }
 
 std::vector<CtPtr> Evaluator::mult_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b) {
     if (a.size() != b.size()) throw Error(FHELIN_ERR_ARG, "mult_batch: operand count mismatch");
     if (!relin_key) throw Error(FHELIN_ERR_KEY, "no relinearisation key (EvalMultKeyGen not called)");
-    const size_t n = a.size();
-    std::vector<CtPtr> x, y, out(n);
+    std::vector<CtPtr> x, y;
     product_operands(a, b, x, y);
-    std::vector<char> done(n, 0);
-    for (size_t first = 0; first < n; ++first) {
-        if (done[first]) continue;
-        std::vector<size_t> idx;
-        for (size_t i = first; i < n && (int)idx.size() < batch_limit; ++i)
-            if (!done[i] && x[i]->ell == x[first]->ell) idx.push_back(i);
-        const int B = (int)idx.size(), ell = x[first]->ell;
+    std::vector<CtPtr> out = for_groups(a.size(), batch_limit, [&](size_t f, size_t i) { return x[i]->ell == x[f]->ell; },
+                                        [&](const std::vector<size_t>& idx) {
+        const int B = (int)idx.size(), ell = x[idx[0]]->ell;
         const size_t pn = (size_t)ell * c_.N;
-        std::vector<CtPtr> d = new_ct_batch(B, 3, ell, 2, 0, x[first]->slots);   // tensor products, contiguous [B][3][ell][N]
-        for (int k0 = 0; k0 < B; k0 += EwItems::MAX_ITEMS) {   // all tensor products of the batch in one launch per 32 pairs
-            EwItems it;
-            it.n = std::min(B - k0, (int)EwItems::MAX_ITEMS);
-            for (int k = 0; k < it.n; ++k) {
-                it.out[k] = d[k0 + k]->d;
-                it.a[k] = x[idx[k0 + k]]->d;
-                it.b[k] = y[idx[k0 + k]]->d;
-            }
-            launch_tensor_items(c_.dt, it, ell, c_.stream);
-        }
-        std::vector<CtPtr> o = new_ct_batch(B, 2, ell, 2, 0, x[first]->slots);
+        const std::vector<CtPtr> d = tensor_products(x, y, idx);
+        std::vector<CtPtr> o = new_ct_batch(B, 2, ell, 2, 0, x[idx[0]]->slots);
         keyswitch_batch(B, d[0]->d + 2 * pn, 3 * pn, ell, *relin_key, o[0]->d, 2 * pn, d[0]->d, d[0]->d + pn, 3 * pn, nullptr, nullptr, 0);
         for (int k = 0; k < B; ++k) {
             const size_t i = idx[k];
             o[k]->deg = x[i]->deg + y[i]->deg;
             o[k]->scale = x[i]->scale * y[i]->scale;
-            out[i] = o[k];
-            done[i] = 1;
         }
-    }
+        return o;
+    });
     launch_ok("mult_batch");
     return out;
 }
@@ -1604,48 +1504,24 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
     if (f != 1 && f != 2) throw Error(FHELIN_ERR_ARG, "mult_affine_rescale_batch: factor 1 or 2");
     if (!relin_key) throw Error(FHELIN_ERR_KEY, "no relinearisation key (EvalMultKeyGen not called)");
     if (c_.K < 1 || c_.K + 1 > 16) throw Error(FHELIN_ERR_STATE, "mult_affine_rescale_batch: 1..15 special primes");
-    const size_t n = a.size();
-    // operands exactly as mult_batch takes them: degree 2 rescaled first (every distinct ciphertext once), pairs brought to one level
-    std::vector<CtPtr> in;
-    std::map<const Ciphertext*, size_t> slot;
-    for (const auto* side : {&a, &b})
-        for (const CtPtr& c : *side) {
-            if (c->npoly != 2) throw Error(FHELIN_ERR_STATE, "mult: operands must have 2 components");
-            if (c->deg >= 2 && !slot.count(c.get())) {
-                slot[c.get()] = in.size();
-                in.push_back(c);
-            }
-        }
-    std::vector<CtPtr> resc = in.empty() ? std::vector<CtPtr>() : rescale_batch(in);
-    auto ready = [&](const CtPtr& c) { return c->deg >= 2 ? resc[slot[c.get()]] : c; };
-    std::vector<CtPtr> x(n), y(n), out(n);
-    for (size_t i = 0; i < n; ++i) match(ready(a[i]), ready(b[i]), x[i], y[i]);
+    // operands as mult_batch takes them (degree 2 rescaled first, every distinct ciphertext once), the pairs brought to one level one by one
+    std::vector<CtPtr> ra = a, rb = b, x(a.size()), y(a.size());
+    rescale_degree2(ra, &rb, "mult: operands must have 2 components");
+    for (size_t i = 0; i < a.size(); ++i) match(ra[i], rb[i], x[i], y[i]);
     const size_t N = c_.N;
     const int K = c_.K, L1 = c_.L + 1;
     hipStream_t s = c_.stream;
-    std::vector<char> done(n, 0);
-    for (size_t first = 0; first < n; ++first) {
-        if (done[first]) continue;
-        std::vector<size_t> idx;
-        for (size_t i = first; i < n && (int)idx.size() < batch_limit; ++i)
-            if (!done[i] && x[i]->ell == x[first]->ell && fabsl(x[i]->scale * y[i]->scale / (x[first]->scale * y[first]->scale) - 1.0L) < 1e-12L)
-                idx.push_back(i);
+    auto product_scale = [&](size_t i) { return x[i]->scale * y[i]->scale; };
+    return for_groups(a.size(), batch_limit,
+                      [&](size_t f0, size_t i) { return x[i]->ell == x[f0]->ell && fabsl(product_scale(i) / product_scale(f0) - 1.0L) < 1e-12L; },
+                      [&](const std::vector<size_t>& idx) {
+        const size_t first = idx[0];
         const int B = (int)idx.size(), ell = x[first]->ell;
         if (ell < 2) throw Error(FHELIN_ERR_STATE, "mult_affine_rescale_batch: no limb left to drop");
         const size_t pn = (size_t)ell * N;
-        const long double sc = x[first]->scale * y[first]->scale;
+        const long double sc = product_scale(first);
         const LevelTables& lt = c_.lvl[ell];
-        std::vector<CtPtr> d = new_ct_batch(B, 3, ell, 2, 0, x[first]->slots);   // tensor products, contiguous [B][3][ell][N]
-        for (int k0 = 0; k0 < B; k0 += EwItems::MAX_ITEMS) {
-            EwItems it;
-            it.n = std::min(B - k0, (int)EwItems::MAX_ITEMS);
-            for (int k = 0; k < it.n; ++k) {
-                it.out[k] = d[k0 + k]->d;
-                it.a[k] = x[idx[k0 + k]]->d;
-                it.b[k] = y[idx[k0 + k]]->d;
-            }
-            launch_tensor_items(c_.dt, it, ell, s);
-        }
+        const std::vector<CtPtr> d = tensor_products(x, y, idx);
         // the subtrahends at the products' (limbs, degree 2, scale), in one block
         std::vector<CtPtr> sadj;
         if (!sub.empty()) {
@@ -1673,14 +1549,9 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
             moddown_rescale(sh, accQ, accP, o[0]->d);   // P and the top limb dropped together
             launch_ok("mult_affine_rescale_batch");
         }
-        for (int k = 0; k < B; ++k) {
-            const size_t i = idx[k];
-            o[k]->scale = x[i]->scale * y[i]->scale / (long double)c_.chain.q[ell - 1];
-            out[i] = o[k];
-            done[i] = 1;
-        }
-    }
-    return out;
+        for (int k = 0; k < B; ++k) o[k]->scale = product_scale(idx[k]) / (long double)c_.chain.q[ell - 1];
+        return o;
+    });
 }
 
 std::vector<CtPtr> Evaluator::mult_affine_unmerged(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<AffineSpec>& spec) {
@@ -1726,7 +1597,7 @@ std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, con
     }
     if (!exact_products_on()) return mult_affine_unmerged(a, b, spec);
     const size_t n = a.size();
-    std::vector<CtPtr> x, y, out(n);
+    std::vector<CtPtr> x, y;
     product_operands(a, b, x, y);
     // where the sequence would adjust the PRODUCT to its addend, or has no limb to drop, it runs itself (on the prepared operands: its own
     // preparation finds nothing left to do)
@@ -1735,26 +1606,13 @@ std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, con
     const size_t N = c_.N;
     const int K = c_.K, L1 = c_.L + 1;
     hipStream_t s = c_.stream;
-    const int limit = std::min(batch_limit, (int)AffineItems::MAX_ITEMS);
-    std::vector<char> done(n, 0);
-    for (size_t first = 0; first < n; ++first) {
-        if (done[first]) continue;
-        std::vector<size_t> idx;
-        for (size_t i = first; i < n && (int)idx.size() < limit; ++i)
-            if (!done[i] && x[i]->ell == x[first]->ell) idx.push_back(i);
+    static_assert(AffineItems::MAX_ITEMS <= EwItems::MAX_ITEMS, "the tensor products of a group are one launch");
+    return for_groups(n, std::min(batch_limit, (int)AffineItems::MAX_ITEMS), [&](size_t f, size_t i) { return x[i]->ell == x[f]->ell; },
+                      [&](const std::vector<size_t>& idx) {
+        const size_t first = idx[0];
         const int B = (int)idx.size(), ell = x[first]->ell;
         const size_t pn = (size_t)ell * N;
-        std::vector<CtPtr> d = new_ct_batch(B, 3, ell, 2, 0, x[first]->slots);   // tensor products, contiguous [B][3][ell][N]
-        {
-            EwItems it;
-            it.n = B;
-            for (int k = 0; k < B; ++k) {
-                it.out[k] = d[k]->d;
-                it.a[k] = x[idx[k]]->d;
-                it.b[k] = y[idx[k]]->d;
-            }
-            launch_tensor_items(c_.dt, it, ell, s);
-        }
+        const std::vector<CtPtr> d = tensor_products(x, y, idx);
         // the affine parts at their products' (limbs, degree 2, scale): the addend as match() brings it to the product, the constant as add_real forms it
         AffineItems items;
         std::vector<CtPtr> adj(B);
@@ -1807,14 +1665,9 @@ std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, con
             moddown_rescale_exact(sh, accQ, accP, o[0]->d, items.f2);
             launch_ok("mult_affine_batch");
         }
-        for (int k = 0; k < B; ++k) {
-            const size_t i = idx[k];
-            o[k]->scale = x[i]->scale * y[i]->scale / (long double)c_.chain.q[ell - 1];
-            out[i] = o[k];
-            done[i] = 1;
-        }
-    }
-    return out;
+        for (int k = 0; k < B; ++k) o[k]->scale = x[idx[k]]->scale * y[idx[k]]->scale / (long double)c_.chain.q[ell - 1];
+        return o;
+    });
 }
 
 std::vector<CtPtr> Evaluator::add_plain_batch(const std::vector<CtPtr>& v, const PtPtr& p) {
@@ -1843,13 +1696,9 @@ std::vector<CtPtr> Evaluator::add_plain_batch(const std::vector<CtPtr>& v, const
 }
 
 CtPtr Evaluator::rotate_add(const CtPtr& a, int index) {
-    const int ns = a->slots > 0 ? a->slots : (1 << c_.prm.log_slots);
-    if (index % ns == 0) return add(a, a);
-    const u64 g = c_.rot_element(index);
-    auto it = rot_keys.find(g);
-    if (it == rot_keys.end())
-        throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
-    return raw_rotate(a, g, *it->second, true);
+    if (index % slot_count(a) == 0) return add(a, a);
+    const RotKey k = rotation_key(index);
+    return raw_rotate(a, k.g, *k.key, true, k.map);
 }
 
 CtPtr Evaluator::raw_mult_relin(const CtPtr& a, const CtPtr& b, const EvalKey& key) {
@@ -2210,14 +2059,9 @@ CtPtr Evaluator::relinearize(const CtPtr& a) {
 CtPtr Evaluator::mult(const CtPtr& a, const CtPtr& b) { return relinearize(mult_no_relin(a, b)); }
 
 CtPtr Evaluator::rotate(const CtPtr& a, int index) {
-    const int ns = a->slots > 0 ? a->slots : (1 << c_.prm.log_slots);
-    int r = index % ns;
-    if (r == 0) return clone(a);
-    const u64 g = c_.rot_element(index);
-    auto it = rot_keys.find(g);
-    if (it == rot_keys.end())
-        throw Error(FHELIN_ERR_KEY, "no rotation key for index " + std::to_string(index) + " (EvalRotateKeyGen list)");
-    return raw_rotate(a, g, *it->second);
+    if (index % slot_count(a) == 0) return clone(a);
+    const RotKey k = rotation_key(index);
+    return raw_rotate(a, k.g, *k.key, false, k.map);
 }
 
 }  // namespace fhelin

@@ -2,6 +2,7 @@
 // operations the reference reaches through OpenFHE's CryptoContext (reference src/FHEController.cpp
 // :409-436 add/mult/rotate, FLEXIBLEAUTO level + scale bookkeeping implied by :18-24).
 #pragma once
+#include <cmath>
 #include <functional>
 #include <map>
 #include <memory>
@@ -111,6 +112,14 @@ struct EvalKey {
     size_t words() const { return (size_t)digits * 2 * (ctx->L + 1 + ctx->K) * ctx->N; }
 };
 typedef std::shared_ptr<EvalKey> KeyPtr;
+
+// two scales that one launch set may treat as one: within 1e-9 of each other (every output still carries its own)
+inline bool same_scale(const Ciphertext& a, const Ciphertext& b) { return fabsl(b.scale / a.scale - 1.0L) < 1e-9L; }
+// "the same shape" of the batched operations: two components, the same limbs and noise degree, the same scale in the sense above.
+// A site that needs more says so (same_shape(..) && ..); one that deliberately tests less keeps its own predicate.
+inline bool same_shape(const Ciphertext& a, const Ciphertext& b) {
+    return a.npoly == 2 && b.npoly == 2 && a.ell == b.ell && a.deg == b.deg && same_scale(a, b);
+}
 
 // round(v) (half away from zero, 80-bit v) modulo the first ell limbs, with Shoup companions (polyeval.cpp)
 void real_to_scalars(const Context& c, long double v, int ell, ScalarSet& sc);
@@ -322,7 +331,7 @@ public:
     void lift_and_ntt(u64* lifted, const u64* last, int P, int ell, const NttEpilogue* ep = nullptr, const u64* qlm_row = nullptr);
     // K5 steps 2-4: out [P][ell-1][N] = (c - NTT(centred lift of last)) * q_{ell-1}^-1, c [P][ell][N]
     void rescale_finish(u64* out, const u64* c, const u64* last, int P, int ell, const u64* qlinv_row = nullptr, const u64* qlm_row = nullptr);
-    CtPtr raw_rotate(const CtPtr& a, u64 galois, const EvalKey& key, bool accumulate = false);
+    CtPtr raw_rotate(const CtPtr& a, u64 galois, const EvalKey& key, bool accumulate = false, const u32* map = nullptr);   // map: galois' own, if at hand
     CtPtr rotate_add(const CtPtr& a, int index);            // a + rot(a, index), one fused key switch (rotsum step :833)
     CtPtr raw_mult_relin(const CtPtr& a, const CtPtr& b, const EvalKey& key);
     // K9 ModRaise (EvalBootstrap's first step): a ciphertext with ONE limb (modulus q0) -> new_ell limbs, every coefficient's
@@ -340,6 +349,31 @@ private:
                  bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr);
     void moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out);
     void moddown_rescale_exact(const KsShape& sh, const u64* accQ, u64* accP, u64* out, u32 f2);
+    // logical slot count of a ciphertext (slots = 0: the context's)
+    int slot_count(int slots) const;
+    int slot_count(const CtPtr& a) const { return slot_count(a->slots); }
+    // key, automorphism map and Galois element of a rotation index; FHELIN_ERR_KEY when the key was not generated
+    struct RotKey {
+        const KeyPtr& key;   // the entry of rot_keys
+        const u32* map;
+        u64 g;
+    };
+    RotKey rotation_key(int index);
+    // the rotations of a merged key switch, looked up once per call: keys, maps, and whether every map keeps the 512-coefficient tiles
+    struct Rotations {
+        int n = 0;
+        const EvalKey* key[KsShape::MAX_ROT] = {};
+        const u32* map[KsShape::MAX_ROT] = {};
+        bool tiles_in_place = true;
+    };
+    Rotations rotations(const int* indices, int n);
+    void set_rotations(KsShape& sh, const Rotations& rot, bool shared_digits, const u64* const* keys = nullptr);
+    void rotation_sum(KsShape& sh, const u64* ext, const u64* c1, const u64* c0, size_t c0_stride, u64* out, const u64* post);
+    // every degree-2 ciphertext of the list(s) replaced by its rescaled one: one rescale_batch over the distinct ones; FHELIN_ERR_STATE
+    // (`what`) for an operand that does not have two components, before anything runs
+    void rescale_degree2(std::vector<CtPtr>& a, std::vector<CtPtr>* b = nullptr, const char* two_components = nullptr);
+    // the tensor products x[idx[k]] (x) y[idx[k]] of one group: a block [B][3][ell][N], one launch per 32 pairs
+    std::vector<CtPtr> tensor_products(const std::vector<CtPtr>& x, const std::vector<CtPtr>& y, const std::vector<size_t>& idx);
     // operands of a batched product as mult_batch takes them: degree 2 rescaled first (every distinct ciphertext once), pairs matched
     void product_operands(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, std::vector<CtPtr>& x, std::vector<CtPtr>& y);
     // the unmerged sequence of mult_affine_batch: mult_batch, add_batch (factor 2), add_real per item, sub_batch / add_batch, rescale_batch

@@ -248,9 +248,6 @@ struct HoistAdd {
     const u64* pmod = nullptr;
 };
 void launch_hoist_addends(const DeviceTables& t, const KsShape& sh, const HoistAdd& h, u64* pre, const u64* ct, hipStream_t s);
-// out[v][n] = sum_r in[v][map_rot[r][n]]  for v in [0, nvec) (the c0 parts of the rotated copies), per batch row
-// (FHELIN_FUSE_GATHER=0 only: by default the sum rides in launch_ks_inner_multi or launch_moddown_finish, KsShape::gsrc)
-void launch_gather_sum(const DeviceTables& t, const KsShape& sh, u64* out, const u64* in, size_t in_stride, hipStream_t s);
 // K8a: accP coefficient form [2][k][N] -> conv [2][ell][N] (coefficient form); sh.gather: with the signs of the row's automorphism
 void launch_moddown_conv(const DeviceTables& t, const KsShape& sh, u64* conv, const u64* accP, const u64* phatinv, const u64* phatmod,
                          hipStream_t s);

@@ -426,22 +426,6 @@ __global__ __launch_bounds__(256) void ks_inner_multi_kernel(DeviceTables t, KsS
     }
 }
 
-// grid (N/256, batch*ell)
-__global__ __launch_bounds__(256) void gather_sum_kernel(DeviceTables t, KsShape sh, u64* __restrict__ out, const u64* __restrict__ in,
-                                                         size_t in_stride) {
-    const int bi = blockIdx.y / sh.ell, tt = blockIdx.y % sh.ell;
-    const size_t N = (size_t)1 << t.log_n;
-    const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const u64 q = t.moduli[tt];
-    const u64* src = in + (size_t)bi * in_stride + (size_t)tt * N;
-    u64 acc = 0;
-    for (int r = 0; r < sh.n_rot; ++r) {
-        const u64* sr = src + (size_t)r * sh.rot_input_stride;
-        acc = add_mod(acc, sr[sh.map_rot[r] ? (size_t)sh.map_rot[r][n] : n], q);
-    }
-    out[((size_t)bi * sh.ell + tt) * N + n] = acc;
-}
-
 // grid (N/256, 2, ceil(ell/TCH)).  MAXK = number of special limbs (exact for k <= 8, then FULL: no per-source conditions)
 // SIGNED (KsShape::gather): accP holds sigma_g of the accumulator; where sigma_g negates (neg) the sources are un-negated, converted
 // and the result negated, which is sigma_g of the plain conversion - conv(p - x) alone is off by a multiple of P.
@@ -913,10 +897,6 @@ void launch_ks_inner_multi(const DeviceTables& t, const KsShape& sh, u64* accQ, 
         hipLaunchKernelGGL((ks_inner_multi_kernel<true, 1>), g, dim3(256), 0, s, t, sh, accQ, accP, ext, c_ntt);
     else
         hipLaunchKernelGGL((ks_inner_multi_kernel<false, 1>), g, dim3(256), 0, s, t, sh, accQ, accP, ext, c_ntt);
-}
-void launch_gather_sum(const DeviceTables& t, const KsShape& sh, u64* out, const u64* in, size_t in_stride, hipStream_t s) {
-    dim3 g((1u << t.log_n) / 256, (unsigned)(sh.batch * sh.ell));
-    hipLaunchKernelGGL(gather_sum_kernel, g, dim3(256), 0, s, t, sh, out, in, in_stride);
 }
 void launch_moddown_conv(const DeviceTables& t, const KsShape& sh_in, u64* conv, const u64* accP, const u64* phatinv, const u64* phatmod,
                          hipStream_t s) {

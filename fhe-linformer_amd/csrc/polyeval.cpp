@@ -63,9 +63,8 @@ CtPtr Evaluator::lincomb_at(const std::vector<CtPtr>& terms_in, const std::vecto
         }
     if (terms.empty()) throw Error(FHELIN_ERR_ARG, "lincomb: all coefficients are zero");
     bool uniform = (int)terms.size() <= LinComb::MAX_TERMS && terms.size() >= 2;
-    for (const CtPtr& t : terms)
-        uniform = uniform && t->deg == 1 && t->npoly == terms[0]->npoly && t->ell == terms[0]->ell &&
-                  fabsl(t->scale / terms[0]->scale - 1.0L) < 1e-9L;
+    for (const CtPtr& t : terms)   // any component count, as long as it is the first term's
+        uniform = uniform && t->deg == 1 && t->npoly == terms[0]->npoly && t->ell == terms[0]->ell && same_scale(*terms[0], *t);
     if (!uniform) {  // the chain of single operations (also the definition of the result)
         if (want_scale > 0 || keep_ell > 0) return CtPtr();
         CtPtr acc;

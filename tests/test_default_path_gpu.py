@@ -1,5 +1,5 @@
 """The path the product runs BY DEFAULT, residue for residue against the oracle (through the C-ABI):
-merged rotate-and-sum key switches (ks_inner_multi + gather_sum, one ModDown), the shared-ModDown giant steps,
+merged rotate-and-sum key switches (ks_inner_multi, which gathers the c0 parts too, one ModDown), the shared-ModDown giant steps,
 ct x pt / scalar / ct + pt element-wise kernels, the FLEXIBLEAUTO level adjustment, ModRaise, the decryption phase,
 and the composites with every default-on knob (FHELIN_MERGE_ROT, FHELIN_EARLY_RESCALE, log-depth shift trees, block
 masks in place of matmulRElarge's -128 shifts, its double-hoisted first step) left ON.  All comparisons are bit-exact (integer functions); plaintext operands enter the
@@ -65,7 +65,7 @@ FORWARD16 = dict(log_n=16, n_q=28, n_p=-1)      # bench.py's forward chain: N=2^
     ("bench", FORWARD16, [28], [128, 256, 384], 1),          # the headline chain
 ])
 def test_rotate_sum_bit_exact(engine_factory, orc, preset, over, ells, idx, rows):
-    """fhelin_rotate_sum (Evaluator::rotate_sum_batch -> ks_inner_multi_kernel + gather_sum_kernel, ONE ModDown) ==
+    """fhelin_rotate_sum (Evaluator::rotate_sum_batch -> ks_inner_multi_kernel, c0 parts included, ONE ModDown) ==
     orc_rotate_sum on every residue, for a batch of rows"""
     eng = engine_factory(preset, **over)
     keys = _keys(orc, eng, idx)

@@ -1,6 +1,6 @@
 """Fixed-shape probe of the hybrid key-switch kernels for rocprofv3 (kernel stats / PMC passes): N=2^16, 24+6 limbs
 (alpha 6, beta 4), batch of 8 rows at ell=24: `reps` plain rotations (modup_conv, ks_inner, moddown_conv, moddown_finish
-+ the NTT passes) and `reps` merged rotate-sums {128,256,384} (ks_inner_multi, gather_sum).  Prints the shape so that the
++ the NTT passes) and `reps` merged rotate-sums {128,256,384} (ks_inner_multi, which gathers the c0 parts too).  Prints the shape so that the
 algorithmic bytes per launch can be computed (tools/pmc_summary.py)."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
