@@ -236,6 +236,8 @@ def load_library():
         "fhelin_evalkeys_interleave": (i32, [C.c_char_p, C.POINTER(i32)]),
         "fhelin_encrypt_interleaved_batch": (i32, [vp, C.POINTER(C.c_double), i32, i32, i32, i32, C.POINTER(vp)]),
         "fhelin_decrypt_interleaved": (i32, [vp, vp, i32, C.POINTER(C.c_double), i32]),
+        "fhelin_decrypt_batch": (i32, [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(i32), i32, C.POINTER(C.c_double), i32]),
+        "fhelin_ctx_set_device_decode": (i32, [vp, i32]),
         "fhelin_client_ingest_interleaved": (i32, [vp, i32, C.POINTER(vp), C.POINTER(vp), vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32,
                                                    C.POINTER(vp), C.POINTER(vp)]),
     }
@@ -823,6 +825,28 @@ class Engine:
         out = np.empty(n, dtype=np.float64)
         self._ck(self.lib.fhelin_decrypt(self.h, ct.h, out.ctypes.data_as(C.POINTER(C.c_double)), n))
         return out
+
+    def decrypt_batch(self, cts, slots=0, flood_bits=0, idx=None, all_lanes=False):
+        """batched decryption (include/fhelin.h "Batched decryption"): the decoder on the device, one download and one synchronisation
+        for the batch.  Returns [n][W] - row b is decrypt(cts[b]), bit for bit - or [n][stride][W] with all_lanes (decrypt_interleaved's
+        order); W = slots, or len(idx) when idx (logical slot numbers) is given.  slots=0: the ciphertexts' own count, which must agree.
+        flood_bits > 0: one key draw for the batch (a batch of one is decrypt_flooded)"""
+        cts = list(cts)
+        n = len(cts)
+        lanes = self.interleave if all_lanes else 1
+        ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        own = int(slots) or (cts[0].slots if n else 0) or (1 << self.params.log_slots)
+        width = own if ix is None else ix.size
+        out = np.empty((n, lanes, width), dtype=np.float64)
+        arr = (C.c_void_p * max(n, 1))(*[c.h for c in cts])
+        self._ck(self.lib.fhelin_decrypt_batch(self.h, arr, n, int(flood_bits), 1 if all_lanes else 0,
+                                               None if ix is None else ix.ctypes.data_as(C.POINTER(C.c_int32)), 0 if ix is None else ix.size,
+                                               out.ctypes.data_as(C.POINTER(C.c_double)), int(slots)))
+        return out if all_lanes else out[:, 0, :]
+
+    def set_device_decode(self, on):
+        """decrypt, decrypt_flooded and decrypt_interleaved through the device decoder, as batches of one (default off; FHELIN_DEVICE_DECODE)"""
+        self._ck(self.lib.fhelin_ctx_set_device_decode(self.h, 1 if on else 0))
 
     def ct_import(self, limbs, deg=1, scale=None, slots=0):
         limbs = np.ascontiguousarray(limbs, dtype=np.uint64)

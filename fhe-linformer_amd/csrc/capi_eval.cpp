@@ -298,6 +298,7 @@ int fhelin_debug_sample(fhelin_ctx* c, int32_t kind, int32_t n_poly, int64_t* ou
 }
 int fhelin_decrypt(fhelin_ctx* c, const fhelin_ct* ct, double* out, int32_t slots) {
     NEED(c && ct && out);
+    if (c->ctx.device_decode) return fhelin_decrypt_batch(c, &ct, 1, 0, 0, nullptr, 0, out, slots);   // the device decoder, a batch of one
     FHELIN_TRY
     if (c->cl.eval_only()) throw Error(FHELIN_ERR_KEY, "decrypt: an evaluation context holds no secret key");
     if (ct->p && ct->p->wrapped()) {   // a wrapped input: its extra limb left out, the slots in the wrapped layout

@@ -35,6 +35,7 @@ int fhelin_ctx_interleave(const fhelin_ctx* c, int32_t* stride) {
 
 int fhelin_decrypt_interleaved(fhelin_ctx* c, const fhelin_ct* ct, int32_t flood_bits, double* out, int32_t slots) {
     NEED(c && ct && out);
+    if (c->ctx.device_decode) return fhelin_decrypt_batch(c, &ct, 1, flood_bits, 1, nullptr, 0, out, slots);   // the device decoder
     FHELIN_TRY
     c->ctx.require_device();
     if (c->cl.eval_only()) throw Error(FHELIN_ERR_KEY, "decrypt: an evaluation context holds no secret key");

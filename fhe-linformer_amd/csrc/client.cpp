@@ -1226,6 +1226,115 @@ std::vector<double> Client::decrypt_physical(const CtPtr& cin, int slots, int fl
     return out;
 }
 
+// The decoder on the device for a whole batch (client.h): what decrypt_physical does per ciphertext on the host after its download -
+// CRT lift in long double, division by the scale, forward special FFT - runs in decode_lift_kernel and the forward FFT kernels, held to
+// the host code bit for bit; the batch then costs one download of the slots asked for and one drain of the stream.
+void Client::decrypt_batch(const std::vector<CtPtr>& cin, int slots, int flood_bits, bool all_lanes, const int* idx, int n_idx, double* out) {
+    c_.require_device();
+    if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+    if (flood_bits < 0 || flood_bits > 62) throw Error(FHELIN_ERR_ARG, "decrypt_batch: flood_bits must lie in [0, 62]");
+    const int n = (int)cin.size();
+    if (n == 0) return;
+    if (!out) throw Error(FHELIN_ERR_ARG, "decrypt_batch: null output");
+    if (cin.size() > 65535) throw Error(FHELIN_ERR_ARG, "decrypt_batch: at most 65535 ciphertexts per call");
+    if (idx && n_idx <= 0) throw Error(FHELIN_ERR_ARG, "decrypt_batch: an index list needs at least one entry");
+    // every refusal before any device work and before the sampler is touched
+    for (const CtPtr& ct : cin)
+        if (!ct || ct->npoly < 2 || ct->npoly > 3) throw Error(FHELIN_ERR_ARG, "decrypt_batch: a ciphertext has 2 or 3 components");
+    if (slots <= 0) {
+        for (const CtPtr& ct : cin) {
+            const int own = ct->slots > 0 ? ct->slots : (1 << c_.prm.log_slots);
+            if (slots > 0 && own != slots) throw Error(FHELIN_ERR_ARG, "decrypt_batch: the ciphertexts' slot counts disagree (pass slots)");
+            slots = own;
+        }
+    }
+    const int st = c_.stride;
+    if ((slots & (slots - 1)) || (long)slots * st > c_.N / 2)
+        throw Error(FHELIN_ERR_ARG, "decrypt_batch: slots x interleave stride must be a power of two <= N/2");
+    if (idx)
+        for (int k = 0; k < n_idx; ++k)
+            if (idx[k] < 0 || idx[k] >= slots) throw Error(FHELIN_ERR_ARG, "decrypt_batch: slot index outside [0, slots)");
+    std::vector<int> nl(n);
+    int nl_max = 1, nl_sum = 0;
+    for (int b = 0; b < n; ++b) {   // the limbs read once the pending rescales have run, a wrapped input's extra limb left out
+        int ell = cin[b]->ell, deg = cin[b]->deg;
+        while (deg > 1 && ell > 2) --ell, --deg;
+        ell -= cin[b]->wrapped() ? 1 : 0;
+        if (ell < 1) throw Error(FHELIN_ERR_ARG, "decrypt_batch: a ciphertext has no limb to read");
+        nl[b] = std::min(ell, 2);
+        nl_max = std::max(nl_max, nl[b]);
+        nl_sum += nl[b];
+        if (flood_bits > 0) check_flood(flood_bits, nl[b], "decrypt_batch");
+    }
+    std::vector<CtPtr> x = cin;
+    for (;;) {   // ONE rescale_batch per pending degree (as decrypt rescales its input)
+        std::vector<CtPtr> need;
+        std::vector<size_t> at;
+        for (size_t i = 0; i < x.size(); ++i)
+            if (x[i]->deg > 1 && x[i]->ell > 2) {
+                need.push_back(x[i]);
+                at.push_back(i);
+            }
+        if (need.empty()) break;
+        std::vector<CtPtr> r = ev_.rescale_batch(need);
+        for (size_t k = 0; k < at.size(); ++k) x[at[k]] = r[k];
+    }
+    const size_t N = c_.N;
+    const int phys = slots * st;
+    const int lanes = all_lanes ? st : 1, width = idx ? n_idx : slots;
+    hipStream_t s = c_.stream;
+    // device tables of the call in one upload: the items, the inverse NTT's limb table (-1: a row the item does not read), the slot list
+    const size_t off_limb = (size_t)n * sizeof(DecodeItem), off_idx = off_limb + (size_t)n * nl_max * sizeof(int);
+    std::vector<char> host(off_idx + (idx ? (size_t)n_idx * sizeof(int) : 0));
+    DecodeItem* items = reinterpret_cast<DecodeItem*>(host.data());
+    int* limb_tab = reinterpret_cast<int*>(host.data() + off_limb);
+    for (int b = 0; b < n; ++b) {
+        const Ciphertext& ct = *x[b];
+        const size_t pn = (size_t)ct.ell * N;
+        int e2 = 0;
+        const long double m = frexpl(ct.scale, &e2);         // scale = m * 2^e2, m in [0.5, 1): a 64-bit significand, exactly
+        items[b].c0 = ct.d;
+        items[b].c1 = ct.d + pn;
+        items[b].c2 = ct.npoly == 3 ? ct.d + 2 * pn : nullptr;
+        items[b].ms = (u64)ldexpl(m, 64);
+        items[b].es = e2 - 64;
+        items[b].deg = ct.npoly - 1;
+        items[b].limb_stride = (int32_t)N;
+        items[b].nl = nl[b];
+        for (int l = 0; l < nl_max; ++l) limb_tab[b * nl_max + l] = l < nl[b] ? l : -1;
+    }
+    if (idx) std::memcpy(host.data() + off_idx, idx, (size_t)n_idx * sizeof(int));
+    Scratch<char> d_tab = c_.scratch<char>(host.size());
+    hip_check(hipMemcpyAsync(d_tab, host.data(), host.size(), hipMemcpyHostToDevice, s), "decrypt_batch tables");
+    const DecodeItem* d_items = reinterpret_cast<const DecodeItem*>(d_tab.get());
+    const int* d_limb = reinterpret_cast<const int*>(d_tab.get() + off_limb);
+    const int* d_idx = idx ? reinterpret_cast<const int*>(d_tab.get() + off_idx) : nullptr;
+    const size_t words = (size_t)n * nl_max * N;
+    Scratch<u64> ph = c_.scratch<u64>(words);
+    launch_phase_batch(c_.dt, ph, d_items, s_all, nl_max, n, s);
+    c_.ntt(LimbBatch{ph, n * nl_max, d_limb, 0, nl_max}, true, nl_sum);
+    if (flood_bits > 0) {   // noise-flooding decryption: phase + f in coefficient form, one sampler call for the batch
+        Scratch<u64> f = c_.scratch<u64>(words);
+        sample_flood_device(f, n, nl_max, flood_bits, false);
+        launch_ew_add(c_.dt, ph, ph, f, n * nl_max, n * nl_max, 0, nl_max, s);
+        hip_check(hipGetLastError(), "decrypt_batch flood kernels");
+        hip_check(hipMemsetAsync(f, 0, words * sizeof(u64), s), "hipMemsetAsync(decrypt_batch flood)");
+    }
+    const u64 q0 = c_.chain.q[0], q1 = nl_max > 1 ? c_.chain.q[1] : 1;
+    const u64 inv = nl_max > 1 ? h_invmod(q0 % q1, q1) : 0;
+    Scratch<double> v = c_.scratch<double>((size_t)n * phys * 2);
+    launch_decode_lift(c_.dt, v, ph, d_items, inv, nl_max > 1 ? h_shoup(inv, q1) : 0, nl_max, phys, n, s);
+    if (phys >= 2) {
+        const Context::FftDev& tab = fft_dev_tables(c_, phys);
+        launch_fft_special_fwd(v, tab.rot, tab.ksi, phys, n, s);
+    }
+    Scratch<double> o = c_.scratch<double>((size_t)n * lanes * width);
+    launch_decode_gather(o, v, d_idx, slots, st, lanes, width, n, s);
+    hip_check(hipGetLastError(), "decrypt_batch kernels");
+    hip_check(hipMemcpyAsync(out, o, (size_t)n * lanes * width * sizeof(double), hipMemcpyDeviceToHost, s), "decrypt_batch download");
+    hip_check(hipStreamSynchronize(s), "decrypt_batch sync");
+}
+
 void Client::export_secret(u64* out) {
     if (!s_all) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     const size_t n = (size_t)(c_.L + 1 + c_.K) * c_.N;

@@ -87,6 +87,14 @@ public:
     // on the device, after the inverse NTT and before the download; 0: the plain decryption, unchanged
     std::vector<double> decrypt(const CtPtr& c, int slots, int flood_bits = 0);   // interleaved samples: lane 0
     std::vector<double> decrypt_interleaved(const CtPtr& c, int slots, int flood_bits = 0);   // [stride][slots]: every lane
+    // Batched decryption (include/fhelin.h "Batched decryption"): the decoder on the device, bit for bit the doubles decrypt gives.
+    // out [n][L][W] on the host: L = stride with all_lanes (decrypt_interleaved's order) else 1 (lane 0, decrypt's), W = n_idx when idx
+    // (logical slot numbers in [0, slots)) is given, else slots; slots <= 0: the ciphertexts' own count, which must agree.  The batch may
+    // mix limb counts, scales, degrees and wrapped inputs.  One phase launch, ONE inverse NTT over every limb read, the lift, the forward
+    // special FFT and the gather for the whole batch, ONE download and ONE stream synchronisation.  flood_bits > 0: one key draw per
+    // call, the flood of ciphertext b on stream (C << 32) + b, C += 2 - a batch of one is decrypt(c, slots, flood_bits), a batch of n
+    // is not n single calls.  Every refusal comes before the first draw.
+    void decrypt_batch(const std::vector<CtPtr>& cts, int slots, int flood_bits, bool all_lanes, const int* idx, int n_idx, double* out);
     // Reply sanitisation (include/fhelin.h "Sanitised replies"): degree-2 inputs rescaled, the optional 0/1 mask applied (product +
     // rescale), then out_b = first out_ell limbs of x_b + Enc_pk(0) + flood in ONE fused launch for the whole batch; the randomness
     // scratch is wiped.  Needs the public key only (works on an evaluation context).

@@ -330,6 +330,7 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
         if (const char* e = std::getenv("FHELIN_FUSE_MODDOWN")) fuse_moddown = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_FINISH")) fuse_finish = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_HOST_ENCODE")) host_encode = std::atoi(e) != 0;
+        if (const char* e = std::getenv("FHELIN_DEVICE_DECODE")) device_decode = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_ROT_GATHER")) rot_gather = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_LIFT")) fuse_lift = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_LDS_DIGITS")) lds_digits = std::atoi(e) != 0;

@@ -305,6 +305,9 @@ struct Context {
     // FHELIN_HOST_ENCODE=1 / fhelin_ctx_set_host_encode: the special FFT of CKKS encoding on the host (the original path, kept
     // as the reference the device encoder is compared with bit for bit); default: on the GPU (kernels_client.hip)
     bool host_encode = false;
+    // FHELIN_DEVICE_DECODE=1 / fhelin_ctx_set_device_decode: fhelin_decrypt, _flooded and _interleaved run as batches of one through
+    // Client::decrypt_batch (lift, division and forward special FFT on the device, the same doubles bit for bit); default: the host decoder
+    bool device_decode = false;
     // Rotations gather at the inner product, so that every ModDown is the identity one that the row pass of NTT(conv) finishes
     // (needs fuse_finish).  A merged rotation sum: launch_ks_inner_multi adds P * sum_r sigma_r(c0) to the
     // accumulator's Q part while it has the maps in hand.  A plain rotation: launch_ks_inner reads digits, own limb and c0 through

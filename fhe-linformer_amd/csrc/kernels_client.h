@@ -42,6 +42,34 @@ static_assert(sizeof(RerandItem) == 24, "RerandItem is 24 bytes");
 void launch_rerandomize_combine(const DeviceTables& t, const RerandItem* tab, const u64* pk, const u64* u, const u64* w, const u64* e1,
                                 int out_ell, int L1, int n_ct, hipStream_t s);
 
+// ---- batched decryption (include/fhelin.h "Batched decryption"): phase, lift, forward special FFT and slot gather on the device
+// one ciphertext of a decrypted batch (device table entry): components [ell][N] each, NTT form; the first nl limbs are read
+struct DecodeItem {
+    const u64* c0;
+    const u64* c1;
+    const u64* c2;          // null: a 2-component ciphertext
+    u64 ms;                 // scale = ms * 2^es (64-bit significand, as launch_encode_round_reduce takes it)
+    int32_t es;
+    int32_t deg;            // components - 1: 1 or 2
+    int32_t limb_stride;    // words between two limbs of a component (N)
+    int32_t nl;             // limbs read: 1 or 2
+};
+static_assert(sizeof(DecodeItem) == 48, "DecodeItem is 48 bytes");
+// out [n][nl_max][N] (NTT form) <- c0 + c1 s (+ c2 s^2) on the first nl limbs of item b = tab[b]; rows nl..nl_max-1 of an item are
+// zeroed.  s [..][N] the secret's Q limbs, NTT form; tab [n] on the device; n <= 65535
+void launch_phase_batch(const DeviceTables& t, u64* out, const DecodeItem* tab, const u64* s, int nl_max, int n, hipStream_t st);
+// v [n][slots] complex <- the decoded coefficients of phase [n][nl_max][N] (coefficient form), element bitrev(i) = (lift(i * gap),
+// lift(i * gap + N/2)) / scale with gap = (N/2) / slots: csrc/decode_lift.h per coefficient, the forward FFT's bit reversal in the store.
+// q0inv = q_0^-1 mod q_1 and its Shoup companion (unused when no item reads two limbs)
+void launch_decode_lift(const DeviceTables& t, double* v, const u64* phase, const DecodeItem* tab, u64 q0inv, u64 q0inv_shoup, int nl_max,
+                        int slots, int n, hipStream_t st);
+// data [n_vec][slots] complex, bit-reversed input: all stages of the forward special FFT in place, bit-identical to the host loop
+// ckks_fft_special(forward).  Stages up to len 512 in ONE launch over 512-element LDS tiles, every later stage one launch.
+// rot / ksi as launch_fft_special_inv.  slots = 1: nothing to do
+void launch_fft_special_fwd(double* data, const u32* rot, const double* ksi, int slots, int n_vec, hipStream_t st);
+// out [n][lanes][width] <- Re v[b][(idx ? idx[k] : k) * stride + lane]; v [n][slots * stride] complex; lanes = 1 (lane 0) or stride;
+// width = n_idx when idx (device, logical slot numbers) is given, else slots
+void launch_decode_gather(double* out, const double* v, const int* idx, int slots, int stride, int lanes, int width, int n, hipStream_t st);
 
 // ---- client-side ingestion of one sample (reference src/python/dimReduce.py:141-160 and the read_expanded_input packing,
 // src/FHEController.cpp:623-650), all in fp64 with the operation order of the NumPy statement and FMA contraction off:

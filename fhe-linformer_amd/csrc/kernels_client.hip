@@ -17,11 +17,15 @@
 //    as residues of every limb (|f| may exceed q_l: reduced with the limb's Barrett constants).
 //  * rerandomize_combine_kernel   : out = in + (b*u + w, a*u + e1) on the first out_ell limbs of a batch of ciphertexts of any limb
 //    counts (a fresh encryption of zero added, the level drop part of the same pass).
+//  * phase_batch_kernel, decode_lift_kernel, fft_special_fwd_tile_kernel / _stage_kernel, decode_gather_kernel : batched decryption
+//    (Client::decrypt_batch): the phase of a batch of any shapes, the centred CRT lift and the division by the scale in integer code
+//    (decode_lift.h), the forward special FFT bit-identical to the host loop, and the slots that were asked for in one buffer.
 // All HBM-bound or trivially small; no MFMA.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "kernels_client.h"
 #include "kernels_chacha.h"
+#include "decode_lift.h"
 
 namespace fhelin {
 namespace {
@@ -325,7 +329,160 @@ __global__ __launch_bounds__(256) void rerandomize_combine_kernel(DeviceTables t
     O[((size_t)out_ell + l) * row + n2] = c1;
 }
 
+// ---- batched decryption (kernels_client.h): everything between the ciphertexts and the slots that were asked for
+// grid (N/512, nl_max, n): item b = tab[blockIdx.z], limb l = blockIdx.y.  out [n][nl_max][N] <- c0 + c1 s (+ c2 s^2) on the item's first
+// nl limbs (Client::phase for a batch of any limb counts and degrees); the rows an item does not read are zeroed
+__global__ __launch_bounds__(256) void phase_batch_kernel(DeviceTables t, u64* __restrict__ out, const DecodeItem* __restrict__ tab,
+                                                          const u64* __restrict__ s, int nl_max) {
+    const int b = blockIdx.z, l = blockIdx.y;
+    const DecodeItem it = tab[b];
+    const size_t row = ((size_t)1 << t.log_n) >> 1;
+    const size_t n2 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    u64x2* O = reinterpret_cast<u64x2*>(out) + ((size_t)b * nl_max + l) * row + n2;
+    u64x2 m;
+    if (l >= it.nl) {
+        m.x = m.y = 0;
+        *O = m;
+        return;
+    }
+    const Barrett br = load_barrett(t, l);
+    const size_t at = (size_t)l * ((size_t)it.limb_stride >> 1) + n2;
+    const u64x2 a0 = reinterpret_cast<const u64x2*>(it.c0)[at], a1 = reinterpret_cast<const u64x2*>(it.c1)[at];
+    const u64x2 ss = reinterpret_cast<const u64x2*>(s)[(size_t)l * row + n2];
+    m.x = add_mod(a0.x, mul_mod(a1.x, ss.x, br), br.q);
+    m.y = add_mod(a0.y, mul_mod(a1.y, ss.y, br), br.q);
+    if (it.deg > 1) {
+        const u64x2 a2 = reinterpret_cast<const u64x2*>(it.c2)[at];
+        m.x = add_mod(m.x, mul_mod(a2.x, mul_mod(ss.x, ss.x, br), br), br.q);
+        m.y = add_mod(m.y, mul_mod(a2.y, mul_mod(ss.y, ss.y, br), br), br.q);
+    }
+    *O = m;
+}
+
+// grid (slots/256 rounded up, n): thread i of item b reads coefficients i * gap and i * gap + N/2 of phase [n][nl_max][N] (coefficient
+// form), lifts each (decode_lift.h: integer code, the host decoder's double bit for bit) and stores the pair at position bitrev(i) of
+// v [n][slots]: the forward FFT begins with a bit reversal, done here so that the stages run in place
+__global__ __launch_bounds__(256) void decode_lift_kernel(DeviceTables t, double2* __restrict__ v, const u64* __restrict__ phase,
+                                                          const DecodeItem* __restrict__ tab, u64 q0inv, u64 q0inv_shoup, int nl_max, int slots,
+                                                          int log_slots) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= slots) return;
+    const DecodeItem it = tab[blockIdx.y];
+    const size_t N = (size_t)1 << t.log_n;
+    const size_t gap = (N / 2) / slots;
+    DecodeLift p;
+    p.q0 = t.moduli[0];
+    p.q1 = it.nl > 1 ? t.moduli[1] : 1;
+    p.inv = q0inv;
+    p.inv_shoup = q0inv_shoup;
+    p.ms = it.ms;
+    p.es = it.es;
+    p.nl = it.nl;
+    const u64* m = phase + (size_t)blockIdx.y * nl_max * N;
+    const size_t ca = (size_t)i * gap, cb = ca + N / 2;
+    double2 o;
+    o.x = decode_lift(m[ca], it.nl > 1 ? m[N + ca] : 0, p);
+    o.y = decode_lift(m[cb], it.nl > 1 ? m[N + cb] : 0, p);
+    const u32 dst = log_slots ? __brev((u32)i) >> (32 - log_slots) : 0;
+    v[(size_t)blockIdx.y * slots + dst] = o;
+}
+
+// one butterfly of the forward special FFT exactly as the host loop in client.cpp ckks_fft_special(forward) does it: w = b * ksi with each
+// product and each sum rounded on its own, then u + w and u - w
+__device__ __forceinline__ void fft_fwd_butterfly(double2& u, double2& b, const double2 k) {
+#pragma clang fp contract(off)
+    double2 w;
+    w.x = b.x * k.x - b.y * k.y;
+    w.y = b.x * k.y + b.y * k.x;
+    const double2 a = u;
+    u.x = a.x + w.x;
+    u.y = a.y + w.y;
+    b.x = a.x - w.x;
+    b.y = a.y - w.y;
+}
+
+// ---- forward special FFT, the stages with len <= 512: they touch only aligned blocks of 512 elements, so one workgroup runs them all
+// on a tile held in LDS (8 KiB, two elements per thread, a barrier per stage).  data [n_vec][size], bit-reversed input;
+// grid (size/512 rounded up, n_vec).  size < 512: one tile of `size` elements and all of the transform
+__global__ __launch_bounds__(256) void fft_special_fwd_tile_kernel(double2* data, const u32* __restrict__ rot, const double2* __restrict__ ksi,
+                                                                   int size) {
+    __shared__ double2 tile[512];
+    const int tsz = size < 512 ? size : 512;
+    double2* v = data + (size_t)blockIdx.y * size + (size_t)blockIdx.x * 512;
+    const int t = threadIdx.x;
+    if (t < tsz) tile[t] = v[t];
+    if (t + 256 < tsz) tile[t + 256] = v[t + 256];
+    for (int len = 2; len <= tsz; len <<= 1) {
+        __syncthreads();
+        if (t < tsz / 2) {
+            const int lenh = len >> 1, lenq = len << 2, gap = (4 * size) / lenq;
+            const int j = t % lenh, i = (t / lenh) * len;
+            const int idx = (int)(rot[j] % (u32)lenq) * gap;
+            double2 u = tile[i + j], b = tile[i + j + lenh];
+            fft_fwd_butterfly(u, b, ksi[idx]);
+            tile[i + j] = u;
+            tile[i + j + lenh] = b;
+        }
+    }
+    __syncthreads();
+    if (t < tsz) v[t] = tile[t];
+    if (t + 256 < tsz) v[t + 256] = tile[t + 256];
+}
+
+// ---- forward special FFT, one later stage (len > 512): the mirror of fft_special_inv_stage_kernel.  grid (size/2 / 256, n_vec)
+__global__ __launch_bounds__(256) void fft_special_fwd_stage_kernel(double2* data, const u32* __restrict__ rot, const double2* __restrict__ ksi,
+                                                                    int size, int len) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= size / 2) return;
+    double2* v = data + (size_t)blockIdx.y * size;
+    const int lenh = len >> 1, lenq = len << 2, gap = (4 * size) / lenq;
+    const int j = t % lenh, i = (t / lenh) * len;
+    const int idx = (int)(rot[j] % (u32)lenq) * gap;
+    double2 u = v[i + j], b = v[i + j + lenh];
+    fft_fwd_butterfly(u, b, ksi[idx]);
+    v[i + j] = u;
+    v[i + j + lenh] = b;
+}
+
+// grid (lanes * width / 256 rounded up, n): out [n][lanes][width] <- the real parts asked for of v [n][slots * stride]: physical slot
+// stride * k + lane holds logical slot k of lane `lane` (interleaved samples); k = idx[e] when a list is given, else e
+__global__ __launch_bounds__(256) void decode_gather_kernel(double* __restrict__ out, const double2* __restrict__ v, const int* __restrict__ idx,
+                                                            int slots, int stride, int lanes, int width) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= lanes * width) return;
+    const int lane = e / width, k = e % width;
+    const int src = idx ? idx[k] : k;
+    out[(size_t)blockIdx.y * lanes * width + e] = v[(size_t)blockIdx.y * slots * stride + (size_t)src * stride + lane].x;
+}
+
 }  // namespace
+
+void launch_phase_batch(const DeviceTables& t, u64* out, const DecodeItem* tab, const u64* s, int nl_max, int n, hipStream_t st) {
+    if (n < 1) return;
+    hipLaunchKernelGGL(phase_batch_kernel, dim3((1u << t.log_n) / 512, (unsigned)nl_max, (unsigned)n), dim3(256), 0, st, t, out, tab, s, nl_max);
+}
+void launch_decode_lift(const DeviceTables& t, double* v, const u64* phase, const DecodeItem* tab, u64 q0inv, u64 q0inv_shoup, int nl_max,
+                        int slots, int n, hipStream_t st) {
+    if (n < 1) return;
+    int log_slots = 0;
+    while ((1 << log_slots) < slots) ++log_slots;
+    hipLaunchKernelGGL(decode_lift_kernel, dim3((unsigned)((slots + 255) / 256), (unsigned)n), dim3(256), 0, st, t, reinterpret_cast<double2*>(v),
+                       phase, tab, q0inv, q0inv_shoup, nl_max, slots, log_slots);
+}
+void launch_fft_special_fwd(double* data, const u32* rot, const double* ksi, int slots, int n_vec, hipStream_t st) {
+    if (n_vec < 1 || slots < 2) return;
+    hipLaunchKernelGGL(fft_special_fwd_tile_kernel, dim3((unsigned)((slots + 511) / 512), (unsigned)n_vec), dim3(256), 0, st,
+                       reinterpret_cast<double2*>(data), rot, reinterpret_cast<const double2*>(ksi), slots);
+    const dim3 g((unsigned)((slots / 2 + 255) / 256), (unsigned)n_vec);
+    for (int len = 1024; len <= slots; len <<= 1)
+        hipLaunchKernelGGL(fft_special_fwd_stage_kernel, g, dim3(256), 0, st, reinterpret_cast<double2*>(data), rot,
+                           reinterpret_cast<const double2*>(ksi), slots, len);
+}
+void launch_decode_gather(double* out, const double* v, const int* idx, int slots, int stride, int lanes, int width, int n, hipStream_t st) {
+    if (n < 1) return;
+    hipLaunchKernelGGL(decode_gather_kernel, dim3((unsigned)((lanes * width + 255) / 256), (unsigned)n), dim3(256), 0, st, out,
+                       reinterpret_cast<const double2*>(v), idx, slots, stride, lanes, width);
+}
 
 void launch_interleave_slots(double* out, const double* in, int slots, int stride, int lanes, int n_vec, hipStream_t s) {
     if (n_vec < 1) return;

@@ -345,6 +345,11 @@ class BatchedController:
     def decrypt(self, c):
         return [self.e.decrypt(h, SLOTS) for h in c]
 
+    def decrypt_batch(self, c, idx=None):
+        """decrypt for the whole batch in ONE call (Engine.decrypt_batch: the decoder on the device, one download, one synchronisation):
+        [B][SLOTS], row b bit for bit decrypt(c)[b]; idx: only these slots, [B][len(idx)] (the 20 logit slots of a reply)"""
+        return self.e.decrypt_batch(list(c), SLOTS, idx=idx)
+
     def decrypt_lanes(self, c):
         """interleaved samples: per batch entry every sample's slots, [B][s][SLOTS]"""
         return [self.e.decrypt_interleaved(h, SLOTS) for h in c]
@@ -538,6 +543,11 @@ class LanedBatchedController:
     def decrypt(self, c):
         self.e.set_lane(0)
         return [self.e.decrypt(h, SLOTS) for h in c]
+
+    def decrypt_batch(self, c, idx=None):
+        """as BatchedController.decrypt_batch, on the main stream"""
+        self.e.set_lane(0)
+        return self.e.decrypt_batch(list(c), SLOTS, idx=idx)
 
 
 def batched_level_plan(plan, B, n_client):

@@ -749,6 +749,7 @@ int fhelin_debug_flood(fhelin_ctx* c, const uint8_t* key, uint64_t stream, int32
  *     out0_b = in0_b + pk_b NTT(u_b) + NTT(e0_b + f_b), out1_b = in1_b + pk_a NTT(u_b) + NTT(e1_b) on the first out_ell limbs.
  *   fhelin_decrypt_flooded (flood_bits > 0): one key draw, f (flood, no Gaussian) at (C << 32); C += 2 (the unused Gaussian range
  *     is skipped).
+ *   fhelin_decrypt_batch (flood_bits > 0; "Batched decryption"): one key draw per CALL, f_b of ciphertext b at (C << 32) + b; C += 2.
  *   seeded fhelin_keygen: the secret's draws from G, then the key-set seed (the next four words of G), then one key draw: the public
  *     key's e (Gaussian, one polynomial over the Q limbs) at (C << 32); C += 1.  pk_b = NTT(e) - pk_a s.
  *   seeded switching keys (fhelin_gen_relin_key, each rotation key, fhelin_gen_conj_key): one key draw per key; digit j's e_j
@@ -764,6 +765,33 @@ int fhelin_debug_sampler_peek(const fhelin_ctx* c, int32_t n_keys, uint32_t* key
  * decryption reads - values a client shares then do not expose the exact noise.  flood_bits = 0: exactly fhelin_decrypt.
  * FHELIN_ERR_ARG: flood_bits outside [0, 62] or 2^(flood_bits + 2) not below the modulus of the limbs read. */
 int fhelin_decrypt_flooded(fhelin_ctx* c, const fhelin_ct* ct, int32_t flood_bits, double* out, int32_t slots);
+
+/* ---- batched decryption: a batch of ciphertexts decoded on the device, one download and one synchronisation ------------------
+ * fhelin_decrypt computes the phase and one inverse NTT on the device, downloads the one or two limbs it reads (N words each), drains
+ * the stream and decodes on one host thread: CRT lift in long double, division by the scale, forward special FFT.
+ * fhelin_decrypt_batch does all of that on the device for n ciphertexts at once - one phase launch, ONE inverse NTT over every limb
+ * read, the lift and division in integer code, the forward FFT, a gather of the slots that were asked for - and then downloads exactly
+ * those doubles with ONE copy and ONE stream synchronisation.  Every double is the one fhelin_decrypt gives, bit for bit.
+ *   out    [n][L][W].  L = 1: sample 0 of every ciphertext, as fhelin_decrypt; all_lanes != 0: L = the context's interleave stride and
+ *          the lanes in fhelin_decrypt_interleaved's order.  W = slots, or n_idx when idx is given.
+ *   idx    NULL, or n_idx logical slot numbers in [0, slots), any order, repeats allowed: out[b][l][k] = slot idx[k].
+ *   slots  <= 0: the ciphertexts' own slot count, which must then agree across the batch.
+ * The batch may mix limb counts (one limb, two or more), scales, degrees and wrapped inputs.  Degree-2 inputs above two limbs are
+ * rescaled first, all of them in one batched rescale; deferred rows are evaluated as for any other reader; under a level plan every
+ * ciphertext counts as one decryption, in order.
+ * Randomness (flood_bits > 0, "Sampler streams"): ONE key draw per call, the flood of ciphertext b at (C << 32) + b; C += 2.  A batch
+ * of one therefore IS fhelin_decrypt_flooded; a batch of n is NOT n single calls (those draw n keys and advance C by 2 n).  The flood
+ * scratch is zeroed afterwards.
+ * FHELIN_ERR_KEY: an evaluation context.  FHELIN_ERR_NO_DEVICE: a context without a device.  FHELIN_ERR_ARG: a null array, entry or
+ * out; n < 0 or above 65535; idx out of range, or n_idx <= 0 with idx given; disagreeing slot counts with slots <= 0; slots x stride
+ * not a power of two <= N/2; flood_bits outside [0, 62] or too wide for the limbs read.  n = 0 is FHELIN_OK and touches nothing.  A
+ * refused call draws nothing and leaves C where it found it. */
+int fhelin_decrypt_batch(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n, int32_t flood_bits, int32_t all_lanes, const int32_t* idx,
+                         int32_t n_idx, double* out, int32_t slots);
+/* on != 0: fhelin_decrypt, fhelin_decrypt_flooded and fhelin_decrypt_interleaved run as batches of one through the device decoder (the
+ * same doubles; slots x stride must then be a power of two); 0, the default, and they execute the host decoder as before.  Also
+ * FHELIN_DEVICE_DECODE=1 in the environment when the context is created. */
+int fhelin_ctx_set_device_decode(fhelin_ctx* c, int32_t on);
 
 #ifdef __cplusplus
 }
