@@ -227,6 +227,13 @@ def load_library():
         "fhelin_decrypt_flooded": (i32, [vp, vp, i32, C.POINTER(C.c_double), i32]),
         "fhelin_debug_sampler_peek": (i32, [vp, i32, vp, u64p]),
         "fhelin_debug_pt_from_residues": (i32, [vp, vp, i32, C.POINTER(vp)]),
+        "fhelin_debug_pt_from_residues_full": (i32, [vp, vp, C.c_double, C.c_double, C.POINTER(vp)]),
+        "fhelin_lt_create": (i32, [vp, C.POINTER(C.c_double), C.POINTER(i32), i32, i32, i32, C.POINTER(vp)]),
+        "fhelin_lt_create_pts": (i32, [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(vp)]),
+        "fhelin_lt_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "fhelin_lt_rotations": (i32, [vp, C.POINTER(i32), i32, C.POINTER(i32)]),
+        "fhelin_lt_apply": (i32, [vp, vp, C.POINTER(vp), i32, i32, C.POINTER(vp)]),
+        "fhelin_lt_free": (None, [vp]),
         "fhelin_debug_dot_plain": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp)]),
         "fhelin_debug_dot_groups": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp), i32, C.POINTER(vp)]),
         "fhelin_debug_dot_cyclic": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
@@ -996,6 +1003,44 @@ class Engine:
         self._ck(self.lib.fhelin_debug_pt_from_residues(self.h, r.ctypes.data_as(C.c_void_p), ell, C.byref(h)))
         return Pt(self, h)
 
+    def debug_pt_from_residues_full(self, residues, scale):
+        """a plaintext whose only encoding is residues [n_q + n_p][N] over the full key basis at `scale` (may be a numpy longdouble)"""
+        r = np.ascontiguousarray(residues, dtype=np.uint64)
+        assert r.shape == (self.n_q + self.n_p, self.N)
+        hi = float(scale)
+        lo = float(np.longdouble(scale) - np.longdouble(hi))
+        h = C.c_void_p()
+        self._ck(self.lib.fhelin_debug_pt_from_residues_full(self.h, r.ctypes.data_as(C.c_void_p), hi, lo, C.byref(h)))
+        return Pt(self, h)
+
+    # ---- linear transforms (include/fhelin.h "Linear transforms")
+    def lt_create(self, diags, indices, n1=0, slots=None):
+        """the plan of out = sum_d diags[d] * rot(x, indices[d]); diags [n_diag][slots]; n1 = 0: the planner chooses the split"""
+        slots = (1 << self.params.log_slots) if slots is None else int(slots)
+        n = len(indices)
+        d = np.ascontiguousarray(diags, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, slots))
+        assert n == 0 or d.shape[1] == slots
+        idx = (C.c_int32 * max(n, 1))(*[int(i) for i in indices])
+        h = C.c_void_p()
+        self._ck(self.lib.fhelin_lt_create(self.h, d.ctypes.data_as(C.POINTER(C.c_double)), idx, n, slots, int(n1), C.byref(h)))
+        return LinearTransform(self, h)
+
+    def lt_create_pts(self, pts, baby, giant):
+        """the plan from its terms: pts [n2][n1] of Pt (None = absent), baby [n1] (baby[0] == 0), giant [n2]"""
+        n2, n1 = len(giant), len(baby)
+        assert len(pts) == n2 and all(len(r) == n1 for r in pts)
+        b = (C.c_int32 * n1)(*[int(i) for i in baby])
+        g = (C.c_int32 * n2)(*[int(i) for i in giant])
+        h = C.c_void_p()
+        self._ck(self.lib.fhelin_lt_create_pts(self.h, self._harr_opt([p for r in pts for p in r]), b, g, n1, n2, C.byref(h)))
+        return LinearTransform(self, h)
+
+    def lt_apply(self, lt, v, rescale=False):
+        """the transform of every ciphertext of v: one ModUp per row, one ModDown per giant-step group, rows of one shape batched"""
+        outs = self._outs(max(len(v), 1))
+        self._ck(self.lib.fhelin_lt_apply(self.h, lt.h, self._harr(v), len(v), int(bool(rescale)), outs))
+        return self._cts(outs, len(v))
+
     def debug_dot_plain(self, cts, pts):
         """sum_i cts[i] * pts[i] (Evaluator::dot_plain)"""
         assert len(cts) == len(pts)
@@ -1323,6 +1368,38 @@ class Pt:
     def free(self):
         if self.h and self.eng.h:
             self.eng.lib.fhelin_pt_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+        self.h = None
+
+
+class LinearTransform:
+    """a linear-transform plan (fhelin_lt): host data, usable on the engine that made it"""
+
+    def __init__(self, eng, h):
+        self.eng, self.h = eng, h
+
+    def info(self):
+        i = [C.c_int32() for _ in range(4)]
+        self.eng._ck(self.eng.lib.fhelin_lt_info(self.h, *[C.byref(x) for x in i]))
+        return dict(n1=i[0].value, n2=i[1].value, n_terms=i[2].value, slots=i[3].value)
+
+    def rotations(self):
+        """the rotation indices whose keys fhelin_lt_apply needs"""
+        n = C.c_int32()
+        self.eng._ck(self.eng.lib.fhelin_lt_rotations(self.h, None, 0, C.byref(n)))
+        out = (C.c_int32 * max(n.value, 1))()
+        self.eng._ck(self.eng.lib.fhelin_lt_rotations(self.h, out, n.value, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
+    def free(self):
+        if self.h and self.eng.h:
+            self.eng.lib.fhelin_lt_free(self.h)
         self.h = None
 
     def __del__(self):

@@ -3,6 +3,7 @@
 // Evaluator methods as they stand: nothing here is on a driver's path.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <vector>
 #include "capi_internal.h"
 
@@ -32,16 +33,8 @@ std::vector<PtPtr> pts_in(const fhelin_pt* const* v, int n, bool nullable = fals
     }
     return in;
 }
-}  // namespace
-
-extern "C" {
-
-int fhelin_debug_pt_from_residues(fhelin_ctx* c, const uint64_t* residues, int32_t ell, fhelin_pt** out) {
-    NEED(c && residues && out);
-    FHELIN_TRY
-    Context& x = c->ctx;
-    x.require_device();
-    if (ell < 1 || ell > x.L + 1) throw Error(FHELIN_ERR_ARG, "pt_from_residues: bad limb count");
+// a plaintext whose one encoding is residues [ell][N] at `scale`; ell = L + 1 + K: over the full key basis (limb ids 0 .. L + K)
+fhelin_pt* pt_from_residues(Context& x, const uint64_t* residues, int ell, long double scale) {
     const size_t N = x.N;
     for (int l = 0; l < ell; ++l)
         for (size_t n = 0; n < N; ++n)
@@ -49,7 +42,7 @@ int fhelin_debug_pt_from_residues(fhelin_ctx* c, const uint64_t* residues, int32
     auto e = std::make_shared<Encoding>();
     e->ctx = &x;
     e->ell = ell;
-    e->scale = x.sf_real[x.L + 1 - ell];   // what dot_plain* asks for at this limb count
+    e->scale = scale;
     e->d = x.dalloc<u64>((size_t)ell * N);
     hip_check(hipMemcpyAsync(e->d, residues, (size_t)ell * N * 8, hipMemcpyHostToDevice, x.stream), "pt import");
     e->made_lane = x.pool.cur_lane;
@@ -63,12 +56,34 @@ int fhelin_debug_pt_from_residues(fhelin_ctx* c, const uint64_t* residues, int32
     auto p = std::make_shared<Plaintext>();
     p->ctx = &x;
     p->slots = 1 << x.prm.log_slots;
-    p->level = x.L + 1 - ell;
+    p->level = std::max(0, x.L + 1 - ell);
     p->fixed = true;
     p->cache.push_back(e);
     auto* h = new fhelin_pt;
     h->p = p;
-    *out = h;
+    return h;
+}
+}  // namespace
+
+extern "C" {
+
+int fhelin_debug_pt_from_residues(fhelin_ctx* c, const uint64_t* residues, int32_t ell, fhelin_pt** out) {
+    NEED(c && residues && out);
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    if (ell < 1 || ell > x.L + 1) throw Error(FHELIN_ERR_ARG, "pt_from_residues: bad limb count");
+    *out = pt_from_residues(x, residues, ell, x.sf_real[x.L + 1 - ell]);   // the scale dot_plain* asks for at this limb count
+    FHELIN_CATCH
+}
+
+int fhelin_debug_pt_from_residues_full(fhelin_ctx* c, const uint64_t* residues, double scale_hi, double scale_lo, fhelin_pt** out) {
+    NEED(c && residues && out);
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    if (!(scale_hi > 0)) throw Error(FHELIN_ERR_ARG, "pt_from_residues_full: the full-basis encoding needs an explicit scale");
+    *out = pt_from_residues(x, residues, x.L + 1 + x.K, (long double)scale_hi + (long double)scale_lo);
     FHELIN_CATCH
 }
 

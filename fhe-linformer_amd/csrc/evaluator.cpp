@@ -615,6 +615,139 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
     });
 }
 
+std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xin, const std::vector<std::vector<PtPtr>>& pts,
+                                                    const std::vector<int>& baby, const std::vector<int>& giant, bool rescale_out) {
+    const int n1 = (int)baby.size(), n2 = (int)giant.size();
+    if (n1 < 1 || n1 > LtDot::MAX_STEPS || n2 < 1 || (int)pts.size() != n2 || baby[0] != 0)
+        throw Error(FHELIN_ERR_ARG, "linear_transform_rows: 1..32 baby steps (the first unrotated), >= 1 giant steps, pts [n2][n1]");
+    for (const auto& row : pts)
+        if ((int)row.size() != n1) throw Error(FHELIN_ERR_ARG, "linear_transform_rows: pts [n2][n1]");
+    c_.require_device();
+    if (c_.stride != 1) throw Error(FHELIN_ERR_STATE, "linear_transform_rows: interleaved samples (slot stride != 1) are not supported");
+    if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "hybrid key switching needs at least one special prime");
+    if (xin.empty()) return {};
+    const int ns = slot_count(xin[0]);
+    // every key the call needs, before anything runs: the baby steps that carry a term, the rotated giant steps
+    struct Step {
+        int b;
+        const EvalKey* key;
+        const u32* map;
+    };
+    std::vector<Step> steps;
+    for (int b = 0; b < n1; ++b) {
+        bool any = false;
+        for (int g = 0; g < n2; ++g) any = any || pts[g][b];
+        if (!any) continue;
+        if (b > 0 && baby[b] % ns == 0) throw Error(FHELIN_ERR_ARG, "linear_transform_rows: a baby step by 0 is the unrotated term (baby[0])");
+        if (b == 0) {
+            steps.push_back(Step{0, nullptr, nullptr});
+        } else {
+            const RotKey rk = rotation_key(baby[b]);
+            steps.push_back(Step{b, rk.key.get(), rk.map});
+        }
+    }
+    if (steps.empty()) throw Error(FHELIN_ERR_ARG, "linear_transform_rows: no term");
+    for (int g : giant)
+        if (g % ns != 0) (void)rotation_key(g);
+    std::vector<CtPtr> x = xin;
+    rescale_degree2(x, nullptr, "linear_transform_rows: ciphertext must have 2 components");   // as before any product with a plaintext
+    const size_t N = c_.N;
+    const int K = c_.K, nl = c_.L + 1 + K;
+    std::vector<CtPtr> out = for_groups(x.size(), std::max(1, batch_limit / n2), [&](size_t f, size_t i) { return same_shape(*x[f], *x[i]); },
+                                        [&](const std::vector<size_t>& idx) {
+        const std::vector<CtPtr> chunk = make_contiguous(pick(x, idx), 0);
+        const int B = (int)chunk.size(), ell = chunk[0]->ell;
+        const size_t pn = (size_t)ell * N, ctw = 2 * pn;
+        const long double sf = c_.sf_real[chunk[0]->level()];
+        // the diagonals over the full key basis at this level's scale: made on first use, kept by the plan's plaintexts
+        std::vector<std::shared_ptr<Encoding>> enc((size_t)n2 * n1);
+        size_t terms = 0;
+        for (int g = 0; g < n2; ++g)
+            for (int b = 0; b < n1; ++b)
+                if (pts[g][b]) {
+                    enc[(size_t)g * n1 + b] = pts[g][b]->at(nl, sf);
+                    ++terms;
+                }
+        std::vector<CtPtr> o = new_ct_batch(B * n2, 2, ell, chunk[0]->deg + 1, chunk[0]->scale * sf, chunk[0]->slots);
+        const u64* base = chunk[0]->d;
+        KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, ctw, ctw, pn, ctw};
+        c_.stats.ct_pt_mult += (u64)B * terms;
+        c_.stats.ct_pt_limbs += (u64)B * terms * ell;
+        {
+            Scratch<u64> ext = modup(sh, base + pn, false);   // of c1, once for all baby steps and groups
+            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * n2 * 2 * ell * N);
+            Scratch<u64> accP = c_.scratch<u64>((size_t)B * n2 * 2 * K * N);
+            std::vector<Scratch<u64>> tabs;
+            for (int g0 = 0; g0 < n2; g0 += LtStep::MAX_G) {
+                LtDot ld;
+                ld.n_groups = std::min((int)LtStep::MAX_G, n2 - g0);
+                ld.g0 = g0;
+                ld.groups = n2;
+                ld.pmod = c_.d_pmod;
+                std::vector<LtStep> tab;
+                for (const Step& st : steps) {
+                    LtStep e{};
+                    if (st.b) {
+                        e.key = permuted(*st.key, st.map);
+                        e.map = st.map;
+                    }
+                    for (int g = 0; g < ld.n_groups; ++g)
+                        if (const auto& v = enc[(size_t)(g0 + g) * n1 + st.b]) {
+                            e.v[g] = v->d;
+                            e.mask |= 1u << g;
+                        }
+                    if (e.mask) tab.push_back(e);
+                }
+                // accounting: a launch forms the key product of each of its rotated steps once per row - with n2 > MAX_G a baby step
+                // is counted (and its key streamed) once per launch that carries one of its terms
+                u64 rotated = 0;
+                for (const LtStep& e : tab) rotated += e.key ? 1 : 0;
+                c_.stats.keyswitch += (u64)B * rotated;
+                c_.stats.keyswitch_limbs += (u64)B * rotated * ell;
+                static_assert(sizeof(LtStep) % sizeof(u64) == 0, "the table is uploaded as 64-bit words");
+                if (!tab.empty()) {     // a launch without steps writes the zero sums of its (empty) groups
+                    const size_t words = tab.size() * sizeof(LtStep) / sizeof(u64);
+                    tabs.push_back(c_.scratch<u64>(words));
+                    c_.upload_async(tabs.back(), reinterpret_cast<const u64*>(tab.data()), words);
+                    ld.steps = reinterpret_cast<const LtStep*>((const u64*)tabs.back());
+                    ld.n_steps = (int)tab.size();
+                }
+                launch_ks_inner_dot(c_.dt, sh, ld, accQ, accP, ext, base, base + pn, c_.stream);
+            }
+            KsShape md = sh;
+            md.batch = B * n2;      // ONE ModDown over rows x groups, identity output map
+            // identity output map: the finish rides in the row pass under the predicate keyswitch_impl uses for its identity ModDowns
+            moddown(md, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, c_.fuse_moddown || c_.fuse_finish);
+            launch_ok("linear_transform_rows");
+        }
+        // the giant steps: sum_g rot(inner_g, giant[g]) as rotate_each_sum forms it - unrotated groups first, then the rotated ones in
+        // groups of <= 7 per shared ModDown (a single leftover through a plain rotation), the rows of the chunk in every launch
+        std::vector<int> plain, rot;
+        for (int g = 0; g < n2; ++g) (giant[g] % ns == 0 ? plain : rot).push_back(g);
+        auto rows_of = [&](const std::vector<int>& gs) {
+            std::vector<std::vector<CtPtr>> rows(B);
+            for (int b = 0; b < B; ++b) {
+                for (int g : gs) {
+                    o[(size_t)b * n2 + g]->scale = x[idx[b]]->scale * sf;
+                    rows[b].push_back(o[(size_t)b * n2 + g]);
+                }
+            }
+            return rows;
+        };
+        std::vector<CtPtr> acc;
+        for (size_t lo = 0; lo == 0 || lo < rot.size(); lo += KsShape::MAX_ROT) {
+            std::vector<int> gs = lo == 0 ? plain : std::vector<int>();
+            gs.insert(gs.end(), rot.begin() + std::min(lo, rot.size()), rot.begin() + std::min(lo + KsShape::MAX_ROT, rot.size()));
+            std::vector<int> gi;
+            for (int g : gs) gi.push_back(giant[g]);
+            std::vector<CtPtr> t = rotate_each_sum_rows(rows_of(gs), gi);
+            acc = acc.empty() ? t : add_batch(acc, t);
+        }
+        return acc;
+    });
+    return rescale_out ? rescale_batch(out) : out;
+}
+
 CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vector<int>& indices) {
     if (vin.empty() || vin.size() != indices.size()) throw Error(FHELIN_ERR_ARG, "rotate_each_sum: one index per ciphertext");
     const int ns = slot_count(vin[0]);

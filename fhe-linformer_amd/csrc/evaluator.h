@@ -188,6 +188,13 @@ public:
     // function from hoisted_dot_rows + rescale (one rounding instead of two), same value up to rounding noise.
     std::vector<CtPtr> hoisted_dot_rows(const std::vector<CtPtr>& xs, const std::vector<PtPtr>& pts, const std::vector<int>& indices,
                                         bool rescale_out = false);
+    // baby-step/giant-step matrix x ciphertext, the baby steps shared in QP (include/fhelin.h "Linear transforms"):
+    //     out[r] = sum_g rot( xs[r] * pts[g][0] + sum_{b>0} rot(xs[r], baby[b]) * pts[g][b],  giant[g] )
+    // pts [n2][n1], null = term absent; baby[0] == 0; n1 <= 32.  ONE ModUp per row, the inner sums of all groups from the rotation keys
+    // as they are (launch_ks_inner_dot: no folded keys, no rotated ciphertext in memory), ONE ModDown over rows x groups, then the
+    // giant steps through rotate_each_sum_rows.  The residues of rotate_each_sum([hoisted_dot(x, pts[g], baby[1:]) for g], giant).
+    std::vector<CtPtr> linear_transform_rows(const std::vector<CtPtr>& xs, const std::vector<std::vector<PtPtr>>& pts,
+                                             const std::vector<int>& baby, const std::vector<int>& giant, bool rescale_out = false);
     // the power steps of a Chebyshev evaluation and EvalMod's double angle through mult_affine_rescale_batch.  OFF by default
     // (FHELIN_MERGED_PRODUCTS=1 turns it on): measured at no gain (282.0 vs 281.2 ms per pass: the launches it saves are replaced by its
     // own) and at 3 x the logit error (0.017 vs 0.006: the merged conversion's rounding has three times the standard deviation of a

@@ -248,6 +248,34 @@ struct HoistAdd {
     const u64* pmod = nullptr;
 };
 void launch_hoist_addends(const DeviceTables& t, const KsShape& sh, const HoistAdd& h, u64* pre, const u64* ct, hipStream_t s);
+// ---- linear transforms (Evaluator::linear_transform_rows): the inner sums of up to MAX_G giant-step groups of a baby-step/giant-step
+// matrix product in ONE pass over the baby steps' keys, with the keys as they are (no folded copies):
+//     acc_g[c][t][n] = sum_b V_{g,b}[t][n] * W_b[c][t][n],    W_b = sigma_b(<digits, evk_b>) + P * sigma_b((c0, 0))   (b rotated)
+//                                                             W_0 = P * (c0, c1)                                        (the unrotated term)
+// (the P multiples on the Q limbs only: they pass through the ModDown as the addends V_{g,0} c + sum_b V_{g,b} sigma_b(c0) of
+// launch_hoist_addends).  W_b is formed once per coefficient, in registers, and multiplied into every group's 128-bit sum; the rotated
+// ciphertexts never exist in memory.  The steps come in a DEVICE table (n reaches 32: past KsShape's fixed arrays); an absent term
+// (mask bit clear) is skipped and contributes nothing.  Output: the accumulator pair of batch row bi, group g at row bi * groups + g0 + g
+// of accQ [.][2][ell][N] / accP [.][2][k][N], ready for ONE ModDown over rows x groups.
+struct LtStep {
+    static constexpr int MAX_G = 4;
+    const u64* key;         // EvalKey::d_perm of the step's rotation key; nullptr: the unrotated term
+    const u32* map;         // the rotation's automorphism map
+    const u64* v[MAX_G];    // V_{g,b} over the FULL key basis [L1 + k][N], NTT form, for the launch's groups
+    u32 mask;               // bit g: the term (g, b) is present
+    u32 pad;
+};
+struct LtDot {
+    static constexpr int MAX_STEPS = 32;   // 128-bit group sums: 32 products of residues below 2^60 stay below 2^125 (modarith.h Acc128)
+    const LtStep* steps = nullptr;         // device, [n_steps]
+    int n_steps = 0;
+    int n_groups = 0;                      // groups of this launch (<= LtStep::MAX_G)
+    int g0 = 0, groups = 0;                // first group of the launch, groups per batch row in accQ / accP
+    const u64* pmod = nullptr;             // [L+1][2] P mod q_t, shoup
+};
+// c0 / c1: the two components of batch row b at + b * sh.c_stride; ext: the digits of c1 from modup (not times 2^64)
+void launch_ks_inner_dot(const DeviceTables& t, const KsShape& sh, const LtDot& ld, u64* accQ, u64* accP, const u64* ext, const u64* c0,
+                         const u64* c1, hipStream_t s);
 // K8a: accP coefficient form [2][k][N] -> conv [2][ell][N] (coefficient form); sh.gather: with the signs of the row's automorphism
 void launch_moddown_conv(const DeviceTables& t, const KsShape& sh, u64* conv, const u64* accP, const u64* phatinv, const u64* phatmod,
                          hipStream_t s);

@@ -426,6 +426,126 @@ __global__ __launch_bounds__(256) void ks_inner_multi_kernel(DeviceTables t, KsS
     }
 }
 
+// grid (N/512, batch*(ell + k)), the geometry and block order of ks_inner_multi_kernel: the coefficient pair (2m, 2m+1) per thread, digit
+// pairs gathered with one 16-byte load and swapped by the SGPR mask, keys from EvalKey::d_perm (contiguous, pre-split, times 2^64).
+// Per step b of the device table (LtDot): the beta digit products as ks_inner_kernel<true> forms them, ONE Montgomery reduction for the
+// four words of W_b = sigma_b(d . evk_b) (+ P sigma_b(c0) on a Q limb), then one 64 x 64 -> 128 multiply-accumulate per word into the
+// sums of the launch's <= G groups, whose plaintext pair V_{g,b}[limb] comes with one 16-byte load.  The table entries and masks are
+// wave-uniform (scalar loads, scalar branches).  Registers: 16 VGPRs of sums per group.
+// Bounds.  Digit products: the redc128 of a step needs a sum below q * 2^64; keys are canonical, digits canonical for q >= 2^53 and below
+// 86q (lazy forward NTT) for q < 2^53: 16 products plus one carried residue stay below 16 q^2 + q < q * 2^64 (q < 2^60) and
+// 16 * 86 q^2 + q < q * 2^64 (q < 2^53) - a chain of more than 16 digits is folded every 16 (the fold reduces, it does not divide: the
+// factor 2^64 stays).  Group sums: W_b and V are canonical, below 2^60; LtDot::MAX_STEPS = 32 products stay below 2^125, no carry is
+// lost, and barrett_reduce128 takes any 128-bit value: one reduction per group at the end, no fold.
+template <int G>
+__global__ __launch_bounds__(256) void ks_inner_dot_kernel(DeviceTables t, KsShape sh, LtDot ld, u64* __restrict__ accQ, u64* __restrict__ accP,
+                                                           const u64* __restrict__ ext, const u64* __restrict__ c0, const u64* __restrict__ c1) {
+    const int nt = sh.ell + sh.k;
+    const KsBlock kb_ = ks_block(sh);
+    const int bi = kb_.bi, tt = kb_.tt;
+    const bool isq = tt < sh.ell;
+    const int limb = isq ? tt : sh.L1 + (tt - sh.ell);
+    const size_t N = (size_t)1 << t.log_n, row = N >> 1;
+    const int own = isq ? tt / sh.alpha : -1;
+    const Barrett br = load_barrett(t, limb);
+    const u64 qi = t.qinv[limb];
+    const size_t n2 = (size_t)kb_.bx * 256 + threadIdx.x;
+    const size_t kstride = (size_t)(sh.L1 + sh.k) * row;  // one evk component, in u64x2 units
+    const u64x2* __restrict__ E = reinterpret_cast<const u64x2*>(ext + (size_t)bi * sh.beta * nt * N);
+    const u64x2* __restrict__ C0 = reinterpret_cast<const u64x2*>(c0 + (size_t)bi * sh.c_stride);
+    const u64x2* __restrict__ C1 = reinterpret_cast<const u64x2*>(c1 + (size_t)bi * sh.c_stride);
+    const u64 pw = isq ? ld.pmod[2 * tt] : 0, pws = isq ? ld.pmod[2 * tt + 1] : 0;
+    Acc128 sum[G][4];      // b.x, b.y, a.x, a.y per group
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sum[g][i] = Acc128{0, 0};
+    for (int b = 0; b < ld.n_steps; ++b) {
+        const LtStep& st = ld.steps[b];
+        u64 w[4];
+        if (!st.key) {     // the unrotated term: P (c0, c1) on the Q limbs, nothing on the special limbs
+            if (!isq) continue;
+            const u64x2 x0 = C0[(size_t)tt * row + n2], x1 = C1[(size_t)tt * row + n2];
+            w[0] = mul_shoup(x0.x, pw, pws, br.q);
+            w[1] = mul_shoup(x0.y, pw, pws, br.q);
+            w[2] = mul_shoup(x1.x, pw, pws, br.q);
+            w[3] = mul_shoup(x1.y, pw, pws, br.q);
+        } else {
+            const u32 m0 = st.map[2 * n2];
+            const size_t mp = m0 >> 1;
+            const unsigned long long swp = __ballot((m0 & 1) != 0);
+            const u64x2* __restrict__ K = reinterpret_cast<const u64x2*>(st.key) + (size_t)limb * row + n2;
+            u64 lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+            for (int j0 = 0; j0 < sh.beta; j0 += 8) {
+                Acc30 b0 = {0, 0, 0}, b1 = {0, 0, 0}, a0 = {0, 0, 0}, a1 = {0, 0, 0};
+                const int j1 = min(sh.beta, j0 + 8);
+                for (int j = j0; j < j1; ++j) {
+                    const u64x2 d = j == own ? C1[(size_t)tt * row + mp] : E[((size_t)j * nt + tt) * row + mp];
+                    const u64x2 kb = K[(size_t)(2 * j) * kstride];
+                    const u64x2 ka = K[(size_t)(2 * j + 1) * kstride];
+                    u32 p0, p1, q0, q1;
+                    split30(d.x, p0, p1);
+                    split30(d.y, q0, q1);
+                    // element 2m of the rotated digit is d.x, or d.y when the map sends 2m to an odd position
+                    const u32 dx0 = sel_mask(p0, q0, swp), dx1 = sel_mask(p1, q1, swp), dy0 = sel_mask(q0, p0, swp), dy1 = sel_mask(q1, p1, swp);
+                    mac30(b0, dx0, dx1, (u32)kb.x, (u32)(kb.x >> 32));
+                    mac30(b1, dy0, dy1, (u32)kb.y, (u32)(kb.y >> 32));
+                    mac30(a0, dx0, dx1, (u32)ka.x, (u32)(ka.x >> 32));
+                    mac30(a1, dy0, dy1, (u32)ka.y, (u32)(ka.y >> 32));
+                }
+                acc30_flush(b0, lo[0], hi[0]);
+                acc30_flush(b1, lo[1], hi[1]);
+                acc30_flush(a0, lo[2], hi[2]);
+                acc30_flush(a1, lo[3], hi[3]);
+                if ((j0 & 8) && j1 < sh.beta) {   // 16 products in the sums and more to come
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        lo[i] = barrett_reduce128(lo[i], hi[i], br);
+                        hi[i] = 0;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) w[i] = redc128(lo[i], hi[i], br.q, qi);   // the keys carry 2^64: the canonical residue of the plain sum
+            if (isq) {     // + P sigma_b(c0)
+                const u64x2 gp = C0[(size_t)tt * row + mp];
+                w[0] = add_mod(w[0], mul_shoup((m0 & 1) ? gp.y : gp.x, pw, pws, br.q), br.q);
+                w[1] = add_mod(w[1], mul_shoup((m0 & 1) ? gp.x : gp.y, pw, pws, br.q), br.q);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if ((st.mask >> g) & 1) {
+                // canonical residues: plaintext encodings come from the plain forward NTT (never LimbBatch::lazy_out), which the 2^125 bound needs
+                const u64x2 v = reinterpret_cast<const u64x2*>(st.v[g])[(size_t)limb * row + n2];
+                acc_mac(sum[g][0], w[0], v.x);
+                acc_mac(sum[g][1], w[1], v.y);
+                acc_mac(sum[g][2], w[2], v.x);
+                acc_mac(sum[g][3], w[3], v.y);
+            }
+    }
+    const int pj = tt - sh.ell;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (g >= ld.n_groups) break;
+        u64x2 rb, ra;
+        rb.x = barrett_reduce128(sum[g][0].lo, sum[g][0].hi, br);
+        rb.y = barrett_reduce128(sum[g][1].lo, sum[g][1].hi, br);
+        ra.x = barrett_reduce128(sum[g][2].lo, sum[g][2].hi, br);
+        ra.y = barrett_reduce128(sum[g][3].lo, sum[g][3].hi, br);
+        const size_t orow = (size_t)bi * ld.groups + ld.g0 + g;
+        if (isq) {
+            u64x2* O = reinterpret_cast<u64x2*>(accQ + orow * 2 * sh.ell * N);
+            O[(size_t)tt * row + n2] = rb;
+            O[(size_t)(sh.ell + tt) * row + n2] = ra;
+        } else {
+            u64x2* O = reinterpret_cast<u64x2*>(accP + orow * 2 * sh.k * N);
+            O[(size_t)pj * row + n2] = rb;
+            O[(size_t)(sh.k + pj) * row + n2] = ra;
+        }
+    }
+}
+
 // grid (N/256, 2, ceil(ell/TCH)).  MAXK = number of special limbs (exact for k <= 8, then FULL: no per-source conditions)
 // SIGNED (KsShape::gather): accP holds sigma_g of the accumulator; where sigma_g negates (neg) the sources are un-negated, converted
 // and the result negated, which is sigma_g of the plain conversion - conv(p - x) alone is off by a multiple of P.
@@ -897,6 +1017,16 @@ void launch_ks_inner_multi(const DeviceTables& t, const KsShape& sh, u64* accQ, 
         hipLaunchKernelGGL((ks_inner_multi_kernel<true, 1>), g, dim3(256), 0, s, t, sh, accQ, accP, ext, c_ntt);
     else
         hipLaunchKernelGGL((ks_inner_multi_kernel<false, 1>), g, dim3(256), 0, s, t, sh, accQ, accP, ext, c_ntt);
+}
+void launch_ks_inner_dot(const DeviceTables& t, const KsShape& sh, const LtDot& ld, u64* accQ, u64* accP, const u64* ext, const u64* c0,
+                         const u64* c1, hipStream_t s) {
+    dim3 g((1u << t.log_n) / 512, (unsigned)(sh.batch * (sh.ell + sh.k)));
+    if (ld.n_groups == 1)
+        hipLaunchKernelGGL(ks_inner_dot_kernel<1>, g, dim3(256), 0, s, t, sh, ld, accQ, accP, ext, c0, c1);
+    else if (ld.n_groups == 2)
+        hipLaunchKernelGGL(ks_inner_dot_kernel<2>, g, dim3(256), 0, s, t, sh, ld, accQ, accP, ext, c0, c1);
+    else
+        hipLaunchKernelGGL((ks_inner_dot_kernel<LtStep::MAX_G>), g, dim3(256), 0, s, t, sh, ld, accQ, accP, ext, c0, c1);
 }
 void launch_moddown_conv(const DeviceTables& t, const KsShape& sh_in, u64* conv, const u64* accP, const u64* phatinv, const u64* phatmod,
                          hipStream_t s) {

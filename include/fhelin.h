@@ -295,6 +295,41 @@ int fhelin_mult_affine_batch(fhelin_ctx* c, const fhelin_ct* const* a, const fhe
                              const fhelin_ct* const* addend, const int32_t* negate, fhelin_ct** outs);
 int fhelin_level_reduce(fhelin_ctx* c, const fhelin_ct* a, int32_t new_ell, fhelin_ct** out);
 
+/* ---- Linear transforms: matrix x ciphertext by the diagonal method, baby-step/giant-step (OpenFHE EvalLinearTransform, Lattigo
+ * LinearTransform).  out = sum_d diag_d (.) rot(x, d), rot = EvalRotate (left rotation): M x for the matrix whose generalised diagonals are
+ * diag_d.  Every index splits as d = g + b with 0 <= b < n1; the term's plaintext is V_{g,b} = rot(diag_{g+b}, -g) and
+ *     inner_g = x V_{g,0} + sum_{b>0} rot(x, b) V_{g,b},        out = sum_g rot(inner_g, g)      (g = 0: a plain addend).
+ * The baby steps share ONE decomposition of x and their key products are formed once, in the extended basis QP, for all groups: no
+ * rotated ciphertext and no plaintext-folded key is ever stored, and a call costs one ModDown per group plus one per <= 7 rotated groups.
+ *
+ * A plan (fhelin_lt) is host data: the split, the two index lists and one plaintext per term.  Creating one needs no device; the
+ * encodings over the full key basis are made on first use per (limb count, scale) and stay with the plan's plaintexts.
+ *
+ * fhelin_lt_create: diags [n_diag][slots], diag_idx [n_diag] (reduced mod slots; duplicates, n_diag < 1, a slots that is not the
+ * context's packing, n1 outside 0..32 and non-finite values are FHELIN_ERR_ARG); n1 = 0 lets the planner choose n1 <= 32.  It builds
+ * the V_{g,b} and calls fhelin_lt_create_pts, the one constructor: pts [n2][n1] (NULL = term absent), baby [n1] with baby[0] == 0,
+ * giant [n2], indices distinct mod slots.  The plan shares the plaintexts: the caller's handles may be freed afterwards.
+ * fhelin_lt_rotations: the EvalRotateKeyGen list the plan needs (baby steps that carry a term, rotated giant steps); *n = its length,
+ * min(cap, *n) entries written.
+ *
+ * fhelin_lt_apply: outs[i] = the transform of v[i]; rows of one shape share every launch.  Bit for bit - limbs, noise degree, scale -
+ *     fhelin_rotate_each_sum([ fhelin_hoisted_dot(v[i], {V_{g,0..n1-1}}, baby[1..], rescale = 0) for g ], giant)
+ * as oracle/residue_eval.py states the two (hoisted_dot reaches only 7 rotations through this ABI; the oracle takes any number): a
+ * degree-2 input is rescaled first, the result has noise degree + 1 and scale x the level's plaintext scale; an absent term contributes
+ * what a plaintext of zeros would.  rescale != 0: the final sum goes through fhelin_rescale.
+ * Errors: a missing rotation key FHELIN_ERR_KEY naming the index; an interleave stride other than 1 FHELIN_ERR_STATE; no device
+ * FHELIN_ERR_NO_DEVICE.  A failed call launches nothing that outlives it, returns no handle and leaves the level plan as it was.
+ * Works on an evaluation context (fhelin_evalkeys_load). */
+typedef struct fhelin_lt fhelin_lt;
+int fhelin_lt_create(fhelin_ctx* c, const double* diags /* [n_diag][slots] */, const int32_t* diag_idx, int32_t n_diag, int32_t slots,
+                     int32_t n1 /* 0 = choose */, fhelin_lt** out);
+int fhelin_lt_create_pts(fhelin_ctx* c, const fhelin_pt* const* pts /* [n2][n1], NULL = absent */, const int32_t* baby /* [n1], baby[0] == 0 */,
+                         const int32_t* giant /* [n2] */, int32_t n1, int32_t n2, fhelin_lt** out);
+int fhelin_lt_info(const fhelin_lt* lt, int32_t* n1, int32_t* n2, int32_t* n_terms, int32_t* slots);
+int fhelin_lt_rotations(const fhelin_lt* lt, int32_t* out, int32_t cap, int32_t* n);
+int fhelin_lt_apply(fhelin_ctx* c, const fhelin_lt* lt, const fhelin_ct* const* v, int32_t n, int32_t rescale, fhelin_ct** outs);
+void fhelin_lt_free(fhelin_lt* lt);
+
 /* ---- the same residue functions without scale/level bookkeeping (bit-exact parity vs oracle/) -- */
 int fhelin_raw_rescale(fhelin_ctx* c, const fhelin_ct* a, fhelin_ct** out);                      /* K5            */
 int fhelin_raw_rotate(fhelin_ctx* c, const fhelin_ct* a, int32_t index, fhelin_ct** out);        /* K4 + K6-K8    */
@@ -313,6 +348,9 @@ int fhelin_raw_phase(fhelin_ctx* c, const fhelin_ct* a, fhelin_ct** out);
  * and the scale the inner sums ask for at that limb count (Delta of level n_q - ell).  It has no slot values: used at any other (limb
  * count, scale) it fails with FHELIN_ERR_STATE.  It never enters the content-keyed plaintext cache of fhelin_encode. */
 int fhelin_debug_pt_from_residues(fhelin_ctx* c, const uint64_t* residues, int32_t ell, fhelin_pt** out);
+/* the same over the FULL key basis: residues [n_q + n_p][N] (Q limbs, then the special limbs) at the scale scale_hi + scale_lo - what
+ * fhelin_hoisted_dot and fhelin_lt_apply ask a plaintext for (the level's Delta, exactly) */
+int fhelin_debug_pt_from_residues_full(fhelin_ctx* c, const uint64_t* residues, double scale_hi, double scale_lo, fhelin_pt** out);
 /* out = sum_i cts[i] * pts[i]: one launch per 32 terms */
 int fhelin_debug_dot_plain(fhelin_ctx* c, const fhelin_ct* const* cts, const fhelin_pt* const* pts, int32_t n, fhelin_ct** out);
 /* outs[x][g] = sum_b cts[x][b] * pts[g][b] for x < nb, g < ng (na <= 16 columns, ng <= 8 groups; pts[g][b] NULL = term absent) in ONE
