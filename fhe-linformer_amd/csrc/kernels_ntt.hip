@@ -24,8 +24,14 @@
 // read out of place and strided (LimbBatch::src / src_group), which is how key switching and rescale avoid staging
 // copies.  The row pass maps workgroups to (limb, tile, repetition) in XCD-contiguous order so that the 4 KiB
 // twiddle slice of a (limb, tile) is shared by the vectors of a batch in one L2.
-// Measured (profiles/): 1.95 M limb-NTT/s at N=2^16, bound by VALU issue slots (88 % busy; 15 VALU
-// instructions per lazy butterfly, 9 of them 32x32 multiplies), 2.07x algorithmic HBM traffic (two passes + twiddles).
+// Addressing: every global access is a workgroup-uniform 64-bit base held in SGPRs (a raw buffer descriptor per stream), one 32-bit
+// lane offset per register window and a per-slot constant in the instruction's immediate / scalar offset; the LDS exchanges form one
+// lane address per window and take the slot from the instruction's offset; limb, tile and vector bookkeeping runs on the scalar unit.
+// Measured (profiles/): 2.11-2.17 M limb-NTT/s at N=2^16 (1.97-2.02 M before the addressing above).  A lazy
+// forward pass issues 935 (columns) / 1123 (rows) VALU instructions per thread, 576 / 626 of them the butterflies' multiplies and
+// 320 their other arithmetic (14 per butterfly, 9 of them 32x32 multiplies); the vector pipe is busy 79 % (columns) and 74 % (rows)
+// of the time with 4 waves per SIMD - it was 88 % and 82 % - and the launches of a forward pass that fill the GPU move their tiles
+// at about 5 TB/s.  2.07x algorithmic HBM traffic (two passes + twiddles).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -74,17 +80,62 @@ constexpr int LDS_WORDS = TILE + TILE / 16;
 
 // tile-local element index held by thread tau in register slot k when the 4-bit register window
 // sits at bit p of the index
-__device__ __forceinline__ int tile_index(int tau, int k, int p) {
+__device__ __forceinline__ constexpr int tile_index(int tau, int k, int p) {
     return ((tau >> p) << (p + 4)) | (k << p) | (tau & ((1 << p) - 1));
 }
 // one pad word per 16 residues keeps every exchange pattern used below bank-conflict free
-__device__ __forceinline__ int lds_slot(int e) { return e + (e >> 4); }
+__device__ __forceinline__ constexpr int lds_slot(int e) { return e + (e >> 4); }
 
 __device__ __forceinline__ int limb_of(const NttArgs& a, int vec) {
     return a.limb_tab ? a.limb_tab[a.tab_len ? vec % a.tab_len : vec] : a.limb_first + (vec % a.limb_count);
 }
 
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+
+// ---- addressing: uniform base + 32-bit lane offset + immediate -------------------------------------------
+// Every global access of the tile passes is  base(vector, tile, limb, ...) + lane(tau) + K(k)  in bytes.  The base is the same
+// for the whole workgroup: it is computed once as a 64-bit value, pinned to SGPRs and wrapped in a raw buffer descriptor (Stream:
+// stride 0, no bound, so an access is plain base + offset).  The lane part is one unsigned byte offset (tile-local, or below
+// N * 8 <= 2^20 for the automorphism scatter), formed once per window.  K depends only on the register slot k: a compile-time
+// constant whose low 12 bits are the instruction's immediate and whose rest, with any further workgroup-uniform offset, is the
+// instruction's scalar offset.  The result is  buffer_load/store v_lane, s[desc], s_off offen offset:imm : no vector
+// instruction per access.  Only tile-local quantities go into the 32-bit parts: vec << log_n (bytes) passes 2^32 from 8192
+// vectors at N = 2^16 and stays in the 64-bit base.  (Plain global accesses do not get there: with constants beyond the 13-bit
+// immediate the compiler goes back to one 64-bit vector address per access.)
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+struct Stream {
+    __amdgpu_buffer_rsrc_t r;
+};
+__device__ __forceinline__ Stream stream(const void* ubase) {
+    const u64 v = reinterpret_cast<u64>(ubase);
+    const u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
+    Stream s;
+    s.r = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((u64)hi << 32) | lo), 0, 0xffffffff, 0x00020000);
+    return s;
+}
+// K >= 0 constant, soff >= 0 workgroup-uniform; lane + soff + K < 2^32
+__device__ __forceinline__ u32 ld32(const Stream& s, u32 lane, int K, int soff = 0) {
+    return __builtin_amdgcn_raw_buffer_load_b32(s.r, lane + (K & 4095), soff + (K & ~4095), 0);
+}
+__device__ __forceinline__ u64 ld64(const Stream& s, u32 lane, int K, int soff = 0) {
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(s.r, lane + (K & 4095), soff + (K & ~4095), 0);
+    return ((u64)v.y << 32) | v.x;
+}
+__device__ __forceinline__ u64x2 ld128(const Stream& s, u32 lane, int K, int soff = 0) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(s.r, lane + (K & 4095), soff + (K & ~4095), 0);
+    u64x2 r;
+    r.x = ((u64)v.y << 32) | v.x;
+    r.y = ((u64)v.w << 32) | v.z;
+    return r;
+}
+__device__ __forceinline__ void st64(const Stream& s, u32 lane, int K, u64 x, int soff = 0) {
+    u32x2 v;
+    v.x = (u32)x;
+    v.y = (u32)(x >> 32);
+    __builtin_amdgcn_raw_buffer_store_b64(v, s.r, lane + (K & 4095), soff + (K & ~4095), 0);
+}
 
 // Per-limb constants of a block.
 struct LimbConst {
@@ -109,21 +160,26 @@ struct LimbConst {
 struct RoundTw {
     u64x2 t[15];
 };
+// hi = hi_u | hi_lane: its workgroup-uniform bits (the tile, row pass) and the thread's own.  One address per stage: the uniform
+// part of m + (hi << (3 - kb)) is the scalar offset, the lane part is one shift, the 8 >> kb entries of a group are immediates 16 j.
 template <int KB_LO, int KB_HI>
-__device__ __forceinline__ void load_round_tw(RoundTw& r, const u64x2* __restrict__ tw, int log_n, int gbase, int hi) {
+__device__ __forceinline__ void load_round_tw(RoundTw& r, const Stream& tw, int log_n, int gbase, int hi_u, u32 hi_lane) {
 #pragma unroll
     for (int kb = KB_LO; kb < KB_HI; ++kb) {
         const int m = 1 << (log_n - (gbase + kb) - 1);
-        const int tbase = m + (hi << (3 - kb));
+        const int soff = 16 * (m + (hi_u << (3 - kb)));
+        const u32 lane = hi_lane << (7 - kb);   // 16 bytes x (hi_lane << (3 - kb))
 #pragma unroll
-        for (int j = 0; j < (8 >> kb); ++j) r.t[(8 >> kb) - 1 + j] = tw[tbase + j];
+        for (int j = 0; j < (8 >> kb); ++j) r.t[(8 >> kb) - 1 + j] = ld128(tw, lane, 16 * j, soff);
     }
 }
 
-// the per-thread twiddles of the row pass (global stage bits 0..3) from the transposed table: lanes read consecutive pairs
-__device__ __forceinline__ void load_round_tw_rows(RoundTw& r, const u64x2* __restrict__ trows, int tau) {
+// the per-thread twiddles of the row pass (global stage bits 0..3) from the transposed table: lanes read consecutive pairs;
+// the 4 KiB stage stride is stepped in the scalar offset
+__device__ __forceinline__ void load_round_tw_rows(RoundTw& r, const Stream& trows, int tau) {
+    const u32 lane = 16u * (u32)tau;
 #pragma unroll
-    for (int s = 0; s < 15; ++s) r.t[s] = trows[s * 256 + tau];
+    for (int s = 0; s < 15; ++s) r.t[s] = ld128(trows, lane, 4096 * s);
 }
 
 template <int KB, bool LAZY>
@@ -205,13 +261,17 @@ __device__ __forceinline__ void inv_round(u64 (&x)[16], const RoundTw& tw, const
     }
 }
 
+// The slot of (tau, k) is the slot of (tau, 0) plus the slot of (0, k): the two indices share no bit, so neither the sum nor its
+// pad term e >> 4 carries.  One lane address per window, the slot of (0, k) is the instruction's offset.
 __device__ __forceinline__ void exchange(u64 (&x)[16], u64* lds, int tau, int p_from, int p_to, bool sync_first) {
     if (sync_first) __syncthreads();
+    u64* const from = lds + lds_slot(tile_index(tau, 0, p_from));
 #pragma unroll
-    for (int k = 0; k < 16; ++k) lds[lds_slot(tile_index(tau, k, p_from))] = x[k];
+    for (int k = 0; k < 16; ++k) from[lds_slot(tile_index(0, k, p_from))] = x[k];
     __syncthreads();
+    const u64* const to = lds + lds_slot(tile_index(tau, 0, p_to));
 #pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = lds[lds_slot(tile_index(tau, k, p_to))];
+    for (int k = 0; k < 16; ++k) x[k] = to[lds_slot(tile_index(0, k, p_to))];
 }
 
 __device__ __forceinline__ LimbConst limb_const(const NttArgs& a, int limb) {
@@ -243,20 +303,22 @@ __device__ __forceinline__ void cols_body(const NttArgs& a, u64* lds, int vec, i
     constexpr int LOGN = A + 8;
     constexpr int NFULL = A / 4;
     constexpr int REM = A % 4;
-    const u64x2* tw = reinterpret_cast<const u64x2*>(a.tw) + ((size_t)limb << LOGN);
-    u64* base = a.data + ((size_t)vec << LOGN) + tile * CW;
-    const u64* sbase = (LIFT ? a.src + ((size_t)(vec / a.limb_count) << LOGN) : a.src + src_offset(a, vec, LOGN)) + tile * CW;
+    const Stream tw = stream(reinterpret_cast<const u64x2*>(a.tw) + ((size_t)limb << LOGN));
+    const Stream base = stream(a.data + ((size_t)vec << LOGN) + tile * CW);
+    const Stream sbase = stream((LIFT ? a.src + ((size_t)(vec / a.limb_count) << LOGN) : a.src + src_offset(a, vec, LOGN)) + tile * CW);
     const int tau = threadIdx.x;
     u64 x[16];
 
-    // global offset (relative to base) of tile-local index e
-    auto goff = [](int e) { return ((e >> LOGCW) << 8) | (e & (CW - 1)); };
+    // global byte offset (relative to base) of tile-local index e.  It moves index bits, so for the window at bit p
+    // goff(tile_index(tau, k, p)) = goff(tile_index(tau, 0, p)) + goff(tile_index(0, k, p)): a lane offset plus a constant
+    auto goff = [](int e) constexpr { return 8 * (((e >> LOGCW) << 8) | (e & (CW - 1))); };
 
     if (!INVERSE) {
         // windows (in tile-index bits), top down: LOGCW+A-4, LOGCW+A-8, ..., then the remainder at LOGCW
         constexpr int P0 = LOGCW + A - 4;
+        const u32 lane_in = goff(tile_index(tau, 0, P0));
 #pragma unroll
-        for (int k = 0; k < 16; ++k) x[k] = sbase[goff(tile_index(tau, k, P0))];
+        for (int k = 0; k < 16; ++k) x[k] = ld64(sbase, lane_in, goff(tile_index(0, k, P0)));
         if constexpr (LIFT) {
             // rescale: x is a coefficient modulo q_lift < 2 q (checked by the host): x mod q is one conditional subtraction,
             // the centred representative subtracts q_lift mod q where x > q_lift / 2  (== rescale_lift_kernel)
@@ -268,19 +330,19 @@ __device__ __forceinline__ void cols_body(const NttArgs& a, u64* lds, int vec, i
             }
         }
         RoundTw rt, rn;
-        load_round_tw<0, 4>(rt, tw, LOGN, 8 + P0 - LOGCW, tau >> P0);
+        load_round_tw<0, 4>(rt, tw, LOGN, 8 + P0 - LOGCW, 0, tau >> P0);
         fwd_round<0, 4, LAZY>(x, rt, c);
         int p_prev = P0;
         if constexpr (NFULL >= 2) {
             constexpr int P1 = LOGCW + A - 8;
-            load_round_tw<0, 4>(rn, tw, LOGN, 8 + P1 - LOGCW, tau >> P1);
+            load_round_tw<0, 4>(rn, tw, LOGN, 8 + P1 - LOGCW, 0, tau >> P1);
             exchange(x, lds, tau, p_prev, P1, false);
             fwd_round<0, 4, LAZY>(x, rn, c);
             p_prev = P1;
         }
         if constexpr (REM > 0) {
             constexpr int PR = LOGCW;
-            load_round_tw<0, REM>(rt, tw, LOGN, 8, tau >> PR);
+            load_round_tw<0, REM>(rt, tw, LOGN, 8, 0, tau >> PR);
             exchange(x, lds, tau, p_prev, PR, NFULL >= 2);
             fwd_round<0, REM, LAZY>(x, rt, c);
             p_prev = PR;
@@ -288,37 +350,40 @@ __device__ __forceinline__ void cols_body(const NttArgs& a, u64* lds, int vec, i
         // lazy path: values up to (1 + 5A)q go to memory as they are; the row pass bounds and reduces them
         constexpr int PL = REM > 0 ? LOGCW : (NFULL >= 2 ? LOGCW + A - 8 : P0);
         (void)p_prev;
+        const u32 lane_out = goff(tile_index(tau, 0, PL));
 #pragma unroll
-        for (int k = 0; k < 16; ++k) base[goff(tile_index(tau, k, PL))] = x[k];
+        for (int k = 0; k < 16; ++k) st64(base, lane_out, goff(tile_index(0, k, PL)), x[k]);
     } else {
         // inverse: bottom up.  full rounds at LOGCW, LOGCW+4, ...; remainder = top REM bits of the window at 8.
         // lazy path: the row pass hands over values below 2q (C0 = 2)
         const u64* ninv = a.ninv + 8 * limb;
         constexpr int P0 = LOGCW;
+        const u32 lane_in = goff(tile_index(tau, 0, P0));
 #pragma unroll
-        for (int k = 0; k < 16; ++k) x[k] = sbase[goff(tile_index(tau, k, P0))];
+        for (int k = 0; k < 16; ++k) x[k] = ld64(sbase, lane_in, goff(tile_index(0, k, P0)));
         RoundTw rt, rn;
-        load_round_tw<0, 4>(rt, tw, LOGN, 8, tau >> P0);
+        load_round_tw<0, 4>(rt, tw, LOGN, 8, 0, tau >> P0);
         inv_round<0, 4, (NFULL == 1 && REM == 0), LAZY, 0, 2>(x, rt, c, ninv);
         int p_prev = P0;
         if constexpr (NFULL >= 2) {
             constexpr int P1 = LOGCW + 4;
-            load_round_tw<0, 4>(rn, tw, LOGN, 8 + 4, tau >> P1);
+            load_round_tw<0, 4>(rn, tw, LOGN, 8 + 4, 0, tau >> P1);
             exchange(x, lds, tau, p_prev, P1, false);
             inv_round<0, 4, (REM == 0), LAZY, 4, 2>(x, rn, c, ninv);
             p_prev = P1;
         }
         if constexpr (REM > 0) {
             constexpr int PR = 8;  // window covers tile bits 8..11; its top REM bits are still to do
-            load_round_tw<4 - REM, 4>(rt, tw, LOGN, 8 + PR - LOGCW, tau >> PR);
+            load_round_tw<4 - REM, 4>(rt, tw, LOGN, 8 + PR - LOGCW, 0, tau >> PR);
             exchange(x, lds, tau, p_prev, PR, NFULL >= 2);
             inv_round<4 - REM, 4, true, LAZY, 4 * NFULL, 2>(x, rt, c, ninv);
             p_prev = PR;
         }
         constexpr int PL = REM > 0 ? 8 : (NFULL >= 2 ? LOGCW + 4 : P0);
         (void)p_prev;
+        const u32 lane_out = goff(tile_index(tau, 0, PL));
 #pragma unroll
-        for (int k = 0; k < 16; ++k) base[goff(tile_index(tau, k, PL))] = x[k];
+        for (int k = 0; k < 16; ++k) st64(base, lane_out, goff(tile_index(0, k, PL)), x[k]);
     }
 }
 
@@ -328,7 +393,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIFT ? 3 : 
     __shared__ u64 lds[LDS_WORDS];
     const int vec = a.vec0 + (blockIdx.x >> LOGTILES);
     const int tile = blockIdx.x & ((1 << LOGTILES) - 1);
-    const int limb = limb_of(a, vec);
+    const int limb = uniform(limb_of(a, vec));   // per-workgroup values: pinned to SGPRs, never recomputed per lane
     if (limb < 0) return;
     const LimbConst c = limb_const(a, limb);
     if (lazy_prime<INVERSE>(c.q))
@@ -345,18 +410,22 @@ template <bool INVERSE, bool LAZY, bool EPI>
 __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, int tile, int limb, const LimbConst& c,
                                           const NttEpilogue* ep) {
     const int log_n = a.log_n;
-    const u64x2* tw = reinterpret_cast<const u64x2*>(a.tw) + ((size_t)limb << log_n);
-    const u64x2* trows = reinterpret_cast<const u64x2*>(a.tw_rows) + (((size_t)limb << (log_n - 12)) + tile) * (15 * 256);
-    u64* base = a.data + ((size_t)vec << log_n) + ((size_t)tile << 12);
-    const u64* sbase = a.src + src_offset(a, vec, log_n) + ((size_t)tile << 12);
+    const Stream tw = stream(reinterpret_cast<const u64x2*>(a.tw) + ((size_t)limb << log_n));
+    const Stream trows = stream(reinterpret_cast<const u64x2*>(a.tw_rows) + (((size_t)limb << (log_n - 12)) + tile) * (15 * 256));
+    [[maybe_unused]] u64* const vbase = a.data + ((size_t)vec << log_n) + ((size_t)tile << 12);
+    const Stream base = stream(vbase);
+    const Stream sbase = stream(a.src + src_offset(a, vec, log_n) + ((size_t)tile << 12));
     const int tau = threadIdx.x;
+    // lane byte offsets of the bit-4 and bit-8 windows; slot k adds the constant 8 * (k << p): 128 k and 2048 k
+    const u32 lane4 = 8u * (u32)tile_index(tau, 0, 4), lane8 = 8u * (u32)tile_index(tau, 0, 8);
+    auto koff = [](int k, int p) constexpr { return 8 * tile_index(0, k, p); };
     u64 x[16];
 
     if (!INVERSE) {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) x[k] = sbase[tile_index(tau, k, 4)];
+        for (int k = 0; k < 16; ++k) x[k] = ld64(sbase, lane4, koff(k, 4));
         RoundTw rt, rn;
-        load_round_tw<0, 4>(rt, tw, log_n, 4, (tile << 4) | (tau >> 4));
+        load_round_tw<0, 4>(rt, tw, log_n, 4, tile << 4, tau >> 4);
         fwd_round<0, 4, LAZY>(x, rt, c);
         load_round_tw_rows(rn, trows, tau);                          // per-thread twiddles of the last four stages
         exchange(x, lds, tau, 4, 0, false);
@@ -367,16 +436,28 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
         [[maybe_unused]] int ell = 0, t = 0, poly = 0;
         if constexpr (EPI) {
             ell = ep->ell;
-            t = vec % ell;
-            poly = vec / ell;
-            const u64* acc = ep->acc + (size_t)poly * ep->acc_poly_stride + ((size_t)t << log_n) + ((size_t)tile << 12);
+            poly = uniform(vec / ell);
+            t = vec - poly * ell;
+            const Stream acc = stream(ep->acc + (size_t)poly * ep->acc_poly_stride + ((size_t)t << log_n) + ((size_t)tile << 12));
 #pragma unroll
-            for (int k = 0; k < 16; ++k) av[k] = acc[tile_index(tau, k, 8)];
+            for (int k = 0; k < 16; ++k) av[k] = ld64(acc, lane8, koff(k, 8));
         }
+        // Epilogue: x only feeds av + B - x into mul_shoup, which takes ANY 64-bit input and returns the canonical residue.  So x
+        // needs no reduction of its own where a multiple B = cq of q bounds it and av + B < 2^64 (av < q): from a canonical input
+        // (every epilogue transform takes the canonical output of a basis conversion or of the lift) the lazy path proves x < 86q
+        // and runs for q < 2^57 (87q < 2^64); the semi-lazy path proves x < 10q, and 11q < 2^64 for q < 2^60.  Same residue class,
+        // hence the same canonical bytes.  Any larger prime keeps the reduction to [0, 2q).
+        [[maybe_unused]] u64 epi_b = 0;
         if constexpr (EPI) {
-            // [0, 2q) is enough: the epilogue's Shoup product takes any 64-bit input and ends canonical
+            if (LAZY) {
+                epi_b = 86 * c.q;
+            } else if (c.q < (1ull << 60)) {
+                epi_b = 10 * c.q;
+            } else {
+                epi_b = 2 * c.q;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) x[k] = reduce_lazy_2q(x[k], c.q, c.sh, c.rr);
+                for (int k = 0; k < 16; ++k) x[k] = reduce_lazy_2q(x[k], c.q, c.sh, c.rr);
+            }
         } else if (!(LAZY && a.lazy_out && c.q < (1ull << 53))) {
 #pragma unroll
             for (int k = 0; k < 16; ++k)
@@ -389,7 +470,7 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
                 u64x2 v;
                 v.x = x[k];
                 v.y = x[k + 1];
-                reinterpret_cast<u64x2*>(base + 16 * tau)[k >> 1] = v;
+                reinterpret_cast<u64x2*>(vbase + 16 * tau)[k >> 1] = v;
             }
             return;
         }
@@ -401,50 +482,51 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
             const int bi = poly >> 1, comp = poly & 1;
             const size_t n = (size_t)1 << log_n;
             const u64 w = ep->w[2 * t], ws = ep->w[2 * t + 1];
-            const u64 q2 = 2 * c.q;   // av + 2q - x in (0, 3q): the same residue as av - x, and mul_shoup returns it canonical
+            // av + B - x in (0, B + q): the same residue as av - x, and mul_shoup returns it canonical
 #pragma unroll
-            for (int k = 0; k < 16; ++k) x[k] = mul_shoup(av[k] + q2 - x[k], w, ws, c.q);
+            for (int k = 0; k < 16; ++k) x[k] = mul_shoup(av[k] + epi_b - x[k], w, ws, c.q);
             const u64* add = comp == 0 ? ep->add0 : ep->add1;
             if (add) {
-                add += (size_t)bi * ep->add_stride + (size_t)t * n + ((size_t)tile << 12);
+                const Stream adds = stream(add + (size_t)bi * ep->add_stride + (size_t)t * n + ((size_t)tile << 12));
 #pragma unroll
-                for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], add[tile_index(tau, k, 8)], c.q);
+                for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], ld64(adds, lane8, koff(k, 8)), c.q);
             }
             const size_t row_off = (size_t)(comp * ell + t) * n;
-            const u64* post = ep->post ? ep->post + (size_t)bi * ep->post_stride + row_off : nullptr;
-            u64* out = ep->out + (size_t)bi * ep->out_stride + row_off;
+            const bool has_post = ep->post != nullptr;
+            const Stream post = stream(ep->post + (has_post ? (size_t)bi * ep->post_stride + row_off : 0));   // read only if has_post
+            const Stream out = stream(ep->out + (size_t)bi * ep->out_stride + row_off);
+            const int toff = tile << 15;   // the tile's byte offset in a row of post / out
             const u32* im = ep->per_row ? ep->invmap_row[bi] : ep->invmap;
-            if (im) {   // rotation: through the inverse automorphism map
+            if (im) {   // rotation: through the inverse automorphism map; a target index is below N, its byte offset below 2^20
+                const Stream ims = stream(im + ((size_t)tile << 12));
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
-                    const size_t j = im[((size_t)tile << 12) + tile_index(tau, k, 8)];
+                    const u32 j8 = 8u * ld32(ims, 4u * (u32)tau, 4 * tile_index(0, k, 8));
                     u64 r = x[k];
-                    if (post) r = add_mod(r, post[j], c.q);
-                    out[j] = r;
+                    if (has_post) r = add_mod(r, ld64(post, j8, 0), c.q);
+                    st64(out, j8, 0, r);
                 }
             } else {
-                out += (size_t)tile << 12;
-                if (post) {
-                    post += (size_t)tile << 12;
+                if (has_post) {
 #pragma unroll
-                    for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], post[tile_index(tau, k, 8)], c.q);
+                    for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], ld64(post, lane8, koff(k, 8), toff), c.q);
                 }
 #pragma unroll
-                for (int k = 0; k < 16; ++k) out[tile_index(tau, k, 8)] = x[k];
+                for (int k = 0; k < 16; ++k) st64(out, lane8, koff(k, 8), x[k], toff);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) base[tile_index(tau, k, 8)] = x[k];
+            for (int k = 0; k < 16; ++k) st64(base, lane8, koff(k, 8), x[k]);
         }
     } else {
         // coalesced load through the bit-8 window, then an LDS exchange to the bit-0 window of the first GS round
 #pragma unroll
-        for (int k = 0; k < 16; ++k) x[k] = sbase[tile_index(tau, k, 8)];
+        for (int k = 0; k < 16; ++k) x[k] = ld64(sbase, lane8, koff(k, 8));
         RoundTw rt, rn;
         load_round_tw_rows(rt, trows, tau);                          // per-thread twiddles of the first four stages
         exchange(x, lds, tau, 8, 0, false);
         inv_round<0, 4, false, LAZY, 0, 1>(x, rt, c, nullptr);
-        load_round_tw<0, 4>(rn, tw, log_n, 4, (tile << 4) | (tau >> 4));
+        load_round_tw<0, 4>(rn, tw, log_n, 4, tile << 4, tau >> 4);
         exchange(x, lds, tau, 0, 4, true);
         inv_round<0, 4, false, LAZY, 4, 1>(x, rn, c, nullptr);
         if (LAZY) {  // sums have grown to < 640q: hand values below 2q to the column pass
@@ -452,7 +534,7 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
             for (int k = 0; k < 16; ++k) x[k] = reduce_lazy_2q(x[k], c.q, c.sh, c.rr);
         }
 #pragma unroll
-        for (int k = 0; k < 16; ++k) base[tile_index(tau, k, 4)] = x[k];
+        for (int k = 0; k < 16; ++k) st64(base, lane4, koff(k, 4), x[k]);
     }
 }
 
@@ -477,7 +559,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
         vec = a.vec0 + (lid >> logtiles);
         tile = lid & ((1 << logtiles) - 1);
     }
-    const int limb = limb_of(a, vec);
+    vec = uniform(vec);   // per-workgroup values: pinned to SGPRs, never recomputed per lane
+    tile = uniform(tile);
+    const int limb = uniform(limb_of(a, vec));
     if (limb < 0) return;
     const LimbConst c = limb_const(a, limb);
     if (lazy_prime<INVERSE>(c.q))

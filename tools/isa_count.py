@@ -21,7 +21,7 @@ def main():
         valu = sum(v for k, v in c.items() if k.startswith('v_'))
         mul = sum(v for k, v in c.items() if 'mul' in k or 'mad' in k)
         print(f"{name[-60:]} total {tot} valu {valu} mul-class {mul} ds {sum(v for k,v in c.items() if k.startswith('ds_'))} "
-              f"global {sum(v for k,v in c.items() if k.startswith('global_'))} salu {sum(v for k,v in c.items() if k.startswith('s_'))}")
+              f"global {sum(v for k,v in c.items() if k.startswith(('global_', 'buffer_')))} salu {sum(v for k,v in c.items() if k.startswith('s_'))}")
         print('   ', ' '.join(f"{k}:{v}" for k, v in c.most_common(24)))
 
 main()
