@@ -220,6 +220,8 @@ def load_library():
         "fhelin_debug_seeded_expand": (i32, [vp, vp, C.c_uint64, i32, i32, i32, vp, f32p]),
         "fhelin_client_ingest_wrapped": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(vp),
                                                C.POINTER(i32), vp]),
+        "fhelin_client_ingest_wrapped_interleaved": (i32, [vp, i32, C.POINTER(vp), C.POINTER(vp), vp, i32, i32, vp, vp, vp, vp, vp, vp, i32,
+                                                           i32, vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp)]),
         "fhelin_wrapped_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, i32]),
         "fhelin_unwrap_inputs": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp)]),
         "fhelin_sanitize": (i32, [vp, C.POINTER(vp), i32, vp, i32, i32, C.POINTER(vp)]),
@@ -440,6 +442,49 @@ class Engine:
         if want_proj:
             res["x_in"], res["proj"] = [a[:S + 1] for a in proj], [a[S + 1:] for a in proj]
         return res
+
+    def client_ingest_wrapped_interleaved(self, cls, pos, E_w, E_b, F_w, F_b, embs=None, tokens=None, table=None, level=0, targets=None,
+                                          want_proj=False):
+        """client_ingest_wrapped for `stride` samples of one length: the group's wrapped handles, the same inputs of every sample in one
+        ciphertext (a group costs the bytes of one sample); embs (or tokens) is the list of the samples' embeddings (token ids),
+        targets [64 + S + 1] (optional) is shared.  want_proj: (handles, [x_in per sample], [proj per sample])"""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        cls, pos, E_w, E_b, F_w, F_b = f(cls), f(pos), f(E_w), f(E_b), f(F_w), f(F_b)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        if embs is not None:
+            xs = [f(e) if e is not None else None for e in embs]
+            tab, vocab = None, 0
+            shape = lambda S: (S, 128)
+        else:
+            xs = [np.ascontiguousarray(t, dtype=np.int32) if t is not None else None for t in tokens]
+            tab = f(table)
+            vocab = tab.shape[0]
+            shape = lambda S: (S,)
+        first = next((x for x in xs if x is not None), None)
+        S = first.shape[0] if first is not None else 1
+        if any(x is not None and x.shape != shape(S) for x in xs):
+            raise FhelinError(1, "client_ingest_wrapped_interleaved: the samples of a group have one length" + (", rows of 128" if embs is not None else ""))
+        if pos.shape[0] < S or pos.shape[1] != 128 or E_w.shape != F_w.shape or E_w.shape[0] != 32 or E_w.shape[1] < S + 1 or cls.size != 128 \
+                or E_b.size != 32 or F_b.size != 32:
+            raise FhelinError(1, "client_ingest_wrapped_interleaved: pos needs >= S rows of 128, E_w / F_w [32][>= S + 1], E_b / F_b [32], cls [128]")
+        ns = len(xs)
+        ptrs = (C.c_void_p * max(ns, 1))(*[x.ctypes.data if x is not None else None for x in xs])
+        n = 64 + S + 1
+        tg = None
+        if targets is not None:
+            tg = np.ascontiguousarray(targets, dtype=np.int32)
+            if tg.size != n:
+                raise FhelinError(1, "client_ingest_wrapped_interleaved: one target per input")
+        outs = self._outs(n)
+        n_out = C.c_int32()
+        proj = [np.empty((S + 1 + 64, 128)) for _ in range(ns)] if want_proj else None
+        pp = (C.c_void_p * max(ns, 1))(*[a.ctypes.data for a in proj]) if want_proj else None
+        self._ck(self.lib.fhelin_client_ingest_wrapped_interleaved(self.h, ns, ptrs if embs is not None else None,
+                                                                   ptrs if embs is None else None, p(tab), vocab, S, p(cls), p(pos), p(E_w),
+                                                                   p(E_b), p(F_w), p(F_b), E_w.shape[1], level, p(tg), outs,
+                                                                   C.byref(n_out), pp))
+        cts = self._cts(outs, n_out.value)
+        return (cts, [a[:S + 1] for a in proj], [a[S + 1:] for a in proj]) if want_proj else cts
 
     def set_lazy_rows(self, on):
         """deferred evaluation of the rows of matmul_pt / unwrapExpanded (default on)"""

@@ -40,6 +40,11 @@ int fhelin_decrypt_interleaved(fhelin_ctx* c, const fhelin_ct* ct, int32_t flood
     c->ctx.require_device();
     if (c->cl.eval_only()) throw Error(FHELIN_ERR_KEY, "decrypt: an evaluation context holds no secret key");
     if (flood_bits < 0 || flood_bits > 62) throw Error(FHELIN_ERR_ARG, "decrypt_interleaved: flood_bits must lie in [0, 62]");
+    if (ct->p && ct->p->wrapped()) {   // as fhelin_decrypt: the extra limb left out, every lane in the wrapped layout
+        auto v = c->cl.decrypt_interleaved(ct->p, slots, flood_bits);
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+        return FHELIN_OK;
+    }
     if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
     c->plan.check_terminal(*ct_in(c, ct), 2);
     auto v = c->cl.decrypt_interleaved(ct_in(c, ct), slots, flood_bits);

@@ -1,5 +1,7 @@
 // Wrapped inputs (include/fhelin.h "Wrapped inputs"): the client packs up to 128 inputs of a sample into one ciphertext over one limb
-// more than they need; the server unwraps them into the expanded inputs fhelin_client_ingest gives.
+// more than they need; the server unwraps them into the expanded inputs fhelin_client_ingest gives.  Under a slot stride the same
+// inputs of every sample of a group share the wrapped ciphertext (fhelin_client_ingest_wrapped_interleaved), and the unwrap below serves
+// all lanes at once: its mask is replicated, its rotation indices are logical.
 //   unwrap, per input t of a wrapped ciphertext W (column t of the layout):
 //     x_t   = drop_last_limb(W * mask_t)      mask_t = the stored mask (slots = 0 mod 128) read through the map of rotation -t,
 //                                             encoded at scale q_drop: x_t has the inputs' limbs and exactly their fresh scale
@@ -71,6 +73,23 @@ void p0_tables(fhelin_ctx* c) {
     c->p0_qlmod = x.upload_table(mod);
 }
 
+// the limbs every input is wanted at: the caller's, or n_q - level, or - while a level plan is applied - the plan's targets of the
+// sources the unwrap will produce (peeked: the unwrap counts them)
+std::vector<int> wrap_targets(fhelin_ctx* c, int n_vec, int level, const int32_t* targets) {
+    const int top = c->ctx.L + 1 - level;
+    std::vector<int> ell(n_vec, top);
+    const LevelPlan& pl = c->plan;
+    for (int i = 0; i < n_vec; ++i) {
+        if (targets) {
+            ell[i] = targets[i];
+        } else if (pl.mode == 2) {
+            const int k = pl.next_ordinal + i;
+            if (k < (int)pl.target.size() && pl.target[k] >= 1) ell[i] = std::max(1, std::min(top, pl.target[k]));
+        }
+    }
+    return ell;
+}
+
 }  // namespace
 
 extern "C" {
@@ -83,25 +102,46 @@ int fhelin_client_ingest_wrapped(fhelin_ctx* c, const double* emb, const int32_t
     FHELIN_TRY
     *n_out = 0;
     if (c->ctx.stride > 1)
-        throw Error(FHELIN_ERR_STATE, "client_ingest_wrapped: wrapped inputs of interleaved samples are not supported (interleave stride > 1)");
+        throw Error(FHELIN_ERR_STATE, "client_ingest_wrapped: a context with interleaved samples takes its samples through fhelin_client_ingest_wrapped_interleaved: "
+                                      "wrapped inputs of interleaved samples are not supported here (interleave stride > 1)");
     if (S < 1) throw Error(FHELIN_ERR_ARG, "ingest: need at least one token");
     if (level < 0 || level > c->ctx.L) throw Error(FHELIN_ERR_ARG, "ingest: level out of range");
     if (c->ctx.K < 1) throw Error(FHELIN_ERR_STATE, "wrapped inputs: a chain without special primes has no p_0 limb");
-    const int n_vec = 64 + S + 1, top = c->ctx.L + 1 - level;
-    std::vector<int> ell(n_vec, top);
-    const LevelPlan& pl = c->plan;
-    for (int i = 0; i < n_vec; ++i) {
-        if (targets) {
-            ell[i] = targets[i];
-        } else if (pl.mode == 2) {   // the plan's targets of the sources the unwrap will produce (peeked: the unwrap counts them)
-            const int k = pl.next_ordinal + i;
-            if (k < (int)pl.target.size() && pl.target[k] >= 1) ell[i] = std::max(1, std::min(top, pl.target[k]));
-        }
-    }
+    const int n_vec = 64 + S + 1;
+    const std::vector<int> ell = wrap_targets(c, n_vec, level, targets);
     std::vector<double> po;
     std::vector<CtPtr> r = c->cl.ingest_sample(emb, tokens, table, vocab, S, cls, pos, E_w, E_b, F_w, F_b, w_cols, level,
                                                std::vector<int>(n_vec, 0), proj_out ? &po : nullptr, &ell);
     if (proj_out) std::memcpy(proj_out, po.data(), po.size() * sizeof(double));
+    for (size_t i = 0; i < r.size(); ++i) outs[i] = wrap(c, r[i]);
+    *n_out = (int32_t)r.size();
+    FHELIN_CATCH
+}
+
+int fhelin_client_ingest_wrapped_interleaved(fhelin_ctx* c, int32_t n_samples, const double* const* emb, const int32_t* const* tokens,
+                                             const double* table, int32_t vocab, int32_t S, const double* cls, const double* pos,
+                                             const double* E_w, const double* E_b, const double* F_w, const double* F_b, int32_t w_cols,
+                                             int32_t level, const int32_t* targets, fhelin_ct** outs, int32_t* n_out,
+                                             double* const* proj_out) {
+    NEED(c && (emb || (tokens && table)) && cls && pos && E_w && E_b && F_w && F_b && outs && n_out);
+    if (c->ctx.stride == 1 && n_samples == 1 && (emb ? emb[0] != nullptr : tokens[0] != nullptr))   // the single-sample call itself
+        return fhelin_client_ingest_wrapped(c, emb ? emb[0] : nullptr, emb ? nullptr : tokens[0], table, vocab, S, cls, pos, E_w, E_b, F_w,
+                                            F_b, w_cols, level, targets, outs, n_out, proj_out ? proj_out[0] : nullptr);
+    FHELIN_TRY
+    *n_out = 0;
+    if (n_samples != c->ctx.stride)
+        throw Error(FHELIN_ERR_ARG, "ingest_wrapped_interleaved: one sample per lane (n_samples == the interleave stride)");
+    if (S < 1) throw Error(FHELIN_ERR_ARG, "ingest: need at least one token");
+    if (level < 0 || level > c->ctx.L) throw Error(FHELIN_ERR_ARG, "ingest: level out of range");
+    if (c->ctx.K < 1) throw Error(FHELIN_ERR_STATE, "wrapped inputs: a chain without special primes has no p_0 limb");
+    const int n_vec = 64 + S + 1;
+    const std::vector<int> ell = wrap_targets(c, n_vec, level, targets);
+    std::vector<std::vector<double>> po;
+    std::vector<CtPtr> r = c->cl.ingest_interleaved(emb, tokens, table, vocab, S, cls, pos, E_w, E_b, F_w, F_b, w_cols, level,
+                                                    std::vector<int>(n_vec, 0), proj_out ? &po : nullptr, &ell);
+    if (proj_out)
+        for (int i = 0; i < n_samples; ++i)
+            if (proj_out[i]) std::memcpy(proj_out[i], po[i].data(), po[i].size() * sizeof(double));
     for (size_t i = 0; i < r.size(); ++i) outs[i] = wrap(c, r[i]);
     *n_out = (int32_t)r.size();
     FHELIN_CATCH

@@ -875,6 +875,67 @@ std::vector<CtPtr> Client::encrypt_batch(const double* vals, int n_vec, int n_pe
     return out;
 }
 
+// Wrapped inputs, the parts ingest_sample and ingest_interleaved share.  wrap_groups: groups of <= 128 inputs that share a target, in read
+// order (runs of one target follow its first input); group_ell per wrapped vector: the inputs' limbs; pos [n_w][128] input positions
+// (-1 = none).
+void Client::wrap_groups(const std::vector<int>& wrap_ell, int n_vec, std::vector<int>& group_ell, std::vector<int>& pos) const {
+    if ((int)wrap_ell.size() != n_vec) throw Error(FHELIN_ERR_ARG, "ingest: one target per input");
+    for (int v : wrap_ell)
+        if (v < 1 || v > c_.L + 1) throw Error(FHELIN_ERR_ARG, "ingest: wrapped target limbs out of range [1, n_q]");
+    std::vector<char> taken(n_vec, 0);
+    for (int i = 0; i < n_vec; ++i) {
+        if (taken[i]) continue;
+        int t = 128;
+        for (int j = i; j < n_vec; ++j) {
+            if (taken[j] || wrap_ell[j] != wrap_ell[i]) continue;
+            if (t == 128) {
+                group_ell.push_back(wrap_ell[i]);
+                pos.resize(pos.size() + 128, -1);
+                t = 0;
+            }
+            pos[pos.size() - 128 + t++] = j;
+            taken[j] = 1;
+        }
+    }
+}
+
+// encrypt_wrapped: dv [n_w][phys] complex (phys = slots x the interleave stride) -> the wrapped ciphertexts.  Seeded secret-key encryption
+// over the first ell + 1 moduli of Q then P at the scale of a fresh encryption at ell limbs; wrapped vectors of one target are
+// consecutive (wrap_groups) and share the batched encoder and encryptor.  get: the caller's wiped temporaries.
+std::vector<CtPtr> Client::encrypt_wrapped(double* dv, int phys, int slots, int n_vec, const std::vector<int>& group_ell,
+                                           const std::vector<int>& pos, const std::function<void*(size_t)>& get) {
+    struct SeededMode {
+        bool& f;
+        bool was;
+        ~SeededMode() { f = was; }
+    } mode{seeded_, seeded_};
+    seeded_ = true;
+    begin_call();
+    const int n_w = (int)group_ell.size();
+    std::vector<CtPtr> out;
+    for (int w0 = 0; w0 < n_w;) {
+        const int ell = group_ell[w0], ell1 = ell + 1;
+        int n = 0;
+        while (w0 + n < n_w && n < 32 && group_ell[w0 + n] == ell) ++n;
+        const size_t pn = (size_t)ell1 * c_.N;
+        const long double scale = c_.sf_real[c_.L + 1 - ell];
+        u64* enc = (u64*)get((size_t)n * pn * sizeof(u64));
+        encode_complex_on_device(c_, enc, dv + (size_t)w0 * phys * 2, n, phys, ell1, scale);
+        std::vector<CtPtr> part;
+        u64 nonces[32];
+        for (int k = 0; k < n; ++k) nonces[k] = (u64)(w0 + k);
+        encrypt_encoded(enc, pn, n, ell1, scale, slots, part, nonces);
+        for (int k = 0; k < n; ++k) {
+            Ciphertext& ct = *part[k];
+            for (int t = 0; t < 128 && pos[(size_t)(w0 + k) * 128 + t] >= 0; ++t) ct.wrap_pos.push_back(pos[(size_t)(w0 + k) * 128 + t]);
+            ct.wrap_total = n_vec;
+            out.push_back(part[k]);
+        }
+        w0 += n;
+    }
+    return out;
+}
+
 // One sample's client side on the device (kernels_client.h "sample ingestion"): embedding rows (given, or gathered from a table by
 // token id) + positional embedding, the two Linformer projections, the expanded packing, encoding and encryption.  drop[v]:
 // limbs vector v starts lower by (level plan); vectors of one level share the batched encryptor.
@@ -889,28 +950,8 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
     if (slots != 16384) throw Error(FHELIN_ERR_ARG, "ingest: the expanded layout needs 16384 slots (128 x 128)");
     if (S < 1 || S1 > w_cols || (!emb && !(tokens && table && vocab > 0))) throw Error(FHELIN_ERR_ARG, "ingest: bad token count / inputs");
     if (level < 0 || level > c_.L || (int)drop.size() != n_vec) throw Error(FHELIN_ERR_ARG, "ingest: level out of range");
-    // wrapped: groups of <= 128 inputs that share a target, in read order (runs of one target follow its first input)
     std::vector<int> wrap_group_ell, wrap_pos;   // per wrapped vector: the inputs' limbs; [n_w][128] input positions (-1 = none)
-    if (wrap_ell) {
-        if ((int)wrap_ell->size() != n_vec) throw Error(FHELIN_ERR_ARG, "ingest: one target per input");
-        for (int v : *wrap_ell)
-            if (v < 1 || v > c_.L + 1) throw Error(FHELIN_ERR_ARG, "ingest: wrapped target limbs out of range [1, n_q]");
-        std::vector<char> taken(n_vec, 0);
-        for (int i = 0; i < n_vec; ++i) {
-            if (taken[i]) continue;
-            int t = 128;
-            for (int j = i; j < n_vec; ++j) {
-                if (taken[j] || (*wrap_ell)[j] != (*wrap_ell)[i]) continue;
-                if (t == 128) {
-                    wrap_group_ell.push_back((*wrap_ell)[i]);
-                    wrap_pos.resize(wrap_pos.size() + 128, -1);
-                    t = 0;
-                }
-                wrap_pos[wrap_pos.size() - 128 + t++] = j;
-                taken[j] = 1;
-            }
-        }
-    }
+    if (wrap_ell) wrap_groups(*wrap_ell, n_vec, wrap_group_ell, wrap_pos);
     hipStream_t s = c_.stream;
     // every temporary of the sample - the embeddings, x_in, the projections, the expanded packing: the client's PLAINTEXT - is wiped
     // before its block goes back to the recycled pool, and freed on every path out of this function (an exception included)
@@ -964,39 +1005,8 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
         hip_check(hipMemcpyAsync(proj_out->data() + (size_t)S1 * 128, proj, (size_t)64 * 128 * 8, hipMemcpyDeviceToHost, s), "ingest download");
     }
     hip_check(hipStreamSynchronize(s), "ingest sync");   // the host buffers are the caller's: done with them
-    if (wrap_ell) {
-        // seeded secret-key encryption over the first ell + 1 moduli of Q then P at the scale of a fresh encryption at ell limbs;
-        // wrapped vectors of one target are consecutive (grouping above) and share the batched encoder and encryptor
-        struct SeededMode {
-            bool& f;
-            bool was;
-            ~SeededMode() { f = was; }
-        } mode{seeded_, seeded_};
-        seeded_ = true;
-        begin_call();
-        std::vector<CtPtr> out;
-        for (int w0 = 0; w0 < n_w;) {
-            const int ell = wrap_group_ell[w0], ell1 = ell + 1;
-            int n = 0;
-            while (w0 + n < n_w && n < 32 && wrap_group_ell[w0 + n] == ell) ++n;
-            const size_t pn = (size_t)ell1 * c_.N;
-            const long double scale = c_.sf_real[c_.L + 1 - ell];
-            u64* enc = (u64*)tmp.get((size_t)n * pn * sizeof(u64));
-            encode_complex_on_device(c_, enc, dv + (size_t)w0 * slots * 2, n, slots, ell1, scale);
-            std::vector<CtPtr> part;
-            u64 nonces[32];
-            for (int k = 0; k < n; ++k) nonces[k] = (u64)(w0 + k);
-            encrypt_encoded(enc, pn, n, ell1, scale, slots, part, nonces);
-            for (int k = 0; k < n; ++k) {
-                Ciphertext& ct = *part[k];
-                for (int t = 0; t < 128 && wrap_pos[(size_t)(w0 + k) * 128 + t] >= 0; ++t) ct.wrap_pos.push_back(wrap_pos[(size_t)(w0 + k) * 128 + t]);
-                ct.wrap_total = n_vec;
-                out.push_back(part[k]);
-            }
-            w0 += n;
-        }
-        return out;
-    }
+    if (wrap_ell)
+        return encrypt_wrapped(dv, slots, slots, n_vec, wrap_group_ell, wrap_pos, [&](size_t bytes) { return tmp.get(bytes); });
     begin_call();
     std::vector<CtPtr> out(n_vec);
     std::vector<char> seen(n_vec, 0);
@@ -1035,12 +1045,14 @@ std::vector<CtPtr> Client::ingest_sample(const double* emb, const int* tokens, c
 // ingest_sample for `stride` samples of one length S that share a ciphertext (include/fhelin.h "Interleaved samples"): x_in and the
 // projections run per sample with ingest_sample's own kernels (so proj_out[i] is ingest_sample's, bit for bit), the expand step writes
 // sample i into lane i of the shared [n_vec][slots * stride] buffer, and the 64 + S + 1 vectors are encoded and encrypted once for the
-// group: the sampler draws of ONE ingest_sample.
+// group: the sampler draws of ONE ingest_sample.  wrap_ell: as ingest_sample's, the group's WRAPPED ciphertexts - the same inputs of
+// every sample in one ciphertext (ingest_wrap_interleaved_kernel), the draws of one wrapped ingest_sample.
 std::vector<CtPtr> Client::ingest_interleaved(const double* const* emb, const int* const* tokens, const double* table, int vocab, int S,
                                               const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w,
                                               const double* F_b, int w_cols, int level, const std::vector<int>& drop,
-                                              std::vector<std::vector<double>>* proj_out) {
-    if (seeded_ ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
+                                              std::vector<std::vector<double>>* proj_out, const std::vector<int>* wrap_ell) {
+    if (wrap_ell && eval_only_) throw Error(FHELIN_ERR_KEY, "wrapped inputs are secret-key encryptions: an evaluation context holds no secret");
+    if ((seeded_ || wrap_ell) ? !s_all : !pk) throw Error(FHELIN_ERR_KEY, "keygen() has not been called");
     const int st = c_.stride, slots = 1 << c_.prm.log_slots, S1 = S + 1, n_vec = 64 + S1, phys = slots * st;
     if (slots != 16384) throw Error(FHELIN_ERR_ARG, "ingest: the expanded layout needs 16384 slots (128 x 128)");
     if ((long)slots * st > c_.N / 2) throw Error(FHELIN_ERR_ARG, "ingest: slots x interleave stride must be <= N/2");
@@ -1052,6 +1064,8 @@ std::vector<CtPtr> Client::ingest_interleaved(const double* const* emb, const in
             for (int t = 0; t < S; ++t)
                 if (tokens[i][t] < 0 || tokens[i][t] >= vocab) throw Error(FHELIN_ERR_ARG, "ingest: token id outside the embedding table");
     }
+    std::vector<int> wrap_group_ell, wrap_pos;
+    if (wrap_ell) wrap_groups(*wrap_ell, n_vec, wrap_group_ell, wrap_pos);
     hipStream_t s = c_.stream;
     // as ingest_sample: every temporary is the client's plaintext - wiped, then freed, on every path out
     struct Temps {
@@ -1086,8 +1100,16 @@ std::vector<CtPtr> Client::ingest_interleaved(const double* const* emb, const in
         launch_ingest_xin(x_in + (size_t)i * S1 * 128, d_emb, d_tok, d_tab, d_cls, d_pos, S, s);
         launch_ingest_project(proj + (size_t)i * 64 * 128, x_in + (size_t)i * S1 * 128, d_Ew, d_Eb, d_Fw, d_Fb, w_cols, S1, s);
     }
-    double* dv = (double*)tmp.get((size_t)n_vec * phys * 16);
-    launch_ingest_expand_interleaved(dv, proj, x_in, S1, slots, st, s);
+    double* dv = nullptr;
+    if (!wrap_ell) {
+        dv = (double*)tmp.get((size_t)n_vec * phys * 16);
+        launch_ingest_expand_interleaved(dv, proj, x_in, S1, slots, st, s);
+    } else {
+        const int n_w = (int)wrap_group_ell.size();
+        dv = (double*)tmp.get((size_t)n_w * phys * 16);
+        const int* d_wpos = (const int*)up(wrap_pos.data(), wrap_pos.size() * sizeof(int));
+        launch_ingest_wrap_interleaved(dv, proj, x_in, d_wpos, n_w, S1, slots, st, s);
+    }
     hip_check(hipGetLastError(), "ingest kernels");
     if (proj_out) {   // per sample: x_in rows then the 64 projected rows, as ingest_sample reports them
         proj_out->assign(st, std::vector<double>((size_t)(S1 + 64) * 128));
@@ -1099,6 +1121,8 @@ std::vector<CtPtr> Client::ingest_interleaved(const double* const* emb, const in
         }
     }
     hip_check(hipStreamSynchronize(s), "ingest sync");   // the host buffers are the caller's: done with them
+    if (wrap_ell)
+        return encrypt_wrapped(dv, phys, slots, n_vec, wrap_group_ell, wrap_pos, [&](size_t bytes) { return tmp.get(bytes); });
     begin_call();
     std::vector<CtPtr> out(n_vec);
     std::vector<char> seen(n_vec, 0);

@@ -3,6 +3,7 @@
 // (src/FHEController.cpp:47-49, :237-273, :348-404).  Sampling and the fp64 FFT run on the host (as in the
 // reference); every residue-polynomial operation (NTT, dyadic products) runs on the GPU kernels.
 #pragma once
+#include <functional>
 #include <vector>
 #include "evaluator.h"
 #include "kernels_client.h"
@@ -74,11 +75,13 @@ public:
                                      int w_cols, int level, const std::vector<int>& drop, std::vector<double>* proj_out = nullptr,
                                      const std::vector<int>* wrap_ell = nullptr);
     // `stride` samples of one length S in one group of 64 + S + 1 ciphertexts (interleaved samples): emb / tokens [stride] pointers (emb
-    // null: token ids), everything else shared; proj_out [stride] as ingest_sample's
+    // null: token ids), everything else shared; proj_out [stride] as ingest_sample's; wrap_ell as ingest_sample's (the group's wrapped
+    // ciphertexts: the same inputs of every sample in one ciphertext)
     std::vector<CtPtr> ingest_interleaved(const double* const* emb, const int* const* tokens, const double* table, int vocab, int S,
                                           const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w,
                                           const double* F_b, int w_cols, int level, const std::vector<int>& drop,
-                                          std::vector<std::vector<double>>* proj_out = nullptr);
+                                          std::vector<std::vector<double>>* proj_out = nullptr,
+                                          const std::vector<int>* wrap_ell = nullptr);
     // wrap_ell (include/fhelin.h "Wrapped inputs"): the limbs every input is wanted at; the result is then the WRAPPED ciphertexts (runs
     // of inputs of one target in read order, <= 128 each, over ell + 1 limbs), always seeded secret-key encryptions; drop is ignored
     // test hook: the sampler's raw output, n_poly polynomials of N centred coefficients (kind 0 Gaussian, 1 ternary)
@@ -134,6 +137,10 @@ private:
     // seeded mode: c0 = m - a s + e, c1 = a instead; nonces [n_vec] are the vectors' output indices within the current call
     void encrypt_encoded(const u64* enc, size_t enc_stride, int n_vec, int ell, long double scale, int slots, std::vector<CtPtr>& out,
                          const u64* nonces);
+    // wrapped inputs, shared by ingest_sample and ingest_interleaved: the grouping by target and the seeded encryption of the packed vectors
+    void wrap_groups(const std::vector<int>& wrap_ell, int n_vec, std::vector<int>& group_ell, std::vector<int>& pos) const;
+    std::vector<CtPtr> encrypt_wrapped(double* dv, int phys, int slots, int n_vec, const std::vector<int>& group_ell,
+                                       const std::vector<int>& pos, const std::function<void*(size_t)>& get);
     std::vector<double> decrypt_physical(const CtPtr& c, int slots, int flood_bits, int mult);
     u64 sample_calls_ = 0;
     bool eval_only_ = false, keygen_run_ = false;

@@ -88,4 +88,8 @@ void launch_ingest_expand_interleaved(double* out, const double* proj, const dou
 // the wrapped layout (include/fhelin.h "Wrapped inputs"): out [n_w][slots][2], slot j*128 + t of vector w = input pos[w][t] [j]
 // (inputs numbered as in launch_ingest_expand: E rows, F rows, tokens); pos [n_w][128] on the device, -1 = empty column
 void launch_ingest_wrap(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int slots, hipStream_t s);
+// the wrapped layout of `stride` samples of one length S1 - 1 (proj, x_in as launch_ingest_expand_interleaved; pos shared by the samples):
+// out [n_w][slots * stride][2], physical slot stride * (j*128 + t) + i of vector w = input pos[w][t] [j] of sample i
+void launch_ingest_wrap_interleaved(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int S1, int slots, int stride,
+                                    hipStream_t s);
 }  // namespace fhelin

@@ -602,6 +602,24 @@ __global__ void ingest_wrap_kernel(double* __restrict__ out, const double* __res
     if (v >= 0 && j < 128) o.x = (v < 64 ? proj + (size_t)v * 128 : x_in + (size_t)(v - 64) * 128)[j];
     reinterpret_cast<double2*>(out)[(size_t)w * slots + slot] = o;
 }
+// The wrapped layout of `stride` samples of one length interleaved: physical slot p of vector w holds slot p >> log_stride of sample
+// p & (stride - 1) in ingest_wrap_kernel's layout; pos is shared by the samples (the same inputs in every lane), the sources are those of
+// ingest_expand_interleaved_kernel.  Consecutive threads write consecutive physical slots, one 16-byte store each.
+__global__ void ingest_wrap_interleaved_kernel(double* __restrict__ out, const double* __restrict__ proj, const double* __restrict__ x_in,
+                                               const int* __restrict__ pos, int S1, int slots, int log_stride) {
+    const int w = blockIdx.y;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const int phys = slots << log_stride;
+    if (p >= phys) return;
+    const int sample = p & ((1 << log_stride) - 1), slot = p >> log_stride;
+    const int j = slot >> 7, t = slot & 127;
+    const int v = pos[w * 128 + t];
+    double2 o;
+    o.x = 0.0;
+    o.y = 0.0;
+    if (v >= 0 && j < 128) o.x = (v < 64 ? proj + ((size_t)sample * 64 + v) * 128 : x_in + ((size_t)sample * S1 + (v - 64)) * 128)[j];
+    reinterpret_cast<double2*>(out)[(size_t)w * phys + p] = o;
+}
 }  // namespace
 void launch_ingest_expand_interleaved(double* out, const double* proj, const double* x_in, int S1, int slots, int stride, hipStream_t s) {
     int log_stride = 0;
@@ -612,6 +630,14 @@ void launch_ingest_expand_interleaved(double* out, const double* proj, const dou
 void launch_ingest_wrap(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int slots, hipStream_t s) {
     if (n_w < 1) return;
     hipLaunchKernelGGL(ingest_wrap_kernel, dim3((slots + 255) / 256, n_w), dim3(256), 0, s, out, proj, x_in, pos, slots);
+}
+void launch_ingest_wrap_interleaved(double* out, const double* proj, const double* x_in, const int* pos, int n_w, int S1, int slots, int stride,
+                                    hipStream_t s) {
+    if (n_w < 1) return;
+    int log_stride = 0;
+    while ((1 << log_stride) < stride) ++log_stride;
+    hipLaunchKernelGGL(ingest_wrap_interleaved_kernel, dim3((unsigned)((((size_t)slots << log_stride) + 255) / 256), n_w), dim3(256), 0, s, out,
+                       proj, x_in, pos, S1, slots, log_stride);
 }
 void launch_ingest_xin(double* x_in, const double* emb, const int* tokens, const double* table, const double* cls, const double* pos,
                        int S, hipStream_t s) {

@@ -101,8 +101,11 @@ class GpuController:
 
     def client_ingest(self, w, x_emb, wrapped=False):
         if wrapped:   # a few wrapped ciphertexts on the wire, unwrapped by the server (include/fhelin.h "Wrapped inputs")
-            cts = self.e.unwrap_inputs(self.e.client_ingest_wrapped(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"],
-                                                                    emb=x_emb))
+            args = (w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"])
+            if self.e.interleave > 1:   # x_emb: the list of the group's samples; the group costs one sample's bytes and one unwrap
+                cts = self.e.unwrap_inputs(self.e.client_ingest_wrapped_interleaved(*args, embs=x_emb))
+            else:
+                cts = self.e.unwrap_inputs(self.e.client_ingest_wrapped(*args, emb=x_emb))
             return {"inputs_E": cts[:32], "inputs_F": cts[32:64], "inputs": cts[64:]}
         if self.e.interleave > 1:   # x_emb: the list of the samples that share every ciphertext (one length)
             return self.e.client_ingest_interleaved(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], embs=x_emb)
@@ -365,7 +368,11 @@ class BatchedController:
 
     def client_ingest_batch(self, w, x_embs, wrapped=False):
         if wrapped:   # every sample's wrapped ciphertexts unwrapped in ONE call: the key switches carry the rows of all samples
-            ws = [self.e.client_ingest_wrapped(w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"], emb=x) for x in x_embs]
+            args = (w["cls_token"], w["posEmb"], w["E_w"], w["E_b"], w["F_w"], w["F_b"])
+            if self.e.interleave > 1:   # x_embs: per batch entry the list of the samples that share its ciphertexts (one group each)
+                ws = [self.e.client_ingest_wrapped_interleaved(*args, embs=x) for x in x_embs]
+            else:
+                ws = [self.e.client_ingest_wrapped(*args, emb=x) for x in x_embs]
             cts = self.e.unwrap_inputs([h for s in ws for h in s])
             n = len(cts) // len(ws)
             encs = [{"inputs_E": cts[x * n:x * n + 32], "inputs_F": cts[x * n + 32:x * n + 64], "inputs": cts[x * n + 64:(x + 1) * n]}
@@ -582,7 +589,7 @@ def ingest_sample(ctl, w, x_emb, wrapped=False):
     wrapped: the sample travels as a few wrapped ciphertexts that the server unwraps (include/fhelin.h "Wrapped inputs"); a
     BatchedController then takes x_emb as the list of its B samples' embeddings.
     On an engine with interleaved samples (Engine(interleave=s)) x_emb is the list [x_0 .. x_{s-1}] of the samples that share every
-    ciphertext, all of one length."""
+    ciphertext, all of one length; wrapped, the group then travels in the bytes of one sample."""
     if wrapped:
         if hasattr(ctl, "client_ingest_batch"):
             return ctl.client_ingest_batch(w, x_emb, wrapped=True)

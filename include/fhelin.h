@@ -658,8 +658,8 @@ int fhelin_evalkeys_save_compact(fhelin_ctx* c, const char* path);
  * Unwrap.  out_t = sum_{k<128} rot(x_t, t - k) with x_t the masked drop; with t = a + 8b + 64c that is three merged rotate-and-sum
  * key switches (fhelin_rotate_sum), offsets {a-7..a}, 8{b-7..b} and {64c-64, 64c} without the identity term: every offset is a
  * +-1..7, +-8..56 (step 8) or +-64, all in the circuit's rotation key list.  A missing key: FHELIN_ERR_KEY naming its index.
- * Handles.  A wrapped handle is accepted by fhelin_unwrap_inputs, fhelin_decrypt (the extra limb left out; the slots come back in
- * the wrapped layout), fhelin_ct_info (ell counts the extra limb; level is the inputs' level), fhelin_ct_scale, fhelin_wrapped_info, the compact functions and
+ * Handles.  A wrapped handle is accepted by fhelin_unwrap_inputs, fhelin_decrypt, fhelin_decrypt_flooded, fhelin_decrypt_interleaved
+ * and fhelin_decrypt_batch (the extra limb left out; the slots come back in the wrapped layout), fhelin_ct_info (ell counts the extra limb; level is the inputs' level), fhelin_ct_scale, fhelin_wrapped_info, the compact functions and
  * fhelin_ct_free; every other entry point returns FHELIN_ERR_ARG.
  * Compact form, version 2 (a wrapped ciphertext; version 1 above is unchanged; exactly H + 8 ell N bytes, H = 104 + 8 ell + 8 ceil(count / 2)):
  *   offset  0 .. 95  as version 1 with version = 2 and header bytes = H; ell = the stored limbs (the inputs' limbs + 1, >= 2)
@@ -673,7 +673,9 @@ int fhelin_evalkeys_save_compact(fhelin_ctx* c, const char* path);
 /* The client side of one sample (fhelin_client_ingest's arguments) as wrapped ciphertexts.  targets [64 + S + 1] (optional): the limbs
  * each input is wanted at (1 .. n_q); NULL: n_q - level for all, or, while a level plan is applied on this context, the plan's targets
  * of the sources the unwrap will produce (read, not consumed: this call is no level-plan source).  outs must hold 64 + S + 1 handles;
- * *n_out = wrapped ciphertexts made.  Needs the secret key (FHELIN_ERR_KEY on an evaluation context) and n_p >= 1. */
+ * *n_out = wrapped ciphertexts made.  Needs the secret key (FHELIN_ERR_KEY on an evaluation context) and n_p >= 1.  A context with
+ * interleaved samples (stride > 1) gets FHELIN_ERR_STATE: fhelin_client_ingest_wrapped_interleaved ("Interleaved samples" below)
+ * takes its place, as fhelin_client_ingest_interleaved takes fhelin_client_ingest's. */
 int fhelin_client_ingest_wrapped(fhelin_ctx* c, const double* emb, const int32_t* tokens, const double* table, int32_t vocab, int32_t S,
                                  const double* cls, const double* pos, const double* E_w, const double* E_b, const double* F_w,
                                  const double* F_b, int32_t w_cols, int32_t level, const int32_t* targets, fhelin_ct** outs,
@@ -707,8 +709,17 @@ int fhelin_unwrap_inputs(fhelin_ctx* c, const fhelin_ct* const* wrapped, int32_t
  *   - fhelin_bootstrap_setup takes logical slots and sets bootstrapping up for slots * s physical slots; the bootstrap's own
  *     rotations, diagonals and keys belong to the physical packing, and fhelin_bootstrap_describe / _diag describe the PHYSICAL
  *     stages (slot counts, giant and baby shifts of the slots * s packing).
- *   - fhelin_client_ingest and fhelin_client_ingest_wrapped return FHELIN_ERR_STATE (wrapped interleaved ingest is not supported);
- *     fhelin_client_ingest_interleaved below takes their place.
+ *   - fhelin_client_ingest and fhelin_client_ingest_wrapped return FHELIN_ERR_STATE; fhelin_client_ingest_interleaved and
+ *     fhelin_client_ingest_wrapped_interleaved below take their place.
+ *   - wrapped inputs: a wrapped ciphertext of a group holds the same inputs of every sample, logical slot j*128 + t = row_{i,t}[j] of
+ *     sample i in the physical slot s (j*128 + t) + i.  fhelin_unwrap_inputs serves all lanes at once - the mask is replicated, the
+ *     rotations are 5^(s r), a missing key is named by its logical index - and output t has, in every lane i, the slot values of
+ *     read_expanded_input(row_{i,t}), with the limbs, degree, logical slots, 80-bit scale and level-plan ordinal of
+ *     fhelin_client_ingest_interleaved's output t.  Every entry point that accepts a wrapped handle does so under a stride:
+ *     fhelin_decrypt returns sample 0 in the wrapped layout (the extra limb left out), fhelin_decrypt_interleaved and
+ *     fhelin_decrypt_batch(all_lanes) every lane, fhelin_ct_info logical slots.  NO FORMAT CHANGE: a version-2 compact blob is
+ *     stride-agnostic, as a version-1 blob of an interleaved ciphertext is; the importing context's stride gives it its meaning, and
+ *     the key set carries the stride.
  * Evaluation-key sets record the stride (header offset 88): fhelin_evalkeys_load into a fresh context adopts it; a context whose
  * stride was set explicitly (fhelin_ctx_set_interleave) to another value gets FHELIN_ERR_STATE.  stride 1, the default, changes
  * nothing: no launch, byte, residue or file. */
@@ -733,6 +744,19 @@ int fhelin_client_ingest_interleaved(fhelin_ctx* c, int32_t n_samples, const dou
                                      const double* table, int32_t vocab, int32_t S, const double* cls, const double* pos,
                                      const double* E_w, const double* E_b, const double* F_w, const double* F_b, int32_t w_cols,
                                      int32_t level, fhelin_ct** outs, double* const* proj_out);
+/* fhelin_client_ingest_wrapped for n_samples == stride samples of one length S (emb / tokens / proj_out as
+ * fhelin_client_ingest_interleaved; cls / pos / E / F and targets are shared by the group): the group's wrapped ciphertexts in the
+ * layout above, columns without an input 0 in every lane.  Grouping by target, the moduli and the scale, targets == NULL and the peek
+ * at an applied level plan, positions, total and *n_out are exactly fhelin_client_ingest_wrapped's; so are the sampler draws (one
+ * fresh seed, nonce = the wrapped ciphertext's index: interleaving draws nothing), and a group costs the bytes of one sample.
+ * proj_out[i] is bit for bit what fhelin_client_ingest_wrapped reports for sample i alone.  At stride 1 with one sample the call IS
+ * fhelin_client_ingest_wrapped.  FHELIN_ERR_ARG: n_samples != stride, a NULL sample, a token id outside the table, bad S / level /
+ * targets (before any launch); FHELIN_ERR_KEY on an evaluation context; FHELIN_ERR_STATE with n_p = 0. */
+int fhelin_client_ingest_wrapped_interleaved(fhelin_ctx* c, int32_t n_samples, const double* const* emb, const int32_t* const* tokens,
+                                             const double* table, int32_t vocab, int32_t S, const double* cls, const double* pos,
+                                             const double* E_w, const double* E_b, const double* F_w, const double* F_b, int32_t w_cols,
+                                             int32_t level, const int32_t* targets, fhelin_ct** outs, int32_t* n_out,
+                                             double* const* proj_out);
 
 /* ---- sanitised replies: mask, shrink, re-randomise and flood what a server hands back -------------------------------------
  * The ciphertext a circuit ends with is no fit reply as it stands: only some slots are the answer (the others hold intermediate
