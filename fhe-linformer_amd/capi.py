@@ -104,6 +104,8 @@ def load_library():
         "fhelin_ntt": (i32, [vp, vp, i32, i32, i32, i32]),
         "fhelin_stats": (i32, [vp, u64p, i32, i32]),
         "fhelin_debug_pool_selftest": (i32, [C.c_uint64, i32, C.c_uint64, u64p, i32]),
+        "fhelin_debug_pool_fill_stats": (i32, [vp, u64p, u64p]),
+        "fhelin_debug_pool_fill_selftest": (i32, [C.c_uint64, i32, C.c_uint32, u64p, i32]),
         "fhelin_keygen": (i32, [vp]),
         "fhelin_gen_relin_key": (i32, [vp]),
         "fhelin_gen_rotation_keys": (i32, [vp, C.POINTER(i32), i32]),
@@ -240,6 +242,7 @@ def load_library():
         "fhelin_debug_dot_groups": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp), i32, C.POINTER(vp)]),
         "fhelin_debug_dot_cyclic": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
         "fhelin_debug_dot_window": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32]),
+        "fhelin_debug_rotate_many_batch": (i32, [vp, C.POINTER(vp), i32, C.POINTER(i32), i32, C.POINTER(vp)]),
         "fhelin_ctx_set_interleave": (i32, [vp, i32]),
         "fhelin_ctx_interleave": (i32, [vp, C.POINTER(i32)]),
         "fhelin_evalkeys_interleave": (i32, [C.c_char_p, C.POINTER(i32)]),
@@ -602,6 +605,12 @@ class Engine:
                 "pool_malloc_calls", "pool_malloc_bytes", "pool_malloc_ns", "pool_reserved_bytes", "pool_live_peak_bytes",
                 "pool_reserved_peak_bytes", "pool_trims"]
         return {k: int(v) for k, v in zip(keys, out)}
+
+    def pool_fill_stats(self):
+        """(blocks, bytes) the device pool has filled under FHELIN_POOL_FILL (a test aid; both 0 with the knob off)"""
+        blocks, nbytes = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.fhelin_debug_pool_fill_stats(self.h, C.byref(blocks), C.byref(nbytes)))
+        return blocks.value, nbytes.value
 
     def cache_stats(self):
         """the plaintext cache of fhelin_encode and the pool's bytes in use right now (fhelin_stats [16..18]; not part of stats(),
@@ -1115,6 +1124,15 @@ class Engine:
         assert len(cur) == len(prev) == len(pts) == len(dest) == 32
         self._ck(self.lib.fhelin_debug_dot_window(self.h, self._harr_opt(cur), self._harr_opt(prev), self._harr(pts), self._harr(dest),
                                                   int(bool(accumulate))))
+
+    def debug_rotate_many_batch(self, cts, indices):
+        """outs[i][k] = rot(cts[i], indices[k]): hoisted rotations of many inputs behind one ModUp (Evaluator::rotate_many_batch)"""
+        n = len(indices)
+        idx = (C.c_int32 * n)(*indices)
+        outs = self._outs(len(cts) * n)
+        self._ck(self.lib.fhelin_debug_rotate_many_batch(self.h, self._harr(cts), len(cts), idx, n, outs))
+        flat = self._cts(outs, len(cts) * n)
+        return [flat[i * n:(i + 1) * n] for i in range(len(cts))]
 
     # ---- FHEController composites (names follow the reference methods)
     @staticmethod

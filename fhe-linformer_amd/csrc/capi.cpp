@@ -548,4 +548,18 @@ int fhelin_debug_pool_selftest(uint64_t seed, int32_t n_ops, uint64_t device_byt
     FHELIN_CATCH
 }
 
+int fhelin_debug_pool_fill_selftest(uint64_t seed, int32_t n_ops, uint32_t w, uint64_t* out, int32_t cap) {
+    if (!out) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    pool_fill_selftest(seed, n_ops, w, out, cap);
+    FHELIN_CATCH
+}
+
+int fhelin_debug_pool_fill_stats(fhelin_ctx* c, uint64_t* blocks, uint64_t* bytes) {
+    if (!c || !blocks || !bytes) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    *blocks = c->ctx.pool.fill_blocks;
+    *bytes = c->ctx.pool.fill_bytes;
+    return FHELIN_OK;
+}
+
 }  // extern "C"

@@ -154,4 +154,20 @@ int fhelin_debug_dot_window(fhelin_ctx* c, const fhelin_ct* const* cur, const fh
     FHELIN_CATCH
 }
 
+int fhelin_debug_rotate_many_batch(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n_ct, const int32_t* indices, int32_t n,
+                                   fhelin_ct** outs) {
+    NEED(c && cts && indices && outs);
+    FHELIN_TRY
+    if (n_ct < 1 || n < 1) throw Error(FHELIN_ERR_ARG, "debug_rotate_many_batch: at least one ciphertext and one index");
+    std::vector<CtPtr> in(n_ct);
+    for (int i = 0; i < n_ct; ++i) {
+        if (!cts[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
+        in[i] = ct_in(c, cts[i]);
+    }
+    const std::vector<std::vector<CtPtr>> o = c->ev.rotate_many_batch(in, std::vector<int>(indices, indices + n));
+    for (int i = 0; i < n_ct; ++i)
+        for (int k = 0; k < n; ++k) outs[(size_t)i * n + k] = wrap(c, o[i][k]);
+    FHELIN_CATCH
+}
+
 }  // extern "C"

@@ -164,6 +164,14 @@ int fhelin_stats(fhelin_ctx* c, uint64_t* out, int32_t cap, int32_t reset);
  * free range per slab and that a trim returns every slab.  out (cap >= 6): [0] peak bytes in use, [1] peak bytes held, [2] slabs
  * obtained, [3] out-of-memory events, [4] coalesced-to-one-range-per-slab (1/0), [5] trim-returned-everything (1/0).  No GPU needed. */
 int fhelin_debug_pool_selftest(uint64_t seed, int32_t n_ops, uint64_t device_bytes, uint64_t* out, int32_t cap);
+/* FHELIN_POOL_FILL=<w>, w in 1..4095 (a test aid; unset or 0: off; any other value: fhelin_ctx_create fails with FHELIN_ERR_ARG): the
+ * arena hands out every block with w in each 32-bit word of its rounded size, so that a result which depends on memory nobody wrote
+ * depends on w.  _fill_stats: blocks and bytes filled so far (both 0 with the knob off).  _fill_selftest: the knob on host memory
+ * (host malloc as the backend, a host fill): n_ops seeded allocations / frees over both granule classes and more than one slab; every
+ * handed-out word is w, every other live block keeps its own marker, w = 0 writes nothing.  out (cap >= 6): [0] blocks handed out,
+ * [1] the sum of their rounded sizes, [2] blocks filled, [3] bytes filled, [4] slabs obtained, [5] hand-outs at the 4 KiB granule. */
+int fhelin_debug_pool_fill_stats(fhelin_ctx* c, uint64_t* blocks, uint64_t* bytes);
+int fhelin_debug_pool_fill_selftest(uint64_t seed, int32_t n_ops, uint32_t w, uint64_t* out, int32_t cap);
 
 
 /* ---- keys (client side; sampling on the host, polynomial arithmetic on the GPU) ---------------- */
@@ -365,6 +373,11 @@ int fhelin_debug_dot_cyclic(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t 
  * present).  dest is in/out: 32 imported ciphertexts of the operands' shape, overwritten - accumulate != 0: added to. */
 int fhelin_debug_dot_window(fhelin_ctx* c, const fhelin_ct* const* cur /* [32] */, const fhelin_ct* const* prev /* [32] */,
                             const fhelin_pt* const* pts /* [32] */, fhelin_ct* const* dest /* [32] */, int32_t accumulate);
+/* outs[i][k] = rot(cts[i], indices[k]) for i < n_ct, k < n: the hoisted rotations of MANY inputs behind one ModUp
+ * (Evaluator::rotate_many_batch, which the composites and bootstrapping call), bit-identical to fhelin_rotate.  Two or more inputs of one
+ * shape and more than 16 non-zero indices take its per-input, per-16-row chunks. */
+int fhelin_debug_rotate_many_batch(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n_ct, const int32_t* indices, int32_t n,
+                                   fhelin_ct** outs /* [n_ct][n] */);
 
 /* ---- FHEController composite circuit ops (callers of the hot path) --------
  * One entry point per reference method; `vector<Ctxt>` travels as (array of handles, count); outputs are

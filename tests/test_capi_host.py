@@ -139,7 +139,7 @@ def test_level_plan_bookkeeping_on_a_host_context(fa):
 
 
 def test_device_arena_logic_on_a_pretend_device(fa):
-    """csrc/context.cpp DevicePool (slabs from the driver, best fit, address-ordered free list with coalescing) against a mock backend:
+    """csrc/pool.cpp DevicePool (slabs from the driver, best fit, address-ordered free list with coalescing) against a mock backend:
     blocks never overlap and lie inside a slab, the pool follows the bytes in use closely (the exact-size caching pool it replaces
     held 1.6 x), freeing everything leaves one free range per slab, and a trim hands every slab back."""
     import ctypes as C

@@ -82,3 +82,23 @@ def test_debug_dot_entry_points_need_a_device_and_their_arguments(fa):
         assert lib.fhelin_debug_dot_window(e.h, arr, arr, arr, arr, 0) == ERR_ARG      # a null destination
     finally:
         e.close()
+
+
+def test_debug_rotate_many_batch_checks_its_arguments(fa):
+    lib = fa.load_library()
+    assert hasattr(lib, "fhelin_debug_rotate_many_batch") and hasattr(fa.Engine, "debug_rotate_many_batch")
+    e = fa.Engine("toy", device=-1)
+    try:
+        outs = (C.c_void_p * 4)()
+        arr = (C.c_void_p * 2)()
+        idx = (C.c_int32 * 2)(1, 2)
+        assert lib.fhelin_debug_rotate_many_batch(None, arr, 2, idx, 2, outs) == ERR_ARG
+        assert lib.fhelin_debug_rotate_many_batch(e.h, None, 2, idx, 2, outs) == ERR_ARG
+        assert lib.fhelin_debug_rotate_many_batch(e.h, arr, 2, None, 2, outs) == ERR_ARG
+        assert lib.fhelin_debug_rotate_many_batch(e.h, arr, 2, idx, 2, None) == ERR_ARG
+        assert lib.fhelin_debug_rotate_many_batch(e.h, arr, 0, idx, 2, outs) == ERR_ARG
+        assert lib.fhelin_debug_rotate_many_batch(e.h, arr, 2, idx, 0, outs) == ERR_ARG
+        assert lib.fhelin_debug_rotate_many_batch(e.h, arr, 2, idx, 2, outs) == ERR_ARG          # a null ciphertext in the array
+        assert not any(outs)
+    finally:
+        e.close()
