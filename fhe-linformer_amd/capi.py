@@ -243,6 +243,7 @@ def load_library():
         "fhelin_debug_dot_cyclic": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
         "fhelin_debug_dot_window": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32]),
         "fhelin_debug_rotate_many_batch": (i32, [vp, C.POINTER(vp), i32, C.POINTER(i32), i32, C.POINTER(vp)]),
+        "fhelin_debug_ks_accp": (i32, [vp, vp, i32, i32, C.POINTER(i32), i32, vp]),
         "fhelin_ctx_set_interleave": (i32, [vp, i32]),
         "fhelin_ctx_interleave": (i32, [vp, C.POINTER(i32)]),
         "fhelin_evalkeys_interleave": (i32, [C.c_char_p, C.POINTER(i32)]),
@@ -1133,6 +1134,17 @@ class Engine:
         self._ck(self.lib.fhelin_debug_rotate_many_batch(self.h, self._harr(cts), len(cts), idx, n, outs))
         flat = self._cts(outs, len(cts) * n)
         return [flat[i * n:(i + 1) * n] for i in range(len(cts))]
+
+    def debug_ks_accp(self, digits, ell, indices=()):
+        """INTT of the special-limb half of a key switch's inner product over the given digits [batch][beta][ell + n_p][N] (any values
+        below 2^60): the identity form over the relinearisation key, or the merged form over `indices` (fhelin.h)"""
+        d = np.ascontiguousarray(digits, dtype=np.uint64)
+        batch, n = d.shape[0], len(indices)
+        assert d.shape[2:] == (ell + self.n_p, self.N)
+        idx = (C.c_int32 * max(n, 1))(*indices)
+        out = np.empty((batch, 2, self.n_p, self.N), dtype=np.uint64)
+        self._ck(self.lib.fhelin_debug_ks_accp(self.h, d.ctypes.data_as(C.c_void_p), ell, batch, idx, n, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     # ---- FHEController composites (names follow the reference methods)
     @staticmethod

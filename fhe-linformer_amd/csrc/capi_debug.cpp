@@ -170,4 +170,24 @@ int fhelin_debug_rotate_many_batch(fhelin_ctx* c, const fhelin_ct* const* cts, i
     FHELIN_CATCH
 }
 
+int fhelin_debug_ks_accp(fhelin_ctx* c, const uint64_t* digits, int32_t ell, int32_t batch, const int32_t* indices, int32_t n_rot,
+                         uint64_t* out) {
+    NEED(c && digits && out && (indices || n_rot == 0));
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    if (ell < 1 || ell > x.L + 1 || batch < 1) throw Error(FHELIN_ERR_ARG, "debug_ks_accp: bad shape");
+    const size_t N = x.N;
+    const size_t nd = (size_t)batch * x.lvl[ell].beta * (ell + x.K) * N, no = (size_t)batch * 2 * x.K * N;
+    for (size_t i = 0; i < nd; ++i)
+        if (digits[i] >> 60) throw Error(FHELIN_ERR_ARG, "debug_ks_accp: a digit is not below 2^60");
+    Scratch<u64> ext = x.scratch<u64>(nd);
+    Scratch<u64> acc = x.scratch<u64>(no);
+    hip_check(hipMemcpyAsync(ext, digits, nd * 8, hipMemcpyHostToDevice, x.stream), "debug_ks_accp upload");
+    c->ev.debug_ks_accp(ext, ell, batch, indices, n_rot, acc);
+    hip_check(hipMemcpyAsync(out, acc, no * 8, hipMemcpyDeviceToHost, x.stream), "debug_ks_accp download");
+    x.sync();
+    FHELIN_CATCH
+}
+
 }  // extern "C"

@@ -200,6 +200,13 @@ struct Context {
     // FHELIN_ROT_GATHER=0: both end in moddown_finish_kernel, which gathers (A/B).  Bit-identical either way.
     bool rot_gather = true;
     bool fuse_lift = true;      // rescale: centred lift formed in the NTT's first-pass load (FHELIN_FUSE_LIFT)
+    // FHELIN_FUSE_ACCP_ROWS: 1 - the special-limb half of a single-key inner product (relinearisation, plain and per-row
+    // rotations; at most 8 digits) is formed in the load stage of the inverse NTT's row pass (kernels_elem.h NttProduct), the inner-product
+    // launch covers the Q limbs only and the ModDown starts at the column pass; 2 - the merged rotation sums too (measured slower: their
+    // inner product shares key words between row pairs and stages digit tiles in LDS, which the row pass does not); 0 - the separate
+    // launches everywhere.  Bit-identical every way.  FHELIN_ACCP_ROWS_MIN_VECS=<n>: only accumulators of at least n special-limb vectors
+    int fuse_accp_rows = 1;
+    int accp_rows_min_vecs = 0;
     bool lds_digits = true;     // merged rotate-and-sum: digit tiles staged once in LDS when every rotation keeps tiles in place (FHELIN_LDS_DIGITS)
     struct FftDev {
         const u32* rot = nullptr;     // [slots]      5^j mod 4 slots

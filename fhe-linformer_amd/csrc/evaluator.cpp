@@ -228,7 +228,7 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     Scratch<u64> ext = modup(shu, c_ntt, !gather);   // digits times 2^64 for the keys as they are stored: launch_ks_inner ends in redc128
     Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
     Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-    launch_ks_inner(c_.dt, sh, accQ, accP, ext, evk, c_ntt, c_.stream);
+    inner_product(sh, accQ, accP, ext, evk, c_ntt, false);
     // the finish in the row pass of NTT(conv): for an identity output map (relinearisation) and for a rotation gathered above; a rotation
     // written through the inverse automorphism map only with FHELIN_FUSE_MODDOWN=1
     if (gather) moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, true);
@@ -274,6 +274,35 @@ Scratch<u64> Evaluator::modup(const KsShape& up, const u64* src, bool times_r2, 
     return ext;
 }
 
+// The inner product of a key switch.  With FHELIN_FUSE_ACCP_ROWS the inner-product launch covers the Q limbs only and the special-limb
+// sums are formed by the inverse row pass of their own transform (launch_ntt_rows_product): accP is never stored in NTT form, read back
+// and stored again, and the ModDown starts at the column pass.  The same residues bit for bit.  Left on the separate launches: the merged
+// rotation sums unless the knob is 2 (Context::fuse_accp_rows: measured slower), the exact-products tail (its accP carries a K+1-th limb
+// that launch_affine_acc_items writes), a caller that works on accP before its tail (fuse = false) and, below
+// Context::accp_rows_min_vecs vectors, the small accumulators.
+void Evaluator::inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse) {
+    const int K = c_.K, nvec = sh.batch * 2 * K;
+    const bool measured_faster = !multi && sh.beta <= 8;   // the classes of tools/accp_rows_probe.py where the fused form wins
+    const bool want = c_.fuse_accp_rows >= 2 || (c_.fuse_accp_rows == 1 && measured_faster);
+    sh.accp_rows = fuse && want && !sh.accp_limbs && sh.k == K && nvec >= c_.accp_rows_min_vecs ? 1 : 0;
+    if (multi) launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, c_ntt, c_.stream);
+    else launch_ks_inner(c_.dt, sh, accQ, accP, ext, evk, c_ntt, c_.stream);
+    if (!sh.accp_rows) return;
+    NttProduct pr;
+    pr.sh = sh;
+    pr.ext = ext;
+    pr.evk = evk;
+    pr.multi = multi ? 1 : 0;
+    c_.stats.limb_ntt += (u64)nvec;   // the transform of accP is counted here, where its first pass runs
+    launch_ntt_rows_product(c_.dt, LimbBatch{accP, nvec, nullptr, c_.L + 1, K}, pr, c_.stream);
+}
+
+void Evaluator::accp_inverse(const KsShape& sh, u64* accP) {
+    const LimbBatch b{accP, sh.batch * 2 * c_.K, nullptr, c_.L + 1, c_.K};
+    if (sh.accp_rows) launch_ntt_cols_inverse(c_.dt, b, c_.stream);
+    else c_.ntt(b, true);
+}
+
 // ModDown of the accumulator pair accQ [sh.batch][2][ell][N], accP [sh.batch][2][K][N] (accP is transformed in place):
 // out = (accQ - NTT(conv(INTT(accP)))) * P^-1 + add0/add1 (+ post), written through `map` / the rows' maps.
 // sh.gather: the pair was gathered through the rotation's map by launch_ks_inner (c0 included): the conversion takes the signs of the
@@ -286,9 +315,9 @@ Scratch<u64> Evaluator::modup(const KsShape& up, const u64* src, bool times_r2, 
 void Evaluator::moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map,
                         const u64* post, bool row_pass, const std::function<void(const u64* conv)>& finish) {
     const size_t N = c_.N;
-    const int B = sh.batch, ell = sh.ell, K = c_.K;
+    const int B = sh.batch, ell = sh.ell;
     if (row_pass && sh.gsrc && !sh.gsrc_pmod) throw Error(FHELIN_ERR_INTERNAL, "moddown: the row pass cannot gather");
-    c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, c_.L + 1, K}, true);
+    accp_inverse(sh, accP);
     Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * ell * N);
     launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, c_.stream);
     const LimbBatch cb{conv, B * 2 * ell, nullptr, 0, ell};
@@ -325,9 +354,9 @@ void Evaluator::moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out,
 // out [sh.batch][2][ell-1][N] (sh.out_stride apart) = (accQ - NTT(conv(INTT(accP), INTT(top limb of accQ)))) * (P q_top)^-1
 void Evaluator::moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out) {
     const size_t N = c_.N;
-    const int B = sh.batch, ell = sh.ell, K = c_.K;
+    const int B = sh.batch, ell = sh.ell;
     const LevelTables& lt = c_.lvl[ell];
-    c_.ntt(LimbBatch{accP, B * 2 * K, nullptr, c_.L + 1, K}, true);
+    accp_inverse(sh, accP);
     Scratch<u64> top = c_.scratch<u64>((size_t)B * 2 * N);
     {
         LimbBatch tb{top, B * 2, nullptr, ell - 1, 1, accQ + (size_t)(ell - 1) * N};
@@ -417,8 +446,26 @@ void Evaluator::rotation_sum(KsShape& sh, const u64* ext, const u64* c1, const u
     if (rp) sh.gsrc_pmod = c_.d_pmod;
     Scratch<u64> accQ = c_.scratch<u64>((size_t)sh.batch * 2 * sh.ell * N);
     Scratch<u64> accP = c_.scratch<u64>((size_t)sh.batch * 2 * sh.k * N);
-    launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, c1, c_.stream);
+    inner_product(sh, accQ, accP, ext, nullptr, c1, true);
     moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, rp);
+}
+
+void Evaluator::debug_ks_accp(const u64* ext, int ell, int batch, const int* indices, int n_rot, u64* out) {
+    const size_t N = c_.N, pn = (size_t)ell * N;
+    if (ell < 1 || ell > c_.L + 1 || batch < 1 || n_rot < 0 || n_rot > (int)KsShape::MAX_ROT) throw Error(FHELIN_ERR_ARG, "debug_ks_accp: bad shape");
+    if (!n_rot && !relin_key) throw Error(FHELIN_ERR_KEY, "debug_ks_accp: no relinearisation key");
+    KsShape sh{ell, c_.K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, batch, pn, 0, 0, 0};
+    Scratch<u64> own = c_.scratch<u64>((size_t)batch * pn);    // the Q limbs' own-digit operand: the Q half is computed and dropped
+    hip_check(hipMemsetAsync(own, 0, (size_t)batch * pn * sizeof(u64), c_.stream), "hipMemsetAsync(debug_ks_accp)");
+    Scratch<u64> accQ = c_.scratch<u64>((size_t)batch * 2 * pn);
+    if (n_rot) {
+        set_rotations(sh, rotations(indices, n_rot), true, nullptr);
+        inner_product(sh, accQ, out, ext, nullptr, own, true);
+    } else {
+        inner_product(sh, accQ, out, ext, relin_key->d, own, false);
+    }
+    accp_inverse(sh, out);
+    launch_ok("debug_ks_accp");
 }
 
 int Evaluator::slot_count(int slots) const { return slots > 0 ? slots : (1 << c_.prm.log_slots); }
@@ -592,7 +639,7 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
             // sum_r V_r . sigma_r(d * evk_r) in the extended basis: the merged inner product with the folded keys
             Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
             Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-            launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, base + pn, s);
+            inner_product(sh, accQ, accP, ext, nullptr, base + pn, true);
             if (!merged) {
                 // what does not pass through the key switch: V_0 (c0, c1) + sum_r V_r sigma_r(c0)
                 Scratch<u64> pre = c_.scratch<u64>((size_t)B * ctw);
@@ -1157,7 +1204,7 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
                 sh.gsrc = base;
                 sh.gsrc_stride = ctw;
                 sh.gsrc_pmod = c_.d_pmod;
-                launch_ks_inner(c_.dt, sh, accQ, accP, ext, nullptr, base + pn, s);
+                inner_product(sh, accQ, accP, ext, nullptr, base + pn, false);
                 moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, true);
             } else {
                 if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), accQ, accP, ext, nullptr, base + pn, s);
@@ -1675,7 +1722,7 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
             Scratch<u64> ext = modup(sh, c_ntt, true);   // digits times 2^64: launch_ks_inner ends in redc128
             Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
             Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-            launch_ks_inner(c_.dt, sh, accQ, accP, ext, relin_key->d, c_ntt, s);
+            inner_product(sh, accQ, accP, ext, relin_key->d, c_ntt, false, f != 2);   // f = 2: accP itself is doubled below
             // X_Q = f acc_Q + P (f (d0, d1) + constant - subtrahend),  X_P = f acc_P
             launch_affine_acc(c_.dt, sh, accQ, d[0]->d, sadj.empty() ? nullptr : sadj[0]->d, cst, cadd != 0.0 ? 1 : 0, f, c_.d_pmod, s);
             if (f == 2) launch_ew_add(c_.dt, accP, accP, accP, B * 2 * K, B * 2 * K, L1, K, s);

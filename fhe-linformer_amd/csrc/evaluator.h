@@ -219,6 +219,11 @@ public:
     // all inputs, per input the inner products of all indices, one ModDown over all inputs x indices.  out[i][k] holds exactly
     // the residues of rotate(xs[i], indices[k]).
     std::vector<std::vector<CtPtr>> rotate_many_batch(const std::vector<CtPtr>& xs, const std::vector<int>& indices);
+    // test hook (fhelin_debug_ks_accp): the special-limb half of a key switch's inner product over digits the caller chooses residue by
+    // residue, through inner_product and accp_inverse as they stand.  ext [batch][beta][ell+K][N] (device), out [batch][2][K][N] (device):
+    // INTT(accP).  n_rot = 0: the identity form over the relinearisation key as stored (the sum comes times 2^-64); else the merged form
+    // over the permuted keys of the n_rot <= 7 rotations.
+    void debug_ks_accp(const u64* ext, int ell, int batch, const int* indices, int n_rot, u64* out);
     // rows of identical shape through one batched key switch with an explicit Galois element and key (conjugation, the SubSum
     // rotations by multiples of the slot count); accumulate: v_i + sigma_g(v_i)
     std::vector<CtPtr> rotate_galois_batch(const std::vector<CtPtr>& v, u64 galois, const EvalKey& key, bool accumulate);
@@ -352,6 +357,11 @@ private:
                         size_t post_stride);
     // the stages every key switch is built from (evaluator.cpp "key-switch stages"): the place to change the pipeline
     Scratch<u64> modup(const KsShape& up, const u64* src, bool times_r2, int group2 = 0, size_t group2_stride = 0);
+    // the inner product of a key switch into the accumulator pair (multi: launch_ks_inner_multi, else launch_ks_inner over evk); where the
+    // special-limb half is formed in the inverse NTT's row pass it sets sh.accp_rows, which the ModDown tails read.  fuse = false: the
+    // caller touches accP before its tail (it must then hold the residues themselves)
+    void inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse = true);
+    void accp_inverse(const KsShape& sh, u64* accP);   // INTT(accP) of a tail: the column pass alone with sh.accp_rows
     void moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
                  bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr);
     void moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out);

@@ -214,7 +214,28 @@ struct KsShape {
     // launch_ks_inner: limbs per component of accP (0: k).  The exact ModDown + rescale keeps one more slot per component, for the
     // accumulator's top Q limb (launch_affine_acc_items), so that ONE inverse transform covers the special limbs and that limb
     int accp_limbs = 0;
+    // accp_rows = 1: accP arrives ROW-TRANSFORMED.  launch_ks_inner / launch_ks_inner_multi then cover the ell Q limbs only, and the special
+    // limbs of the same sum are formed by launch_ntt_rows_product, the inverse row pass that takes the products as its input; the ModDown
+    // tails run the inverse column pass alone (launch_ntt_cols_inverse).  Set by Evaluator::inner_product (FHELIN_FUSE_ACCP_ROWS).
+    int accp_rows = 0;
 };
+// The special-limb half of a key switch's inner product as the load stage of the inverse NTT's row pass (kernels_ntt.hip):
+//     accP[b][c][p][.] = rows( redc128( sum_{r < R} sum_{j < beta} d_{r,j}[p][ m_r(e) ] * key_{r,j,c}[p][e] ) )
+// with sh, ext and evk exactly as the inner-product launch of the same key switch takes them: multi = 0 the operands of launch_ks_inner
+// (R = 1; sh.gather: the row's map and its permuted, pre-split key, else the identity and the keys as stored with digits times 2^64),
+// multi = 1 those of launch_ks_inner_multi (sh.n_rot maps and pre-split keys).  A special limb has no own-digit slot and no c0 addend.
+// The 128-bit sums are flushed every 8 and folded every 16 terms like ks_inner_multi_kernel's: the canonical residues the inner-product
+// kernels store, whatever the order.
+struct NttProduct {
+    KsShape sh;
+    const u64* ext = nullptr;
+    const u64* evk = nullptr;
+    int multi = 0;
+};
+// accP [sh.batch][2][sh.k][N] <- the inverse row pass of the products (b describes accP: sh.batch * 2 * sh.k vectors, limb_count = sh.k)
+void launch_ntt_rows_product(const DeviceTables& t, const LimbBatch& b, const NttProduct& p, hipStream_t s);
+// the inverse column pass alone, in place, on vectors whose row pass has run (launch_ntt_rows_product)
+void launch_ntt_cols_inverse(const DeviceTables& t, const LimbBatch& b, hipStream_t s);
 // K6: cc [ell][N] coefficient form, c_ntt [ell][N] NTT form -> ext [beta][ell+k][N]
 //     (own-digit slots stay unused — K7 reads c_ntt there; the others get the fast-basis-extended values, coefficient form)
 void launch_modup_conv(const DeviceTables& t, const KsShape& sh, u64* ext, const u64* cc, const u64* c_ntt, const u64* hatinv,

@@ -994,7 +994,8 @@ void launch_modup_conv(const DeviceTables& t, const KsShape& sh_in, u64* ext, co
 }
 void launch_ks_inner(const DeviceTables& t, const KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt,
                      hipStream_t s) {
-    dim3 g((1u << t.log_n) / 512, (unsigned)(sh.batch * (sh.ell + sh.k)));
+    // ks_block derives the target limb from the grid: with sh.accp_rows the launch ends at the Q limbs (accP: launch_ntt_rows_product)
+    dim3 g((1u << t.log_n) / 512, (unsigned)(sh.batch * (sh.accp_rows ? sh.ell : sh.ell + sh.k)));
     if (sh.gather)
         hipLaunchKernelGGL(ks_inner_kernel<true>, g, dim3(256), 0, s, t, sh, accQ, accP, ext, evk, c_ntt);
     else
@@ -1004,15 +1005,16 @@ void launch_ks_inner_multi(const DeviceTables& t, const KsShape& sh, u64* accQ, 
                            hipStream_t s) {
     static const int pair_rows = [] { const char* e = std::getenv("FHELIN_KS_ROW_PAIRS"); return e ? std::atoi(e) : 1; }();
     const bool stage = sh.lds_digits && sh.rot_ext_stride == 0 && sh.beta <= 4;
+    const int nt = sh.accp_rows ? sh.ell : sh.ell + sh.k;   // target limbs of the launch (KsShape::accp_rows: the Q limbs only)
     if (pair_rows && sh.batch >= 2) {       // two rows per thread: the rows' key words are loaded once
-        dim3 g((1u << t.log_n) / 512, (unsigned)(((sh.batch + 1) / 2) * (sh.ell + sh.k)));
+        dim3 g((1u << t.log_n) / 512, (unsigned)(((sh.batch + 1) / 2) * nt));
         if (stage)
             hipLaunchKernelGGL((ks_inner_multi_kernel<true, 2>), g, dim3(256), 0, s, t, sh, accQ, accP, ext, c_ntt);
         else
             hipLaunchKernelGGL((ks_inner_multi_kernel<false, 2>), g, dim3(256), 0, s, t, sh, accQ, accP, ext, c_ntt);
         return;
     }
-    dim3 g((1u << t.log_n) / 512, (unsigned)(sh.batch * (sh.ell + sh.k)));
+    dim3 g((1u << t.log_n) / 512, (unsigned)(sh.batch * nt));
     if (stage)
         hipLaunchKernelGGL((ks_inner_multi_kernel<true, 1>), g, dim3(256), 0, s, t, sh, accQ, accP, ext, c_ntt);
     else

@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "kernels.h"
+#include "kernels_elem.h"
 
 namespace fhelin {
 
@@ -406,7 +407,126 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIFT ? 3 : 
 // pass B: row transforms over the low 8 bits of the index.  Tile = 16 consecutive rows of 256
 // (4096 contiguous residues); tile-local index e == global index - tile*4096.
 // ------------------------------------------------------------------------------------------------
-template <bool INVERSE, bool LAZY, bool EPI>
+// The product load stage of the inverse row pass (NttProduct, kernels_elem.h): the residue at tile-local position e = tau + 256 k (the
+// bit-8 window: every key load of a wave is 512 contiguous bytes, every digit gather moves with whole 128-byte lines as the maps do) becomes
+// the canonical residue of the special-limb inner product at e and goes straight to the LDS slot that exchange(8 -> 0) would have written
+// it to: the transform's sixteen registers are not live yet, so PG slots at a time carry their sums (an Acc30 and a 128-bit pair each)
+// through the (rotation, digit) terms, with 2 PG independent loads per term, and the slot groups are a real loop.  Limb, row, component,
+// key and map bookkeeping is workgroup-uniform: scalar loads, scalar branches.
+// Bounds: as ks_inner_multi_kernel - keys canonical, digits canonical or below 86q (q < 2^53): a flush every 8 terms, a fold every 16.
+// SHORT: at most 8 terms in all (one rotation of up to 8 digits - every plain key switch of the default chain): no flush inside the
+// loops, the 128-bit pairs exist only at the end, and PG = 8 slots fit; else PG = 4.
+template <int PG, bool SHORT>
+__device__ __forceinline__ void product_to_lds(u64* lds, const NttArgs& a, const NttProduct& pr, const u64* __restrict__ barrett,
+                                               const u64* __restrict__ qinv, int vec, int tile, int limb, u64 q, int tau) {
+    const KsShape& sh = pr.sh;
+    const int log_n = a.log_n;
+    const int K = sh.k, nt = sh.ell + K;
+    const int poly = uniform(vec / K), p = vec - poly * K, bi = poly >> 1, comp = poly & 1;
+    const int tt = sh.ell + p;
+    const size_t N = (size_t)1 << log_n;
+    const u64* ext = pr.ext;
+    const u64* key0 = pr.evk;
+    const u32* map0 = nullptr;
+    int n_rot = 1;
+    if (pr.multi) {
+        ext += (size_t)bi * (sh.ext_batch_stride ? sh.ext_batch_stride : (size_t)sh.beta * nt * N);
+        n_rot = sh.n_rot;
+    } else {
+        int ri = 0;
+        if (sh.row_mod) {
+            ri = bi % sh.row_mod;
+            ext += (size_t)(bi / sh.row_mod) * sh.ext_batch_stride;
+            key0 = sh.evk_row[ri];
+        } else {
+            if (!sh.shared_input) ext += (size_t)bi * sh.beta * nt * N;
+            if (sh.per_row) {
+                ri = bi;
+                key0 = sh.evk_row[bi];
+            }
+        }
+        if (sh.gather) map0 = sh.map_row[ri];
+    }
+    const int khi = pr.multi || sh.gather ? 32 : 30;   // pre-split keys (EvalKey::d_perm, folded keys) or keys as stored
+    Barrett br;
+    br.q = q;
+    br.r0 = barrett[2 * limb];
+    br.r1 = barrett[2 * limb + 1];
+    const u64 qi = qinv[limb];
+    const size_t kstride = (size_t)(sh.L1 + K) << log_n;   // one evk component
+    const size_t klimb = ((size_t)limb << log_n) + ((size_t)tile << 12);
+    const u32 lane8 = 8u * (u32)tau;
+    u64* const from = lds + lds_slot(tile_index(tau, 0, 8));
+#pragma unroll 1
+    for (int g = 0; g < 16; g += PG) {
+        u64 lo[PG], hi[PG];
+        Acc30 acc[PG];
+#pragma unroll
+        for (int i = 0; i < PG; ++i) {
+            lo[i] = hi[i] = 0;
+            acc[i] = Acc30{0, 0, 0};
+        }
+        int pending = 0, folded = 0;
+#pragma unroll 1
+        for (int r = 0; r < n_rot; ++r) {
+            const u32* map = pr.multi ? sh.map_rot[r] : map0;
+            const u64* key = pr.multi ? sh.evk_rot[r] : key0;
+            const u64* dig = ext + (size_t)r * sh.rot_ext_stride + ((size_t)tt << log_n);
+            u32 off[PG];   // byte offset of the digit in its limb vector (below N * 8 <= 2^20)
+            if (map) {
+                const Stream ms = stream(map + ((size_t)tile << 12));
+#pragma unroll
+                for (int i = 0; i < PG; ++i) off[i] = 8u * ld32(ms, 4u * (u32)tau, 1024 * i, 1024 * g);
+            } else {
+#pragma unroll
+                for (int i = 0; i < PG; ++i) off[i] = ((u32)tile << 15) + lane8 + 2048u * (u32)(g + i);
+            }
+#pragma unroll 1
+            for (int j = 0; j < sh.beta; ++j) {
+                const Stream ds = stream(dig + ((size_t)j * nt << log_n));
+                const Stream ks = stream(key + (size_t)(2 * j + comp) * kstride + klimb);
+                u64 d[PG], kw[PG];
+#pragma unroll
+                for (int i = 0; i < PG; ++i) {
+                    d[i] = ld64(ds, off[i], 0);
+                    kw[i] = ld64(ks, lane8, 2048 * i, 2048 * g);
+                }
+#pragma unroll
+                for (int i = 0; i < PG; ++i) {
+                    u32 d0, d1;
+                    split30(d[i], d0, d1);
+                    // the key's halves without a branch: pack30 keeps the low half (below 2^30) in the low dword and the high half in
+                    // the high dword, a key as stored is split here
+                    mac30(acc[i], d0, d1, (u32)kw[i] & 0x3FFFFFFFu, (u32)(kw[i] >> khi));
+                }
+                if (!SHORT && ++pending == 8) {
+                    pending = 0;
+                    const bool fold = ++folded == 2;
+                    if (fold) folded = 0;
+#pragma unroll
+                    for (int i = 0; i < PG; ++i) {
+                        acc30_flush(acc[i], lo[i], hi[i]);
+                        acc[i] = Acc30{0, 0, 0};
+                        if (fold) {   // reduces, does not divide: the factor 2^64 stays
+                            lo[i] = barrett_reduce128(lo[i], hi[i], br);
+                            hi[i] = 0;
+                        }
+                    }
+                }
+            }
+        }
+        u64* const fg = from + lds_slot(tile_index(0, 1, 8)) * g;   // the slot of (0, k) is k times the slot of (0, 1) in this window
+#pragma unroll
+        for (int i = 0; i < PG; ++i) {
+            acc30_flush(acc[i], lo[i], hi[i]);
+            // every term carries 2^64 once: the canonical residue of the plain sum
+            fg[lds_slot(tile_index(0, i, 8))] = redc128(lo[i], hi[i], q, qi);
+        }
+    }
+}
+
+// PROD (inverse only): the input is not loaded: product_to_lds has left it in LDS, as the first half of exchange(8 -> 0) would have
+template <bool INVERSE, bool LAZY, bool EPI, bool PROD = false>
 __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, int tile, int limb, const LimbConst& c,
                                           const NttEpilogue* ep) {
     const int log_n = a.log_n;
@@ -520,11 +640,19 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
         }
     } else {
         // coalesced load through the bit-8 window, then an LDS exchange to the bit-0 window of the first GS round
-#pragma unroll
-        for (int k = 0; k < 16; ++k) x[k] = ld64(sbase, lane8, koff(k, 8));
         RoundTw rt, rn;
-        load_round_tw_rows(rt, trows, tau);                          // per-thread twiddles of the first four stages
-        exchange(x, lds, tau, 8, 0, false);
+        if constexpr (PROD) {
+            load_round_tw_rows(rt, trows, tau);
+            __syncthreads();
+            const u64* const to = lds + lds_slot(tile_index(tau, 0, 0));
+#pragma unroll
+            for (int k = 0; k < 16; ++k) x[k] = to[lds_slot(tile_index(0, k, 0))];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) x[k] = ld64(sbase, lane8, koff(k, 8));
+            load_round_tw_rows(rt, trows, tau);                      // per-thread twiddles of the first four stages
+            exchange(x, lds, tau, 8, 0, false);
+        }
         inv_round<0, 4, false, LAZY, 0, 1>(x, rt, c, nullptr);
         load_round_tw<0, 4>(rn, tw, log_n, 4, tile << 4, tau >> 4);
         exchange(x, lds, tau, 0, 4, true);
@@ -538,18 +666,15 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
     }
 }
 
-template <bool INVERSE, bool EPI = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ntt_rows_kernel(NttArgs a, NttEpilogue ep) {
-    __shared__ u64 lds[LDS_WORDS];
+// Block -> (vector, tile) map of the row pass.  A row tile needs its own 4 KiB twiddle slice per (limb, tile); vectors of the same
+// limb (the two polys of a ciphertext, the rows of a batch) reuse it.  Blocks b and b+8 share an XCD (L2), so
+// each XCD gets a contiguous range of logical ids, ordered (limb, tile, repetition): the slice is fetched once
+// per XCD instead of once per block.  Placement affects speed only.
+__device__ __forceinline__ void rows_block(const NttArgs& a, int& vec, int& tile) {
     const int logtiles = a.log_n - 12;
-    // Block -> (vector, tile) map.  A row tile needs its own 4 KiB twiddle slice per (limb, tile); vectors of the same
-    // limb (the two polys of a ciphertext, the rows of a batch) reuse it.  Blocks b and b+8 share an XCD (L2), so
-    // each XCD gets a contiguous range of logical ids, ordered (limb, tile, repetition): the slice is fetched once
-    // per XCD instead of once per block.  Placement affects speed only.
     int lid = blockIdx.x;
     const int nblk = gridDim.x;
     if ((nblk & 7) == 0) lid = (lid & 7) * (nblk >> 3) + (lid >> 3);
-    int vec, tile;
     if (a.period > 0) {
         const int nper = a.nvec / a.period;
         const int rep = lid % nper, r = lid / nper;
@@ -561,6 +686,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
     }
     vec = uniform(vec);   // per-workgroup values: pinned to SGPRs, never recomputed per lane
     tile = uniform(tile);
+}
+
+template <bool INVERSE, bool EPI = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ntt_rows_kernel(NttArgs a, NttEpilogue ep) {
+    __shared__ u64 lds[LDS_WORDS];
+    int vec, tile;
+    rows_block(a, vec, tile);
     const int limb = uniform(limb_of(a, vec));
     if (limb < 0) return;
     const LimbConst c = limb_const(a, limb);
@@ -568,6 +700,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
         rows_body<INVERSE, true, EPI>(a, lds, vec, tile, limb, c, &ep);
     else
         rows_body<INVERSE, false, EPI>(a, lds, vec, tile, limb, c, &ep);
+}
+
+// The inverse row pass over the special-limb products of a key switch (NttProduct).  Vectors are (row, component, special limb) with
+// the limb fastest, so the period of the block map is k and its repetitions are (row, component): component b and component a of one
+// (row, limb, tile), which gather the same digit tile, are neighbours in one XCD's share.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ntt_rows_product_kernel(NttArgs a, NttProduct pr, const u64* barrett,
+                                                                                                        const u64* qinv) {
+    __shared__ u64 lds[LDS_WORDS];
+    int vec, tile;
+    rows_block(a, vec, tile);
+    const int limb = uniform(limb_of(a, vec));
+    const LimbConst c = limb_const(a, limb);
+    if ((pr.multi ? pr.sh.n_rot : 1) * pr.sh.beta <= 8)
+        product_to_lds<8, true>(lds, a, pr, barrett, qinv, vec, tile, limb, c.q, threadIdx.x);
+    else
+        product_to_lds<4, false>(lds, a, pr, barrett, qinv, vec, tile, limb, c.q, threadIdx.x);
+    if (lazy_prime<true>(c.q))
+        rows_body<true, true, false, true>(a, lds, vec, tile, limb, c, nullptr);
+    else
+        rows_body<true, false, false, true>(a, lds, vec, tile, limb, c, nullptr);
 }
 
 template <int A>
@@ -582,14 +734,22 @@ void launch_cols(const NttArgs& a, bool inverse, int blocks, hipStream_t s) {
 
 }  // namespace
 
-static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s);
+// which = ROWS_PRODUCT: only the inverse row pass, its input formed from *prod; COLS_ONLY: only the inverse column pass
+enum NttPasses { BOTH_PASSES, ROWS_PRODUCT, COLS_ONLY };
+static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s,
+                            NttPasses which = BOTH_PASSES, const NttProduct* prod = nullptr);
 
 void launch_ntt(const DeviceTables& t, const LimbBatch& b, bool inverse, hipStream_t s) { launch_ntt_impl(t, b, inverse, nullptr, s); }
 void launch_ntt_epilogue(const DeviceTables& t, const LimbBatch& b, const NttEpilogue& ep, hipStream_t s) {
     launch_ntt_impl(t, b, false, &ep, s);
 }
+void launch_ntt_rows_product(const DeviceTables& t, const LimbBatch& b, const NttProduct& p, hipStream_t s) {
+    launch_ntt_impl(t, b, true, nullptr, s, ROWS_PRODUCT, &p);
+}
+void launch_ntt_cols_inverse(const DeviceTables& t, const LimbBatch& b, hipStream_t s) { launch_ntt_impl(t, b, true, nullptr, s, COLS_ONLY); }
 
-static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s) {
+static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s, NttPasses which,
+                            const NttProduct* prod) {
     if (b.nvec <= 0) return;
     NttArgs a;
     a.data = b.data;
@@ -626,7 +786,7 @@ static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inve
         return e ? std::atoi(e) : 0;
     }();
     int chunk = b.nvec;
-    if (chunk_mb > 0 && !ep) {
+    if (chunk_mb > 0 && !ep && which == BOTH_PASSES) {
         const size_t vec_bytes = (size_t)8 << t.log_n;
         const int want = (int)std::max<size_t>(1, ((size_t)chunk_mb << 20) / vec_bytes);
         if (b.nvec > want + want / 2) {
@@ -667,7 +827,11 @@ static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inve
             else
                 hipLaunchKernelGGL((ntt_rows_kernel<false, false>), dim3(blocks), dim3(256), 0, s, a, NttEpilogue());
         } else {
-            hipLaunchKernelGGL((ntt_rows_kernel<true, false>), dim3(blocks), dim3(256), 0, s, a, NttEpilogue());
+            if (which == ROWS_PRODUCT) {
+                hipLaunchKernelGGL(ntt_rows_product_kernel, dim3(blocks), dim3(256), 0, s, a, *prod, t.barrett, t.qinv);
+                continue;
+            }
+            if (which != COLS_ONLY) hipLaunchKernelGGL((ntt_rows_kernel<true, false>), dim3(blocks), dim3(256), 0, s, a, NttEpilogue());
             a.src = a.data;
             a.src_group = 0;
             a.src_group2 = 0;

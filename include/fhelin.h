@@ -378,6 +378,13 @@ int fhelin_debug_dot_window(fhelin_ctx* c, const fhelin_ct* const* cur /* [32] *
  * shape and more than 16 non-zero indices take its per-input, per-16-row chunks. */
 int fhelin_debug_rotate_many_batch(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n_ct, const int32_t* indices, int32_t n,
                                    fhelin_ct** outs /* [n_ct][n] */);
+/* The special-limb half of a key switch's inner product over digits chosen residue by residue (any value below 2^60), followed by its
+ * inverse transform, through the evaluator's own stages (FHELIN_FUSE_ACCP_ROWS decides which launches run):
+ *   n_rot = 0: out[b][c][p] = INTT( sum_j digits[b][j][ell+p] * relin[j][c][p] * 2^-64 )   (the identity form: digits come times 2^64)
+ *   n_rot > 0: out[b][c][p] = INTT( sum_r sigma_r( sum_j digits[b][j][ell+p] * key_r[j][c][p] ) ),  r over the n_rot <= 7 indices
+ * digits [batch][beta(ell)][ell + n_p][N]; the own-digit slots of the Q limbs count as zero and the Q half is dropped. */
+int fhelin_debug_ks_accp(fhelin_ctx* c, const uint64_t* digits, int32_t ell, int32_t batch, const int32_t* indices, int32_t n_rot,
+                         uint64_t* out /* [batch][2][n_p][N] */);
 
 /* ---- FHEController composite circuit ops (callers of the hot path) --------
  * One entry point per reference method; `vector<Ctxt>` travels as (array of handles, count); outputs are
