@@ -244,6 +244,7 @@ def load_library():
         "fhelin_debug_dot_window": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32]),
         "fhelin_debug_rotate_many_batch": (i32, [vp, C.POINTER(vp), i32, C.POINTER(i32), i32, C.POINTER(vp)]),
         "fhelin_debug_ks_accp": (i32, [vp, vp, i32, i32, C.POINTER(i32), i32, vp]),
+        "fhelin_debug_ks_accq": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
         "fhelin_ctx_set_interleave": (i32, [vp, i32]),
         "fhelin_ctx_interleave": (i32, [vp, C.POINTER(i32)]),
         "fhelin_evalkeys_interleave": (i32, [C.c_char_p, C.POINTER(i32)]),
@@ -1144,6 +1145,21 @@ class Engine:
         idx = (C.c_int32 * max(n, 1))(*indices)
         out = np.empty((batch, 2, self.n_p, self.N), dtype=np.uint64)
         self._ck(self.lib.fhelin_debug_ks_accp(self.h, d.ctypes.data_as(C.c_void_p), ell, batch, idx, n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def debug_ks_accq(self, digits, own, conv, ell, index=0):
+        """(accQ - NTT(conv)) * P^-1 [batch][2][ell][N] with accQ the Q-limb half of a key switch's inner product over the given digits
+        [batch][beta][ell + n_p][N] (any values below 2^60) and own limb [batch][ell][N], conv [batch][2][ell][N] in coefficient form:
+        the identity form over the relinearisation key, or the gathered form of rotation `index` (fhelin.h)"""
+        d = np.ascontiguousarray(digits, dtype=np.uint64)
+        o = np.ascontiguousarray(own, dtype=np.uint64)
+        cv = np.ascontiguousarray(conv, dtype=np.uint64)
+        batch = d.shape[0]
+        assert d.shape[2:] == (ell + self.n_p, self.N) and o.shape == (batch, ell, self.N) and cv.shape == (batch, 2, ell, self.N)
+        out = np.empty((batch, 2, ell, self.N), dtype=np.uint64)
+        vp = C.c_void_p
+        self._ck(self.lib.fhelin_debug_ks_accq(self.h, d.ctypes.data_as(vp), o.ctypes.data_as(vp), cv.ctypes.data_as(vp), ell, batch, index,
+                                               out.ctypes.data_as(vp)))
         return out
 
     # ---- FHEController composites (names follow the reference methods)

@@ -190,4 +190,32 @@ int fhelin_debug_ks_accp(fhelin_ctx* c, const uint64_t* digits, int32_t ell, int
     FHELIN_CATCH
 }
 
+int fhelin_debug_ks_accq(fhelin_ctx* c, const uint64_t* digits, const uint64_t* own, const uint64_t* conv, int32_t ell, int32_t batch,
+                         int32_t index, uint64_t* out) {
+    NEED(c && digits && own && conv && out);
+    FHELIN_TRY
+    Context& x = c->ctx;
+    x.require_device();
+    if (ell < 1 || ell > x.L + 1 || batch < 1) throw Error(FHELIN_ERR_ARG, "debug_ks_accq: bad shape");
+    const size_t N = x.N;
+    const size_t nd = (size_t)batch * x.lvl[ell].beta * (ell + x.K) * N, nw = (size_t)batch * ell * N, no = 2 * nw;
+    for (size_t i = 0; i < nd; ++i)
+        if (digits[i] >> 60) throw Error(FHELIN_ERR_ARG, "debug_ks_accq: a digit is not below 2^60");
+    for (size_t i = 0; i < no; ++i)
+        if (conv[i] >= x.moduli[(i / N) % ell]) throw Error(FHELIN_ERR_ARG, "debug_ks_accq: conv is not canonical");
+    for (size_t i = 0; i < nw; ++i)
+        if (own[i] >= x.moduli[(i / N) % ell]) throw Error(FHELIN_ERR_ARG, "debug_ks_accq: the own limb is not canonical");
+    Scratch<u64> ext = x.scratch<u64>(nd);
+    Scratch<u64> down = x.scratch<u64>(nw);
+    Scratch<u64> dconv = x.scratch<u64>(no);
+    Scratch<u64> res = x.scratch<u64>(no);
+    hip_check(hipMemcpyAsync(ext, digits, nd * 8, hipMemcpyHostToDevice, x.stream), "debug_ks_accq upload");
+    hip_check(hipMemcpyAsync(down, own, nw * 8, hipMemcpyHostToDevice, x.stream), "debug_ks_accq upload");
+    hip_check(hipMemcpyAsync(dconv, conv, no * 8, hipMemcpyHostToDevice, x.stream), "debug_ks_accq upload");
+    c->ev.debug_ks_accq(ext, down, dconv, ell, batch, index, res);
+    hip_check(hipMemcpyAsync(out, res, no * 8, hipMemcpyDeviceToHost, x.stream), "debug_ks_accq download");
+    x.sync();
+    FHELIN_CATCH
+}
+
 }  // extern "C"

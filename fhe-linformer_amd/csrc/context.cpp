@@ -138,6 +138,8 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
         if (const char* e = std::getenv("FHELIN_LDS_DIGITS")) lds_digits = std::atoi(e) != 0;
         if (const char* e = std::getenv("FHELIN_FUSE_ACCP_ROWS")) fuse_accp_rows = std::atoi(e);
         if (const char* e = std::getenv("FHELIN_ACCP_ROWS_MIN_VECS")) accp_rows_min_vecs = std::atoi(e);
+        if (const char* e = std::getenv("FHELIN_FUSE_ACCQ_ROWS")) fuse_accq_rows = std::atoi(e);
+        if (const char* e = std::getenv("FHELIN_ACCQ_ROWS_MIN_VECS")) accq_rows_min_vecs = std::atoi(e);
         if (const char* e = std::getenv("FHELIN_NTT_TRACE")) trace_small_ntt = std::atoi(e);
         if (const char* e = std::getenv("FHELIN_SCALAR_TRACE")) trace_scalar = std::atoi(e);
         if (const char* e = std::getenv("FHELIN_HOST_WAITS")) trace_waits = std::atoi(e) != 0;

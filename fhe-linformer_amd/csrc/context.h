@@ -14,7 +14,7 @@
 #include "../../include/fhelin.h"  // status codes
 #include "hostmath.h"
 #include "pool.h"
-#include "kernels.h"
+#include "kernels_elem.h"
 
 namespace fhelin {
 
@@ -207,6 +207,13 @@ struct Context {
     // launches everywhere.  Bit-identical every way.  FHELIN_ACCP_ROWS_MIN_VECS=<n>: only accumulators of at least n special-limb vectors
     int fuse_accp_rows = 1;
     int accp_rows_min_vecs = 0;
+    // FHELIN_FUSE_ACCQ_ROWS: 1 - the Q-limb half of the same single-key inner products, where the ModDown ends in the row pass
+    // of NTT(conv), is formed by that row pass (launch_ntt_epilogue_product): no inner-product launch, no accQ; only the classes that
+    // tools/accq_rows_probe.py shows faster (Evaluator::accq_in_rows); 2 - every single-key class that is built; 0 - launch_ks_inner and the
+    // accQ round trip everywhere.  Needs the special-limb half in its row pass (fuse_accp_rows).  Bit-identical every way.
+    // FHELIN_ACCQ_ROWS_MIN_VECS=<n>: with 1, only accumulators of at least n Q-limb vectors
+    int fuse_accq_rows = 1;
+    int accq_rows_min_vecs = 0;
     bool lds_digits = true;     // merged rotate-and-sum: digit tiles staged once in LDS when every rotation keeps tiles in place (FHELIN_LDS_DIGITS)
     struct FftDev {
         const u32* rot = nullptr;     // [slots]      5^j mod 4 slots
@@ -240,6 +247,11 @@ struct Context {
         stats.limb_ntt += (u64)b.nvec;
         if (trace_small_ntt && b.nvec <= trace_small_ntt) note_small_ntt(b.nvec);
         launch_ntt_epilogue(dt, b, ep, stream);
+    }
+    void ntt_epilogue_product(const LimbBatch& b, const NttEpilogue& ep, const NttProduct& p) {
+        stats.limb_ntt += (u64)b.nvec;
+        if (trace_small_ntt && b.nvec <= trace_small_ntt) note_small_ntt(b.nvec);
+        launch_ntt_epilogue_product(dt, b, ep, p, stream);
     }
 };
 

@@ -226,13 +226,17 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
         }
     }
     Scratch<u64> ext = modup(shu, c_ntt, !gather);   // digits times 2^64 for the keys as they are stored: launch_ks_inner ends in redc128
-    Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
-    Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-    inner_product(sh, accQ, accP, ext, evk, c_ntt, false);
     // the finish in the row pass of NTT(conv): for an identity output map (relinearisation) and for a rotation gathered above; a rotation
     // written through the inverse automorphism map only with FHELIN_FUSE_MODDOWN=1
-    if (gather) moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, true);
-    else moddown(sh, accQ, accP, out, add0, add1, map, post, c_.fuse_moddown || (c_.fuse_finish && identity));
+    const bool row_pass = gather || c_.fuse_moddown || (c_.fuse_finish && identity);
+    // ... which then forms the Q-limb sums itself where accq_in_rows says so: no accQ, and the digits live until that last kernel
+    NttProduct qprod;
+    Scratch<u64> accQ;
+    if (!(row_pass && accq_in_rows(sh))) accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
+    Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
+    inner_product(sh, accQ, accP, ext, evk, c_ntt, false, true, row_pass ? &qprod : nullptr);
+    if (gather) moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, true, nullptr, &qprod);
+    else moddown(sh, accQ, accP, out, add0, add1, map, post, row_pass, nullptr, &qprod);
     launch_ok("keyswitch");
 }
 
@@ -280,19 +284,40 @@ Scratch<u64> Evaluator::modup(const KsShape& up, const u64* src, bool times_r2, 
 // rotation sums unless the knob is 2 (Context::fuse_accp_rows: measured slower), the exact-products tail (its accP carries a K+1-th limb
 // that launch_affine_acc_items writes), a caller that works on accP before its tail (fuse = false) and, below
 // Context::accp_rows_min_vecs vectors, the small accumulators.
-void Evaluator::inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse) {
+bool Evaluator::accp_in_rows(const KsShape& sh, bool multi, bool fuse) const {
     const int K = c_.K, nvec = sh.batch * 2 * K;
     const bool measured_faster = !multi && sh.beta <= 8;   // the classes of tools/accp_rows_probe.py where the fused form wins
     const bool want = c_.fuse_accp_rows >= 2 || (c_.fuse_accp_rows == 1 && measured_faster);
-    sh.accp_rows = fuse && want && !sh.accp_limbs && sh.k == K && nvec >= c_.accp_rows_min_vecs ? 1 : 0;
+    return fuse && want && !sh.accp_limbs && sh.k == K && nvec >= c_.accp_rows_min_vecs;
+}
+
+// FHELIN_FUSE_ACCQ_ROWS: the Q-limb half of a single-key inner product whose ModDown ends in the row pass of NTT(conv) is
+// formed by that row pass, where it used to read accQ back: launch_ks_inner does not run and accQ does not exist.  Only together with the
+// special-limb half (accp_in_rows).  Left alone: the merged sums, moddown_rescale and the exact-products tail (they work on accQ), the
+// linear transforms' dot kernel, every ModDown that ends in launch_moddown_finish.
+bool Evaluator::accq_in_rows(const KsShape& sh) const {
+    const bool measured_faster = sh.beta <= 8 && sh.batch * 2 * sh.ell >= c_.accq_rows_min_vecs;   // tools/accq_rows_probe.py
+    const bool want = c_.fuse_accq_rows >= 2 || (c_.fuse_accq_rows == 1 && measured_faster);
+    return want && accp_in_rows(sh, false, true);
+}
+
+// The launches that the two rules above leave to the inner product, and the special-limb row pass; the Q-limb row pass is the ModDown's
+// (moddown_rows), which *qprod describes to it.
+void Evaluator::inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse,
+                              NttProduct* qprod) {
+    const int K = c_.K, nvec = sh.batch * 2 * K;
+    sh.accp_rows = accp_in_rows(sh, multi, fuse) ? 1 : 0;
+    sh.accq_rows = qprod && !multi && fuse && accq_in_rows(sh) ? 1 : 0;
     if (multi) launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, c_ntt, c_.stream);
-    else launch_ks_inner(c_.dt, sh, accQ, accP, ext, evk, c_ntt, c_.stream);
+    else if (!sh.accq_rows) launch_ks_inner(c_.dt, sh, accQ, accP, ext, evk, c_ntt, c_.stream);
     if (!sh.accp_rows) return;
     NttProduct pr;
     pr.sh = sh;
     pr.ext = ext;
     pr.evk = evk;
     pr.multi = multi ? 1 : 0;
+    pr.c_ntt = c_ntt;
+    if (sh.accq_rows) *qprod = pr;
     c_.stats.limb_ntt += (u64)nvec;   // the transform of accP is counted here, where its first pass runs
     launch_ntt_rows_product(c_.dt, LimbBatch{accP, nvec, nullptr, c_.L + 1, K}, pr, c_.stream);
 }
@@ -313,41 +338,53 @@ void Evaluator::accp_inverse(const KsShape& sh, u64* accP) {
 // finish (optional): called with NTT(conv) [sh.batch][2][ell][N] in place of the one launch_moddown_finish over all rows (a caller whose
 // rows need several finish launches over slices); out .. post are then unused.
 void Evaluator::moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map,
-                        const u64* post, bool row_pass, const std::function<void(const u64* conv)>& finish) {
+                        const u64* post, bool row_pass, const std::function<void(const u64* conv)>& finish, const NttProduct* qprod) {
     const size_t N = c_.N;
     const int B = sh.batch, ell = sh.ell;
     if (row_pass && sh.gsrc && !sh.gsrc_pmod) throw Error(FHELIN_ERR_INTERNAL, "moddown: the row pass cannot gather");
+    if (sh.accq_rows && !(row_pass && qprod)) throw Error(FHELIN_ERR_INTERNAL, "moddown: accQ was left to a row pass that does not run");
     accp_inverse(sh, accP);
     Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * ell * N);
     launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, c_.stream);
-    const LimbBatch cb{conv, B * 2 * ell, nullptr, 0, ell};
     if (row_pass) {
-        NttEpilogue ep;
-        ep.acc = accQ;
-        ep.acc_poly_stride = (size_t)ell * N;
-        ep.out = out;
-        ep.out_stride = sh.out_stride;
-        ep.w = c_.d_pinv;
-        ep.ell = ell;
-        ep.add0 = add0;
-        ep.add1 = add1;
-        ep.add_stride = sh.add_stride;
-        ep.post = post;
-        ep.post_stride = sh.post_stride;
-        if (sh.gather) {
-            // the accumulator pair and the conversion are sigma_g of the ungathered ones already: identity output
-        } else if (sh.per_row) {
-            ep.per_row = 1;
-            for (int b = 0; b < B; ++b) ep.invmap_row[b] = c_.automorph_inverse_of(sh.map_row[b]);
-        } else if (map) {
-            ep.invmap = c_.automorph_inverse_of(map);
-        }
-        c_.ntt_epilogue(cb, ep);
+        moddown_rows(sh, accQ, conv, out, add0, add1, map, post, qprod);
         return;
     }
-    c_.ntt(cb, false);
+    c_.ntt(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, false);
     if (finish) finish(conv);
     else launch_moddown_finish(c_.dt, sh, out, accQ, conv, c_.d_pinv, add0, add1, map, post, c_.stream);
+}
+
+void Evaluator::moddown_rows(const KsShape& sh, const u64* accQ, u64* conv, u64* out, const u64* add0, const u64* add1, const u32* map,
+                             const u64* post, const NttProduct* qprod) {
+    const int B = sh.batch, ell = sh.ell;
+    const LimbBatch cb{conv, B * 2 * ell, nullptr, 0, ell};
+    NttEpilogue ep;
+    ep.acc = accQ;
+    ep.acc_poly_stride = (size_t)ell * c_.N;
+    ep.out = out;
+    ep.out_stride = sh.out_stride;
+    ep.w = c_.d_pinv;
+    ep.ell = ell;
+    ep.add0 = add0;
+    ep.add1 = add1;
+    ep.add_stride = sh.add_stride;
+    ep.post = post;
+    ep.post_stride = sh.post_stride;
+    if (sh.gather) {
+        // the accumulator pair and the conversion are sigma_g of the ungathered ones already: identity output
+    } else if (sh.per_row) {
+        ep.per_row = 1;
+        for (int b = 0; b < B; ++b) ep.invmap_row[b] = c_.automorph_inverse_of(sh.map_row[b]);
+    } else if (map) {
+        ep.invmap = c_.automorph_inverse_of(map);
+    }
+    if (sh.accq_rows) {
+        ep.acc = nullptr;   // formed by the row pass from the key switch's own operands
+        c_.ntt_epilogue_product(cb, ep, *qprod);
+    } else {
+        c_.ntt_epilogue(cb, ep);
+    }
 }
 
 // ModDown and rescale as ONE basis conversion (sh.ell >= 2, K + 1 <= 16): P and the top limb of the accumulator pair are dropped together,
@@ -466,6 +503,28 @@ void Evaluator::debug_ks_accp(const u64* ext, int ell, int batch, const int* ind
     }
     accp_inverse(sh, out);
     launch_ok("debug_ks_accp");
+}
+
+void Evaluator::debug_ks_accq(const u64* ext, const u64* own, u64* conv, int ell, int batch, int index, u64* out) {
+    const size_t N = c_.N, pn = (size_t)ell * N;
+    if (ell < 1 || ell > c_.L + 1 || batch < 1) throw Error(FHELIN_ERR_ARG, "debug_ks_accq: bad shape");
+    if (!index && !relin_key) throw Error(FHELIN_ERR_KEY, "debug_ks_accq: no relinearisation key");
+    KsShape sh{ell, c_.K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, batch, pn, 2 * pn, 0, 0};
+    const u64* evk = index ? nullptr : relin_key->d;
+    if (index) {
+        const RotKey k = rotation_key(index);
+        sh.gather = 1;
+        evk = permuted(*k.key, k.map);
+        sh.map_row[0] = k.map;
+        sh.ginv = c_.automorph_ginv_of(k.map);
+    }
+    NttProduct qprod;
+    Scratch<u64> accQ;
+    if (!accq_in_rows(sh)) accQ = c_.scratch<u64>((size_t)batch * 2 * pn);
+    Scratch<u64> accP = c_.scratch<u64>((size_t)batch * 2 * c_.K * N);   // the special-limb half is computed and dropped
+    inner_product(sh, accQ, accP, ext, evk, own, false, true, &qprod);
+    moddown_rows(sh, accQ, conv, out, nullptr, nullptr, nullptr, nullptr, &qprod);
+    launch_ok("debug_ks_accq");
 }
 
 int Evaluator::slot_count(int slots) const { return slots > 0 ? slots : (1 << c_.prm.log_slots); }
@@ -1161,7 +1220,7 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
             // ModUp of the B inputs' c1, once; digits times 2^64 for the keys as they are stored: launch_ks_inner ends in redc128
             Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B, ctw, 0, 0, 0}, base + pn, !gather);
             // inner products: per input, rows of <= MAX_ROWS indices with their own keys, all reading that input's digits
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)rows * 2 * ell * N);
+            Scratch<u64> accQ;   // allocated below: not at all where the ModDown's row pass forms the Q-limb sums
             Scratch<u64> accP = c_.scratch<u64>((size_t)rows * 2 * K * N);
             // ONE launch per chunk of <= MAX_ROWS indices over ALL inputs (KsShape::row_mod): row (i, r) = rotation r of input i; in the
             // XCD-aware block order a key tile is fetched once for all inputs and a digit tile once for all indices
@@ -1204,9 +1263,12 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
                 sh.gsrc = base;
                 sh.gsrc_stride = ctw;
                 sh.gsrc_pmod = c_.d_pmod;
-                inner_product(sh, accQ, accP, ext, nullptr, base + pn, false);
-                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, true);
+                NttProduct qprod;   // one launch covers the indices: the row pass may form the Q-limb sums itself
+                if (!accq_in_rows(sh)) accQ = c_.scratch<u64>((size_t)rows * 2 * ell * N);
+                inner_product(sh, accQ, accP, ext, nullptr, base + pn, false, true, &qprod);
+                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, true, nullptr, &qprod);
             } else {
+                accQ = c_.scratch<u64>((size_t)rows * 2 * ell * N);
                 if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), accQ, accP, ext, nullptr, base + pn, s);
                 else
                     for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {

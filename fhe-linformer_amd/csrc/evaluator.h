@@ -224,6 +224,12 @@ public:
     // INTT(accP).  n_rot = 0: the identity form over the relinearisation key as stored (the sum comes times 2^-64); else the merged form
     // over the permuted keys of the n_rot <= 7 rotations.
     void debug_ks_accp(const u64* ext, int ell, int batch, const int* indices, int n_rot, u64* out);
+    // test hook (fhelin_debug_ks_accq): the Q-limb half of a single-key inner product and the row-pass finish of its ModDown over operands the
+    // caller chooses residue by residue, through inner_product and moddown_rows as they stand.  ext [batch][beta][ell+K][N], own [batch][ell][N]
+    // (the switched polynomial, NTT form), conv [batch][2][ell][N] (coefficient form, canonical; overwritten), out [batch][2][ell][N], all
+    // device: out = (accQ - NTT(conv)) * P^-1.  index = 0: the identity form over the relinearisation key as stored (digit terms times 2^-64,
+    // the own-limb term plain); else the gathered form of that rotation (operands read through its map, no c0 addend).
+    void debug_ks_accq(const u64* ext, const u64* own, u64* conv, int ell, int batch, int index, u64* out);
     // rows of identical shape through one batched key switch with an explicit Galois element and key (conjugation, the SubSum
     // rotations by multiples of the slot count); accumulate: v_i + sigma_g(v_i)
     std::vector<CtPtr> rotate_galois_batch(const std::vector<CtPtr>& v, u64 galois, const EvalKey& key, bool accumulate);
@@ -360,10 +366,19 @@ private:
     // the inner product of a key switch into the accumulator pair (multi: launch_ks_inner_multi, else launch_ks_inner over evk); where the
     // special-limb half is formed in the inverse NTT's row pass it sets sh.accp_rows, which the ModDown tails read.  fuse = false: the
     // caller touches accP before its tail (it must then hold the residues themselves)
-    void inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse = true);
+    // qprod != nullptr: the caller's tail is moddown(row_pass = true) over *qprod, and where accq_in_rows(sh) holds the Q-limb half is left
+    // to that row pass too: no inner-product launch at all, sh.accq_rows is set, *qprod describes the sums, accQ is not touched (may be null)
+    void inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse = true,
+                       NttProduct* qprod = nullptr);
+    bool accp_in_rows(const KsShape& sh, bool multi, bool fuse) const;   // FHELIN_FUSE_ACCP_ROWS: the class rule of DESIGN.md 6j
+    bool accq_in_rows(const KsShape& sh) const;                          // FHELIN_FUSE_ACCQ_ROWS: a single-key shape, the class rule of 6k
     void accp_inverse(const KsShape& sh, u64* accP);   // INTT(accP) of a tail: the column pass alone with sh.accp_rows
     void moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
-                 bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr);
+                 bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr, const NttProduct* qprod = nullptr);
+    // the last kernel of a row-pass ModDown: out = (accQ - NTT(conv)) * P^-1 + add (+ post) in the row pass of NTT(conv); with sh.accq_rows
+    // accQ is formed there from *qprod
+    void moddown_rows(const KsShape& sh, const u64* accQ, u64* conv, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
+                      const NttProduct* qprod);
     void moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out);
     void moddown_rescale_exact(const KsShape& sh, const u64* accQ, u64* accP, u64* out, u32 f2);
     // logical slot count of a ciphertext (slots = 0: the context's)

@@ -218,6 +218,10 @@ struct KsShape {
     // limbs of the same sum are formed by launch_ntt_rows_product, the inverse row pass that takes the products as its input; the ModDown
     // tails run the inverse column pass alone (launch_ntt_cols_inverse).  Set by Evaluator::inner_product (FHELIN_FUSE_ACCP_ROWS).
     int accp_rows = 0;
+    // accq_rows = 1 (with accp_rows): accQ is NEVER stored.  No launch_ks_inner at all: the Q-limb sums of the same inner product are formed by
+    // the ModDown's last kernel, the epilogue row pass of NTT(conv), where it used to read them back (launch_ntt_epilogue_product).  Set by
+    // Evaluator::inner_product (FHELIN_FUSE_ACCQ_ROWS) for the single-key forms whose ModDown ends in that row pass.
+    int accq_rows = 0;
 };
 // The special-limb half of a key switch's inner product as the load stage of the inverse NTT's row pass (kernels_ntt.hip):
 //     accP[b][c][p][.] = rows( redc128( sum_{r < R} sum_{j < beta} d_{r,j}[p][ m_r(e) ] * key_{r,j,c}[p][e] ) )
@@ -231,9 +235,16 @@ struct NttProduct {
     const u64* ext = nullptr;
     const u64* evk = nullptr;
     int multi = 0;
+    const u64* c_ntt = nullptr;   // launch_ntt_epilogue_product: the polynomial that is switched, as launch_ks_inner takes it (the own-digit operand)
 };
 // accP [sh.batch][2][sh.k][N] <- the inverse row pass of the products (b describes accP: sh.batch * 2 * sh.k vectors, limb_count = sh.k)
 void launch_ntt_rows_product(const DeviceTables& t, const LimbBatch& b, const NttProduct& p, hipStream_t s);
+// The Q-limb half of a single-key inner product (p.multi = 0) as the accumulator operand of the FORWARD row pass's epilogue: launch_ntt_epilogue
+// with ep.acc unused, its place taken at every position e of limb t, component c, row b by what launch_ks_inner stores to accQ there:
+//     redc128( sum_{j < beta} d_j[t][m(e)] * key_{j,c}[t][e] )  (+ P * c0[t][m(e)] on component 0: sh.gsrc, sh.gsrc_pmod)
+// with the ciphertext's own limb p.c_ntt[t] in place of digit j = t / alpha (times 2^64 through DeviceTables::mont where the keys are as stored).
+// The same canonical residues, so the same output bytes; accQ does not exist.
+void launch_ntt_epilogue_product(const DeviceTables& t, const LimbBatch& b, const NttEpilogue& ep, const NttProduct& p, hipStream_t s);
 // the inverse column pass alone, in place, on vectors whose row pass has run (launch_ntt_rows_product)
 void launch_ntt_cols_inverse(const DeviceTables& t, const LimbBatch& b, hipStream_t s);
 // K6: cc [ell][N] coefficient form, c_ntt [ell][N] NTT form -> ext [beta][ell+k][N]

@@ -264,12 +264,16 @@ __device__ __forceinline__ void inv_round(u64 (&x)[16], const RoundTw& tw, const
 
 // The slot of (tau, k) is the slot of (tau, 0) plus the slot of (0, k): the two indices share no bit, so neither the sum nor its
 // pad term e >> 4 carries.  One lane address per window, the slot of (0, k) is the instruction's offset.
-__device__ __forceinline__ void exchange(u64 (&x)[16], u64* lds, int tau, int p_from, int p_to, bool sync_first) {
+// the first half of an exchange: the registers of window p_from to their LDS slots, visible to the workgroup on return
+__device__ __forceinline__ void park(const u64 (&x)[16], u64* lds, int tau, int p_from, bool sync_first) {
     if (sync_first) __syncthreads();
     u64* const from = lds + lds_slot(tile_index(tau, 0, p_from));
 #pragma unroll
     for (int k = 0; k < 16; ++k) from[lds_slot(tile_index(0, k, p_from))] = x[k];
     __syncthreads();
+}
+__device__ __forceinline__ void exchange(u64 (&x)[16], u64* lds, int tau, int p_from, int p_to, bool sync_first) {
+    park(x, lds, tau, p_from, sync_first);
     const u64* const to = lds + lds_slot(tile_index(tau, 0, p_to));
 #pragma unroll
     for (int k = 0; k < 16; ++k) x[k] = to[lds_slot(tile_index(0, k, p_to))];
@@ -407,128 +411,297 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIFT ? 3 : 
 // pass B: row transforms over the low 8 bits of the index.  Tile = 16 consecutive rows of 256
 // (4096 contiguous residues); tile-local index e == global index - tile*4096.
 // ------------------------------------------------------------------------------------------------
-// The product load stage of the inverse row pass (NttProduct, kernels_elem.h): the residue at tile-local position e = tau + 256 k (the
-// bit-8 window: every key load of a wave is 512 contiguous bytes, every digit gather moves with whole 128-byte lines as the maps do) becomes
-// the canonical residue of the special-limb inner product at e and goes straight to the LDS slot that exchange(8 -> 0) would have written
-// it to: the transform's sixteen registers are not live yet, so PG slots at a time carry their sums (an Acc30 and a 128-bit pair each)
-// through the (rotation, digit) terms, with 2 PG independent loads per term, and the slot groups are a real loop.  Limb, row, component,
-// key and map bookkeeping is workgroup-uniform: scalar loads, scalar branches.
-// Bounds: as ks_inner_multi_kernel - keys canonical, digits canonical or below 86q (q < 2^53): a flush every 8 terms, a fold every 16.
-// SHORT: at most 8 terms in all (one rotation of up to 8 digits - every plain key switch of the default chain): no flush inside the
-// loops, the 128-bit pairs exist only at the end, and PG = 8 slots fit; else PG = 4.
-template <int PG, bool SHORT>
-__device__ __forceinline__ void product_to_lds(u64* lds, const NttArgs& a, const NttProduct& pr, const u64* __restrict__ barrett,
-                                               const u64* __restrict__ qinv, int vec, int tile, int limb, u64 q, int tau) {
+// ---- product stages (NttProduct, kernels_elem.h): a key switch's inner product formed where a row pass would load it from memory - the
+// special limbs as the input of the inverse row pass (product_to_lds), the Q limbs as the accumulator operand of the forward row pass's
+// epilogue (epilogue_products).
+// The operands of one (row, component, target limb) of a product stage, all workgroup-uniform: resolved once per workgroup by product_row
+// and product_limb, read by product_sums.  OWN (the Q limbs, launch_ntt_epilogue_product): digit `own` is the ciphertext's own limb and
+// component 0 may take the c0 addend; a special limb has neither.
+struct ProdOperands {
+    const u64* ext;     // digits of the row's input (rotation 0)
+    const u64* key0;    // single key of the row (multi: sh.evk_rot)
+    const u32* map0;    // its gather map, or nullptr
+    int n_rot;
+    int khi;            // shift that yields a key word's high half: pre-split keys (EvalKey::d_perm, folded keys) 32, keys as stored 30
+    int tt, limb, comp; // digit slot, limb of modulus / key, component
+    Barrett br;
+    u64 qi;
+    int own;            // OWN: the digit that holds limb tt
+    const u64* own_src; // OWN: the own limb's vector
+    u64 mont, monts;    // OWN: 2^64 mod q and its Shoup companion, applied to the own limb where own_mont
+    bool own_mont;
+    const u64* gsrc;    // OWN: c0's limb vector (component 0 of a gathered rotation) or nullptr; enters times (pw, pws) = P mod q
+    u64 pw, pws;
+};
+__device__ __forceinline__ void product_row(ProdOperands& o, const NttArgs& a, const NttProduct& pr, int bi, int& in) {
     const KsShape& sh = pr.sh;
-    const int log_n = a.log_n;
-    const int K = sh.k, nt = sh.ell + K;
-    const int poly = uniform(vec / K), p = vec - poly * K, bi = poly >> 1, comp = poly & 1;
-    const int tt = sh.ell + p;
-    const size_t N = (size_t)1 << log_n;
-    const u64* ext = pr.ext;
-    const u64* key0 = pr.evk;
-    const u32* map0 = nullptr;
-    int n_rot = 1;
+    const size_t N = (size_t)1 << a.log_n;
+    const int nt = sh.ell + sh.k;
+    o.ext = pr.ext;
+    o.key0 = pr.evk;
+    o.map0 = nullptr;
+    o.n_rot = 1;
+    in = bi;   // the input of batch row bi
     if (pr.multi) {
-        ext += (size_t)bi * (sh.ext_batch_stride ? sh.ext_batch_stride : (size_t)sh.beta * nt * N);
-        n_rot = sh.n_rot;
+        o.ext += (size_t)bi * (sh.ext_batch_stride ? sh.ext_batch_stride : (size_t)sh.beta * nt * N);
+        o.n_rot = sh.n_rot;
     } else {
         int ri = 0;
         if (sh.row_mod) {
             ri = bi % sh.row_mod;
-            ext += (size_t)(bi / sh.row_mod) * sh.ext_batch_stride;
-            key0 = sh.evk_row[ri];
+            in = bi / sh.row_mod;
+            o.ext += (size_t)in * sh.ext_batch_stride;
+            o.key0 = sh.evk_row[ri];
         } else {
-            if (!sh.shared_input) ext += (size_t)bi * sh.beta * nt * N;
+            if (!sh.shared_input) o.ext += (size_t)bi * sh.beta * nt * N;
             if (sh.per_row) {
                 ri = bi;
-                key0 = sh.evk_row[bi];
+                o.key0 = sh.evk_row[bi];
             }
         }
-        if (sh.gather) map0 = sh.map_row[ri];
+        if (sh.gather) o.map0 = sh.map_row[ri];
     }
-    const int khi = pr.multi || sh.gather ? 32 : 30;   // pre-split keys (EvalKey::d_perm, folded keys) or keys as stored
-    Barrett br;
-    br.q = q;
-    br.r0 = barrett[2 * limb];
-    br.r1 = barrett[2 * limb + 1];
-    const u64 qi = qinv[limb];
-    const size_t kstride = (size_t)(sh.L1 + K) << log_n;   // one evk component
-    const size_t klimb = ((size_t)limb << log_n) + ((size_t)tile << 12);
+    o.khi = pr.multi || sh.gather ? 32 : 30;
+}
+__device__ __forceinline__ void product_limb(ProdOperands& o, int tt, int limb, int comp, u64 q, const u64* __restrict__ barrett,
+                                             const u64* __restrict__ qinv) {
+    o.tt = tt;
+    o.limb = limb;
+    o.comp = comp;
+    o.br.q = q;
+    o.br.r0 = barrett[2 * limb];
+    o.br.r1 = barrett[2 * limb + 1];
+    o.qi = qinv[limb];
+}
+
+// byte offsets (below N * 8 <= 2^20) of the PG positions e = tau + 256 (g + i) of a tile in a limb vector, through the map where there is one
+template <int PG>
+__device__ __forceinline__ void product_offsets(u32 (&off)[PG], const u32* map, int tile, int g, int tau) {
+    if (map) {
+        const Stream ms = stream(map + ((size_t)tile << 12));
+#pragma unroll
+        for (int i = 0; i < PG; ++i) off[i] = 8u * ld32(ms, 4u * (u32)tau, 1024 * i, 1024 * g);
+    } else {
+#pragma unroll
+        for (int i = 0; i < PG; ++i) off[i] = ((u32)tile << 15) + 8u * (u32)tau + 2048u * (u32)(g + i);
+    }
+}
+
+// The term loop of both product stages: res[i] = the canonical residue of the inner product at tile-local position e = tau + 256 (g + i)
+// (the bit-8 window: every key load of a wave is 512 contiguous bytes, every digit gather moves with whole 128-byte lines as the maps do).
+// PG slots at a time carry their sums (an Acc30 and a 128-bit pair each) through the (rotation, digit) terms, with 2 PG independent loads per
+// term.  Limb, row, component, key and map bookkeeping is workgroup-uniform: scalar loads, scalar branches.
+// Bounds: as ks_inner_multi_kernel - keys canonical, digits canonical or below 86q (q < 2^53): a flush every 8 terms, a fold every 16.
+// SHORT: at most 8 terms in all (one rotation of up to 8 digits - every plain key switch of the default chain): no flush inside the
+// loops, the 128-bit pairs exist only at the end, and PG = 8 slots fit; else PG = 4.
+template <int PG, bool SHORT, bool OWN>
+__device__ __forceinline__ void product_sums(u64 (&res)[PG], const NttArgs& a, const NttProduct& pr, const ProdOperands& o, int tile, int g,
+                                             int tau) {
+    const KsShape& sh = pr.sh;
+    const int log_n = a.log_n;
+    const int nt = sh.ell + sh.k;
+    const size_t kstride = (size_t)(sh.L1 + sh.k) << log_n;   // one evk component
+    const size_t klimb = ((size_t)o.limb << log_n) + ((size_t)tile << 12);
     const u32 lane8 = 8u * (u32)tau;
-    u64* const from = lds + lds_slot(tile_index(tau, 0, 8));
+    u64 lo[PG], hi[PG];
+    Acc30 acc[PG];
+#pragma unroll
+    for (int i = 0; i < PG; ++i) {
+        lo[i] = hi[i] = 0;
+        acc[i] = Acc30{0, 0, 0};
+    }
+    int pending = 0, folded = 0;
 #pragma unroll 1
-    for (int g = 0; g < 16; g += PG) {
-        u64 lo[PG], hi[PG];
-        Acc30 acc[PG];
-#pragma unroll
-        for (int i = 0; i < PG; ++i) {
-            lo[i] = hi[i] = 0;
-            acc[i] = Acc30{0, 0, 0};
-        }
-        int pending = 0, folded = 0;
+    for (int r = 0; r < o.n_rot; ++r) {
+        const u32* map = pr.multi ? sh.map_rot[r] : o.map0;
+        const u64* key = pr.multi ? sh.evk_rot[r] : o.key0;
+        const u64* dig = o.ext + (size_t)r * sh.rot_ext_stride + ((size_t)o.tt << log_n);
+        u32 off[PG];
+        product_offsets<PG>(off, map, tile, g, tau);
 #pragma unroll 1
-        for (int r = 0; r < n_rot; ++r) {
-            const u32* map = pr.multi ? sh.map_rot[r] : map0;
-            const u64* key = pr.multi ? sh.evk_rot[r] : key0;
-            const u64* dig = ext + (size_t)r * sh.rot_ext_stride + ((size_t)tt << log_n);
-            u32 off[PG];   // byte offset of the digit in its limb vector (below N * 8 <= 2^20)
-            if (map) {
-                const Stream ms = stream(map + ((size_t)tile << 12));
+        for (int j = 0; j < sh.beta; ++j) {
+            const bool is_own = OWN && j == o.own;
+            const Stream ds = stream(is_own ? o.own_src : dig + ((size_t)j * nt << log_n));
+            const Stream ks = stream(key + (size_t)(2 * j + o.comp) * kstride + klimb);
+            u64 d[PG], kw[PG];
 #pragma unroll
-                for (int i = 0; i < PG; ++i) off[i] = 8u * ld32(ms, 4u * (u32)tau, 1024 * i, 1024 * g);
-            } else {
-#pragma unroll
-                for (int i = 0; i < PG; ++i) off[i] = ((u32)tile << 15) + lane8 + 2048u * (u32)(g + i);
+            for (int i = 0; i < PG; ++i) {
+                d[i] = ld64(ds, off[i], 0);
+                kw[i] = ld64(ks, lane8, 2048 * i, 2048 * g);
             }
-#pragma unroll 1
-            for (int j = 0; j < sh.beta; ++j) {
-                const Stream ds = stream(dig + ((size_t)j * nt << log_n));
-                const Stream ks = stream(key + (size_t)(2 * j + comp) * kstride + klimb);
-                u64 d[PG], kw[PG];
+            if constexpr (OWN) {
+                if (is_own && o.own_mont) {   // the digits of this form come times 2^64 (up_hatmod_r2); the ciphertext's own limb gets the factor here
+#pragma unroll
+                    for (int i = 0; i < PG; ++i) d[i] = mul_shoup(d[i], o.mont, o.monts, o.br.q);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < PG; ++i) {
+                u32 d0, d1;
+                split30(d[i], d0, d1);
+                // the key's halves without a branch: pack30 keeps the low half (below 2^30) in the low dword and the high half in
+                // the high dword, a key as stored is split here
+                mac30(acc[i], d0, d1, (u32)kw[i] & 0x3FFFFFFFu, (u32)(kw[i] >> o.khi));
+            }
+            if (!SHORT && ++pending == 8) {
+                pending = 0;
+                const bool fold = ++folded == 2;
+                if (fold) folded = 0;
 #pragma unroll
                 for (int i = 0; i < PG; ++i) {
-                    d[i] = ld64(ds, off[i], 0);
-                    kw[i] = ld64(ks, lane8, 2048 * i, 2048 * g);
-                }
-#pragma unroll
-                for (int i = 0; i < PG; ++i) {
-                    u32 d0, d1;
-                    split30(d[i], d0, d1);
-                    // the key's halves without a branch: pack30 keeps the low half (below 2^30) in the low dword and the high half in
-                    // the high dword, a key as stored is split here
-                    mac30(acc[i], d0, d1, (u32)kw[i] & 0x3FFFFFFFu, (u32)(kw[i] >> khi));
-                }
-                if (!SHORT && ++pending == 8) {
-                    pending = 0;
-                    const bool fold = ++folded == 2;
-                    if (fold) folded = 0;
-#pragma unroll
-                    for (int i = 0; i < PG; ++i) {
-                        acc30_flush(acc[i], lo[i], hi[i]);
-                        acc[i] = Acc30{0, 0, 0};
-                        if (fold) {   // reduces, does not divide: the factor 2^64 stays
-                            lo[i] = barrett_reduce128(lo[i], hi[i], br);
-                            hi[i] = 0;
-                        }
+                    acc30_flush(acc[i], lo[i], hi[i]);
+                    acc[i] = Acc30{0, 0, 0};
+                    if (fold) {   // reduces, does not divide: the factor 2^64 stays
+                        lo[i] = barrett_reduce128(lo[i], hi[i], o.br);
+                        hi[i] = 0;
                     }
                 }
             }
         }
-        u64* const fg = from + lds_slot(tile_index(0, 1, 8)) * g;   // the slot of (0, k) is k times the slot of (0, 1) in this window
+    }
 #pragma unroll
-        for (int i = 0; i < PG; ++i) {
-            acc30_flush(acc[i], lo[i], hi[i]);
-            // every term carries 2^64 once: the canonical residue of the plain sum
-            fg[lds_slot(tile_index(0, i, 8))] = redc128(lo[i], hi[i], q, qi);
+    for (int i = 0; i < PG; ++i) {
+        acc30_flush(acc[i], lo[i], hi[i]);
+        // every term carries 2^64 once: the canonical residue of the plain sum
+        res[i] = redc128(lo[i], hi[i], o.br.q, o.qi);
+    }
+    if constexpr (OWN) {
+        if (o.gsrc) {   // + P * sigma_g(c0), as ks_inner_kernel<true> adds it: the addend passes through the ModDown with the rest
+            u32 off[PG];
+            product_offsets<PG>(off, o.map0, tile, g, tau);
+            const Stream gs = stream(o.gsrc);
+#pragma unroll
+            for (int i = 0; i < PG; ++i) res[i] = add_mod(res[i], mul_shoup(ld64(gs, off[i], 0), o.pw, o.pws, o.br.q), o.br.q);
         }
     }
 }
 
-// PROD (inverse only): the input is not loaded: product_to_lds has left it in LDS, as the first half of exchange(8 -> 0) would have
+// The product load stage of the inverse row pass (NttProduct, kernels_elem.h): the residue at tile-local position e = tau + 256 k becomes
+// the canonical residue of the special-limb inner product at e (product_sums) and goes straight to the LDS slot that exchange(8 -> 0) would
+// have written it to: the transform's sixteen registers are not live yet, and the slot groups are a real loop.
+template <int PG, bool SHORT>
+__device__ __forceinline__ void product_to_lds(u64* lds, const NttArgs& a, const NttProduct& pr, const u64* __restrict__ barrett,
+                                               const u64* __restrict__ qinv, int vec, int tile, int limb, u64 q, int tau) {
+    const KsShape& sh = pr.sh;
+    const int K = sh.k;
+    const int poly = uniform(vec / K), p = vec - poly * K;
+    ProdOperands o;
+    int in;
+    product_row(o, a, pr, poly >> 1, in);
+    product_limb(o, sh.ell + p, limb, poly & 1, q, barrett, qinv);
+    u64* const from = lds + lds_slot(tile_index(tau, 0, 8));
+#pragma unroll 1
+    for (int g = 0; g < 16; g += PG) {
+        u64 res[PG];
+        product_sums<PG, SHORT, false>(res, a, pr, o, tile, g, tau);
+        u64* const fg = from + lds_slot(tile_index(0, 1, 8)) * g;   // the slot of (0, k) is k times the slot of (0, 1) in this window
+#pragma unroll
+        for (int i = 0; i < PG; ++i) fg[lds_slot(tile_index(0, i, 8))] = res[i];
+    }
+}
+
+// The epilogue's arithmetic and store on NK slots of the bit-8 window, slots g .. g + NK - 1 (g workgroup-uniform; all sixteen at g = 0):
+// x = the transform, av = the accumulator operand at the same positions; vector = (poly, limb t) of ell limbs per poly.
+template <int NK>
+__device__ __forceinline__ void epilogue_finish(u64 (&x)[NK], const u64 (&av)[NK], int g, const NttEpilogue* ep, const LimbConst& c, u64 epi_b,
+                                                int log_n, int tile, int tau, int poly, int t, int ell) {
+    const u32 lane8 = 8u * (u32)tile_index(tau, 0, 8);
+    auto koff = [](int k) constexpr { return 8 * tile_index(0, k, 8); };
+    const int goff = koff(1) * g;   // slot k of this window lies k times the offset of slot 1 away
+    const int bi = poly >> 1, comp = poly & 1;
+    const size_t n = (size_t)1 << log_n;
+    const u64 w = ep->w[2 * t], ws = ep->w[2 * t + 1];
+    // av + B - x in (0, B + q): the same residue as av - x, and mul_shoup returns it canonical
+#pragma unroll
+    for (int k = 0; k < NK; ++k) x[k] = mul_shoup(av[k] + epi_b - x[k], w, ws, c.q);
+    const u64* add = comp == 0 ? ep->add0 : ep->add1;
+    if (add) {
+        const Stream adds = stream(add + (size_t)bi * ep->add_stride + (size_t)t * n + ((size_t)tile << 12));
+#pragma unroll
+        for (int k = 0; k < NK; ++k) x[k] = add_mod(x[k], ld64(adds, lane8, koff(k), goff), c.q);
+    }
+    const size_t row_off = (size_t)(comp * ell + t) * n;
+    const bool has_post = ep->post != nullptr;
+    const Stream post = stream(ep->post + (has_post ? (size_t)bi * ep->post_stride + row_off : 0));   // read only if has_post
+    const Stream out = stream(ep->out + (size_t)bi * ep->out_stride + row_off);
+    const int toff = (tile << 15) + goff;   // the slots' byte offset in a row of post / out
+    const u32* im = ep->per_row ? ep->invmap_row[bi] : ep->invmap;
+    if (im) {   // rotation: through the inverse automorphism map; a target index is below N, its byte offset below 2^20
+        const Stream ims = stream(im + ((size_t)tile << 12));
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const u32 j8 = 8u * ld32(ims, 4u * (u32)tau, 4 * tile_index(0, k, 8), goff >> 1);
+            u64 r = x[k];
+            if (has_post) r = add_mod(r, ld64(post, j8, 0), c.q);
+            st64(out, j8, 0, r);
+        }
+    } else {
+        if (has_post) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) x[k] = add_mod(x[k], ld64(post, lane8, koff(k), toff), c.q);
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k) st64(out, lane8, koff(k), x[k], toff);
+    }
+}
+
+// what a forward row pass whose epilogue forms its own accumulator operand needs besides the epilogue (launch_ntt_epilogue_product)
+struct ProdTabs {
+    const NttProduct* pr;
+    const u64* barrett;
+    const u64* qinv;
+    const u64* mont;
+};
+
+// The epilogue over a product stage: the transform x sits in LDS (park(x, 0): the layout exchange(0 -> 8) reads), and per group of PG slots the
+// Q-limb sums of the key switch are formed (product_sums, operands as ks_inner_kernel<GATHER> takes them), the group's x comes back from LDS in
+// the bit-8 window and the epilogue finishes and stores the group.  Nothing of the transform is live in registers during the sums.
+template <int PG, bool SHORT>
+__device__ __forceinline__ void epilogue_products(const u64* lds, const NttArgs& a, const NttEpilogue* ep, const ProdTabs& pt, const LimbConst& c,
+                                                  u64 epi_b, bool reduce_x, int tile, int tau, int poly, int t, int ell) {
+    const NttProduct& pr = *pt.pr;
+    const KsShape& sh = pr.sh;
+    const int log_n = a.log_n;
+    const int bi = poly >> 1, comp = poly & 1;
+    ProdOperands o;
+    int in;
+    product_row(o, a, pr, bi, in);
+    product_limb(o, t, t, comp, c.q, pt.barrett, pt.qinv);   // Q limb t: digit slot t, key and modulus limb t
+    o.own = t / sh.alpha;
+    // the polynomial of the row's input: as ks_inner_kernel offsets c_ntt
+    const int cin = sh.row_mod ? in : sh.shared_input ? 0 : bi;
+    o.own_src = pr.c_ntt + (size_t)cin * sh.c_stride + ((size_t)t << log_n);
+    o.own_mont = !sh.gather;
+    o.mont = pt.mont[2 * t];
+    o.monts = pt.mont[2 * t + 1];
+    o.gsrc = nullptr;
+    o.pw = o.pws = 0;
+    if (sh.gather && sh.gsrc_pmod && comp == 0) {
+        o.gsrc = sh.gsrc + (size_t)in * sh.gsrc_stride + ((size_t)t << log_n);
+        o.pw = sh.gsrc_pmod[2 * t];
+        o.pws = sh.gsrc_pmod[2 * t + 1];
+    }
+    const u64* const to = lds + lds_slot(tile_index(tau, 0, 8));
+#pragma unroll 1
+    for (int g = 0; g < 16; g += PG) {
+        u64 av[PG], x[PG];
+        product_sums<PG, SHORT, true>(av, a, pr, o, tile, g, tau);
+        const u64* const tg = to + lds_slot(tile_index(0, 1, 8)) * g;   // the slot of (0, k) is k times the slot of (0, 1) in this window
+#pragma unroll
+        for (int i = 0; i < PG; ++i) x[i] = tg[lds_slot(tile_index(0, i, 8))];
+        if (reduce_x) {
+#pragma unroll
+            for (int i = 0; i < PG; ++i) x[i] = reduce_lazy_2q(x[i], c.q, c.sh, c.rr);
+        }
+        epilogue_finish<PG>(x, av, g, ep, c, epi_b, log_n, tile, tau, poly, t, ell);
+    }
+}
+
+// PROD: an operand is not loaded but formed by a product stage.  Inverse: the input - product_to_lds has left it in LDS, as the first half of
+// exchange(8 -> 0) would have.  Forward (with EPI): the epilogue's accumulator operand (epilogue_products, pt).
 template <bool INVERSE, bool LAZY, bool EPI, bool PROD = false>
 __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, int tile, int limb, const LimbConst& c,
-                                          const NttEpilogue* ep) {
+                                          const NttEpilogue* ep, const ProdTabs* pt = nullptr) {
     const int log_n = a.log_n;
     const Stream tw = stream(reinterpret_cast<const u64x2*>(a.tw) + ((size_t)limb << log_n));
     const Stream trows = stream(reinterpret_cast<const u64x2*>(a.tw_rows) + (((size_t)limb << (log_n - 12)) + tile) * (15 * 256));
@@ -558,6 +731,8 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
             ell = ep->ell;
             poly = uniform(vec / ell);
             t = vec - poly * ell;
+        }
+        if constexpr (EPI && !PROD) {
             const Stream acc = stream(ep->acc + (size_t)poly * ep->acc_poly_stride + ((size_t)t << log_n) + ((size_t)tile << 12));
 #pragma unroll
             for (int k = 0; k < 16; ++k) av[k] = ld64(acc, lane8, koff(k, 8));
@@ -575,8 +750,10 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
                 epi_b = 10 * c.q;
             } else {
                 epi_b = 2 * c.q;
+                if constexpr (!PROD) {   // PROD: per slot group, where x comes back from LDS
 #pragma unroll
-                for (int k = 0; k < 16; ++k) x[k] = reduce_lazy_2q(x[k], c.q, c.sh, c.rr);
+                    for (int k = 0; k < 16; ++k) x[k] = reduce_lazy_2q(x[k], c.q, c.sh, c.rr);
+                }
             }
         } else if (!(LAZY && a.lazy_out && c.q < (1ull << 53))) {
 #pragma unroll
@@ -597,46 +774,21 @@ __device__ __forceinline__ void rows_body(const NttArgs& a, u64* lds, int vec, i
 #endif
         // window at bit 0 leaves 16 consecutive residues per thread (128-byte lane stride); one more LDS exchange
         // to the bit-8 window makes every store instruction a contiguous 512-byte wave access
-        exchange(x, lds, tau, 0, 8, true);
-        if constexpr (EPI) {
-            const int bi = poly >> 1, comp = poly & 1;
-            const size_t n = (size_t)1 << log_n;
-            const u64 w = ep->w[2 * t], ws = ep->w[2 * t + 1];
-            // av + B - x in (0, B + q): the same residue as av - x, and mul_shoup returns it canonical
-#pragma unroll
-            for (int k = 0; k < 16; ++k) x[k] = mul_shoup(av[k] + epi_b - x[k], w, ws, c.q);
-            const u64* add = comp == 0 ? ep->add0 : ep->add1;
-            if (add) {
-                const Stream adds = stream(add + (size_t)bi * ep->add_stride + (size_t)t * n + ((size_t)tile << 12));
-#pragma unroll
-                for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], ld64(adds, lane8, koff(k, 8)), c.q);
-            }
-            const size_t row_off = (size_t)(comp * ell + t) * n;
-            const bool has_post = ep->post != nullptr;
-            const Stream post = stream(ep->post + (has_post ? (size_t)bi * ep->post_stride + row_off : 0));   // read only if has_post
-            const Stream out = stream(ep->out + (size_t)bi * ep->out_stride + row_off);
-            const int toff = tile << 15;   // the tile's byte offset in a row of post / out
-            const u32* im = ep->per_row ? ep->invmap_row[bi] : ep->invmap;
-            if (im) {   // rotation: through the inverse automorphism map; a target index is below N, its byte offset below 2^20
-                const Stream ims = stream(im + ((size_t)tile << 12));
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const u32 j8 = 8u * ld32(ims, 4u * (u32)tau, 4 * tile_index(0, k, 8));
-                    u64 r = x[k];
-                    if (has_post) r = add_mod(r, ld64(post, j8, 0), c.q);
-                    st64(out, j8, 0, r);
-                }
-            } else {
-                if (has_post) {
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) x[k] = add_mod(x[k], ld64(post, lane8, koff(k, 8), toff), c.q);
-                }
-#pragma unroll
-                for (int k = 0; k < 16; ++k) st64(out, lane8, koff(k, 8), x[k], toff);
-            }
+        if constexpr (EPI && PROD) {
+            park(x, lds, tau, 0, true);
+            const bool reduce_x = !LAZY && c.q >= (1ull << 60);
+            if (pt->pr->sh.beta <= 8)
+                epilogue_products<8, true>(lds, a, ep, *pt, c, epi_b, reduce_x, tile, tau, poly, t, ell);
+            else
+                epilogue_products<4, false>(lds, a, ep, *pt, c, epi_b, reduce_x, tile, tau, poly, t, ell);
         } else {
+            exchange(x, lds, tau, 0, 8, true);
+            if constexpr (EPI) {
+                epilogue_finish<16>(x, av, 0, ep, c, epi_b, log_n, tile, tau, poly, t, ell);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) st64(base, lane8, koff(k, 8), x[k]);
+                for (int k = 0; k < 16; ++k) st64(base, lane8, koff(k, 8), x[k]);
+            }
         }
     } else {
         // coalesced load through the bit-8 window, then an LDS exchange to the bit-0 window of the first GS round
@@ -722,6 +874,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
         rows_body<true, false, false, true>(a, lds, vec, tile, limb, c, nullptr);
 }
 
+// The epilogue row pass of a ModDown's NTT(conv) over the Q-limb products of its key switch (launch_ntt_epilogue_product): ntt_rows_kernel<false,
+// true> with the accumulator operand formed in place of loaded.  Vectors are (row, component, Q limb) with the limb fastest: as above, the two
+// components of one (row, limb, tile) are neighbours in one XCD's share.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ntt_rows_epilogue_product_kernel(NttArgs a, NttEpilogue ep, NttProduct pr,
+                                                                                                                 const u64* barrett, const u64* qinv,
+                                                                                                                 const u64* mont) {
+    __shared__ u64 lds[LDS_WORDS];
+    int vec, tile;
+    rows_block(a, vec, tile);
+    const int limb = uniform(limb_of(a, vec));
+    const LimbConst c = limb_const(a, limb);
+    const ProdTabs pt{&pr, barrett, qinv, mont};
+    if (lazy_prime<false>(c.q))
+        rows_body<false, true, true, true>(a, lds, vec, tile, limb, c, &ep, &pt);
+    else
+        rows_body<false, false, true, true>(a, lds, vec, tile, limb, c, &ep, &pt);
+}
+
 template <int A>
 void launch_cols(const NttArgs& a, bool inverse, int blocks, hipStream_t s) {
     if (inverse)
@@ -734,7 +904,8 @@ void launch_cols(const NttArgs& a, bool inverse, int blocks, hipStream_t s) {
 
 }  // namespace
 
-// which = ROWS_PRODUCT: only the inverse row pass, its input formed from *prod; COLS_ONLY: only the inverse column pass
+// which = ROWS_PRODUCT: only the inverse row pass, its input formed from *prod; COLS_ONLY: only the inverse column pass;
+// forward with ep and prod: the epilogue's accumulator operand formed from *prod
 enum NttPasses { BOTH_PASSES, ROWS_PRODUCT, COLS_ONLY };
 static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s,
                             NttPasses which = BOTH_PASSES, const NttProduct* prod = nullptr);
@@ -747,6 +918,10 @@ void launch_ntt_rows_product(const DeviceTables& t, const LimbBatch& b, const Nt
     launch_ntt_impl(t, b, true, nullptr, s, ROWS_PRODUCT, &p);
 }
 void launch_ntt_cols_inverse(const DeviceTables& t, const LimbBatch& b, hipStream_t s) { launch_ntt_impl(t, b, true, nullptr, s, COLS_ONLY); }
+void launch_ntt_epilogue_product(const DeviceTables& t, const LimbBatch& b, const NttEpilogue& ep, const NttProduct& p, hipStream_t s) {
+    // the product stage takes Q limb t for vector (poly, t): b is the dense [poly][ell] batch of a ModDown (Evaluator::moddown checks)
+    launch_ntt_impl(t, b, false, &ep, s, BOTH_PASSES, &p);
+}
 
 static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inverse, const NttEpilogue* ep, hipStream_t s, NttPasses which,
                             const NttProduct* prod) {
@@ -822,7 +997,9 @@ static void launch_ntt_impl(const DeviceTables& t, const LimbBatch& b, bool inve
             a.src = a.data;
             a.src_group = 0;
             a.src_group2 = 0;
-            if (ep)
+            if (ep && prod)
+                hipLaunchKernelGGL(ntt_rows_epilogue_product_kernel, dim3(blocks), dim3(256), 0, s, a, *ep, *prod, t.barrett, t.qinv, t.mont);
+            else if (ep)
                 hipLaunchKernelGGL((ntt_rows_kernel<false, true>), dim3(blocks), dim3(256), 0, s, a, *ep);
             else
                 hipLaunchKernelGGL((ntt_rows_kernel<false, false>), dim3(blocks), dim3(256), 0, s, a, NttEpilogue());

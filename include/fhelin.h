@@ -385,6 +385,14 @@ int fhelin_debug_rotate_many_batch(fhelin_ctx* c, const fhelin_ct* const* cts, i
  * digits [batch][beta(ell)][ell + n_p][N]; the own-digit slots of the Q limbs count as zero and the Q half is dropped. */
 int fhelin_debug_ks_accp(fhelin_ctx* c, const uint64_t* digits, int32_t ell, int32_t batch, const int32_t* indices, int32_t n_rot,
                          uint64_t* out /* [batch][2][n_p][N] */);
+/* The Q-limb half of a single-key inner product and the row-pass finish of its ModDown over operands chosen residue by residue, through
+ * the evaluator's own stages (FHELIN_FUSE_ACCQ_ROWS decides which launches run):  out[b][c][t] = (acc[b][c][t] - NTT(conv[b][c][t])) * P^-1,
+ *   index = 0: acc[b][c][t] = sum_{j != t / alpha} digits[b][j][t] * relin[j][c][t] * 2^-64 + own[b][t] * relin[t / alpha][c][t]
+ *   index != 0: acc[b][c][t] = sigma_g( sum_{j != t / alpha} digits[b][j][t] * key[j][c][t] + own[b][t] * key[t / alpha][c][t] ),  g of that rotation
+ * digits [batch][beta(ell)][ell + n_p][N] below 2^60 (the own-digit slots are not read); own [batch][ell][N] and conv [batch][2][ell][N]
+ * (coefficient form) canonical. */
+int fhelin_debug_ks_accq(fhelin_ctx* c, const uint64_t* digits, const uint64_t* own, const uint64_t* conv, int32_t ell, int32_t batch,
+                         int32_t index, uint64_t* out /* [batch][2][ell][N] */);
 
 /* ---- FHEController composite circuit ops (callers of the hot path) --------
  * One entry point per reference method; `vector<Ctxt>` travels as (array of handles, count); outputs are
