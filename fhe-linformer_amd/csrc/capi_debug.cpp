@@ -182,9 +182,8 @@ int fhelin_debug_ks_accp(fhelin_ctx* c, const uint64_t* digits, int32_t ell, int
     for (size_t i = 0; i < nd; ++i)
         if (digits[i] >> 60) throw Error(FHELIN_ERR_ARG, "debug_ks_accp: a digit is not below 2^60");
     Scratch<u64> ext = x.scratch<u64>(nd);
-    Scratch<u64> acc = x.scratch<u64>(no);
     hip_check(hipMemcpyAsync(ext, digits, nd * 8, hipMemcpyHostToDevice, x.stream), "debug_ks_accp upload");
-    c->ev.debug_ks_accp(ext, ell, batch, indices, n_rot, acc);
+    Scratch<u64> acc = c->ev.debug_ks_accp(ext, ell, batch, indices, n_rot);
     hip_check(hipMemcpyAsync(out, acc, no * 8, hipMemcpyDeviceToHost, x.stream), "debug_ks_accp download");
     x.sync();
     FHELIN_CATCH

@@ -188,9 +188,7 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     c_.require_device();
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "hybrid key switching needs at least one special prime");
     if (B < 1) return;
-    const size_t N = c_.N;
-    const int K = c_.K;
-    KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, c_stride, out_stride, add_stride, post_stride};
+    KsShape sh = ks_shape(ell, B, {c_stride, out_stride, add_stride, post_stride});
     const bool shared = rows && rows->shared_input;
     if (rows) {
         sh.per_row = 1;
@@ -207,45 +205,60 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     const bool identity = !map && !rows;
     const bool gather = !identity && !add1 && rot_in_gather();
     const u64* evk = key ? key->d : nullptr;
-    if (gather) {   // the rotation is applied while the inner product loads its operands; c0 (add0) enters accQ there, times P
-        sh.gather = 1;
-        if (rows) {
-            for (int b = 0; b < B; ++b) {
-                sh.evk_row[b] = permuted(*rows->keys[b], rows->maps[b]);
-                sh.ginv_row[b] = c_.automorph_ginv_of(rows->maps[b]);
-            }
-        } else {
-            evk = permuted(*key, map);
-            sh.map_row[0] = map;
-            sh.ginv = c_.automorph_ginv_of(map);
-        }
-        if (add0) {
-            sh.gsrc = add0;
-            sh.gsrc_stride = add_stride;
-            sh.gsrc_pmod = c_.d_pmod;
-        }
-    }
+    // the rotation is applied while the inner product loads its operands; c0 (add0) enters accQ there, times P
+    if (gather) evk = set_gather(sh, rows ? rows->keys.data() : &key, rows ? rows->maps.data() : &map, add0, add_stride);
     Scratch<u64> ext = modup(shu, c_ntt, !gather);   // digits times 2^64 for the keys as they are stored: launch_ks_inner ends in redc128
-    // the finish in the row pass of NTT(conv): for an identity output map (relinearisation) and for a rotation gathered above; a rotation
-    // written through the inverse automorphism map only with FHELIN_FUSE_MODDOWN=1
-    const bool row_pass = gather || c_.fuse_moddown || (c_.fuse_finish && identity);
-    // ... which then forms the Q-limb sums itself where accq_in_rows says so: no accQ, and the digits live until that last kernel
-    NttProduct qprod;
-    Scratch<u64> accQ;
-    if (!(row_pass && accq_in_rows(sh))) accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
-    Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-    inner_product(sh, accQ, accP, ext, evk, c_ntt, false, true, row_pass ? &qprod : nullptr);
-    if (gather) moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, true, nullptr, &qprod);
-    else moddown(sh, accQ, accP, out, add0, add1, map, post, row_pass, nullptr, &qprod);
+    KsAcc acc = inner_product(sh, ext, evk, c_ntt, moddown_tail(gather ? KsOutput::Gathered : identity ? KsOutput::Identity : KsOutput::Scattered));
+    moddown(acc, gather ? KsOut{out, nullptr, nullptr, post} : KsOut{out, add0, add1, post, map});
     launch_ok("keyswitch");
 }
 
 // ------------------------------------------------------------------------------------------------ key-switch stages
-// Every hybrid key switch of this file is modup -> its own inner product(s) -> one of the tails moddown / moddown_rescale /
-// moddown_rescale_exact.  A merged rotation sum is set_rotations, modup and rotation_sum, which owns the inner product and what it hands
-// to moddown.  A change to the pipeline (what the conversions compute, where a transform's epilogue takes over a finish, how a merged
-// sum feeds its ModDown) belongs HERE, once.  Which operands share a launch set is decided before that, also once: for_groups (top of
-// this file) with same_shape (evaluator.h).
+// Every hybrid key switch of this file is ks_shape -> modup -> inner_product -> one of the tails moddown / moddown_rescale /
+// moddown_rescale_exact.  inner_product is told the tail (KsTail) and returns the accumulator (KsAcc): the shape as decided, accQ / accP
+// as far as they exist, and what the tail's row pass needs where the Q-limb sums are left to it.  It alone allocates them and asks
+// accp_in_rows / accq_in_rows; a tail takes that object and where its output goes (KsOut), nothing else.  A caller with an inner-product
+// kernel of its own takes the same object from accumulators().  A merged rotation sum is set_rotations, modup and rotation_sum; a plain
+// rotation that gathers puts set_gather in front.  A change to the pipeline (what the conversions compute, where a transform's epilogue
+// takes over a finish or a product, how a merged sum feeds its ModDown) belongs HERE, once.  Which operands share a launch set is
+// decided before that, also once: for_groups (top of this file) with same_shape (evaluator.h).
+
+KsShape Evaluator::ks_shape(int ell, int batch, const KsStrides& st) const {
+    return KsShape{ell, c_.K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, batch, st.c, st.out, st.add, st.post};
+}
+
+// Does a plain ModDown finish in the row pass of NTT(conv) (RowPass), or in launch_moddown_finish over the stored transform (Finish)?
+//   output of the ModDown                          RowPass when
+//   Identity   (relinearisation, linear transform)  FHELIN_FUSE_MODDOWN=1 or FHELIN_FUSE_FINISH=1
+//   Gathered   (set_gather)                         always: callers gather only under rot_in_gather(), FUSE_FINISH && ROT_GATHER && !FUSE_MODDOWN
+//   Scattered  (through the rotation's map)         FHELIN_FUSE_MODDOWN=1
+//   MergedSum  (rotation_sum, hoisted_dot_rows)     FHELIN_FUSE_FINISH=1 and FHELIN_ROT_GATHER=1 (c0 parts then enter accQ times P)
+Evaluator::KsTail Evaluator::moddown_tail(KsOutput o) const {
+    const bool rows = o == KsOutput::Gathered || (o == KsOutput::Identity && (c_.fuse_moddown || c_.fuse_finish)) ||
+                      (o == KsOutput::Scattered && c_.fuse_moddown) || (o == KsOutput::MergedSum && c_.fuse_finish && c_.rot_gather);
+    return rows ? KsTail::RowPass : KsTail::Finish;
+}
+
+const u64* Evaluator::set_gather(KsShape& sh, const EvalKey* const* keys, const u32* const* maps, const u64* c0, size_t c0_stride) {
+    const u64* evk = nullptr;
+    sh.gather = 1;
+    if (sh.per_row) {
+        for (int b = 0; b < (sh.row_mod ? sh.row_mod : sh.batch); ++b) {
+            sh.evk_row[b] = permuted(*keys[b], maps[b]);
+            sh.ginv_row[b] = c_.automorph_ginv_of(maps[b]);
+        }
+    } else {
+        evk = permuted(*keys[0], maps[0]);
+        sh.map_row[0] = maps[0];
+        sh.ginv = c_.automorph_ginv_of(maps[0]);
+    }
+    if (c0) {
+        sh.gsrc = c0;
+        sh.gsrc_stride = c0_stride;
+        sh.gsrc_pmod = c_.d_pmod;
+    }
+    return evk;
+}
 
 // ModUp of up.batch polynomials of up.ell limbs, NTT form at src, up.c_stride words apart (group2 > 0: only within runs of group2
 // polynomials; the runs lie group2_stride apart): coefficient form, basis conversion of every digit to the other limbs of QP, forward NTT
@@ -282,156 +295,160 @@ Scratch<u64> Evaluator::modup(const KsShape& up, const u64* src, bool times_r2, 
 // sums are formed by the inverse row pass of their own transform (launch_ntt_rows_product): accP is never stored in NTT form, read back
 // and stored again, and the ModDown starts at the column pass.  The same residues bit for bit.  Left on the separate launches: the merged
 // rotation sums unless the knob is 2 (Context::fuse_accp_rows: measured slower), the exact-products tail (its accP carries a K+1-th limb
-// that launch_affine_acc_items writes), a caller that works on accP before its tail (fuse = false) and, below
+// that launch_affine_acc_items writes), a caller that works on accP before its tail (KsTail::EditsAccP) and, below
 // Context::accp_rows_min_vecs vectors, the small accumulators.
-bool Evaluator::accp_in_rows(const KsShape& sh, bool multi, bool fuse) const {
+bool Evaluator::accp_in_rows(const KsShape& sh, KsTail tail) const {
     const int K = c_.K, nvec = sh.batch * 2 * K;
-    const bool measured_faster = !multi && sh.beta <= 8;   // the classes of tools/accp_rows_probe.py where the fused form wins
+    const bool measured_faster = !sh.n_rot && sh.beta <= 8;   // the single-key classes of tools/accp_rows_probe.py where the fused form wins
     const bool want = c_.fuse_accp_rows >= 2 || (c_.fuse_accp_rows == 1 && measured_faster);
-    return fuse && want && !sh.accp_limbs && sh.k == K && nvec >= c_.accp_rows_min_vecs;
+    return tail != KsTail::EditsAccP && want && !sh.accp_limbs && sh.k == K && nvec >= c_.accp_rows_min_vecs;
 }
 
 // FHELIN_FUSE_ACCQ_ROWS: the Q-limb half of a single-key inner product whose ModDown ends in the row pass of NTT(conv) is
 // formed by that row pass, where it used to read accQ back: launch_ks_inner does not run and accQ does not exist.  Only together with the
-// special-limb half (accp_in_rows).  Left alone: the merged sums, moddown_rescale and the exact-products tail (they work on accQ), the
-// linear transforms' dot kernel, every ModDown that ends in launch_moddown_finish.
-bool Evaluator::accq_in_rows(const KsShape& sh) const {
+// special-limb half (inner_product asks accp_in_rows first).  Left alone: the merged sums, moddown_rescale and the exact-products tail
+// (they work on accQ), the linear transforms' dot kernel, every ModDown that ends in launch_moddown_finish.
+bool Evaluator::accq_in_rows(const KsShape& sh, KsTail tail) const {
     const bool measured_faster = sh.beta <= 8 && sh.batch * 2 * sh.ell >= c_.accq_rows_min_vecs;   // tools/accq_rows_probe.py
     const bool want = c_.fuse_accq_rows >= 2 || (c_.fuse_accq_rows == 1 && measured_faster);
-    return want && accp_in_rows(sh, false, true);
+    return tail == KsTail::RowPass && !sh.n_rot && want;
 }
 
-// The launches that the two rules above leave to the inner product, and the special-limb row pass; the Q-limb row pass is the ModDown's
-// (moddown_rows), which *qprod describes to it.
-void Evaluator::inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse,
-                              NttProduct* qprod) {
-    const int K = c_.K, nvec = sh.batch * 2 * K;
-    sh.accp_rows = accp_in_rows(sh, multi, fuse) ? 1 : 0;
-    sh.accq_rows = qprod && !multi && fuse && accq_in_rows(sh) ? 1 : 0;
-    if (multi) launch_ks_inner_multi(c_.dt, sh, accQ, accP, ext, c_ntt, c_.stream);
-    else if (!sh.accq_rows) launch_ks_inner(c_.dt, sh, accQ, accP, ext, evk, c_ntt, c_.stream);
-    if (!sh.accp_rows) return;
-    NttProduct pr;
-    pr.sh = sh;
-    pr.ext = ext;
-    pr.evk = evk;
-    pr.multi = multi ? 1 : 0;
-    pr.c_ntt = c_ntt;
-    if (sh.accq_rows) *qprod = pr;
+Evaluator::KsAcc Evaluator::accumulators(const KsShape& sh, KsTail tail) {
+    const size_t pairs = (size_t)sh.batch * 2 * c_.N;
+    return KsAcc{sh, tail, c_.scratch<u64>(pairs * sh.ell), c_.scratch<u64>(pairs * (sh.accp_limbs ? sh.accp_limbs : sh.k)), {}};
+}
+
+// The two rules above, the launches they leave to the inner product, and the special-limb row pass; the Q-limb row pass is the ModDown's
+// (moddown_rows), which acc.qprod describes to it - accQ is then not even allocated.
+Evaluator::KsAcc Evaluator::inner_product(const KsShape& shape, const u64* ext, const u64* evk, const u64* c_ntt, KsTail tail) {
+    const int K = c_.K, nvec = shape.batch * 2 * K;
+    KsAcc acc{shape, tail, {}, {}, {}};
+    KsShape& sh = acc.sh;
+    sh.accp_rows = accp_in_rows(sh, tail) ? 1 : 0;
+    sh.accq_rows = sh.accp_rows && accq_in_rows(sh, tail) ? 1 : 0;
+    if (!sh.accq_rows) acc.accQ = c_.scratch<u64>((size_t)sh.batch * 2 * sh.ell * c_.N);
+    acc.accP = c_.scratch<u64>((size_t)nvec * c_.N);
+    if (sh.n_rot) launch_ks_inner_multi(c_.dt, sh, acc.accQ, acc.accP, ext, c_ntt, c_.stream);   // a merged sum
+    else if (!sh.accq_rows) launch_ks_inner(c_.dt, sh, acc.accQ, acc.accP, ext, evk, c_ntt, c_.stream);
+    if (!sh.accp_rows) return acc;
+    acc.qprod = NttProduct{sh, ext, evk, sh.n_rot ? 1 : 0, c_ntt};
     c_.stats.limb_ntt += (u64)nvec;   // the transform of accP is counted here, where its first pass runs
-    launch_ntt_rows_product(c_.dt, LimbBatch{accP, nvec, nullptr, c_.L + 1, K}, pr, c_.stream);
+    launch_ntt_rows_product(c_.dt, LimbBatch{acc.accP, nvec, nullptr, c_.L + 1, K}, acc.qprod, c_.stream);
+    return acc;
 }
 
-void Evaluator::accp_inverse(const KsShape& sh, u64* accP) {
-    const LimbBatch b{accP, sh.batch * 2 * c_.K, nullptr, c_.L + 1, c_.K};
-    if (sh.accp_rows) launch_ntt_cols_inverse(c_.dt, b, c_.stream);
+void Evaluator::accp_inverse(KsAcc& acc) {
+    const LimbBatch b{acc.accP, acc.sh.batch * 2 * c_.K, nullptr, c_.L + 1, c_.K};
+    if (acc.sh.accp_rows) launch_ntt_cols_inverse(c_.dt, b, c_.stream);
     else c_.ntt(b, true);
 }
 
-// ModDown of the accumulator pair accQ [sh.batch][2][ell][N], accP [sh.batch][2][K][N] (accP is transformed in place):
-// out = (accQ - NTT(conv(INTT(accP)))) * P^-1 + add0/add1 (+ post), written through `map` / the rows' maps.
-// sh.gather: the pair was gathered through the rotation's map by launch_ks_inner (c0 included): the conversion takes the signs of the
-// automorphism into account (launch_moddown_conv) and the output map is the identity - row_pass, no map, no add0.
-// row_pass: the finish rides in the row pass of NTT(conv) - (accQ - NTT(conv)) * P^-1 + add (+ post) is formed in registers and
-// NTT(conv) never goes to memory; else launch_moddown_finish reads the stored transform.  The row pass knows no gather: the c0 parts
-// of a merged rotation sum (sh.gsrc) must then be in accQ already, times P (sh.gsrc_pmod, launch_ks_inner_multi).
-// finish (optional): called with NTT(conv) [sh.batch][2][ell][N] in place of the one launch_moddown_finish over all rows (a caller whose
-// rows need several finish launches over slices); out .. post are then unused.
-void Evaluator::moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map,
-                        const u64* post, bool row_pass, const std::function<void(const u64* conv)>& finish, const NttProduct* qprod) {
-    const size_t N = c_.N;
-    const int B = sh.batch, ell = sh.ell;
-    if (row_pass && sh.gsrc && !sh.gsrc_pmod) throw Error(FHELIN_ERR_INTERNAL, "moddown: the row pass cannot gather");
-    if (sh.accq_rows && !(row_pass && qprod)) throw Error(FHELIN_ERR_INTERNAL, "moddown: accQ was left to a row pass that does not run");
-    accp_inverse(sh, accP);
-    Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * ell * N);
-    launch_moddown_conv(c_.dt, sh, conv, accP, c_.d_phatinv, c_.d_phatmod, c_.stream);
-    if (row_pass) {
-        moddown_rows(sh, accQ, conv, out, add0, add1, map, post, qprod);
-        return;
-    }
-    c_.ntt(LimbBatch{conv, B * 2 * ell, nullptr, 0, ell}, false);
-    if (finish) finish(conv);
-    else launch_moddown_finish(c_.dt, sh, out, accQ, conv, c_.d_pinv, add0, add1, map, post, c_.stream);
+static void made_for(bool ok, const char* tail) {   // what inner_product left to a tail's transforms is left to THAT tail's
+    if (!ok) throw Error(FHELIN_ERR_INTERNAL, std::string(tail) + ": the accumulator was made for another tail");
 }
 
-void Evaluator::moddown_rows(const KsShape& sh, const u64* accQ, u64* conv, u64* out, const u64* add0, const u64* add1, const u32* map,
-                             const u64* post, const NttProduct* qprod) {
+// ModDown of the accumulator pair accQ [sh.batch][2][ell][N], accP [sh.batch][2][K][N] (accP is transformed in place):
+// o.out = (accQ - NTT(conv(INTT(accP)))) * P^-1 + add0/add1 (+ post), written through o.map / the rows' maps.
+// sh.gather: the pair was gathered through the rotation's map by launch_ks_inner (c0 included): the conversion takes the signs of the
+// automorphism into account (launch_moddown_conv) and the output map is the identity - tail RowPass, no map, no add0.
+// KsTail::RowPass: the finish rides in the row pass of NTT(conv) - (accQ - NTT(conv)) * P^-1 + add (+ post) is formed in registers and
+// NTT(conv) never goes to memory; else launch_moddown_finish reads the stored transform.  The row pass knows no gather: the c0 parts
+// of a merged rotation sum (sh.gsrc) must then be in accQ already, times P (sh.gsrc_pmod, launch_ks_inner_multi).
+Scratch<u64> Evaluator::moddown_conv(KsAcc& acc) {
+    const KsShape& sh = acc.sh;
+    made_for(acc.tail == KsTail::RowPass || acc.tail == KsTail::Finish, "moddown");
+    if (acc.tail == KsTail::RowPass && sh.gsrc && !sh.gsrc_pmod) throw Error(FHELIN_ERR_INTERNAL, "moddown: the row pass cannot gather");
+    accp_inverse(acc);
+    Scratch<u64> conv = c_.scratch<u64>((size_t)sh.batch * 2 * sh.ell * c_.N);
+    launch_moddown_conv(c_.dt, sh, conv, acc.accP, c_.d_phatinv, c_.d_phatmod, c_.stream);
+    if (acc.tail != KsTail::RowPass) c_.ntt(LimbBatch{conv, sh.batch * 2 * sh.ell, nullptr, 0, sh.ell}, false);
+    return conv;
+}
+
+void Evaluator::moddown(KsAcc& acc, const KsOut& o) {
+    Scratch<u64> conv = moddown_conv(acc);
+    if (acc.tail == KsTail::RowPass) moddown_rows(acc, conv, o);
+    else launch_moddown_finish(c_.dt, acc.sh, o.out, acc.accQ, conv, c_.d_pinv, o.add0, o.add1, o.map, o.post, c_.stream);
+}
+
+void Evaluator::moddown_rows(const KsAcc& acc, u64* conv, const KsOut& o) {
+    const KsShape& sh = acc.sh;
     const int B = sh.batch, ell = sh.ell;
     const LimbBatch cb{conv, B * 2 * ell, nullptr, 0, ell};
     NttEpilogue ep;
-    ep.acc = accQ;
+    ep.acc = acc.accQ;
     ep.acc_poly_stride = (size_t)ell * c_.N;
-    ep.out = out;
+    ep.out = o.out;
     ep.out_stride = sh.out_stride;
     ep.w = c_.d_pinv;
     ep.ell = ell;
-    ep.add0 = add0;
-    ep.add1 = add1;
+    ep.add0 = o.add0;
+    ep.add1 = o.add1;
     ep.add_stride = sh.add_stride;
-    ep.post = post;
+    ep.post = o.post;
     ep.post_stride = sh.post_stride;
     if (sh.gather) {
         // the accumulator pair and the conversion are sigma_g of the ungathered ones already: identity output
     } else if (sh.per_row) {
         ep.per_row = 1;
         for (int b = 0; b < B; ++b) ep.invmap_row[b] = c_.automorph_inverse_of(sh.map_row[b]);
-    } else if (map) {
-        ep.invmap = c_.automorph_inverse_of(map);
+    } else if (o.map) {
+        ep.invmap = c_.automorph_inverse_of(o.map);
     }
-    if (sh.accq_rows) {
-        ep.acc = nullptr;   // formed by the row pass from the key switch's own operands
-        c_.ntt_epilogue_product(cb, ep, *qprod);
-    } else {
-        c_.ntt_epilogue(cb, ep);
-    }
+    if (sh.accq_rows) c_.ntt_epilogue_product(cb, ep, acc.qprod);   // ep.acc is null: formed by the row pass from the key switch's own operands
+    else c_.ntt_epilogue(cb, ep);
 }
 
 // ModDown and rescale as ONE basis conversion (sh.ell >= 2, K + 1 <= 16): P and the top limb of the accumulator pair are dropped together,
 // out [sh.batch][2][ell-1][N] (sh.out_stride apart) = (accQ - NTT(conv(INTT(accP), INTT(top limb of accQ)))) * (P q_top)^-1
-void Evaluator::moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out) {
+void Evaluator::moddown_rescale(KsAcc& acc, u64* out) {
+    const KsShape& sh = acc.sh;
     const size_t N = c_.N;
     const int B = sh.batch, ell = sh.ell;
     const LevelTables& lt = c_.lvl[ell];
-    accp_inverse(sh, accP);
+    made_for(acc.tail == KsTail::Rescale || acc.tail == KsTail::EditsAccP, "moddown_rescale");
+    accp_inverse(acc);
     Scratch<u64> top = c_.scratch<u64>((size_t)B * 2 * N);
     {
-        LimbBatch tb{top, B * 2, nullptr, ell - 1, 1, accQ + (size_t)(ell - 1) * N};
+        LimbBatch tb{top, B * 2, nullptr, ell - 1, 1, acc.accQ + (size_t)(ell - 1) * N};
         tb.src_group = 1;
         tb.src_group_stride = (size_t)ell * N;
         c_.ntt(tb, true);
     }
     Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * (ell - 1) * N);
-    launch_moddown_rescale_conv(c_.dt, sh, conv, accP, top, lt.md_hatinv, lt.md_hatmod, lt.md_mmod, c_.stream);
-    moddown_rescale_finish(sh, out, accQ, conv, lt.md_minv);
+    launch_moddown_rescale_conv(c_.dt, sh, conv, acc.accP, top, lt.md_hatinv, lt.md_hatmod, lt.md_mmod, c_.stream);
+    moddown_rescale_finish(acc, out, conv, lt.md_minv);
 }
 
 // ModDown, the affine step and the rescale of a relinearised product with their own two roundings, from ONE inverse and ONE forward
 // transform (sh.ell >= 2, K + 1 <= 16; kernels_elem.h "the EXACT merged tail").  accQ [sh.batch][2][ell][N] holds X_Q on the limbs below
 // the top one, accP [sh.batch][2][K+1][N] the special limbs as the inner product left them and X_Q,top (launch_affine_acc_items); f2: the
 // items whose factor is 2.  out [sh.batch][2][ell-1][N] = the residues of rescale(ModDown + affine step).
-void Evaluator::moddown_rescale_exact(const KsShape& sh, const u64* accQ, u64* accP, u64* out, u32 f2) {
-    const size_t N = c_.N;
+void Evaluator::moddown_rescale_exact(KsAcc& acc, u64* out, u32 f2) {
+    const KsShape& sh = acc.sh;
     const int B = sh.batch, ell = sh.ell, K = c_.K;
     const LevelTables& lt = c_.lvl[ell];
+    made_for(acc.tail == KsTail::Exact, "moddown_rescale_exact");
     {
-        LimbBatch ib{accP, B * 2 * (K + 1), lt.mdx_limb_tab, 0, 1};
+        LimbBatch ib{acc.accP, B * 2 * (K + 1), lt.mdx_limb_tab, 0, 1};
         ib.tab_len = K + 1;
         c_.ntt(ib, true);
     }
-    Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * (ell - 1) * N);
-    launch_moddown_rescale_exact_conv(c_.dt, sh, f2, conv, accP, c_.d_phatinv, c_.d_phatmod, c_.d_pinv, c_.d_pmod,
+    Scratch<u64> conv = c_.scratch<u64>((size_t)B * 2 * (ell - 1) * c_.N);
+    launch_moddown_rescale_exact_conv(c_.dt, sh, f2, conv, acc.accP, c_.d_phatinv, c_.d_phatmod, c_.d_pinv, c_.d_pmod,
                                       c_.d_qlmod + (size_t)(ell - 1) * (c_.L + 1), c_.stream);
-    moddown_rescale_finish(sh, out, accQ, conv, lt.md_minv);   // md_minv = (P q_top)^-1 mod q_t
+    moddown_rescale_finish(acc, out, conv, lt.md_minv);   // md_minv = (P q_top)^-1 mod q_t
 }
 
 // the row pass of NTT(conv) finishes (accQ - NTT(conv)) * minv into out (FHELIN_FUSE_FINISH=0: moddown_rescale_finish_kernel)
-void Evaluator::moddown_rescale_finish(const KsShape& sh, u64* out, const u64* accQ, u64* conv, const u64* minv) {
+void Evaluator::moddown_rescale_finish(const KsAcc& acc, u64* out, u64* conv, const u64* minv) {
+    const KsShape& sh = acc.sh;
     const int e1 = sh.ell - 1;
     const LimbBatch cb{conv, sh.batch * 2 * e1, nullptr, 0, e1};
     if (c_.fuse_finish) {
         NttEpilogue ep;
-        ep.acc = accQ;
+        ep.acc = acc.accQ;
         ep.acc_poly_stride = (size_t)sh.ell * c_.N;
         ep.out = out;
         ep.out_stride = sh.out_stride;
@@ -441,7 +458,7 @@ void Evaluator::moddown_rescale_finish(const KsShape& sh, u64* out, const u64* a
         return;
     }
     c_.ntt(cb, false);
-    launch_moddown_rescale_finish(c_.dt, sh, out, accQ, conv, minv, c_.stream);
+    launch_moddown_rescale_finish(c_.dt, sh, out, acc.accQ, conv, minv, c_.stream);
 }
 
 Evaluator::Rotations Evaluator::rotations(const int* indices, int n) {
@@ -470,60 +487,47 @@ void Evaluator::set_rotations(KsShape& sh, const Rotations& rot, bool shared_dig
     if (shared_digits) sh.lds_digits = c_.lds_digits && rot.tiles_in_place ? 1 : 0;
 }
 
-// A merged rotation sum from its digits on: out = ModDown(sum_r sigma_r(<digits_r, key_r>)) + sum_r sigma_r(c0_r) (+ post).  sh: the
+// A merged rotation sum from its digits on: o.out = ModDown(sum_r sigma_r(<digits_r, key_r>)) + sum_r sigma_r(c0_r) (+ o.post).  sh: the
 // prepared shape (strides, set_rotations, rot_ext_stride / rot_input_stride / ext_batch_stride as the caller's layout needs them); ext:
-// the digits from modup; c1 / c0: the bases of the two components, c0 of batch row b at c0 + b * c0_stride.  All rotated inner products
-// are gathered and accumulated in the extended basis, and the inner product gathers the c0 parts too: into accQ times P where the one
-// ModDown finishes in the row pass, else for moddown_finish to gather (sh.gsrc).
-void Evaluator::rotation_sum(KsShape& sh, const u64* ext, const u64* c1, const u64* c0, size_t c0_stride, u64* out, const u64* post) {
-    const size_t N = c_.N;
-    const bool rp = sum_in_row_pass();
-    sh.gsrc = c0;
+// the digits from modup; base: the ciphertexts, c0 of batch row b at base + b * c0_stride and c1 one polynomial further.  All rotated
+// inner products are gathered and accumulated in the extended basis, and the inner product gathers the c0 parts too: into accQ times P
+// where the one ModDown finishes in the row pass, else for moddown_finish to gather (sh.gsrc).
+void Evaluator::rotation_sum(KsShape& sh, const u64* ext, const u64* base, size_t c0_stride, const KsOut& o) {
+    const KsTail tail = moddown_tail(KsOutput::MergedSum);
+    sh.gsrc = base;
     sh.gsrc_stride = c0_stride;
-    if (rp) sh.gsrc_pmod = c_.d_pmod;
-    Scratch<u64> accQ = c_.scratch<u64>((size_t)sh.batch * 2 * sh.ell * N);
-    Scratch<u64> accP = c_.scratch<u64>((size_t)sh.batch * 2 * sh.k * N);
-    inner_product(sh, accQ, accP, ext, nullptr, c1, true);
-    moddown(sh, accQ, accP, out, nullptr, nullptr, nullptr, post, rp);
+    if (tail == KsTail::RowPass) sh.gsrc_pmod = c_.d_pmod;
+    KsAcc acc = inner_product(sh, ext, nullptr, base + (size_t)sh.ell * c_.N, tail);
+    moddown(acc, o);
 }
 
-void Evaluator::debug_ks_accp(const u64* ext, int ell, int batch, const int* indices, int n_rot, u64* out) {
-    const size_t N = c_.N, pn = (size_t)ell * N;
+Scratch<u64> Evaluator::debug_ks_accp(const u64* ext, int ell, int batch, const int* indices, int n_rot) {
+    const size_t pn = (size_t)ell * c_.N;
     if (ell < 1 || ell > c_.L + 1 || batch < 1 || n_rot < 0 || n_rot > (int)KsShape::MAX_ROT) throw Error(FHELIN_ERR_ARG, "debug_ks_accp: bad shape");
     if (!n_rot && !relin_key) throw Error(FHELIN_ERR_KEY, "debug_ks_accp: no relinearisation key");
-    KsShape sh{ell, c_.K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, batch, pn, 0, 0, 0};
+    KsShape sh = ks_shape(ell, batch, {pn});
     Scratch<u64> own = c_.scratch<u64>((size_t)batch * pn);    // the Q limbs' own-digit operand: the Q half is computed and dropped
     hip_check(hipMemsetAsync(own, 0, (size_t)batch * pn * sizeof(u64), c_.stream), "hipMemsetAsync(debug_ks_accp)");
-    Scratch<u64> accQ = c_.scratch<u64>((size_t)batch * 2 * pn);
-    if (n_rot) {
-        set_rotations(sh, rotations(indices, n_rot), true, nullptr);
-        inner_product(sh, accQ, out, ext, nullptr, own, true);
-    } else {
-        inner_product(sh, accQ, out, ext, relin_key->d, own, false);
-    }
-    accp_inverse(sh, out);
+    if (n_rot) set_rotations(sh, rotations(indices, n_rot), true, nullptr);
+    KsAcc acc = inner_product(sh, ext, n_rot ? nullptr : relin_key->d, own, KsTail::Finish);
+    accp_inverse(acc);
     launch_ok("debug_ks_accp");
+    return std::move(acc.accP);
 }
 
 void Evaluator::debug_ks_accq(const u64* ext, const u64* own, u64* conv, int ell, int batch, int index, u64* out) {
-    const size_t N = c_.N, pn = (size_t)ell * N;
+    const size_t pn = (size_t)ell * c_.N;
     if (ell < 1 || ell > c_.L + 1 || batch < 1) throw Error(FHELIN_ERR_ARG, "debug_ks_accq: bad shape");
     if (!index && !relin_key) throw Error(FHELIN_ERR_KEY, "debug_ks_accq: no relinearisation key");
-    KsShape sh{ell, c_.K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, batch, pn, 2 * pn, 0, 0};
+    KsShape sh = ks_shape(ell, batch, {pn, 2 * pn});
     const u64* evk = index ? nullptr : relin_key->d;
     if (index) {
         const RotKey k = rotation_key(index);
-        sh.gather = 1;
-        evk = permuted(*k.key, k.map);
-        sh.map_row[0] = k.map;
-        sh.ginv = c_.automorph_ginv_of(k.map);
+        const EvalKey* key = k.key.get();
+        evk = set_gather(sh, &key, &k.map);
     }
-    NttProduct qprod;
-    Scratch<u64> accQ;
-    if (!accq_in_rows(sh)) accQ = c_.scratch<u64>((size_t)batch * 2 * pn);
-    Scratch<u64> accP = c_.scratch<u64>((size_t)batch * 2 * c_.K * N);   // the special-limb half is computed and dropped
-    inner_product(sh, accQ, accP, ext, evk, own, false, true, &qprod);
-    moddown_rows(sh, accQ, conv, out, nullptr, nullptr, nullptr, nullptr, &qprod);
+    KsAcc acc = inner_product(sh, ext, evk, own, KsTail::RowPass);   // the special-limb half is computed and dropped
+    moddown_rows(acc, conv, KsOut{out});
     launch_ok("debug_ks_accq");
 }
 
@@ -572,7 +576,7 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
         const u64* base = chunk[0]->d;
-        KsShape sh{ell, c_.K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, ctw, ctw, pn, ctw};
+        KsShape sh = ks_shape(ell, B, {ctw, ctw, pn, ctw});
         set_rotations(sh, rot, true);
         // accounting in units of the reference's rotations: R = 2^k - 1 merged terms stand for k tree steps
         int steps = 0;
@@ -581,7 +585,7 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
         c_.stats.keyswitch_limbs += (u64)B * steps * ell;
         {
             Scratch<u64> ext = modup(sh, base + pn, false);   // of c1, once for all rotations
-            rotation_sum(sh, ext, base + pn, base, ctw, o[0]->d, base);   // one ModDown; its finish adds the unrotated input
+            rotation_sum(sh, ext, base, ctw, KsOut{o[0]->d, nullptr, nullptr, base});   // one ModDown; its finish adds the unrotated input
             launch_ok("rotate_sum_batch");
         }
         for (int b = 0; b < B; ++b) o[b]->scale = vin[idx[b]]->scale;
@@ -671,7 +675,7 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
         const int oell = merged ? ell - 1 : ell;
         std::vector<CtPtr> o = new_ct_batch(B, 2, oell, merged ? chunk[0]->deg : chunk[0]->deg + 1, chunk[0]->scale * sf, chunk[0]->slots);
         const u64* base = chunk[0]->d;
-        KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, ctw, (size_t)2 * oell * N, pn, ctw};
+        KsShape sh = ks_shape(ell, B, {ctw, (size_t)2 * oell * N, pn, ctw});
         HoistAdd h;
         h.n_rot = R;
         std::vector<FoldedKey> hold;            // the folded keys and encodings of this launch set stay alive across a cache eviction
@@ -696,20 +700,18 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
         {
             Scratch<u64> ext = modup(sh, base + pn, false);   // of c1, once for all rotations
             // sum_r V_r . sigma_r(d * evk_r) in the extended basis: the merged inner product with the folded keys
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
-            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-            inner_product(sh, accQ, accP, ext, nullptr, base + pn, true);
+            KsAcc acc = inner_product(sh, ext, nullptr, base + pn, merged ? KsTail::Rescale : moddown_tail(KsOutput::MergedSum));
             if (!merged) {
                 // what does not pass through the key switch: V_0 (c0, c1) + sum_r V_r sigma_r(c0)
                 Scratch<u64> pre = c_.scratch<u64>((size_t)B * ctw);
                 launch_hoist_addends(c_.dt, sh, h, pre, base, s);
-                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, pre, sum_in_row_pass());   // one ModDown
+                moddown(acc, KsOut{o[0]->d, nullptr, nullptr, pre});   // one ModDown
             } else {
                 // the same addends times P into the accumulator's Q part, then P and the top limb are dropped together
-                h.acc = accQ;
+                h.acc = acc.accQ;
                 h.pmod = c_.d_pmod;
                 launch_hoist_addends(c_.dt, sh, h, nullptr, base, s);
-                moddown_rescale(sh, accQ, accP, o[0]->d);
+                moddown_rescale(acc, o[0]->d);
             }
             launch_ok("hoisted_dot_rows");
         }
@@ -776,13 +778,13 @@ std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xi
                 }
         std::vector<CtPtr> o = new_ct_batch(B * n2, 2, ell, chunk[0]->deg + 1, chunk[0]->scale * sf, chunk[0]->slots);
         const u64* base = chunk[0]->d;
-        KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, c_.L + 1, B, ctw, ctw, pn, ctw};
+        KsShape sh = ks_shape(ell, B, {ctw, ctw, pn, ctw});
         c_.stats.ct_pt_mult += (u64)B * terms;
         c_.stats.ct_pt_limbs += (u64)B * terms * ell;
         {
             Scratch<u64> ext = modup(sh, base + pn, false);   // of c1, once for all baby steps and groups
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * n2 * 2 * ell * N);
-            Scratch<u64> accP = c_.scratch<u64>((size_t)B * n2 * 2 * K * N);
+            // ONE accumulator and ONE ModDown over rows x groups, identity output map
+            KsAcc acc = accumulators(ks_shape(ell, B * n2, {ctw, ctw, pn, ctw}), moddown_tail(KsOutput::Identity));
             std::vector<Scratch<u64>> tabs;
             for (int g0 = 0; g0 < n2; g0 += LtStep::MAX_G) {
                 LtDot ld;
@@ -818,12 +820,9 @@ std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xi
                     ld.steps = reinterpret_cast<const LtStep*>((const u64*)tabs.back());
                     ld.n_steps = (int)tab.size();
                 }
-                launch_ks_inner_dot(c_.dt, sh, ld, accQ, accP, ext, base, base + pn, c_.stream);
+                launch_ks_inner_dot(c_.dt, sh, ld, acc.accQ, acc.accP, ext, base, base + pn, c_.stream);
             }
-            KsShape md = sh;
-            md.batch = B * n2;      // ONE ModDown over rows x groups, identity output map
-            // identity output map: the finish rides in the row pass under the predicate keyswitch_impl uses for its identity ModDowns
-            moddown(md, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, c_.fuse_moddown || c_.fuse_finish);
+            moddown(acc, KsOut{o[0]->d});
             launch_ok("linear_transform_rows");
         }
         // the giant steps: sum_g rot(inner_g, giant[g]) as rotate_each_sum forms it - unrotated groups first, then the rotated ones in
@@ -882,22 +881,22 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
         }
         chunk = make_contiguous(chunk, 1);
         const size_t N = c_.N;
-        const int K = c_.K, L1 = c_.L + 1, ell = chunk[0]->ell;
+        const int K = c_.K, ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
         const LevelTables& lt = c_.lvl[ell];
         const u64* base = chunk[0]->d;
         CtPtr o = new_ct(2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
         {
             // ModUp of the R inputs as one batch
-            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, R, ctw, 0, 0, 0}, base + pn, false);
+            Scratch<u64> ext = modup(ks_shape(ell, R, {ctw}), base + pn, false);
             // one accumulator for all R rotated inner products, one ModDown
-            KsShape sh{ell, K, c_.alpha, lt.beta, L1, 1, 0, ctw, pn, 0};
+            KsShape sh = ks_shape(ell, 1, {0, ctw, pn});
             sh.rot_ext_stride = (size_t)lt.beta * (ell + K) * N;
             sh.rot_input_stride = ctw;
             set_rotations(sh, rotations(ridx.data() + first, R), false);
             c_.stats.keyswitch += (u64)R;
             c_.stats.keyswitch_limbs += (u64)R * ell;
-            rotation_sum(sh, ext, base + pn, base, 0, o->d, nullptr);
+            rotation_sum(sh, ext, base, 0, KsOut{o->d});
             launch_ok("rotate_each_sum");
         }
         acc = acc ? add(acc, o) : o;
@@ -929,7 +928,7 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
         return out;
     }
     const size_t N = c_.N;
-    const int K = c_.K, L1 = c_.L + 1, ell = f->ell;
+    const int K = c_.K, ell = f->ell;
     const size_t pn = (size_t)ell * N, ctw = 2 * pn;
     const LevelTables& lt = c_.lvl[ell];
     const int nt = ell + K;
@@ -966,16 +965,16 @@ std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell, f->deg, f->scale, f->slots);
         {
             const bool spaced = row_stride != (size_t)R * ctw;   // the rows' runs of R terms lie further apart than the terms
-            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B * R, ctw, 0, 0, 0}, base + pn, false, spaced ? R : 0,
+            Scratch<u64> ext = modup(ks_shape(ell, B * R, {ctw}), base + pn, false, spaced ? R : 0,
                                      spaced ? row_stride : 0);
-            KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, row_stride, ctw, pn, 0};
+            KsShape sh = ks_shape(ell, B, {row_stride, ctw, pn});
             sh.rot_ext_stride = (size_t)lt.beta * nt * N;
             sh.rot_input_stride = ctw;
             sh.ext_batch_stride = (size_t)R * lt.beta * nt * N;
             set_rotations(sh, rot, false);
             c_.stats.keyswitch += (u64)B * R;
             c_.stats.keyswitch_limbs += (u64)B * R * ell;
-            rotation_sum(sh, ext, base + pn, base, row_stride, o[0]->d, nullptr);
+            rotation_sum(sh, ext, base, row_stride, KsOut{o[0]->d});
             launch_ok("rotate_each_sum_rows");
         }
         for (int b = 0; b < B; ++b) out[lo + b] = o[b];
@@ -1200,7 +1199,7 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
         maps.push_back(rk.map);
     }
     const size_t N = c_.N;
-    const int K = c_.K, L1 = c_.L + 1, ell = xs[0]->ell;
+    const int K = c_.K, ell = xs[0]->ell;
     const size_t pn = (size_t)ell * N, ctw = 2 * pn;
     const LevelTables& lt = c_.lvl[ell];
     const int nt = ell + K;
@@ -1218,22 +1217,23 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
         std::vector<CtPtr> o = new_ct_batch(rows, 2, ell, xs[lo]->deg, xs[lo]->scale, xs[lo]->slots);
         {
             // ModUp of the B inputs' c1, once; digits times 2^64 for the keys as they are stored: launch_ks_inner ends in redc128
-            Scratch<u64> ext = modup(KsShape{ell, K, c_.alpha, lt.beta, L1, B, ctw, 0, 0, 0}, base + pn, !gather);
+            Scratch<u64> ext = modup(ks_shape(ell, B, {ctw}), base + pn, !gather);
             // inner products: per input, rows of <= MAX_ROWS indices with their own keys, all reading that input's digits
-            Scratch<u64> accQ;   // allocated below: not at all where the ModDown's row pass forms the Q-limb sums
-            Scratch<u64> accP = c_.scratch<u64>((size_t)rows * 2 * K * N);
-            // ONE launch per chunk of <= MAX_ROWS indices over ALL inputs (KsShape::row_mod): row (i, r) = rotation r of input i; in the
-            // XCD-aware block order a key tile is fetched once for all inputs and a digit tile once for all indices
-            auto row_shape = [&](int first, int cnt) {
-                KsShape sh{ell, K, c_.alpha, lt.beta, L1, B * cnt, ctw, ctw, ctw, 0};
+            auto row_keys = [&](KsShape sh, int first, int cnt) {
                 sh.per_row = 1;
                 sh.shared_input = 1;
-                sh.row_mod = cnt;
-                sh.ext_batch_stride = (size_t)lt.beta * nt * N;
                 for (int b = 0; b < cnt; ++b) {
                     sh.evk_row[b] = keys[first + b]->d;
                     sh.map_row[b] = maps[first + b];
                 }
+                return sh;
+            };
+            // ONE launch per chunk of <= MAX_ROWS indices over ALL inputs (KsShape::row_mod): row (i, r) = rotation r of input i; in the
+            // XCD-aware block order a key tile is fetched once for all inputs and a digit tile once for all indices
+            auto row_shape = [&](int first, int cnt) {
+                KsShape sh = row_keys(ks_shape(ell, B * cnt, {ctw, ctw, ctw}), first, cnt);
+                sh.row_mod = cnt;
+                sh.ext_batch_stride = (size_t)lt.beta * nt * N;
                 return sh;
             };
             // R > MAX_ROWS: per input and per chunk of <= MAX_ROWS indices, launch(shape, first row of the chunk, input)
@@ -1241,52 +1241,33 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
                 for (int i = 0; i < B; ++i)
                     for (int first = 0; first < R; first += KsShape::MAX_ROWS) {
                         const int cnt = std::min(R - first, (int)KsShape::MAX_ROWS);
-                        KsShape sh1{ell, K, c_.alpha, lt.beta, L1, cnt, 0, ctw, 0, 0};
-                        sh1.per_row = 1;
-                        sh1.shared_input = 1;
-                        for (int b = 0; b < cnt; ++b) {
-                            sh1.evk_row[b] = keys[first + b]->d;
-                            sh1.map_row[b] = maps[first + b];
-                        }
-                        launch(sh1, (size_t)i * R + first, i);
+                        launch(row_keys(ks_shape(ell, cnt, {0, ctw}), first, cnt), (size_t)i * R + first, i);
                     }
             };
             const bool one_chunk = R <= (int)KsShape::MAX_ROWS;     // rows then lie [input][index] as the outputs do
             if (gather) {
                 // every row gathers through its map at the inner product (its input's c0 included, times P); ONE identity ModDown over all rows
                 KsShape sh = row_shape(0, R);
-                sh.gather = 1;
-                for (int b = 0; b < R; ++b) {
-                    sh.evk_row[b] = permuted(*keys[b], maps[b]);
-                    sh.ginv_row[b] = c_.automorph_ginv_of(maps[b]);
-                }
-                sh.gsrc = base;
-                sh.gsrc_stride = ctw;
-                sh.gsrc_pmod = c_.d_pmod;
-                NttProduct qprod;   // one launch covers the indices: the row pass may form the Q-limb sums itself
-                if (!accq_in_rows(sh)) accQ = c_.scratch<u64>((size_t)rows * 2 * ell * N);
-                inner_product(sh, accQ, accP, ext, nullptr, base + pn, false, true, &qprod);
-                moddown(sh, accQ, accP, o[0]->d, nullptr, nullptr, nullptr, nullptr, true, nullptr, &qprod);
+                set_gather(sh, keys.data(), maps.data(), base, ctw);
+                KsAcc acc = inner_product(sh, ext, nullptr, base + pn, moddown_tail(KsOutput::Gathered));
+                moddown(acc, KsOut{o[0]->d});
             } else {
-                accQ = c_.scratch<u64>((size_t)rows * 2 * ell * N);
-                if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), accQ, accP, ext, nullptr, base + pn, s);
+                // ONE ModDown over all rows up to its finish, which takes them in slices and adds the input's c0 (gathered through each row's map)
+                KsAcc acc = accumulators(ks_shape(ell, rows, {0, ctw}), KsTail::Finish);
+                if (one_chunk) launch_ks_inner(c_.dt, row_shape(0, R), acc.accQ, acc.accP, ext, nullptr, base + pn, s);
                 else
                     for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
-                        launch_ks_inner(c_.dt, sh1, accQ + row0 * 2 * ell * N, accP + row0 * 2 * K * N, ext + (size_t)i * lt.beta * nt * N, nullptr,
-                                        base + pn + (size_t)i * ctw, s);
+                        launch_ks_inner(c_.dt, sh1, acc.accQ + row0 * 2 * ell * N, acc.accP + row0 * 2 * K * N,
+                                        ext + (size_t)i * lt.beta * nt * N, nullptr, base + pn + (size_t)i * ctw, s);
                     });
-                // ONE ModDown over all rows; the epilogue adds the input's c0 (gathered through each row's map)
-                moddown(KsShape{ell, K, c_.alpha, lt.beta, L1, rows, 0, ctw, 0, 0}, accQ, accP, nullptr, nullptr, nullptr, nullptr, nullptr, false,
-                        [&](const u64* conv) {
-                            if (one_chunk)
-                                launch_moddown_finish(c_.dt, row_shape(0, R), o[0]->d, accQ, conv, c_.d_pinv, base, nullptr, nullptr, nullptr, s);
-                            else
-                                for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
-                                    // add_stride 0 = the same c0 for every row
-                                    launch_moddown_finish(c_.dt, sh1, o[row0]->d, accQ + row0 * 2 * ell * N, conv + row0 * 2 * ell * N,
-                                                          c_.d_pinv, base + (size_t)i * ctw, nullptr, nullptr, nullptr, s);
-                                });
-                        });
+                Scratch<u64> conv = moddown_conv(acc);
+                if (one_chunk) launch_moddown_finish(c_.dt, row_shape(0, R), o[0]->d, acc.accQ, conv, c_.d_pinv, base, nullptr, nullptr, nullptr, s);
+                else
+                    for_row_chunks([&](const KsShape& sh1, size_t row0, int i) {
+                        // add_stride 0 = the same c0 for every row
+                        launch_moddown_finish(c_.dt, sh1, o[row0]->d, acc.accQ + row0 * 2 * ell * N, conv + row0 * 2 * ell * N, c_.d_pinv,
+                                              base + (size_t)i * ctw, nullptr, nullptr, nullptr, s);
+                    });
             }
             launch_ok("rotate_many_batch");
         }
@@ -1762,7 +1743,6 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
         if (ell < 2) throw Error(FHELIN_ERR_STATE, "mult_affine_rescale_batch: no limb left to drop");
         const size_t pn = (size_t)ell * N;
         const long double sc = product_scale(first);
-        const LevelTables& lt = c_.lvl[ell];
         const std::vector<CtPtr> d = tensor_products(x, y, idx);
         // the subtrahends at the products' (limbs, degree 2, scale), in one block
         std::vector<CtPtr> sadj;
@@ -1773,7 +1753,7 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
         ScalarSet cst;
         if (cadd != 0.0) real_to_scalars(c_, (long double)cadd * sc, ell, cst);
         // key switch of d2 up to the accumulator
-        KsShape sh{ell, K, c_.alpha, lt.beta, L1, B, 3 * pn, (size_t)2 * (ell - 1) * N, pn, 0};
+        KsShape sh = ks_shape(ell, B, {3 * pn, (size_t)2 * (ell - 1) * N, pn});
         c_.stats.keyswitch += (u64)B;
         c_.stats.keyswitch_limbs += (u64)B * ell;
         c_.stats.rescale += (u64)B;
@@ -1782,13 +1762,11 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell - 1, 1, 0, x[first]->slots);
         {
             Scratch<u64> ext = modup(sh, c_ntt, true);   // digits times 2^64: launch_ks_inner ends in redc128
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
-            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * K * N);
-            inner_product(sh, accQ, accP, ext, relin_key->d, c_ntt, false, f != 2);   // f = 2: accP itself is doubled below
+            KsAcc acc = inner_product(sh, ext, relin_key->d, c_ntt, f == 2 ? KsTail::EditsAccP : KsTail::Rescale);   // f = 2: accP itself is doubled below
             // X_Q = f acc_Q + P (f (d0, d1) + constant - subtrahend),  X_P = f acc_P
-            launch_affine_acc(c_.dt, sh, accQ, d[0]->d, sadj.empty() ? nullptr : sadj[0]->d, cst, cadd != 0.0 ? 1 : 0, f, c_.d_pmod, s);
-            if (f == 2) launch_ew_add(c_.dt, accP, accP, accP, B * 2 * K, B * 2 * K, L1, K, s);
-            moddown_rescale(sh, accQ, accP, o[0]->d);   // P and the top limb dropped together
+            launch_affine_acc(c_.dt, sh, acc.accQ, d[0]->d, sadj.empty() ? nullptr : sadj[0]->d, cst, cadd != 0.0 ? 1 : 0, f, c_.d_pmod, s);
+            if (f == 2) launch_ew_add(c_.dt, acc.accP, acc.accP, acc.accP, B * 2 * K, B * 2 * K, L1, K, s);
+            moddown_rescale(acc, o[0]->d);   // P and the top limb dropped together
             launch_ok("mult_affine_rescale_batch");
         }
         for (int k = 0; k < B; ++k) o[k]->scale = product_scale(idx[k]) / (long double)c_.chain.q[ell - 1];
@@ -1846,7 +1824,7 @@ std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, con
     for (size_t i = 0; i < n; ++i)
         if (x[i]->ell < 2 || (spec[i].addend && spec[i].addend->ell < x[i]->ell)) return mult_affine_unmerged(x, y, spec);
     const size_t N = c_.N;
-    const int K = c_.K, L1 = c_.L + 1;
+    const int K = c_.K;
     hipStream_t s = c_.stream;
     static_assert(AffineItems::MAX_ITEMS <= EwItems::MAX_ITEMS, "the tensor products of a group are one launch");
     return for_groups(n, std::min(batch_limit, (int)AffineItems::MAX_ITEMS), [&](size_t f, size_t i) { return x[i]->ell == x[f]->ell; },
@@ -1889,7 +1867,7 @@ std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, con
         }
         Scratch<u64> dcst = c_.scratch<u64>(cst.size());
         if (items.cst) c_.upload_async(dcst, cst.data(), cst.size());
-        KsShape sh{ell, K, c_.alpha, c_.lvl[ell].beta, L1, B, 3 * pn, (size_t)2 * (ell - 1) * N, pn, 0};
+        KsShape sh = ks_shape(ell, B, {3 * pn, (size_t)2 * (ell - 1) * N, pn});
         sh.accp_limbs = K + 1;
         // counted as the unmerged sequence counts: one key switch and one rescale per product
         c_.stats.keyswitch += (u64)B;
@@ -1900,11 +1878,10 @@ std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, con
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell - 1, 1, 0, x[first]->slots);
         {
             Scratch<u64> ext = modup(sh, c_ntt, true);   // digits times 2^64: launch_ks_inner ends in redc128
-            Scratch<u64> accQ = c_.scratch<u64>((size_t)B * 2 * ell * N);
-            Scratch<u64> accP = c_.scratch<u64>((size_t)B * 2 * (K + 1) * N);
-            launch_ks_inner(c_.dt, sh, accQ, accP, ext, relin_key->d, c_ntt, s);
-            launch_affine_acc_items(c_.dt, sh, items, accQ, accP, d[0]->d, dcst, c_.d_pmod, s);
-            moddown_rescale_exact(sh, accQ, accP, o[0]->d, items.f2);
+            KsAcc acc = accumulators(sh, KsTail::Exact);   // accP with its K+1-th slot (sh.accp_limbs)
+            launch_ks_inner(c_.dt, sh, acc.accQ, acc.accP, ext, relin_key->d, c_ntt, s);
+            launch_affine_acc_items(c_.dt, sh, items, acc.accQ, acc.accP, d[0]->d, dcst, c_.d_pmod, s);
+            moddown_rescale_exact(acc, o[0]->d, items.f2);
             launch_ok("mult_affine_batch");
         }
         for (int k = 0; k < B; ++k) o[k]->scale = x[idx[k]]->scale * y[idx[k]]->scale / (long double)c_.chain.q[ell - 1];

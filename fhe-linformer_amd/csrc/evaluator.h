@@ -3,7 +3,6 @@
 // :409-436 add/mult/rotate, FLEXIBLEAUTO level + scale bookkeeping implied by :18-24).
 #pragma once
 #include <cmath>
-#include <functional>
 #include <map>
 #include <memory>
 #include <vector>
@@ -220,10 +219,10 @@ public:
     // the residues of rotate(xs[i], indices[k]).
     std::vector<std::vector<CtPtr>> rotate_many_batch(const std::vector<CtPtr>& xs, const std::vector<int>& indices);
     // test hook (fhelin_debug_ks_accp): the special-limb half of a key switch's inner product over digits the caller chooses residue by
-    // residue, through inner_product and accp_inverse as they stand.  ext [batch][beta][ell+K][N] (device), out [batch][2][K][N] (device):
-    // INTT(accP).  n_rot = 0: the identity form over the relinearisation key as stored (the sum comes times 2^-64); else the merged form
-    // over the permuted keys of the n_rot <= 7 rotations.
-    void debug_ks_accp(const u64* ext, int ell, int batch, const int* indices, int n_rot, u64* out);
+    // residue, through inner_product and accp_inverse as they stand.  ext [batch][beta][ell+K][N] (device); returns the accumulator's own
+    // [batch][2][K][N]: INTT(accP).  n_rot = 0: the identity form over the relinearisation key as stored (the sum comes times 2^-64);
+    // else the merged form over the permuted keys of the n_rot <= 7 rotations.
+    Scratch<u64> debug_ks_accp(const u64* ext, int ell, int batch, const int* indices, int n_rot);
     // test hook (fhelin_debug_ks_accq): the Q-limb half of a single-key inner product and the row-pass finish of its ModDown over operands the
     // caller chooses residue by residue, through inner_product and moddown_rows as they stand.  ext [batch][beta][ell+K][N], own [batch][ell][N]
     // (the switched polynomial, NTT form), conv [batch][2][ell][N] (coefficient form, canonical; overwritten), out [batch][2][ell][N], all
@@ -361,26 +360,51 @@ private:
     void keyswitch_impl(int batch, const KsRows* rows, const u64* c_ntt, size_t c_stride, int ell, const EvalKey* key, u64* out,
                         size_t out_stride, const u64* add0, const u64* add1, size_t add_stride, const u32* map, const u64* post,
                         size_t post_stride);
-    // the stages every key switch is built from (evaluator.cpp "key-switch stages"): the place to change the pipeline
+    // ---- the stages every key switch is built from (evaluator.cpp "key-switch stages"): the place to change the pipeline
+    struct KsStrides { size_t c = 0, out = 0, add = 0, post = 0; };   // the element strides of a KsShape, in the struct's own order
+    KsShape ks_shape(int ell, int batch, const KsStrides& st) const;    // ell, k, alpha, beta, L1 from the context
+    // the tail an accumulator is meant for, named when it is made: what may be left to the tail's transforms follows from it alone
+    enum class KsTail {
+        RowPass,     // moddown, finished in the row pass of NTT(conv)
+        Finish,      // moddown, finished by launch_moddown_finish (or by the caller's own launches after moddown_conv)
+        Rescale,     // moddown_rescale
+        Exact,       // moddown_rescale_exact
+        EditsAccP,   // moddown_rescale after the caller has worked on accP, which must then hold the residues themselves
+    };
+    // what lives between a key switch's inner product and its tail: made by inner_product or accumulators, consumed by ONE tail
+    struct KsAcc {
+        KsShape sh;          // the shape as decided: accp_rows / accq_rows are set here and nowhere else
+        KsTail tail;
+        Scratch<u64> accQ;   // [sh.batch][2][ell][N]; empty with sh.accq_rows
+        Scratch<u64> accP;   // [sh.batch][2][K, or sh.accp_limbs][N]
+        NttProduct qprod;    // with sh.accq_rows: the Q-limb sums, for the tail's row pass to form
+    };
+    // where a ModDown's result goes: out = .. + add0 / add1 (+ post), written through `map`; as constructed: the identity, no addends
+    struct KsOut {
+        u64* out = nullptr;
+        const u64 *add0 = nullptr, *add1 = nullptr, *post = nullptr;
+        const u32* map = nullptr;
+    };
+    enum class KsOutput { Identity, Gathered, Scattered, MergedSum };
+    KsTail moddown_tail(KsOutput o) const;   // RowPass or Finish: the one reading of FHELIN_FUSE_MODDOWN / _FUSE_FINISH / _ROT_GATHER
+    // a plain rotation that gathers at the inner product (KsShape::gather) into its shape: the keys' permuted copies, the inverse Galois
+    // elements, optionally c0 (into accQ times P).  sh.per_row: one key and map per row; else one of each, and that key is returned
+    const u64* set_gather(KsShape& sh, const EvalKey* const* keys, const u32* const* maps, const u64* c0 = nullptr, size_t c0_stride = 0);
     Scratch<u64> modup(const KsShape& up, const u64* src, bool times_r2, int group2 = 0, size_t group2_stride = 0);
-    // the inner product of a key switch into the accumulator pair (multi: launch_ks_inner_multi, else launch_ks_inner over evk); where the
-    // special-limb half is formed in the inverse NTT's row pass it sets sh.accp_rows, which the ModDown tails read.  fuse = false: the
-    // caller touches accP before its tail (it must then hold the residues themselves)
-    // qprod != nullptr: the caller's tail is moddown(row_pass = true) over *qprod, and where accq_in_rows(sh) holds the Q-limb half is left
-    // to that row pass too: no inner-product launch at all, sh.accq_rows is set, *qprod describes the sums, accQ is not touched (may be null)
-    void inner_product(KsShape& sh, u64* accQ, u64* accP, const u64* ext, const u64* evk, const u64* c_ntt, bool multi, bool fuse = true,
-                       NttProduct* qprod = nullptr);
-    bool accp_in_rows(const KsShape& sh, bool multi, bool fuse) const;   // FHELIN_FUSE_ACCP_ROWS: the class rule of DESIGN.md 6j
-    bool accq_in_rows(const KsShape& sh) const;                          // FHELIN_FUSE_ACCQ_ROWS: a single-key shape, the class rule of 6k
-    void accp_inverse(const KsShape& sh, u64* accP);   // INTT(accP) of a tail: the column pass alone with sh.accp_rows
-    void moddown(const KsShape& sh, const u64* accQ, u64* accP, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
-                 bool row_pass = false, const std::function<void(const u64* conv)>& finish = nullptr, const NttProduct* qprod = nullptr);
-    // the last kernel of a row-pass ModDown: out = (accQ - NTT(conv)) * P^-1 + add (+ post) in the row pass of NTT(conv); with sh.accq_rows
-    // accQ is formed there from *qprod
-    void moddown_rows(const KsShape& sh, const u64* accQ, u64* conv, u64* out, const u64* add0, const u64* add1, const u32* map, const u64* post,
-                      const NttProduct* qprod);
-    void moddown_rescale(const KsShape& sh, const u64* accQ, u64* accP, u64* out);
-    void moddown_rescale_exact(const KsShape& sh, const u64* accQ, u64* accP, u64* out, u32 f2);
+    // evk: the one key of every row, or null: the shape's own - per row (sh.evk_row) or, a merged sum (sh.n_rot > 0), per rotation (sh.evk_rot)
+    KsAcc inner_product(const KsShape& sh, const u64* ext, const u64* evk, const u64* c_ntt, KsTail tail);
+    KsAcc accumulators(const KsShape& sh, KsTail tail);   // for a caller that launches its own inner product: both buffers, nothing decided
+    bool accp_in_rows(const KsShape& sh, KsTail tail) const;   // FHELIN_FUSE_ACCP_ROWS: the class rule of DESIGN.md 6j
+    bool accq_in_rows(const KsShape& sh, KsTail tail) const;   // FHELIN_FUSE_ACCQ_ROWS: the class rule of 6k
+    void accp_inverse(KsAcc& acc);   // INTT(accP) of a tail: the column pass alone with sh.accp_rows
+    // the first half of moddown: conv [sh.batch][2][ell][N] from accP, in NTT form unless the tail is RowPass (whose row pass transforms it)
+    Scratch<u64> moddown_conv(KsAcc& acc);
+    void moddown(KsAcc& acc, const KsOut& o);
+    // the last kernel of a row-pass ModDown: o.out = (accQ - NTT(conv)) * P^-1 + add (+ post) in the row pass of NTT(conv); with sh.accq_rows
+    // accQ is formed there from acc.qprod
+    void moddown_rows(const KsAcc& acc, u64* conv, const KsOut& o);
+    void moddown_rescale(KsAcc& acc, u64* out);
+    void moddown_rescale_exact(KsAcc& acc, u64* out, u32 f2);
     // logical slot count of a ciphertext (slots = 0: the context's)
     int slot_count(int slots) const;
     int slot_count(const CtPtr& a) const { return slot_count(a->slots); }
@@ -400,7 +424,7 @@ private:
     };
     Rotations rotations(const int* indices, int n);
     void set_rotations(KsShape& sh, const Rotations& rot, bool shared_digits, const u64* const* keys = nullptr);
-    void rotation_sum(KsShape& sh, const u64* ext, const u64* c1, const u64* c0, size_t c0_stride, u64* out, const u64* post);
+    void rotation_sum(KsShape& sh, const u64* ext, const u64* base, size_t c0_stride, const KsOut& o);
     // every degree-2 ciphertext of the list(s) replaced by its rescaled one: one rescale_batch over the distinct ones; FHELIN_ERR_STATE
     // (`what`) for an operand that does not have two components, before anything runs
     void rescale_degree2(std::vector<CtPtr>& a, std::vector<CtPtr>* b = nullptr, const char* two_components = nullptr);
@@ -410,13 +434,11 @@ private:
     void product_operands(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, std::vector<CtPtr>& x, std::vector<CtPtr>& y);
     // the unmerged sequence of mult_affine_batch: mult_batch, add_batch (factor 2), add_real per item, sub_batch / add_batch, rescale_batch
     std::vector<CtPtr> mult_affine_unmerged(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<AffineSpec>& spec);
-    // a merged rotation sum ends in the identity ModDown of the row pass, its rotated c0 parts added to the accumulator by the inner product
-    bool sum_in_row_pass() const { return c_.fuse_finish && c_.rot_gather; }
     // a plain rotation gathers at the inner product and ends in the same identity ModDown (KsShape::gather); FHELIN_FUSE_MODDOWN=1 keeps
     // its scattered epilogue
     bool rot_in_gather() const { return c_.fuse_finish && c_.rot_gather && !c_.fuse_moddown; }
     // NTT(conv) [batch][2][ell-1][N] and the merged ModDown + rescale finish into out (launch_moddown_rescale_finish)
-    void moddown_rescale_finish(const KsShape& sh, u64* out, const u64* accQ, u64* conv, const u64* minv);
+    void moddown_rescale_finish(const KsAcc& acc, u64* out, u64* conv, const u64* minv);
     typedef std::vector<CtPtr> CtRow;  // one value per input ciphertext
     CtRow cheb_recurse(const std::vector<double>& c, const std::vector<CtRow>& T, const std::map<int, CtRow>& G, int baby);
     std::vector<CtPtr> add_sub_batch(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, int op);
