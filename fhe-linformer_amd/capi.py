@@ -192,6 +192,14 @@ def load_library():
         "fhelin_bootstrap_iter": (i32, [vp, vp, i32, C.POINTER(vp)]),
         "fhelin_bootstrap_iter_batch": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp)]),
         "fhelin_bootstrap_iter_drop": (i32, [vp, vp, i32, i32, C.POINTER(vp)]),
+        "fhelin_bootstrap_pair": (i32, [vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
+        "fhelin_bootstrap_paired_batch": (i32, [vp, C.POINTER(vp), i32, C.POINTER(vp)]),
+        "fhelin_bootstrap_pair_drop": (i32, [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(vp)]),
+        "fhelin_bootstrap_pair_partial": (i32, [vp, vp, vp, i32, C.POINTER(vp)]),
+        "fhelin_ctx_set_bootstrap_pairing": (i32, [vp, i32]),
+        "fhelin_ctx_bootstrap_pairing": (i32, [vp, C.POINTER(i32)]),
+        "fhelin_debug_pair_pack": (i32, [vp, C.POINTER(vp), C.POINTER(vp), u64p, u64p, i32, C.POINTER(vp)]),
+        "fhelin_debug_pair_split": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
         "fhelin_bootstrap_describe": (i32, [vp, C.POINTER(i32), i32, C.POINTER(i32)]),
         "fhelin_bootstrap_diag": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
         "fhelin_bootstrap_cheb": (i32, [vp, C.POINTER(C.c_double), i32, C.POINTER(i32)]),
@@ -1238,6 +1246,56 @@ class Engine:
     def bootstrap_iter_drop(self, a, precision, drop):
         """bootstrap_iter with both bootstraps raising to L+1-drop limbs only"""
         return self._un(self.lib.fhelin_bootstrap_iter_drop, a, int(precision), int(drop))
+
+    def bootstrap_pair(self, a, b):
+        """two ciphertexts with REAL slot values through one bootstrap as a + i b (include/fhelin.h "Paired bootstrapping"): (a', b')"""
+        ha, hb = C.c_void_p(), C.c_void_p()
+        self._ck(self.lib.fhelin_bootstrap_pair(self.h, a.h, b.h, C.byref(ha), C.byref(hb)))
+        return Ct(self, ha), Ct(self, hb)
+
+    def bootstrap_paired_batch(self, v):
+        """bootstrap_batch with consecutive inputs paired: ceil(n / 2) pipelines; an odd last input comes out as bootstrap() gives it"""
+        outs = self._outs(max(len(v), 1))
+        self._ck(self.lib.fhelin_bootstrap_paired_batch(self.h, self._harr(v), len(v), outs))
+        return self._cts(outs, len(v))
+
+    def bootstrap_pair_drop(self, a, b, drop):
+        """bootstrap_pair raising to L+1-drop limbs only"""
+        ha, hb = C.c_void_p(), C.c_void_p()
+        self._ck(self.lib.fhelin_bootstrap_pair_drop(self.h, a.h, b.h, int(drop), C.byref(ha), C.byref(hb)))
+        return Ct(self, ha), Ct(self, hb)
+
+    def bootstrap_pair_partial(self, a, b, stage):
+        """the pair's pipeline stopped after stage 1, 2 or 3 (as bootstrap_partial)"""
+        h = C.c_void_p()
+        self._ck(self.lib.fhelin_bootstrap_pair_partial(self.h, a.h, b.h, int(stage), C.byref(h)))
+        return Ct(self, h)
+
+    def set_bootstrap_pairing(self, on):
+        """deferred bootstrap() calls that are ready together go through the paired pipeline (off by default; FHELIN_BOOT_PAIRS=1)"""
+        self._ck(self.lib.fhelin_ctx_set_bootstrap_pairing(self.h, int(bool(on))))
+
+    def bootstrap_pairing(self):
+        on = C.c_int32()
+        self._ck(self.lib.fhelin_ctx_bootstrap_pairing(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def debug_pair_pack(self, a, b, k0_a, k0_b):
+        """outs[i] = k0_a[i] a[i] + X^(N/2) k0_b[i] b[i] on the two bottom limbs, every pair in one launch (launch_ew_pair_pack)"""
+        n = len(a)
+        assert len(b) == len(k0_a) == len(k0_b) == n
+        ka, kb = (C.c_uint64 * n)(*[int(k) for k in k0_a]), (C.c_uint64 * n)(*[int(k) for k in k0_b])
+        outs = self._outs(n)
+        self._ck(self.lib.fhelin_debug_pair_pack(self.h, self._harr(a), self._harr(b), ka, kb, n, outs))
+        return self._cts(outs, n)
+
+    def debug_pair_split(self, w, wc):
+        """(w[i] + wc[i], X^(N/2) (wc[i] - w[i])) for every pair in one launch (launch_ew_pair_split): (list of a, list of b)"""
+        n = len(w)
+        assert len(wc) == n
+        oa, ob = self._outs(n), self._outs(n)
+        self._ck(self.lib.fhelin_debug_pair_split(self.h, self._harr(w), self._harr(wc), n, oa, ob))
+        return self._cts(oa, n), self._cts(ob, n)
 
     def bootstrap_describe(self):
         """the bootstrapping set-up as the residue-level oracle needs it: parameters + per linear stage the stage's slot count

@@ -243,17 +243,26 @@ void Bootstrapper::setup(int budget_enc, int budget_dec, int slots) {
         cheb_[k] = 2.0 * s / nn;
     }
 
-    // multiplication by i == multiplication by the monomial X^{N/2}
+    ensure_mono_i();
+    depth_ = budget_enc + budget_dec + R + 6;
+}
+
+// multiplication by i == multiplication by the monomial X^{N/2}.  Depends on the ring alone: made once, by setup() or by the first use of
+// the pair kernels on their own (pack_pairs / split_pairs need no keys)
+void Bootstrapper::ensure_mono_i() {
+    if (mono_i_) return;
+    Context& c = ev_.ctx();
+    c.require_device();
     const int L1 = c.L + 1;
     const size_t N = c.N;
-    if (!mono_i_) mono_i_ = c.dalloc<u64>((size_t)L1 * N);
+    u64* m = c.dalloc<u64>((size_t)L1 * N);
     std::vector<u64> h((size_t)L1 * N, 0);
     for (int l = 0; l < L1; ++l) h[(size_t)l * N + N / 2] = 1;
-    hip_check(hipMemcpyAsync(mono_i_, h.data(), h.size() * 8, hipMemcpyHostToDevice, c.stream), "monomial upload");
+    hip_check(hipMemcpyAsync(m, h.data(), h.size() * 8, hipMemcpyHostToDevice, c.stream), "monomial upload");
     hip_check(hipStreamSynchronize(c.stream), "monomial sync");
-    launch_ntt(c.dt, LimbBatch{mono_i_, L1, nullptr, 0, L1}, false, c.stream);
+    launch_ntt(c.dt, LimbBatch{m, L1, nullptr, 0, L1}, false, c.stream);
     hip_check(hipGetLastError(), "monomial ntt");
-    depth_ = budget_enc + budget_dec + R + 6;
+    mono_i_ = m;
 }
 
 CtPtr Bootstrapper::mult_i(const CtPtr& x) {
@@ -491,44 +500,172 @@ std::vector<CtPtr> Bootstrapper::apply_batch(const LinStage& st, const std::vect
     return ev_.rotate_each_sum_rows(rows, gidx);
 }
 
-std::vector<CtPtr> Bootstrapper::run_batch(const std::vector<CtPtr>& cts, int drop) {
+// ---- the two kernels of a paired bootstrap ------------------------------------------------------------------------------------------
+std::vector<CtPtr> Bootstrapper::pack_pairs(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<u64>& ka,
+                                            const std::vector<u64>& kb) {
+    Context& c = ev_.ctx();
+    const size_t n = a.size();
+    if (b.size() != n || ka.size() != n || kb.size() != n) throw Error(FHELIN_ERR_ARG, "pair pack: one partner and two constants per pair");
+    if (n == 0) return {};
+    for (size_t i = 0; i < n; ++i) {
+        if (a[i]->npoly != 2 || b[i]->npoly != 2) throw Error(FHELIN_ERR_STATE, "bootstrap: ciphertext must be relinearised");
+        if (a[i]->ell < 2 || b[i]->ell < 2)
+            throw Error(FHELIN_ERR_STATE, "bootstrap: need at least two limbs to set the message scale (bootstrap one level earlier)");
+    }
+    ensure_mono_i();
+    std::vector<u64> consts(n * 2 * 4);
+    for (size_t i = 0; i < n; ++i)
+        for (int l = 0; l < 2; ++l) {
+            const u64 q = c.chain.q[l], ra = ka[i] % q, rb = kb[i] % q;
+            u64* k = &consts[(i * 2 + l) * 4];
+            k[0] = ra;
+            k[1] = h_shoup(ra, q);
+            k[2] = rb;
+            k[3] = h_shoup(rb, q);
+        }
+    Scratch<u64> dk = c.scratch<u64>(consts.size());
+    for (size_t off = 0; off < consts.size(); off += 2 * c.N)   // upload_async takes <= 2N words per call
+        c.upload_async(dk + off, consts.data() + off, std::min(consts.size() - off, (size_t)2 * c.N));
+    std::vector<CtPtr> out = ev_.new_ct_batch((int)n, 2, 2, 2, 0, a[0]->slots);
+    for (size_t lo = 0; lo < n; lo += EwPairPack::MAX_PAIRS) {
+        EwPairPack d;
+        d.n = (int)std::min(n - lo, (size_t)EwPairPack::MAX_PAIRS);
+        for (int k = 0; k < d.n; ++k) {
+            d.a[k] = a[lo + k]->d;
+            d.b[k] = b[lo + k]->d;
+            d.ell_a[k] = a[lo + k]->ell;
+            d.ell_b[k] = b[lo + k]->ell;
+        }
+        launch_ew_pair_pack(c.dt, d, out[lo]->d, mono_i_, dk + lo * 8, c.stream);
+    }
+    hip_check(hipGetLastError(), "pair pack");
+    dk.reset();
+    for (size_t i = 0; i < n; ++i) {
+        out[i]->deg = a[i]->deg + 1;
+        out[i]->scale = a[i]->scale * (long double)ka[i];
+        out[i]->slots = a[i]->slots;
+    }
+    return out;
+}
+
+void Bootstrapper::split_pairs(const std::vector<CtPtr>& w, const std::vector<CtPtr>& wc, std::vector<CtPtr>& out_a, std::vector<CtPtr>& out_b) {
+    Context& c = ev_.ctx();
+    const size_t n = w.size();
+    if (wc.size() != n) throw Error(FHELIN_ERR_ARG, "pair split: one conjugate per ciphertext");
+    out_a.clear();
+    out_b.clear();
+    if (n == 0) return;
+    const int ell = w[0]->ell;
+    for (size_t i = 0; i < n; ++i)
+        if (w[i]->npoly != 2 || wc[i]->npoly != 2 || w[i]->ell != ell || wc[i]->ell != ell)
+            throw Error(FHELIN_ERR_STATE, "pair split: operands of different shapes");
+    ensure_mono_i();
+    std::vector<CtPtr> o = ev_.new_ct_batch((int)(2 * n), 2, ell, 1, 0, w[0]->slots);
+    for (size_t lo = 0; lo < n; lo += EwPairSplit::MAX_PAIRS) {
+        EwPairSplit d;
+        d.n = (int)std::min(n - lo, (size_t)EwPairSplit::MAX_PAIRS);
+        d.ell = ell;
+        for (int k = 0; k < d.n; ++k) {
+            d.w[k] = w[lo + k]->d;
+            d.wc[k] = wc[lo + k]->d;
+            d.a[k] = o[2 * (lo + k)]->d;
+            d.b[k] = o[2 * (lo + k) + 1]->d;
+        }
+        launch_ew_pair_split(c.dt, d, mono_i_, c.stream);
+    }
+    hip_check(hipGetLastError(), "pair split");
+    for (size_t i = 0; i < n; ++i)
+        for (int h = 0; h < 2; ++h) {
+            const CtPtr& x = o[2 * i + h];
+            x->deg = w[i]->deg;
+            x->scale = w[i]->scale;
+            x->slots = w[i]->slots;
+            (h ? out_b : out_a).push_back(x);
+        }
+}
+
+// Per-item prologue, shared core, per-item epilogue.  A single goes through what run() does to it; a pair (a, b) enters as
+// rescale(k0_a a + i k0_b b) - one pack launch over all pairs, the bottom limbs of both inputs read in place - and leaves through half of
+// the exact 2^correction, one conjugation at the output level and the split (w + conj(w), i (conj(w) - w)) = (a, b) up to rho_a, rho_b,
+// which go into the scales as a single's rho does.  Everything in between is message-agnostic and runs once over all items.
+std::vector<CtPtr> Bootstrapper::run_items(const std::vector<Item>& items, int drop, int stop_after) {
     if (!ready()) throw Error(FHELIN_ERR_STATE, "EvalBootstrapSetup has not been called");
     Context& c = ev_.ctx();
     if (drop < 0 || c.L + 1 - drop - depth_ < 1) throw Error(FHELIN_ERR_ARG, "bootstrap: level plan leaves no limb for the result");
-    const size_t B = cts.size();
+    const size_t B = items.size();
+    if (B == 0) return {};
     const int top_ell = c.L + 1 - drop;
-    // ---- ModRaise (mod_raise() per ciphertext: the integer constant depends on each one's scale)
-    std::vector<CtPtr> xs(B);
+    // ---- prologue.  Inputs: item i has in[2 i] and, a pair, in[2 i + 1]; degree 2 is rescaled first (one batch over all of them)
+    std::vector<CtPtr> in(2 * B);
+    size_t n_pairs = 0;
     {
         std::vector<CtPtr> need;
         std::vector<size_t> pos;
         for (size_t i = 0; i < B; ++i) {
-            if (cts[i]->deg >= 2) {
-                need.push_back(cts[i]);
-                pos.push_back(i);
-            } else {
-                xs[i] = cts[i];
+            in[2 * i] = items[i].a;
+            in[2 * i + 1] = items[i].b;
+            if (items[i].b) {
+                ++n_pairs;
+                const int sa = items[i].a->slots > 0 ? items[i].a->slots : logical_slots_;
+                const int sb = items[i].b->slots > 0 ? items[i].b->slots : logical_slots_;
+                if (sa != sb) throw Error(FHELIN_ERR_ARG, "bootstrap pair: the two ciphertexts must have the same slot count");
             }
         }
+        if (n_pairs && correction < 1)
+            throw Error(FHELIN_ERR_STATE, "bootstrap pair: correction 0 leaves no bit for the 1/2 of the split (bootstrap_config)");
+        for (size_t k = 0; k < 2 * B; ++k)
+            if (in[k] && in[k]->deg >= 2) {
+                need.push_back(in[k]);
+                pos.push_back(k);
+            }
         if (!need.empty()) {
             std::vector<CtPtr> r = ev_.rescale_batch(need);
-            for (size_t k = 0; k < pos.size(); ++k) xs[pos[k]] = r[k];
+            for (size_t k = 0; k < pos.size(); ++k) in[pos[k]] = r[k];
         }
     }
-    std::vector<long double> rho(B);
     const long double q0 = (long double)c.chain.q[0], q1 = (long double)c.chain.q[1];
-    const long double target = q0 / (long double)(1ull << correction);
-    for (size_t i = 0; i < B; ++i) {
-        CtPtr x = xs[i];
+    const long double two_corr = (long double)(1ull << correction);
+    const long double target = q0 / two_corr;
+    std::vector<u64> k0(2 * B, 0);
+    for (size_t k = 0; k < 2 * B; ++k) {
+        if (!in[k]) continue;
+        const CtPtr& x = in[k];
         if (x->npoly != 2) throw Error(FHELIN_ERR_STATE, "bootstrap: ciphertext must be relinearised");
         if (x->ell < 2) throw Error(FHELIN_ERR_STATE, "bootstrap: need at least two limbs to set the message scale (bootstrap one level earlier)");
+        k0[k] = (u64)llroundl(target * q1 / x->scale);
+        if (k0[k] < 2) throw Error(FHELIN_ERR_STATE, "bootstrap: ciphertext scale too large for the correction factor");
+    }
+    std::vector<CtPtr> xs(B);
+    std::vector<long double> rho(B), rho_b(B, 1);
+    if (n_pairs) {
+        std::vector<CtPtr> pa, pb;
+        std::vector<u64> ka, kb;
+        for (size_t i = 0; i < B; ++i)
+            if (in[2 * i + 1]) {
+                pa.push_back(in[2 * i]);
+                pb.push_back(in[2 * i + 1]);
+                ka.push_back(k0[2 * i]);
+                kb.push_back(k0[2 * i + 1]);
+            }
+        std::vector<CtPtr> packed = pack_pairs(pa, pb, ka, kb);
+        size_t k = 0;
+        for (size_t i = 0; i < B; ++i)
+            if (in[2 * i + 1]) xs[i] = packed[k++];
+    }
+    for (size_t i = 0; i < B; ++i) {
+        if (in[2 * i + 1]) {
+            // the partner's rho: what mod_raise would compute for it alone (the scale of rescale(k0_b b), times 2^correction / q0)
+            const CtPtr& y = in[2 * i + 1];
+            rho_b[i] = y->scale * (long double)k0[2 * i + 1] / q1 * two_corr / q0;
+            continue;
+        }
+        CtPtr x = in[2 * i];
         if (x->ell > 2) x = ev_.level_reduce(x, 2);
-        const u64 k0 = (u64)llroundl(target * q1 / x->scale);
-        if (k0 < 2) throw Error(FHELIN_ERR_STATE, "bootstrap: ciphertext scale too large for the correction factor");
-        xs[i] = ev_.mult_int(x, k0, true, x->scale * (long double)k0);
+        xs[i] = ev_.mult_int(x, k0[2 * i], true, x->scale * (long double)k0[2 * i]);
     }
     xs = ev_.rescale_batch(xs);
-    for (size_t i = 0; i < B; ++i) rho[i] = xs[i]->scale * (long double)(1ull << correction) / q0;
+    for (size_t i = 0; i < B; ++i) rho[i] = xs[i]->scale * two_corr / q0;
+    // ---- the shared core: ModRaise, SubSum, CoeffsToSlots, conjugation, EvalMod, SlotsToCoeffs
     c.stats.bootstrap += B;
     std::vector<CtPtr> w = ev_.raw_modraise_batch(xs, top_ell);
     for (CtPtr& u : w) {
@@ -543,16 +680,19 @@ std::vector<CtPtr> Bootstrapper::run_batch(const std::vector<CtPtr>& cts, int dr
         if (it == ev_.rot_keys.end()) throw Error(FHELIN_ERR_KEY, "bootstrap: SubSum rotation key missing");
         w = ev_.rotate_galois_batch(w, g, *it->second, true);     // u + sigma_g(u), the sum in the key switch's epilogue
     }
-    // ---- CoeffsToSlots, conjugation, EvalMod, SlotsToCoeffs
+    if (stop_after == 1) return w;
     for (const auto& st : c2s_) w = apply_batch(st, w);
     if (packed_)
         for (CtPtr& u : w) u->slots = 2 * slots_;
     std::vector<CtPtr> wc = ev_.conjugate_batch(w);
     std::vector<CtPtr> a = ev_.add_batch(w, wc);
+    if (stop_after == 2) return a;
     std::vector<CtPtr> v;
     if (packed_) {
         v = eval_mod(a);
+        if (stop_after == 3) return v;
     } else {
+        if (stop_after == 3) return eval_mod(a);
         std::vector<CtPtr> d = ev_.sub_batch(wc, w), all = a;
         for (const CtPtr& t : d) all.push_back(mult_i(t));
         std::vector<CtPtr> ab = eval_mod(all);
@@ -565,14 +705,77 @@ std::vector<CtPtr> Bootstrapper::run_batch(const std::vector<CtPtr>& cts, int dr
         if (packed_ && k == 0)
             for (CtPtr& u : v) u->slots = slots_;
     }
-    std::vector<CtPtr> out(B);
+    // ---- epilogue.  A single: the exact 2^correction, rho into the scale.  A pair: half of it, so that the slots hold (a + i b) / 2 and
+    // the split's sums come out at a and b themselves; its rhos go into the scales of the two halves
+    std::vector<CtPtr> fin(B);
     for (size_t i = 0; i < B; ++i) {
-        out[i] = ev_.mult_int(v[i], 1ull << correction, false, v[i]->scale);
-        out[i]->scale = out[i]->scale * rho[i];
+        const bool pair = (bool)items[i].b;
+        fin[i] = ev_.mult_int(v[i], 1ull << (pair ? correction - 1 : correction), false, v[i]->scale);
+        if (!pair) fin[i]->scale = fin[i]->scale * rho[i];
     }
-    if (out[0]->deg >= 2) out = ev_.rescale_batch(out);
-    for (size_t i = 0; i < B; ++i) out[i]->slots = cts[i]->slots > 0 ? cts[i]->slots : logical_slots_;
+    if (fin[0]->deg >= 2) fin = ev_.rescale_batch(fin);
+    std::vector<CtPtr> half_a, half_b;
+    if (n_pairs) {
+        std::vector<CtPtr> pv;
+        for (size_t i = 0; i < B; ++i)
+            if (items[i].b) pv.push_back(fin[i]);
+        split_pairs(pv, ev_.conjugate_batch(pv), half_a, half_b);
+    }
+    auto slots_of = [&](const CtPtr& ct) { return ct->slots > 0 ? ct->slots : logical_slots_; };
+    std::vector<CtPtr> out;
+    size_t k = 0;
+    for (size_t i = 0; i < B; ++i) {
+        if (!items[i].b) {
+            fin[i]->slots = slots_of(items[i].a);
+            out.push_back(fin[i]);
+            continue;
+        }
+        const long double s = fin[i]->scale;
+        half_a[k]->scale = s * rho[i];
+        half_b[k]->scale = s * rho_b[i];
+        half_a[k]->slots = slots_of(items[i].a);
+        half_b[k]->slots = slots_of(items[i].b);
+        out.push_back(half_a[k]);
+        out.push_back(half_b[k]);
+        ++k;
+    }
     return out;
+}
+
+std::vector<CtPtr> Bootstrapper::run_batch(const std::vector<CtPtr>& cts, int drop) {
+    std::vector<Item> items;
+    for (const CtPtr& ct : cts) items.push_back(Item{ct, CtPtr()});
+    return run_items(items, drop);
+}
+
+std::vector<CtPtr> Bootstrapper::bootstrap_pairs(const std::vector<CtPtr>& cts, int drop) {
+    if (cts.empty()) return {};
+    Context::PhysicalScope physical(ev_.ctx());
+    if (cts.size() == 1) return {run(cts[0], 0, drop)};
+    if (!ready()) throw Error(FHELIN_ERR_STATE, "EvalBootstrapSetup has not been called");
+    auto slots_of = [&](const CtPtr& ct) { return ct->slots > 0 ? ct->slots : logical_slots_; };
+    std::vector<Item> items;
+    for (size_t i = 0; i < cts.size(); i += 2) {
+        if (i + 1 < cts.size() && slots_of(cts[i]) == slots_of(cts[i + 1])) {
+            items.push_back(Item{cts[i], cts[i + 1]});
+            continue;
+        }
+        items.push_back(Item{cts[i], CtPtr()});
+        if (i + 1 < cts.size()) items.push_back(Item{cts[i + 1], CtPtr()});
+    }
+    return run_items(items, drop);   // item order is input order: two results per pair, one per single
+}
+
+std::pair<CtPtr, CtPtr> Bootstrapper::bootstrap_pair(const CtPtr& a, const CtPtr& b, int drop) {
+    Context::PhysicalScope physical(ev_.ctx());
+    std::vector<CtPtr> o = run_items({Item{a, b}}, drop);
+    return {o[0], o[1]};
+}
+
+CtPtr Bootstrapper::pair_partial(const CtPtr& a, const CtPtr& b, int stage) {
+    if (stage < 1 || stage > 3) throw Error(FHELIN_ERR_ARG, "bootstrap pair: stage must be 1, 2 or 3");
+    Context::PhysicalScope physical(ev_.ctx());
+    return run_items({Item{a, b}}, 0, stage)[0];
 }
 
 std::vector<CtPtr> Bootstrapper::bootstrap_batch(const std::vector<CtPtr>& cts, int drop) {

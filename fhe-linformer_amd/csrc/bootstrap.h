@@ -48,8 +48,22 @@ public:
     // both bootstraps as bootstrap_batch over all inputs; out[i] holds exactly the residues of bootstrap_iter(cts[i], p, drop)
     std::vector<CtPtr> bootstrap_iter_batch(const std::vector<CtPtr>& cts, int p, int drop = 0);
     static constexpr int MAX_ITER_PRECISION = 30;
+    // Paired bootstrapping: two ciphertexts with REAL slot values go through one pipeline as a + i b and are taken apart by
+    // one conjugation at the output level.  Consecutive inputs are paired, (0,1), (2,3), ...; an odd last input, and both inputs of a pair
+    // whose slot counts differ, travel in the same batched pipeline as singles (exactly the residues of bootstrap(ct, drop)).  Every
+    // output has the limbs, degree and nominal scale of bootstrap(cts[i], drop); correction == 0 leaves no bit for the 1/2 of the split
+    // (FHELIN_ERR_STATE).  The bootstrap counter advances once per pipeline.
+    std::vector<CtPtr> bootstrap_pairs(const std::vector<CtPtr>& cts, int drop = 0);
+    // a and b as one pair whatever else holds: unequal slot counts are FHELIN_ERR_ARG
+    std::pair<CtPtr, CtPtr> bootstrap_pair(const CtPtr& a, const CtPtr& b, int drop = 0);
     // debug / test hook: stop after stage 1 (ModRaise+SubSum), 2 (CoeffsToSlots, real part), 3 (EvalMod, real part)
     CtPtr partial(const CtPtr& ct, int stage);
+    CtPtr pair_partial(const CtPtr& a, const CtPtr& b, int stage);   // the same stages of the pair's one pipeline
+    // the two kernels of a paired bootstrap on their own (kernels_elem.h launch_ew_pair_pack / launch_ew_pair_split; the debug entries
+    // of include/fhelin.h reach them): out[i] = ka[i] a[i] + i kb[i] b[i] on the two bottom limbs, one block, degree a's + 1, scale
+    // a's x ka; and (w + wc, i (wc - w)) per pair of one shape, at w's degree, scale and slots
+    std::vector<CtPtr> pack_pairs(const std::vector<CtPtr>& a, const std::vector<CtPtr>& b, const std::vector<u64>& ka, const std::vector<u64>& kb);
+    void split_pairs(const std::vector<CtPtr>& w, const std::vector<CtPtr>& wc, std::vector<CtPtr>& out_a, std::vector<CtPtr>& out_b);
     int depth() const { return depth_; }
     int out_ell() const { return ev_.ctx().L + 1 - depth_; }   // limbs of the result when nothing is dropped
     // read-only views for the residue-level parity tests (include/fhelin.h fhelin_bootstrap_describe / _diag / _cheb): the
@@ -88,6 +102,15 @@ private:
     CtPtr run(const CtPtr& ct, int stop_after, int drop = 0);
     std::vector<CtPtr> apply_batch(const LinStage& st, const std::vector<CtPtr>& xs);
     std::vector<CtPtr> run_batch(const std::vector<CtPtr>& cts, int drop);
+    // one item of a batched pipeline: the single a, or (b set) the pair a + i b
+    struct Item {
+        CtPtr a, b;
+    };
+    // per-item prologue (message to q0 / 2^correction: integer multiply, or the pack of a pair), the shared core over all items, per-item
+    // epilogue (the exact 2^correction, or half of it and the split of a pair).  Results in item order, two per pair; stop_after > 0: one
+    // per item, the pipeline's state after that stage (partial())
+    std::vector<CtPtr> run_items(const std::vector<Item>& items, int drop, int stop_after = 0);
+    void ensure_mono_i();
 };
 
 }  // namespace fhelin

@@ -23,6 +23,7 @@ int capi_fail(int code, const std::string& msg) {
 fhelin_ctx::fhelin_ctx(const fhelin::Params& p) : ctx(p), ev(ctx), cl(ev, ctx.prm.seed_bytes), comp(ev, cl), boot(ev, cl) {
     if (const char* e = std::getenv("FHELIN_LAZY_ROWS")) lazy_rows = std::atoi(e) != 0;
     if (const char* e = std::getenv("FHELIN_LAZY_HEAVY")) lazy_heavy = std::atoi(e) != 0;
+    if (const char* e = std::getenv("FHELIN_BOOT_PAIRS")) boot_pairs = std::atoi(e) != 0;
 }
 
 #define NEED(x) if (!(x)) return capi_fail(FHELIN_ERR_ARG, "null argument")
@@ -176,6 +177,18 @@ int fhelin_ctx_set_stream(fhelin_ctx* c, void* hip_stream) {
 int fhelin_ctx_set_lazy_rows(fhelin_ctx* c, int32_t on) {
     if (!c) return capi_fail(FHELIN_ERR_ARG, "null context");
     c->lazy_rows = on != 0;
+    return FHELIN_OK;
+}
+
+int fhelin_ctx_set_bootstrap_pairing(fhelin_ctx* c, int32_t on) {
+    if (!c) return capi_fail(FHELIN_ERR_ARG, "null context");
+    c->boot_pairs = on != 0;
+    return FHELIN_OK;
+}
+
+int fhelin_ctx_bootstrap_pairing(fhelin_ctx* c, int32_t* on) {
+    if (!c || !on) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    *on = c->boot_pairs ? 1 : 0;
     return FHELIN_OK;
 }
 

@@ -206,10 +206,13 @@ void flush_heavy(fhelin_ctx* c, bool report) {
         for (size_t first = 0; first < ready.size(); ++first) {
             if (taken[first]) continue;
             LazyHeavy& f = *ready[first];
+            // pairing on: the single bootstraps of one planned drop that are ready together share ONE paired pipeline, in call order,
+            // whatever their limbs and degree (the pipeline reads two limbs of each)
+            const bool paired = c->boot_pairs && f.kind == LazyHeavy::Boot && f.precision == 0;
             std::vector<LazyHeavy*> grp;
             for (size_t k = first; k < ready.size(); ++k) {
                 LazyHeavy& g = *ready[k];
-                const bool same = !taken[k] && g.kind == f.kind && g.in->ell == f.in->ell && g.in->deg == f.in->deg &&
+                const bool same = !taken[k] && g.kind == f.kind && (paired || (g.in->ell == f.in->ell && g.in->deg == f.in->deg)) &&
                                   g.in->npoly == f.in->npoly &&
                                   (f.kind == LazyHeavy::Boot ? g.drop == f.drop && g.precision == f.precision : (g.a == f.a && g.b == f.b && g.coeffs == f.coeffs));
                 if (same) {
@@ -222,6 +225,7 @@ void flush_heavy(fhelin_ctx* c, bool report) {
                 for (LazyHeavy* g : grp) in.push_back(g->in);
                 CtVec out = f.kind != LazyHeavy::Boot ? c->ev.eval_chebyshev_many(in, f.coeffs, f.a, f.b)
                             : f.precision > 0         ? c->boot.bootstrap_iter_batch(in, f.precision, f.drop)
+                            : paired                  ? c->boot.bootstrap_pairs(in, f.drop)
                                                       : c->boot.bootstrap_batch(in, f.drop);
                 for (size_t k = 0; k < grp.size(); ++k) {
                     grp[k]->result = out[k];
@@ -861,6 +865,76 @@ int fhelin_bootstrap_drop(fhelin_ctx* c, const fhelin_ct* a, int32_t drop, fheli
     NEED(c && a && out);
     FHELIN_TRY
     *out = wrap(c, c->boot.bootstrap(ct_in(c, a), drop));
+    FHELIN_CATCH
+}
+// ---- paired bootstrapping (include/fhelin.h "Paired bootstrapping")
+// outs of one call as sources of the level plan, in call order from first_ordinal
+static void emit_sources(fhelin_ctx* c, const CtVec& r, int first_ordinal, fhelin_ct** outs) {
+    plan_inputs().clear();
+    for (size_t i = 0; i < r.size(); ++i) {
+        outs[i] = wrap(c, r[i]);
+        if (c->plan.live(outs[i]->node, outs[i]->node_epoch)) c->plan.nodes[outs[i]->node].ordinal = first_ordinal + (int)i;
+    }
+}
+int fhelin_bootstrap_pair(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, fhelin_ct** out_a, fhelin_ct** out_b) {
+    NEED(c && a && b && out_a && out_b);
+    FHELIN_TRY
+    const CtPtr x = ct_in(c, a), y = ct_in(c, b);
+    // two sources of the level plan, a's first; one pipeline serves both, so it raises to what the larger target asks for
+    const int da = c->plan.next_drop(c->boot.out_ell()), db = c->plan.next_drop(c->boot.out_ell());
+    for (const fhelin_ct* h : {a, b})
+        if (c->plan.live(h->node, h->node_epoch)) c->plan.terminal(h->node, 2);
+    const std::pair<CtPtr, CtPtr> o = c->boot.bootstrap_pair(x, y, std::min(da, db));
+    fhelin_ct* outs[2];
+    emit_sources(c, CtVec{o.first, o.second}, c->plan.next_ordinal - 2, outs);
+    *out_a = outs[0];
+    *out_b = outs[1];
+    FHELIN_CATCH
+}
+int fhelin_bootstrap_paired_batch(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, fhelin_ct** outs) {
+    NEED(c && v && outs && n >= 0);
+    FHELIN_TRY
+    // as fhelin_bootstrap_batch: every ciphertext is a source of the level plan of its own (call order); those with the same planned
+    // drop share a pipeline and are paired inside it
+    CtVec in = vec_of(c, v, n);
+    std::vector<int> drop(n);
+    for (int i = 0; i < n; ++i) {
+        drop[i] = c->plan.next_drop(c->boot.out_ell());
+        if (c->plan.live(v[i]->node, v[i]->node_epoch)) c->plan.terminal(v[i]->node, 2);
+    }
+    const int first_ordinal = c->plan.next_ordinal - n;
+    CtVec r(n);
+    std::vector<char> done(n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (done[i]) continue;
+        std::vector<int> pick;
+        CtVec sub;
+        for (int k = i; k < n; ++k)
+            if (!done[k] && drop[k] == drop[i]) {
+                pick.push_back(k);
+                sub.push_back(in[k]);
+                done[k] = 1;
+            }
+        CtVec o = c->boot.bootstrap_pairs(sub, drop[i]);
+        for (size_t k = 0; k < pick.size(); ++k) r[pick[k]] = o[k];
+    }
+    emit_sources(c, r, first_ordinal, outs);
+    FHELIN_CATCH
+}
+int fhelin_bootstrap_pair_drop(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, int32_t drop, fhelin_ct** out_a, fhelin_ct** out_b) {
+    NEED(c && a && b && out_a && out_b);
+    FHELIN_TRY
+    const CtPtr x = ct_in(c, a), y = ct_in(c, b);
+    const std::pair<CtPtr, CtPtr> o = c->boot.bootstrap_pair(x, y, drop);
+    *out_a = wrap(c, o.first);
+    *out_b = wrap(c, o.second);
+    FHELIN_CATCH
+}
+int fhelin_bootstrap_pair_partial(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, int32_t stage, fhelin_ct** out) {
+    NEED(c && a && b && out);
+    FHELIN_TRY
+    const CtPtr x = ct_in(c, a), y = ct_in(c, b);
+    *out = wrap(c, c->boot.pair_partial(x, y, stage));
     FHELIN_CATCH
 }
 static void check_precision(int32_t precision) {

@@ -1,6 +1,7 @@
 // extern "C" boundary, test-only part: the plaintext inner-product kernels (kernels_elem.h launch_ew_dot, launch_ew_dot_groups,
-// launch_ew_cyclic_dot, launch_ew_window_dot) reached directly, with operands the caller chooses residue by residue.  Thin forwards to the
-// Evaluator methods as they stand: nothing here is on a driver's path.
+// launch_ew_cyclic_dot, launch_ew_window_dot) and the two kernels of a paired bootstrap (launch_ew_pair_pack, launch_ew_pair_split) reached
+// directly, with operands the caller chooses residue by residue.  Thin forwards to the Evaluator / Bootstrapper methods as they stand:
+// nothing here is on a driver's path.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -214,6 +215,43 @@ int fhelin_debug_ks_accq(fhelin_ctx* c, const uint64_t* digits, const uint64_t* 
     c->ev.debug_ks_accq(ext, down, dconv, ell, batch, index, res);
     hip_check(hipMemcpyAsync(out, res, no * 8, hipMemcpyDeviceToHost, x.stream), "debug_ks_accq download");
     x.sync();
+    FHELIN_CATCH
+}
+
+int fhelin_debug_pair_pack(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct* const* b, const uint64_t* k0_a, const uint64_t* k0_b,
+                           int32_t n, fhelin_ct** outs) {
+    NEED(c && a && b && k0_a && k0_b && outs);
+    FHELIN_TRY
+    c->ctx.require_device();
+    if (n < 1 || n > EwPairPack::MAX_PAIRS) throw Error(FHELIN_ERR_ARG, "debug_pair_pack: 1 to 32 pairs");
+    std::vector<CtPtr> va(n), vb(n);
+    for (int i = 0; i < n; ++i) {
+        if (!a[i] || !b[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
+        va[i] = ct_in(c, a[i]);
+        vb[i] = ct_in(c, b[i]);
+    }
+    const std::vector<CtPtr> o = c->boot.pack_pairs(va, vb, std::vector<u64>(k0_a, k0_a + n), std::vector<u64>(k0_b, k0_b + n));
+    for (int i = 0; i < n; ++i) outs[i] = wrap(c, o[i]);
+    FHELIN_CATCH
+}
+
+int fhelin_debug_pair_split(fhelin_ctx* c, const fhelin_ct* const* w, const fhelin_ct* const* wc, int32_t n, fhelin_ct** out_a,
+                            fhelin_ct** out_b) {
+    NEED(c && w && wc && out_a && out_b);
+    FHELIN_TRY
+    c->ctx.require_device();
+    if (n < 1 || n > EwPairSplit::MAX_PAIRS) throw Error(FHELIN_ERR_ARG, "debug_pair_split: 1 to 32 pairs");
+    std::vector<CtPtr> vw(n), vc(n), oa, ob;
+    for (int i = 0; i < n; ++i) {
+        if (!w[i] || !wc[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
+        vw[i] = ct_in(c, w[i]);
+        vc[i] = ct_in(c, wc[i]);
+    }
+    c->boot.split_pairs(vw, vc, oa, ob);
+    for (int i = 0; i < n; ++i) {
+        out_a[i] = wrap(c, oa[i]);
+        out_b[i] = wrap(c, ob[i]);
+    }
     FHELIN_CATCH
 }
 

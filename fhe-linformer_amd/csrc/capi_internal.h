@@ -132,6 +132,7 @@ struct fhelin_ctx {
     fhelin::Bootstrapper boot;
     bool lazy_rows = true;      // FHELIN_LAZY_ROWS
     bool lazy_heavy = true;     // FHELIN_LAZY_HEAVY
+    bool boot_pairs = false;    // FHELIN_BOOT_PAIRS / fhelin_ctx_set_bootstrap_pairing: deferred single bootstraps go through Bootstrapper::bootstrap_pairs
     // deferred operations, per lane: a lane's pending operations are evaluated on that lane's stream (fhelin_ctx_set_lane)
     std::vector<std::shared_ptr<fhelin::LazyHeavy>> pending_heavy[fhelin::DevicePool::MAX_LANES];
     bool any_pending() const {

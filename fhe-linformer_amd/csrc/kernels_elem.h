@@ -99,6 +99,34 @@ struct EwScalarItems {
     const u64* a[MAX_ITEMS];
 };
 void launch_ew_scalar_items(const DeviceTables& t, const EwScalarItems& d, u64* out, const u64* consts, hipStream_t s);
+// ---- paired bootstrapping (Bootstrapper::bootstrap_pairs): two real ciphertexts travel as a + i b
+// pack: for up to MAX_PAIRS pairs in ONE launch, both polynomials and the two bottom limbs,
+//     out[i][c][l] = (ka_{i,l} * a_i[c][l] + mono_i[l] * (kb_{i,l} * b_i[c][l])) mod q_l,   c < 2, l < 2
+// a_i: [2][ell_a[i]][N], b_i: [2][ell_b[i]][N] with ell >= 2, read in place (the limbs above the second are not touched); out: one dense block
+// [n][2][2][N]; mono_i: [>= 2][N], the NTT of X^(N/2) (multiplication by i); consts: device array [n][2][4] = (ka, shoup(ka), kb, shoup(kb))
+// per pair and limb, the integers already reduced.  Canonical output: the residues of add(mult_int(a, ka), mult_i(mult_int(b, kb))).
+struct EwPairPack {
+    static constexpr int MAX_PAIRS = 32;
+    int n = 0;
+    int ell_a[MAX_PAIRS];
+    int ell_b[MAX_PAIRS];
+    const u64* a[MAX_PAIRS];
+    const u64* b[MAX_PAIRS];
+};
+void launch_ew_pair_pack(const DeviceTables& t, const EwPairPack& d, u64* out, const u64* mono_i, const u64* consts, hipStream_t s);
+// split: for up to MAX_PAIRS pairs of identical shape [2][ell][N] in ONE launch, w the bootstrapped a + i b (halved) and wc its conjugate,
+//     a_i = (w_i + wc_i) mod q_l,     b_i = mono_i[l] * (wc_i - w_i) mod q_l
+// two reads and two writes per residue where add, sub and mult_i are three launches with an intermediate.  Canonical output.
+struct EwPairSplit {
+    static constexpr int MAX_PAIRS = 32;
+    int n = 0;
+    int ell = 0;
+    const u64* w[MAX_PAIRS];
+    const u64* wc[MAX_PAIRS];
+    u64* a[MAX_PAIRS];
+    u64* b[MAX_PAIRS];
+};
+void launch_ew_pair_split(const DeviceTables& t, const EwPairSplit& d, const u64* mono_i, hipStream_t s);
 // out[v] = sum_i a_i[v] * b_i[v % b_vecs] over the n items (n <= MAX_ITEMS): an inner product of ciphertexts with plaintexts in
 // one pass (the diagonal sums of the bootstrapping linear transforms, wrapUpRepeated, matmulCRlarge) instead of n product
 // launches and a tree of additions.  128-bit accumulation, one reduction: the canonical residue of the sum - 32 products below 2^120 each

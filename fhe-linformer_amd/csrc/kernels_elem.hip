@@ -503,6 +503,62 @@ __global__ __launch_bounds__(256) void ew_scaled_diff_kernel(DeviceTables t, EwS
     reinterpret_cast<u64x2*>(d.out[item])[at] = r;
 }
 
+// The block of a paired-bootstrap kernel: grid (N/512, items * 2 * ell).  In XCD-aware order (logical id = (limb, tile, item x component),
+// the last fastest, contiguous id ranges per XCD) the blocks that read one tile of mono_i run back to back on one XCD: the tile comes
+// from HBM once per launch, every other operand is read once anyway.
+struct PairBlock {
+    int item, comp, limb;
+    size_t n2;
+};
+__device__ __forceinline__ PairBlock pair_block(int items) {
+    const unsigned nx = gridDim.x, nblk = gridDim.x * gridDim.y;
+    unsigned id = blockIdx.y * nx + blockIdx.x;
+    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);
+    const unsigned per = 2u * (unsigned)items, sub = id % per, rest = id / per;
+    PairBlock b;
+    b.item = (int)(sub >> 1);
+    b.comp = (int)(sub & 1);
+    b.limb = (int)(rest / nx);
+    b.n2 = (size_t)(rest % nx) * 256 + threadIdx.x;
+    return b;
+}
+
+// out[i][c][l] = ka_{i,l} * a_i[c][l] + mono_i[l] * (kb_{i,l} * b_i[c][l])  for l < 2: the two bottom limbs of both inputs read in place
+// (polynomials ell_a[i] / ell_b[i] limbs apart), the four constants of (pair, limb) wave-uniform.  Canonical output.
+__global__ __launch_bounds__(256) void ew_pair_pack_kernel(DeviceTables t, EwPairPack d, u64* __restrict__ out, const u64* __restrict__ mono_i,
+                                                           const u64* __restrict__ consts) {
+    const PairBlock p = pair_block(d.n);
+    const Barrett br = load_barrett(t, p.limb);
+    const u64* k = consts + ((size_t)p.item * 2 + p.limb) * 4;
+    const u64 ka = k[0], kas = k[1], kb = k[2], kbs = k[3];
+    const size_t row = ((size_t)1 << t.log_n) >> 1;
+    const u64x2 x = reinterpret_cast<const u64x2*>(d.a[p.item])[((size_t)p.comp * d.ell_a[p.item] + p.limb) * row + p.n2];
+    const u64x2 y = reinterpret_cast<const u64x2*>(d.b[p.item])[((size_t)p.comp * d.ell_b[p.item] + p.limb) * row + p.n2];
+    const u64x2 m = reinterpret_cast<const u64x2*>(mono_i)[(size_t)p.limb * row + p.n2];
+    u64x2 r;
+    r.x = add_mod(mul_shoup(x.x, ka, kas, br.q), mul_mod(mul_shoup(y.x, kb, kbs, br.q), m.x, br), br.q);
+    r.y = add_mod(mul_shoup(x.y, ka, kas, br.q), mul_mod(mul_shoup(y.y, kb, kbs, br.q), m.y, br), br.q);
+    reinterpret_cast<u64x2*>(out)[(((size_t)p.item * 2 + p.comp) * 2 + p.limb) * row + p.n2] = r;
+}
+
+// a_i = w_i + wc_i,  b_i = mono_i * (wc_i - w_i)  over ell limbs: two reads and two writes per residue.  Canonical output.
+__global__ __launch_bounds__(256) void ew_pair_split_kernel(DeviceTables t, EwPairSplit d, const u64* __restrict__ mono_i) {
+    const PairBlock p = pair_block(d.n);
+    const Barrett br = load_barrett(t, p.limb);
+    const size_t row = ((size_t)1 << t.log_n) >> 1;
+    const size_t at = ((size_t)p.comp * d.ell + p.limb) * row + p.n2;
+    const u64x2 w = reinterpret_cast<const u64x2*>(d.w[p.item])[at];
+    const u64x2 c = reinterpret_cast<const u64x2*>(d.wc[p.item])[at];
+    const u64x2 m = reinterpret_cast<const u64x2*>(mono_i)[(size_t)p.limb * row + p.n2];
+    u64x2 ra, rb;
+    ra.x = add_mod(w.x, c.x, br.q);
+    ra.y = add_mod(w.y, c.y, br.q);
+    rb.x = mul_mod(sub_mod(c.x, w.x, br.q), m.x, br);
+    rb.y = mul_mod(sub_mod(c.y, w.y, br.q), m.y, br);
+    reinterpret_cast<u64x2*>(d.a[p.item])[at] = ra;
+    reinterpret_cast<u64x2*>(d.b[p.item])[at] = rb;
+}
+
 // out[v] = a[v] + s[limb]   (adds a constant to every NTT slot == adds the constant polynomial)
 // add_vecs: only the first add_vecs vectors (component 0 of a ciphertext) get the constant, the others are copied through
 __global__ __launch_bounds__(256) void ew_addscalar_kernel(DeviceTables t, u64* out, const u64* a, ScalarSet sc, int limb_first,
@@ -820,6 +876,16 @@ void launch_ew_scalar_items(const DeviceTables& t, const EwScalarItems& d, u64* 
 void launch_ew_scaled_diff(const DeviceTables& t, const EwScaledDiff& d, const u64* consts, hipStream_t s) {
     if (d.n <= 0 || d.vecs <= 0 || d.ell <= 0) return;
     hipLaunchKernelGGL(ew_scaled_diff_kernel, grid2(t.log_n, d.n * d.vecs), dim3(256), 0, s, t, d, consts);
+}
+void launch_ew_pair_pack(const DeviceTables& t, const EwPairPack& d, u64* out, const u64* mono_i, const u64* consts, hipStream_t s) {
+    if (d.n <= 0 || d.n > EwPairPack::MAX_PAIRS || t.n_limbs < 2) return;
+    for (int i = 0; i < d.n; ++i)
+        if (d.ell_a[i] < 2 || d.ell_b[i] < 2) return;   // callers check (Bootstrapper::pack_pairs)
+    hipLaunchKernelGGL(ew_pair_pack_kernel, grid2(t.log_n, d.n * 4), dim3(256), 0, s, t, d, out, mono_i, consts);
+}
+void launch_ew_pair_split(const DeviceTables& t, const EwPairSplit& d, const u64* mono_i, hipStream_t s) {
+    if (d.n <= 0 || d.n > EwPairSplit::MAX_PAIRS || d.ell <= 0 || d.ell > t.n_limbs) return;
+    hipLaunchKernelGGL(ew_pair_split_kernel, grid2(t.log_n, d.n * 2 * d.ell), dim3(256), 0, s, t, d, mono_i);
 }
 void launch_ew_addscalar(const DeviceTables& t, u64* out, const u64* a, const ScalarSet& sc, int nvec, int limb_first, int limb_count, hipStream_t s,
                          int add_vecs) {

@@ -59,10 +59,15 @@ def _keep_mask(keep_slots):
 class GpuController:
     """The reference's FHEController surface on top of fhe_linformer_amd.Engine."""
 
-    def __init__(self, eng, verbose=False):
+    def __init__(self, eng, verbose=False, pair_bootstraps=False):
         self.e, self.verbose = eng, verbose
         self.num_slots = SLOTS
         self.n_boot = 0
+        # bootstraps of real ciphertexts that are ready together travel two per pipeline (Engine.set_bootstrap_pairing; off: the engine's
+        # setting, FHELIN_BOOT_PAIRS, stays as it is)
+        self.pair_bootstraps = bool(pair_bootstraps)
+        if self.pair_bootstraps:
+            eng.set_bootstrap_pairing(True)
 
     # handles
     def level(self, c):
@@ -315,10 +320,13 @@ class BatchedController:
     of a sample run in batches of 2B, 5B and B.  Sample x ends in EXACTLY the residues its own single pass gives
     (tests/test_batched_forward_gpu.py).  All samples of a batch have one token count."""
 
-    def __init__(self, eng, B, verbose=False):
+    def __init__(self, eng, B, verbose=False, pair_bootstraps=False):
         self.e, self.B, self.verbose = eng, int(B), verbose
         self.num_slots = SLOTS
         self.n_boot = 0
+        self.pair_bootstraps = bool(pair_bootstraps)   # as GpuController's
+        if self.pair_bootstraps:
+            eng.set_bootstrap_pairing(True)
 
     # ---- layout helpers: a list of n Batches <-> the flat sample-major handle list the C ABI takes
     def _flat(self, rows):
@@ -421,6 +429,8 @@ class BatchedController:
             return Batch(self.e.bootstrap_iter_batch(list(a), precision))
         if self.e.lazy_heavy:
             return Batch(self.e.bootstrap(h) for h in a)
+        if self.pair_bootstraps:
+            return Batch(self.e.bootstrap_paired_batch(list(a)))
         return Batch(self.e.bootstrap_batch(list(a)))
 
     # composites: same names as the reference
@@ -499,10 +509,10 @@ class LanedBatchedController:
 
     _ONCE = ("level", "encode", "read_plain_input", "read_plain_repeated_input", "read_plain_expanded_input")
 
-    def __init__(self, eng, B, lanes=2):
+    def __init__(self, eng, B, lanes=2, pair_bootstraps=False):
         assert B % lanes == 0 and lanes >= 1
         self.e, self.B, self.lanes, self.h = eng, B, lanes, B // lanes
-        self.sub = [BatchedController(eng, self.h) for _ in range(lanes)]
+        self.sub = [BatchedController(eng, self.h, pair_bootstraps=pair_bootstraps) for _ in range(lanes)]
         self.num_slots = SLOTS
 
     @property

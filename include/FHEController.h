@@ -502,6 +502,9 @@ public:
         if (timing) print_duration(start, "Bootstrapping " + to_string(c->GetSlots()) + " slots");
         return wrap(o);
     }
+    // paired bootstrapping (include/fhelin.h fhelin_ctx_set_bootstrap_pairing; off by default), once the context exists: bootstrap(c) calls on
+    // real ciphertexts that are evaluated together travel two per pipeline
+    void set_bootstrap_pairing(bool on) { fhelin_shim::check(fhelin_ctx_set_bootstrap_pairing(context, on ? 1 : 0), "SetBootstrapPairing"); }
     // EvalBootstrap(c, 2, precision): the iterative bootstrap (include/fhelin.h fhelin_bootstrap_iter), one limb fewer than bootstrap(c)
     Ctxt bootstrap(const Ctxt& c, int precision, bool timing = false) {
         if (static_cast<int>(c->GetLevel()) + 2 < circuit_depth)

@@ -76,6 +76,7 @@ public:
     /* interleaved samples (FHEController::set_interleave on the single controller before its context exists): every batch entry carries
      * `stride` samples.  encrypt_interleaved: per batch entry one vector per sample; decrypt_tovector_lanes: [entry][sample][slots] */
     void set_interleave(int stride) { c_.set_interleave(stride); }
+    void set_bootstrap_pairing(bool on) { c_.set_bootstrap_pairing(on); }   // FHEController::set_bootstrap_pairing
     CtxtBatch encrypt_interleaved(const vector<vector<vector<double>>>& samples_per_entry, int level = 0, int plaintext_num_slots = 0) {
         need_B(samples_per_entry.size());
         vector<Ctxt> v;

@@ -393,6 +393,17 @@ int fhelin_debug_ks_accp(fhelin_ctx* c, const uint64_t* digits, int32_t ell, int
  * (coefficient form) canonical. */
 int fhelin_debug_ks_accq(fhelin_ctx* c, const uint64_t* digits, const uint64_t* own, const uint64_t* conv, int32_t ell, int32_t batch,
                          int32_t index, uint64_t* out /* [batch][2][ell][N] */);
+/* The two kernels of a paired bootstrap on their own, over n <= 32 pairs of (imported) ciphertexts in ONE launch each; they need no key
+ * and no bootstrap set-up.
+ *   pack:  outs[i] = (k0_a[i] a[i] + X^(N/2) k0_b[i] b[i]) mod q_l on the two bottom limbs l < 2 of both components; a[i], b[i] with two
+ *          components and any limb count >= 2 (FHELIN_ERR_STATE otherwise), read in place; k0 any 64-bit integers, reduced per limb.
+ *          outs[i]: 2 limbs, a[i]'s degree + 1, scale a[i]'s x k0_a[i].
+ *   split: out_a[i] = w[i] + wc[i], out_b[i] = X^(N/2) (wc[i] - w[i]) mod q_l over all limbs; all operands of one shape (FHELIN_ERR_STATE
+ *          otherwise); degree, scale and slots of w[i]. */
+int fhelin_debug_pair_pack(fhelin_ctx* c, const fhelin_ct* const* a, const fhelin_ct* const* b, const uint64_t* k0_a, const uint64_t* k0_b,
+                           int32_t n, fhelin_ct** outs);
+int fhelin_debug_pair_split(fhelin_ctx* c, const fhelin_ct* const* w, const fhelin_ct* const* wc, int32_t n, fhelin_ct** out_a,
+                            fhelin_ct** out_b);
 
 /* ---- FHEController composite circuit ops (callers of the hot path) --------
  * One entry point per reference method; `vector<Ctxt>` travels as (array of handles, count); outputs are
@@ -507,6 +518,33 @@ int fhelin_bootstrap_iter_batch(fhelin_ctx* c, const fhelin_ct* const* v, int32_
 /* test hook: fhelin_bootstrap_iter with both bootstraps raising to L+1-drop limbs (fhelin_bootstrap_drop); a drop that leaves a
  * single bootstrap fewer than 3 limbs is FHELIN_ERR_STATE */
 int fhelin_bootstrap_iter_drop(fhelin_ctx* c, const fhelin_ct* a, int32_t precision, int32_t drop, fhelin_ct** out);
+/* Paired bootstrapping: two ciphertexts whose slot values are REAL are refreshed by ONE bootstrap, as a + i b, and taken
+ * apart by one conjugation at the output level.  The engine's definition, residue-exact (corr = the correction of fhelin_bootstrap_config,
+ * target = q_0 / 2^corr): for x in {a, b} (rescaled first if degree 2, two components, >= 2 limbs, equal slot counts) k0_x =
+ * round(target q_1 / scale_x) and rho_x = (scale_x k0_x / q_1) 2^corr / q_0, exactly as fhelin_bootstrap computes them for x alone;
+ * p = rescale(k0_a a + i k0_b b) on the two bottom limbs; the pipeline of fhelin_bootstrap from ModRaise on; v = 2^(corr-1) v (half of
+ * the single bootstrap's exact 2^corr: the slots hold (a + i b) / 2 and no level is spent on the 1/2), rescaled if degree 2;
+ * out_a = v + conj(v) at scale scale_v rho_a, out_b = i (conj(v) - v) at scale scale_v rho_b.  Both have the limbs, degree and nominal
+ * scale of fhelin_bootstrap(a) / fhelin_bootstrap(b).  The inputs' imaginary parts must be zero (every ciphertext the drivers make): an
+ * imaginary part of b would land in out_a.  No new key: the conjugation key of fhelin_bootstrap_setup (stored in evaluation-key sets).
+ * Errors: as fhelin_bootstrap, plus unequal slot counts FHELIN_ERR_ARG and correction 0 FHELIN_ERR_STATE.  The `bootstrap` counter of
+ * fhelin_stats advances by one per pipeline.  Each output is a source of the level plan of its own (a first); the pipeline raises to
+ * the limbs the larger of the two planned targets asks for. */
+int fhelin_bootstrap_pair(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, fhelin_ct** out_a, fhelin_ct** out_b);
+/* n ciphertexts through ONE batched pipeline of ceil(n / 2) bootstraps: consecutive inputs are paired, (0,1), (2,3), ...; an odd last
+ * input, and both inputs of a pair whose slot counts differ, travel in the same pipeline as singles and come out with exactly the
+ * residues of fhelin_bootstrap.  Level plan as in fhelin_bootstrap_batch: every output is a source of its own in call order; inputs with
+ * different planned drops are grouped by drop first and paired inside their group. */
+int fhelin_bootstrap_paired_batch(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, fhelin_ct** outs);
+/* test hooks: fhelin_bootstrap_pair raising to L+1-drop limbs only; and the pair's pipeline stopped after stage 1 (pack + ModRaise +
+ * SubSum), 2 (CoeffsToSlots + conjugation, real part) or 3 (approximate mod), as fhelin_bootstrap_partial */
+int fhelin_bootstrap_pair_drop(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, int32_t drop, fhelin_ct** out_a, fhelin_ct** out_b);
+int fhelin_bootstrap_pair_partial(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, int32_t stage, fhelin_ct** out);
+/* Runtime knob, off by default (FHELIN_BOOT_PAIRS=1 turns it on at context creation): deferred fhelin_bootstrap calls (not the iterative
+ * ones) of one lane and one planned drop that are ready together are evaluated through the paired pipeline, in call order, as
+ * fhelin_bootstrap_paired_batch would.  The results are bootstraps of the same values with different residues; off, nothing changes. */
+int fhelin_ctx_set_bootstrap_pairing(fhelin_ctx* c, int32_t on);
+int fhelin_ctx_bootstrap_pairing(fhelin_ctx* c, int32_t* on);
 /* ---- read-only views of the bootstrapping set-up: the residue-level oracle (oracle/residue_boot.py, tests only) composes
  * EvalBootstrap (:445) from the same linear stages, Chebyshev coefficients and keys and must reach the same residues.
  * describe: out = {packed, slots, K, R, cheb_degree, correction, depth, n_c2s, n_s2c, then per stage (CoeffsToSlots stages
