@@ -207,8 +207,9 @@ class ResidueEvaluator:
         k = (tuple(id(e) for e in encs), float(sf), float(sf - LD(float(sf))))
         if k not in self._full:           # the same few plaintexts serve every row of a call
             self._full.clear()
-            self._full[k] = np.stack([e(nl, sf) for e in encs])
-        d = orc.hoisted_dot(x.d, self._stack(indices), [self._g(r) for r in indices], self._full[k], self.alpha, self.q, self.p,
+            # the entry holds its encoders: while it lives none of them is collected, so no later callable can take one's id
+            self._full[k] = (tuple(encs), np.stack([e(nl, sf) for e in encs]))
+        d = orc.hoisted_dot(x.d, self._stack(indices), [self._g(r) for r in indices], self._full[k][1], self.alpha, self.q, self.p,
                             self.psi_q, self.psi_p, drop=rescale)
         if rescale:
             return RCt(d, x.deg, x.scale * sf / LD(int(self.q[x.ell - 1])))

@@ -29,6 +29,11 @@ ACCEPTED = [
     ("toy", dict(log_n=17, n_q=64, dnum=16, n_p=16, first_bits=60, scale_bits=59, log_slots=16), 4, 16, 16),
     ("reference", dict(n_q=6, n_p=2, dnum=3, first_bits=60, scale_bits=59), 2, 3, 2),
     ("toy", dict(n_q=2, scale_bits=60), 1, 2, 2),      # one scaling prime, the largest below 2^60: the limit is on the primes
+    # the chains tests/test_kernel_corners_gpu.py adds
+    ("toy", dict(n_q=16, dnum=16, first_bits=60, scale_bits=59), 1, 16, 2),     # 16 digits of 59/60-bit residues
+    ("toy", dict(n_q=20, dnum=10), 2, 10, 2),                                   # more than 8 digits with alpha > 1
+    ("toy", dict(n_q=8, dnum=8, first_bits=60, scale_bits=59), 1, 8, 2),        # eight digits of 59/60-bit residues
+    ("toy", dict(n_p=8), 2, 3, 8),
 ]
 
 REFUSED = [
