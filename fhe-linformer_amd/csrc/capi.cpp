@@ -168,9 +168,7 @@ int fhelin_ctx_set_stream(fhelin_ctx* c, void* hip_stream) {
     c->ctx.require_device();
     c->ctx.sync();
     if (c->ctx.own_stream && c->ctx.main_stream) hip_check(hipStreamDestroy(c->ctx.main_stream), "hipStreamDestroy");
-    c->ctx.stream = c->ctx.main_stream = (hipStream_t)hip_stream;
-    c->ctx.pool.lane_stream[0] = c->ctx.main_stream;
-    c->ctx.own_stream = false;
+    c->ctx.set_main_stream((hipStream_t)hip_stream);
     FHELIN_CATCH
 }
 
@@ -255,8 +253,7 @@ int fhelin_ctx_set_lane(fhelin_ctx* c, int32_t lane) {
     c->ctx.require_device();
     if (lane < 0 || lane > c->ctx.n_lanes) throw Error(FHELIN_ERR_ARG, "set_lane: the context has lanes 0.." + std::to_string(c->ctx.n_lanes));
     c->user_lane = lane;
-    c->ctx.stream = lane == 0 ? c->ctx.main_stream : c->ctx.lane_stream[lane];
-    c->ctx.pool.cur_lane = lane;
+    c->ctx.select_lane(lane);
     FHELIN_CATCH
 }
 int fhelin_ctx_lane_wait(fhelin_ctx* c, int32_t from_lane) {
@@ -266,21 +263,7 @@ int fhelin_ctx_lane_wait(fhelin_ctx* c, int32_t from_lane) {
     if (from_lane < 0 || from_lane > c->ctx.n_lanes) throw Error(FHELIN_ERR_ARG, "lane_wait: no such lane");
     if (from_lane != c->ctx.pool.cur_lane) {
         // what was DEFERRED under that lane is issued there first, then this lane's stream goes behind everything queued on it
-        if (!c->pending_heavy[from_lane].empty()) {
-            const int cur = c->ctx.pool.cur_lane;
-            hipStream_t cur_stream = c->ctx.stream;
-            c->ctx.stream = from_lane == 0 ? c->ctx.main_stream : c->ctx.lane_stream[from_lane];
-            c->ctx.pool.cur_lane = from_lane;
-            try {
-                flush_heavy(c);
-            } catch (...) {
-                c->ctx.stream = cur_stream;
-                c->ctx.pool.cur_lane = cur;
-                throw;
-            }
-            c->ctx.stream = cur_stream;
-            c->ctx.pool.cur_lane = cur;
-        }
+        if (!c->pending_heavy[from_lane].empty()) flush_lane(c, from_lane);
         wait_for_lane(c, from_lane);
     }
     FHELIN_CATCH

@@ -403,7 +403,7 @@ void fhelin_ct_free(fhelin_ct* ct) { delete ct; }
         FHELIN_TRY                                                                          \
         const fhelin_ct* both[2] = {a, b};                                                  \
         force_many(c, both, 2); /* deferred operands of one group: one batched call */      \
-        *out = wrap(c, expr);                                                                  \
+        *out = wrap(c, expr);                                                               \
         FHELIN_CATCH                                                                        \
     }
 int fhelin_add(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, fhelin_ct** out) {
@@ -411,7 +411,7 @@ int fhelin_add(fhelin_ctx* c, const fhelin_ct* a, const fhelin_ct* b, fhelin_ct*
     FHELIN_TRY
     const fhelin_ct* both[2] = {a, b};
     // deferred rows among the operands are evaluated now (their own batching rules apply); the SUM is deferred: additions issued
-    // in a loop over independent rows are aligned and added as one batch when a result is first read (capi_internal.h LazyHeavy)
+    // in a loop over independent rows are aligned and added as one batch when a result is first read (deferred.h LazyHeavy)
     for (const fhelin_ct* h : both)
         if (!h->p && h->lazy) force(c, h);
     if (defer_allowed(c)) {
@@ -461,12 +461,7 @@ int fhelin_rotate_many(fhelin_ctx* c, const fhelin_ct* a, const int32_t* indices
 int fhelin_rotate_each(fhelin_ctx* c, const fhelin_ct* const* v, const int32_t* indices, int32_t n, fhelin_ct** outs) {
     NEED(c && v && indices && outs && n >= 0);
     FHELIN_TRY
-    std::vector<CtPtr> in;
-    for (int i = 0; i < n; ++i)
-        if (!v[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
-    force_many(c, v, n);
-    for (int i = 0; i < n; ++i) in.push_back(ct_in(c, v[i]));
-    std::vector<CtPtr> r = c->ev.rotate_each(in, std::vector<int>(indices, indices + n));
+    std::vector<CtPtr> r = c->ev.rotate_each(vec_of(c, v, n), std::vector<int>(indices, indices + n));
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, r[i]);
     FHELIN_CATCH
 }
@@ -474,41 +469,26 @@ int fhelin_hoisted_dot(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, cons
                        int32_t rescale, fhelin_ct** outs) {
     NEED(c && v && pts && indices && outs && n >= 0 && n_rot >= 1);
     FHELIN_TRY
-    std::vector<CtPtr> in;
     std::vector<PtPtr> p;
-    for (int i = 0; i < n; ++i)
-        if (!v[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
     for (int i = 0; i <= n_rot; ++i) {
         if (!pts[i]) throw Error(FHELIN_ERR_ARG, "null plaintext in array");
         p.push_back(pts[i]->p);
     }
-    force_many(c, v, n);
-    for (int i = 0; i < n; ++i) in.push_back(ct_in(c, v[i]));
-    std::vector<CtPtr> r = c->ev.hoisted_dot_rows(in, p, std::vector<int>(indices, indices + n_rot), rescale != 0);
+    std::vector<CtPtr> r = c->ev.hoisted_dot_rows(vec_of(c, v, n), p, std::vector<int>(indices, indices + n_rot), rescale != 0);
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, r[i]);
     FHELIN_CATCH
 }
 int fhelin_rotate_sum(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, const int32_t* indices, int32_t n_rot, fhelin_ct** outs) {
     NEED(c && v && indices && outs && n >= 0 && n_rot >= 1);
     FHELIN_TRY
-    std::vector<CtPtr> in;
-    for (int i = 0; i < n; ++i)
-        if (!v[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
-    force_many(c, v, n);
-    for (int i = 0; i < n; ++i) in.push_back(ct_in(c, v[i]));
-    std::vector<CtPtr> r = c->ev.rotate_sum_batch(in, std::vector<int>(indices, indices + n_rot));
+    std::vector<CtPtr> r = c->ev.rotate_sum_batch(vec_of(c, v, n), std::vector<int>(indices, indices + n_rot));
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, r[i]);
     FHELIN_CATCH
 }
 int fhelin_rotate_each_sum(fhelin_ctx* c, const fhelin_ct* const* v, const int32_t* indices, int32_t n, fhelin_ct** out) {
     NEED(c && v && indices && out && n >= 1);
     FHELIN_TRY
-    std::vector<CtPtr> in;
-    for (int i = 0; i < n; ++i)
-        if (!v[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
-    force_many(c, v, n);
-    for (int i = 0; i < n; ++i) in.push_back(ct_in(c, v[i]));
-    *out = wrap(c, c->ev.rotate_each_sum(in, std::vector<int>(indices, indices + n)));
+    *out = wrap(c, c->ev.rotate_each_sum(vec_of(c, v, n), std::vector<int>(indices, indices + n)));
     FHELIN_CATCH
 }
 int fhelin_raw_modraise(fhelin_ctx* c, const fhelin_ct* a, int32_t new_ell, fhelin_ct** out) {

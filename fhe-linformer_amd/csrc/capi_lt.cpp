@@ -149,11 +149,7 @@ int fhelin_lt_apply(fhelin_ctx* c, const fhelin_lt* lt, const fhelin_ct* const* 
     c->ctx.require_device();
     if (c->ctx.stride != 1) throw Error(FHELIN_ERR_STATE, "lt_apply: interleaved samples (slot stride != 1) are not supported");
     if (lt->slots != (1 << c->ctx.prm.log_slots)) throw Error(FHELIN_ERR_ARG, "lt_apply: the plan was made for another packing");
-    std::vector<CtPtr> in;
-    for (int i = 0; i < n; ++i)
-        if (!v[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext in array");
-    force_many(c, v, n);
-    for (int i = 0; i < n; ++i) in.push_back(ct_in(c, v[i]));
+    const CtVec in = vec_of(c, v, n);
     // no handle exists before the whole call has succeeded; nothing here makes a source of the level plan
     std::vector<CtPtr> r = c->ev.linear_transform_rows(in, lt->pts, lt->baby, lt->giant, rescale != 0);
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, r[i]);

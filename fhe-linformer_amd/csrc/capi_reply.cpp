@@ -18,12 +18,7 @@ int fhelin_sanitize(fhelin_ctx* c, const fhelin_ct* const* v, int32_t n, const f
     NEED(c && v && outs && n > 0);
     FHELIN_TRY
     c->ctx.require_device();
-    for (int i = 0; i < n; ++i)
-        if (!v[i]) throw Error(FHELIN_ERR_ARG, "null ciphertext handle in array");
-    force_many(c, v, n);
-    std::vector<CtPtr> in;
-    for (int i = 0; i < n; ++i) in.push_back(ct_in(c, v[i]));
-    std::vector<CtPtr> r = c->cl.sanitize(in, mask ? mask->p : PtPtr(), flood_bits, out_ell);
+    std::vector<CtPtr> r = c->cl.sanitize(vec_of(c, v, n), mask ? mask->p : PtPtr(), flood_bits, out_ell);
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, r[i]);
     FHELIN_CATCH
 }

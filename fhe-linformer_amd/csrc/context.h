@@ -102,18 +102,26 @@ struct Context {
     void release_holds(int lane, u64 up_to_seq);
     void fork_lanes();              // lanes wait for everything enqueued on the main stream so far
     void join_lanes();              // the main stream waits for every lane
-    struct LaneScope {              // route launches and allocations to lane k (1-based) until destruction
+    DevicePool pool;
+    hipStream_t stream_of(int lane) const { return pool.lane_stream[lane]; }   // lane 0: the main stream
+    void select_lane(int lane) {    // launches and allocations go to `lane` from here on
+        stream = stream_of(lane);
+        pool.cur_lane = lane;
+    }
+    void set_main_stream(hipStream_t s) {   // lane 0 moves to a stream of the caller's
+        stream = main_stream = pool.lane_stream[0] = s;
+        own_stream = false;
+    }
+    struct LaneScope {              // lane k until destruction, then back to the stream and lane it was entered from
         Context& c;
-        LaneScope(Context& ctx, int k) : c(ctx) {
-            c.stream = c.lane_stream[k];
-            c.pool.cur_lane = k;
-        }
+        hipStream_t was_stream;
+        int was_lane;
+        LaneScope(Context& ctx, int k) : c(ctx), was_stream(ctx.stream), was_lane(ctx.pool.cur_lane) { c.select_lane(k); }
         ~LaneScope() {
-            c.stream = c.main_stream;
-            c.pool.cur_lane = 0;
+            c.stream = was_stream;
+            c.pool.cur_lane = was_lane;
         }
     };
-    DevicePool pool;
     DeviceTables dt{};
     std::vector<void*> table_allocs;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;

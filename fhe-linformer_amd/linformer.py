@@ -216,7 +216,7 @@ class DataflowController:
     rule is data flow.  Scheduling only - the residues of the plain single pass (tests/test_batched_forward_gpu.py).
     Use: ctl.begin() ... forward_encrypted(ctl, ...) ... ctl.end()."""
 
-    # calls whose outputs are deferred rows when they return more than one (capi_composite.cpp): evaluated later, under the lane that reads them
+    # calls whose outputs are deferred rows when they return more than one (csrc/deferred.h): evaluated later, under the lane that reads them
     _DEFERRED = ("matmulRE", "matmulCR", "unwrapExpanded", "matmulRElarge")
     BULK_ROWS = 8        # a call that reads this many ciphertexts is a row loop: its launches fill the GPU
     _PLAIN = ("level", "encode", "read_plain_input", "read_plain_repeated_input", "read_plain_expanded_input", "decrypt")

@@ -266,7 +266,7 @@ class ResidueController:
 
     def matmulRElarge(self, rows, weights, bias, mask_val=1.0):
         """rows that nobody has read when generate_containers takes them are never evaluated on their own (the C ABI defers them the
-        same way: csrc/capi_internal.h); a row that is read is Composite::matmulRElarge"""
+        same way: csrc/deferred.h); a row that is read is Composite::matmulRElarge"""
         v = self._relarge_v(weights)
         m512 = self._block_mask(0, 512, mask_val).enc
         rows = list(rows)

@@ -174,6 +174,24 @@ def test_paired_batch_of_three_and_of_four(pair10):
         assert np.array_equal(out4[2 + k].export(), second[k].export()) and out4[2 + k].scale_parts() == second[k].scale_parts()
 
 
+def test_paired_batch_groups_inputs_by_planned_drop(pair10):
+    """an applied level plan gives the three inputs of ONE fhelin_bootstrap_paired_batch the drops [2, 4, 2]: the first and the third
+    share a pipeline and are its pair (fhelin_bootstrap_pair_drop), the second runs alone (fhelin_bootstrap_drop); three sources"""
+    eng, boot, (ca, cb) = pair10["eng"], pair10["boot"], pair10["ct"]
+    _, cc, _ = _boot_input(eng, boot, ell_left=4, seed=9)
+    pair = [o.export() for o in eng.bootstrap_pair_drop(ca, cc, 2)]
+    alone = eng.bootstrap_drop(cb, 4).export()
+    full = eng.n_q - boot.desc["depth"]
+    eng.set_level_plan([full - 2, full - 4, full - 2])
+    eng.level_plan_begin("apply")
+    out = eng.bootstrap_paired_batch([ca, cb, cc])
+    assert eng.level_plan_tell() == ("apply", 3)
+    eng.level_plan_begin("off")
+    assert [o.info()["ell"] for o in out] == [full - 2, full - 4, full - 2]
+    assert np.array_equal(out[0].export(), pair[0]) and np.array_equal(out[2].export(), pair[1])
+    assert np.array_equal(out[1].export(), alone)
+
+
 def test_pairing_knob_routes_deferred_bootstraps(pair10):
     """set_bootstrap_pairing(1): three deferred bootstrap() calls, read afterwards, are bootstrap_paired_batch; off (the default) they
     are bootstrap_batch as before"""

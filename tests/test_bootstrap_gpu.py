@@ -67,7 +67,7 @@ def test_bootstrap_requires_setup_and_two_limbs(fa):
 
 def test_async_heavy_ops_match_the_synchronous_path(fa, monkeypatch):
     """Heavy ops issued back to back run on alternating worker lanes and are joined when their results are used
-    (capi_internal.h run_heavy).  The residues must not depend on that: the same call sequence with FHELIN_ASYNC=0
+    (deferred.h run_heavy).  The residues must not depend on that: the same call sequence with FHELIN_ASYNC=0
     (everything on the main stream) has to export bit-identical ciphertexts — chains on one ciphertext (polynomial then
     bootstrap), independent ciphertexts interleaved, results consumed in the opposite order, and an input freed by the
     host while its consumer may still be running."""
@@ -171,6 +171,27 @@ def test_batched_bootstrap_gives_the_single_bootstraps_residues(fa, log_slots):
         eng.level_plan_begin("off")
         for g, s in zip(planned, dropped):
             assert np.array_equal(g.export(), s)
+    finally:
+        eng.close()
+
+
+def test_batched_bootstrap_groups_inputs_by_planned_drop(fa):
+    """an applied level plan gives the three inputs of ONE fhelin_bootstrap_batch the drops [3, 1, 3]: inputs of equal drop share a
+    batch, every output holds the residues of fhelin_bootstrap_drop with its own drop, and the call takes three sources of the plan"""
+    eng = _engine(fa, 10)
+    try:
+        rng = np.random.default_rng(22)
+        cts = [eng.encrypt(rng.uniform(-1, 1, 1 << 10), level=eng.n_q - ell) for ell in (3, 2, 4)]
+        drops = [3, 1, 3]
+        single = [eng.bootstrap_drop(c, d).export() for c, d in zip(cts, drops)]
+        full = eng.n_q - eng.bootstrap_describe()["depth"]
+        eng.set_level_plan([full - d for d in drops])
+        eng.level_plan_begin("apply")
+        got = eng.bootstrap_batch(cts)
+        assert eng.level_plan_tell() == ("apply", 3)
+        eng.level_plan_begin("off")
+        for g, s, d in zip(got, single, drops):
+            assert g.info()["ell"] == full - d and np.array_equal(g.export(), s)
     finally:
         eng.close()
 

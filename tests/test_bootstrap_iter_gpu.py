@@ -158,6 +158,30 @@ def test_bootstrap_iter_batch_deferral_and_plan(fa, orc):
         eng.close()
 
 
+def test_bootstrap_iter_batch_groups_inputs_by_planned_drop(fa):
+    """an applied level plan gives the three inputs of ONE fhelin_bootstrap_iter_batch the drops [2, 1, 2]: inputs of equal drop share
+    a batch, every output holds the residues of fhelin_bootstrap_iter_drop with its own drop, and the call takes three sources"""
+    eng = fa.Engine("boot12", seed=77, log_slots=10)
+    try:
+        eng.keygen()
+        eng.gen_relin_key()
+        eng.bootstrap_setup(3, 3, 1 << 10)
+        rng = np.random.default_rng(23)
+        cts = [eng.encrypt(rng.uniform(-1, 1, 1 << 10), level=eng.n_q - ell) for ell in (3, 2, 4)]
+        drops = [2, 1, 2]
+        single = [eng.bootstrap_iter_drop(c, 10, d).export() for c, d in zip(cts, drops)]
+        full = eng.n_q - eng.bootstrap_describe()["depth"] - 1
+        eng.set_level_plan([full - d for d in drops])
+        eng.level_plan_begin("apply")
+        got = eng.bootstrap_iter_batch(cts, 10)
+        assert eng.level_plan_tell() == ("apply", 3)
+        eng.level_plan_begin("off")
+        for g, s, d in zip(got, single, drops):
+            assert g.info()["ell"] == full - d and np.array_equal(g.export(), s)
+    finally:
+        eng.close()
+
+
 def test_bootstrap_iter_errors(boot12, fa):
     eng, boot = boot12
     _, ct, _ = _input(eng, boot.n, 3, 5)

@@ -1,5 +1,5 @@
 """Deferred heavy operations (fhelin_add / fhelin_bootstrap / fhelin_eval_chebyshev return handles that are evaluated, batched, when a
-result is first read - csrc/capi_internal.h LazyHeavy): a batched call that throws fails ONLY its own group and the operations that read
+result is first read - csrc/deferred.h LazyHeavy): a batched call that throws fails ONLY its own group and the operations that read
 its results; independent operations of the same flush are evaluated and read normally; the failure is reported by the read of the
 failed handle (and by fhelin_sync for a flush nobody read), with the message of the call that threw.  Argument errors that can be seen
 when the call is made are reported by the call.  fhelin_timer_stop evaluates what is pending (a timed region that ends on a deferred
