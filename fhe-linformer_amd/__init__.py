@@ -7,5 +7,5 @@ evaluation call fails loudly when the library or a HIP device is missing.
 """
 from .capi import (  # noqa: F401
     FhelinError, Params, Engine, load_library, library_path, PRESETS, circuit_rotation_indices, compact_info,
-    interleave, deinterleave,
+    interleave, deinterleave, caps_from_usage,
 )

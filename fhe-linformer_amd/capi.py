@@ -114,6 +114,10 @@ def load_library():
         "fhelin_secret_import": (i32, [vp, vp, C.c_size_t]),
         "fhelin_key_export": (i32, [vp, i32, i32, vp, C.c_size_t]),
         "fhelin_key_import": (i32, [vp, i32, i32, vp, C.c_size_t]),
+        "fhelin_ctx_set_key_caps": (i32, [vp, C.POINTER(i32), u64p, C.POINTER(i32), i32]),
+        "fhelin_key_info": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "fhelin_key_usage_begin": (i32, [vp]),
+        "fhelin_key_usage_end": (i32, [vp, C.POINTER(i32), u64p, C.POINTER(i32), i32, C.POINTER(i32)]),
         "fhelin_encode": (i32, [vp, C.POINTER(C.c_double), i32, i32, i32, C.POINTER(vp)]),
         "fhelin_pt_free": (None, [vp]),
         "fhelin_pt_export": (i32, [vp, vp, i32, C.c_double, C.c_double, vp, C.c_size_t]),
@@ -301,6 +305,37 @@ def deinterleave(physical, stride):
 def _np_u64(a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     return a, a.ctypes.data_as(C.c_void_p)
+
+
+def caps_from_usage(table, n_q, margin=0):
+    """A usage table (Engine.key_usage: (kind, galois, max_ell) per key that was used) as the cap table Engine.set_key_caps takes:
+    every key capped at the most limbs the recorded pass switched it at (+ margin, at most n_q).  Keys the pass never used have no
+    entry and stay uncapped.  The caps hold for the recorded program under the recorded level plan only: a pass that goes higher is
+    refused with FHELIN_ERR_KEY."""
+    return [(int(k), int(g), min(int(n_q), int(m) + int(margin))) for k, g, m in table]
+
+
+class _KeyUsage:
+    def __init__(self, eng):
+        self.eng = eng
+        self.table = None
+
+    def __enter__(self):
+        self.eng._ck(self.eng.lib.fhelin_key_usage_begin(self.eng.h))
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        n = C.c_int32(0)
+        rc = self.eng.lib.fhelin_key_usage_end(self.eng.h, None, None, None, 0, C.byref(n))
+        if exc_type is not None:
+            return False        # the block's own error is the one to report; the recording is over either way
+        self.eng._ck(rc)
+        m = max(1, n.value)
+        kind, gal, cap = (C.c_int32 * m)(), (C.c_uint64 * m)(), (C.c_int32 * m)()
+        # the recorder has stopped; its table stays readable until the next begin
+        self.eng._ck(self.eng.lib.fhelin_key_usage_end(self.eng.h, kind, gal, cap, n.value, C.byref(n)))
+        self.table = [(kind[i], gal[i], cap[i]) for i in range(n.value)]
+        return False
 
 
 class DevBuf:
@@ -661,9 +696,37 @@ class Engine:
         self._ck(self.lib.fhelin_secret_import(self.h, arr.ctypes.data_as(C.c_void_p), arr.size))
 
     def key_export(self, kind, index=0):
-        out = np.empty((self.dnum_digits, 2, self.n_limbs, self.N), dtype=np.uint64)
+        """[digits][2][n_q + n_p][N]; a level-capped key has digits_at(max_ell) digits and its absent rows zero"""
+        out = np.empty((self.key_info(kind, index)["digits"], 2, self.n_limbs, self.N), dtype=np.uint64)
         self._ck(self.lib.fhelin_key_export(self.h, kind, index, out.ctypes.data_as(C.c_void_p), out.size))
         return out
+
+    # ---- level-capped keys (include/fhelin.h "Level-capped keys")
+    def set_key_caps(self, table):
+        """table: (kind, galois, max_ell) entries - kind 1 relinearisation (galois 0), 2 rotation, 3 conjugation (galois 2N-1), as
+        key_usage() returns them; every matching key generated afterwards holds only what a switch at <= max_ell limbs reads"""
+        table = [tuple(int(v) for v in e) for e in table]
+        n = len(table)
+        kind = (C.c_int32 * max(1, n))(*[e[0] for e in table])
+        gal = (C.c_uint64 * max(1, n))(*[e[1] for e in table])
+        cap = (C.c_int32 * max(1, n))(*[e[2] for e in table])
+        self._ck(self.lib.fhelin_ctx_set_key_caps(self.h, kind, gal, cap, n))
+
+    def key_info(self, kind, index=0):
+        """digits held, max_ell and seeded flag of a key; kind / index as key_export"""
+        d, m, s = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.lib.fhelin_key_info(self.h, kind, index, C.byref(d), C.byref(m), C.byref(s)))
+        return {"digits": d.value, "max_ell": m.value, "seeded": bool(s.value)}
+
+    def key_usage(self):
+        """context manager: records, for every key, the most limbs it is switched at inside the block; the table (a list of
+        (kind, galois, max_ell), sorted, the encoding of set_key_caps) is in `.table` once the block has ended.  Everything deferred is
+        evaluated when the block ends."""
+        return _KeyUsage(self)
+
+    def galois_of(self, index):
+        """Galois element of a rotation index at interleave stride 1: 5^index mod 2N"""
+        return pow(5, index % (self.N // 2), 2 * self.N)
 
     def key_import(self, kind, index, arr):
         arr = np.ascontiguousarray(arr, dtype=np.uint64)

@@ -176,7 +176,12 @@ int fhelin_key_import(fhelin_ctx* c, int32_t kind, int32_t index, const uint64_t
     if (words != k->words()) throw Error(FHELIN_ERR_ARG, "key must be [dnum][2][L+1+k][N]");
     hip_check(hipMemcpyAsync(k->d, in, words * 8, hipMemcpyHostToDevice, c->ctx.stream), "key import");
     c->ctx.sync();
-    key_slot(c, kind, index) = k;
+    KeyPtr& slot = key_slot(c, kind, index);   // throws for an unknown kind
+    k->kind = kind + 1;                        // the key-set file's numbering (EvalKey::kind): what the usage recorder reports
+    k->galois = kind == 0 ? 0 : kind == 1 ? c->ctx.rot_element(index) : 2ull * c->ctx.N - 1;
+    k->has_index = kind == 1;
+    k->index = index;
+    slot = k;
     FHELIN_CATCH
 }
 

@@ -4,6 +4,11 @@
 // on the way out and on the way in; the file is streamed through two pinned staging buffers, so host memory stays bounded by them.
 // A compact set ("FHELINEC") stores the b halves and the key-set seed; the loader expands every a half in one launch
 // (kernels_seeded.hip) before it digests.
+// Version 2 of both formats (include/fhelin.h "Level-capped keys") stores the present rows of capped keys only.  Payloads are dense in
+// the file and full-stride on the device: the staging pipeline copies run by run (one run of Q rows and one of special rows per digit
+// and half - plain 1D copies, a few MB each at driver scale), and the digest reads the rows where they lie through the strided digest
+// launch (kernels_keys.h), one launch for the Q rows and one for the special rows of a key.  No scatter kernel: a scatter would need
+// the dense payload in device memory first, which is exactly the copy the cap saves.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -21,7 +26,8 @@ namespace {
 constexpr char EK_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'K'};
 constexpr char EC_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'C'};   // compact (seeded) set
 constexpr uint32_t EK_VERSION = 1, EC_VERSION = 1;
-constexpr size_t EK_HEADER = 96, EC_HEADER = 128, EK_ENTRY = 40, EK_ALIGN = 4096;
+constexpr uint32_t EK_VERSION_CAPS = 2;   // both magics: 48-byte table entries (the 40 of version 1, u32 max_ell, u32 0), present rows only
+constexpr size_t EK_HEADER = 96, EC_HEADER = 128, EK_ENTRY = 40, EK_ENTRY_CAPS = 48, EK_ALIGN = 4096;
 constexpr uint32_t EK_MAX_KEYS = 1u << 16;
 constexpr size_t EK_STAGE_BYTES = size_t(4) << 20;   // per staging buffer (two of them)
 enum : uint32_t { EK_PUBLIC = 0, EK_RELIN = 1, EK_ROTATION = 2, EK_CONJ = 3 };
@@ -29,6 +35,7 @@ enum : uint32_t { EK_PUBLIC = 0, EK_RELIN = 1, EK_ROTATION = 2, EK_CONJ = 3 };
 struct EkEntry {
     uint32_t kind = 0, digits = 0;
     uint64_t galois = 0, offset = 0, words = 0, digest = 0;
+    uint32_t max_ell = 0;   // n_q for the public key, for an uncapped key and for every key of a version 1 set
 };
 struct EkFile {
     int32_t prm[9] = {};    // log_n, n_q, first_bits, scale_bits, n_p, special_bits, dnum, log_slots, hamming
@@ -38,6 +45,7 @@ struct EkFile {
     uint64_t data_offset = 0;
     int32_t stride = 1;       // interleave stride (header word 88: 0 = 1)
     bool compact = false;     // "FHELINEC": b halves only, a expanded from `seed`
+    uint32_t version = 1;
     uint8_t seed[32] = {};
 };
 
@@ -87,7 +95,10 @@ EkFile read_header(const char* path) {
     EkFile e;
     if (std::memcmp(h, EC_MAGIC, 8) == 0) e.compact = true;
     else if (std::memcmp(h, EK_MAGIC, 8) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad magic");
-    if (get<uint32_t>(h, 8) != (e.compact ? EC_VERSION : EK_VERSION)) throw Error(FHELIN_ERR_ARG, "evaluation-key set: unsupported version");
+    e.version = get<uint32_t>(h, 8);
+    if (e.version != (e.compact ? EC_VERSION : EK_VERSION) && e.version != EK_VERSION_CAPS)
+        throw Error(FHELIN_ERR_ARG, "evaluation-key set: unsupported version");
+    const size_t entry = e.version == EK_VERSION_CAPS ? EK_ENTRY_CAPS : EK_ENTRY;
     const uint64_t head = e.compact ? EC_HEADER : EK_HEADER;
     if (e.compact && (fsize < EC_HEADER || std::fread(e.seed, 1, 32, fh.f) != 32)) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
     const uint32_t n_keys = get<uint32_t>(h, 12);
@@ -109,11 +120,12 @@ EkFile read_header(const char* path) {
     if (!boot_ok) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad bootstrap configuration");
     if (n_keys > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evaluation-key set: too many keys");
     const uint64_t N = 1ull << log_n, nm = (uint64_t)n_q + n_p;
-    const uint64_t table_end = head + 8 * nm + EK_ENTRY * (uint64_t)n_keys;
+    const uint64_t table_end = head + 8 * nm + entry * (uint64_t)n_keys;
+    const uint32_t alpha = ((uint32_t)n_q + (uint32_t)e.prm[6] - 1) / (uint32_t)e.prm[6];   // Context: limbs per digit
     if (fsize < table_end) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated key table");
     e.moduli.resize(nm);
     if (std::fread(e.moduli.data(), 8, nm, fh.f) != nm) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated moduli");
-    std::vector<uint8_t> t((size_t)EK_ENTRY * n_keys);
+    std::vector<uint8_t> t(entry * n_keys);
     if (n_keys && std::fread(t.data(), 1, t.size(), fh.f) != t.size()) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated key table");
     if (e.data_offset != (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN)
         throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad payload offset");
@@ -121,7 +133,7 @@ EkFile read_header(const char* path) {
     int seen[4] = {};
     uint64_t last_g = 0;
     for (uint32_t k = 0; k < n_keys; ++k) {
-        const uint8_t* r = t.data() + (size_t)EK_ENTRY * k;
+        const uint8_t* r = t.data() + entry * k;
         EkEntry x;
         x.kind = get<uint32_t>(r, 0);
         x.digits = get<uint32_t>(r, 4);
@@ -129,11 +141,20 @@ EkFile read_header(const char* path) {
         x.offset = get<uint64_t>(r, 16);
         x.words = get<uint64_t>(r, 24);
         x.digest = get<uint64_t>(r, 32);
+        x.max_ell = (uint32_t)n_q;
+        if (e.version == EK_VERSION_CAPS) {
+            x.max_ell = get<uint32_t>(r, 40);
+            if (get<uint32_t>(r, 44) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: non-zero reserved word in the key table");
+            if (x.max_ell < 1 || x.max_ell > (uint32_t)n_q || (x.kind == EK_PUBLIC && x.max_ell != (uint32_t)n_q))
+                throw Error(FHELIN_ERR_ARG, "evaluation-key set: max_ell outside 1 .. n_q");
+            if (x.kind != EK_PUBLIC && x.kind <= EK_CONJ && x.digits != (x.max_ell + alpha - 1) / alpha)
+                throw Error(FHELIN_ERR_ARG, "evaluation-key set: digit count is not that of a key switch at max_ell limbs");
+        }
         if (x.kind > EK_CONJ) throw Error(FHELIN_ERR_ARG, "evaluation-key set: unknown key kind");
         if (x.kind != EK_ROTATION && ++seen[x.kind] > 1) throw Error(FHELIN_ERR_ARG, "evaluation-key set: duplicate key");
         // the compact form stores the b halves only
         const uint64_t halves = e.compact ? 1 : 2;
-        const uint64_t want = x.kind == EK_PUBLIC ? halves * (uint64_t)n_q * N : (uint64_t)x.digits * halves * nm * N;
+        const uint64_t want = x.kind == EK_PUBLIC ? halves * (uint64_t)n_q * N : (uint64_t)x.digits * halves * ((uint64_t)x.max_ell + n_p) * N;
         if ((x.kind == EK_PUBLIC) != (x.digits == 0) || x.digits > (uint32_t)n_q || x.words != want)
             throw Error(FHELIN_ERR_ARG, "evaluation-key set: key size does not match the parameters");
         const uint64_t g_want = x.kind == EK_CONJ ? 2 * N - 1 : 0;
@@ -185,7 +206,22 @@ struct Pinned {
 struct Seg {
     u64* d;
     size_t words;
+    // > 0: a capped switching key [digits][2][n_q + n_p][N] at d; words counts its PRESENT rows, [digits][2][max_ell + n_p][N]
+    int max_ell = 0;
+    int digits = 0;
 };
+
+// the runs of a capped key's present rows in storage order ([digits][halves][max_ell + n_p][N]; halves 1: the b halves): per digit and
+// half the Q rows 0 .. max_ell-1, then the special rows, where they lie in the full-stride layout
+void present_runs(std::vector<Seg>& out, const Context& x, u64* d, int digits, int halves, int max_ell) {
+    const size_t N = x.N, nl = (size_t)x.L + 1 + x.K;
+    for (int j = 0; j < digits; ++j)
+        for (int h = 0; h < halves; ++h) {
+            u64* base = d + ((size_t)2 * j + h) * nl * N;
+            out.push_back({base, (size_t)max_ell * N});
+            out.push_back({base + (size_t)(x.L + 1) * N, (size_t)x.K * N});
+        }
+}
 
 // per-vector digests / range flags of every key on the device, folded into one digest per key on the host.  ok[k] = every
 // residue of key k below its limb's modulus.
@@ -206,7 +242,17 @@ void key_digests(Context& x, const std::vector<Seg>& segs, const std::vector<uin
     for (size_t k = 0; k < segs.size(); ++k) {
         const int n_vec = (int)(segs[k].words / N);
         const int limb_count = kinds[k] == EK_PUBLIC ? x.L + 1 : x.L + 1 + x.K;
-        launch_key_digest(x.dt, segs[k].d, n_vec, 0, limb_count, part, out + 2 * v0, x.stream);
+        if (segs[k].max_ell > 0) {
+            // a capped key's present rows where they lie (row-to-limb mapping of version 2: stored row r of a group is Q limb r below
+            // max_ell, else special limb r - max_ell): the Q rows of all groups, then the special rows of all groups; folded in storage
+            // order below
+            const int groups = 2 * segs[k].digits, mq = segs[k].max_ell;
+            launch_key_digest_strided(x.dt, segs[k].d, groups * mq, 0, mq, limb_count, part, out + 2 * v0, x.stream);
+            launch_key_digest_strided(x.dt, segs[k].d + (size_t)(x.L + 1) * N, groups * x.K, x.L + 1, x.K, limb_count, part,
+                                      out + 2 * (v0 + (size_t)groups * mq), x.stream);
+        } else {
+            launch_key_digest(x.dt, segs[k].d, n_vec, 0, limb_count, part, out + 2 * v0, x.stream);
+        }
         v0 += n_vec;
     }
     hip_check(hipGetLastError(), "key digest kernels");
@@ -219,6 +265,17 @@ void key_digests(Context& x, const std::vector<Seg>& segs, const std::vector<uin
     for (size_t k = 0; k < segs.size(); ++k) {
         const size_t n_vec = segs[k].words / N;
         bool in_range;
+        if (segs[k].max_ell > 0) {   // device order (all Q rows, all special rows) -> storage order (per group: Q rows, special rows)
+            const size_t groups = (size_t)2 * segs[k].digits, mq = (size_t)segs[k].max_ell, K = (size_t)x.K;
+            std::vector<u64> st(2 * n_vec);
+            for (size_t g = 0; g < groups; ++g)
+                for (size_t r = 0; r < mq + K; ++r) {
+                    const size_t from = r < mq ? g * mq + r : groups * mq + g * K + (r - mq), to = g * (mq + K) + r;
+                    st[2 * to] = h[2 * (v0 + from)];
+                    st[2 * to + 1] = h[2 * (v0 + from) + 1];
+                }
+            std::copy(st.begin(), st.end(), h.begin() + 2 * v0);
+        }
         digest[k] = fold_key_digest(&h[2 * v0], n_vec, in_range);
         ok[k] = in_range ? 1 : 0;
         v0 += n_vec;
@@ -246,24 +303,35 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
     std::vector<Seg> segs;
     std::vector<EkEntry> ents;
     std::vector<char> seeded;
+    bool any_capped = false;   // then version 2: 48-byte entries, capped keys as their present rows; else version 1, byte for byte
     auto add = [&](uint32_t kind, uint32_t digits, uint64_t g, u64* d, size_t words, bool sd) {
         EkEntry e;
         e.kind = kind;
         e.digits = digits;
         e.galois = g;
         e.words = words;
+        e.max_ell = (uint32_t)(x.L + 1);
         ents.push_back(e);
         segs.push_back({d, words});
         seeded.push_back(sd);
+    };
+    auto add_key = [&](uint32_t kind, uint64_t g, const EvalKey& k) {
+        add(kind, k.digits, g, k.d, k.words(), k.seeded);
+        if (!k.capped()) return;
+        any_capped = true;
+        const size_t present = (size_t)k.digits * 2 * (k.max_ell + x.K) * x.N;
+        ents.back().max_ell = (uint32_t)k.max_ell;
+        ents.back().words = present;
+        segs.back() = Seg{k.d, present, k.max_ell, k.digits};
     };
     if (c->cl.has_public_key())
         add(EK_PUBLIC, 0, 0, const_cast<u64*>(c->cl.public_key()), (size_t)2 * (x.L + 1) * x.N, c->cl.public_key_seeded());
     const KeyPtr& rk = c->ev.relin_key;
     const KeyPtr& ck = c->ev.conj_key;
-    if (rk) add(EK_RELIN, rk->digits, 0, rk->d, rk->words(), rk->seeded);
-    if (ck) add(EK_CONJ, ck->digits, g_conj, ck->d, ck->words(), ck->seeded);
+    if (rk) add_key(EK_RELIN, 0, *rk);
+    if (ck) add_key(EK_CONJ, g_conj, *ck);
     for (const auto& kv : c->ev.rot_keys)   // ordered by Galois element; the conjugation key is stored once, above
-        if (kv.second && kv.first != g_conj) add(EK_ROTATION, kv.second->digits, kv.first, kv.second->d, kv.second->words(), kv.second->seeded);
+        if (kv.second && kv.first != g_conj) add_key(EK_ROTATION, kv.first, *kv.second);
     if (ents.empty()) throw Error(FHELIN_ERR_KEY, "evalkeys_save: the context holds no keys");
     if (ents.size() > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evalkeys_save: too many keys");
     if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "evalkeys_save: ring dimension below 2^12");
@@ -291,20 +359,26 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
         for (size_t k = 0; k < ents.size(); ++k) {
             const size_t half = ents[k].kind == EK_PUBLIC ? (size_t)(x.L + 1) * x.N : (size_t)(x.L + 1 + x.K) * x.N;
             const uint32_t nd = ents[k].kind == EK_PUBLIC ? 1 : ents[k].digits;
-            for (uint32_t j = 0; j < nd; ++j) out.push_back({segs[k].d + (size_t)2 * j * half, half});
+            if (segs[k].max_ell > 0) present_runs(out, x, segs[k].d, segs[k].digits, 1, segs[k].max_ell);
+            else
+                for (uint32_t j = 0; j < nd; ++j) out.push_back({segs[k].d + (size_t)2 * j * half, half});
             ents[k].words /= 2;
         }
     } else {
-        out = segs;
+        for (const Seg& s : segs) {
+            if (s.max_ell > 0) present_runs(out, x, s.d, s.digits, 2, s.max_ell);
+            else out.push_back(s);
+        }
     }
 
     const size_t nm = x.moduli.size();
     const size_t head = compact ? EC_HEADER : EK_HEADER;
-    const uint64_t table_end = head + 8 * nm + EK_ENTRY * ents.size();
+    const size_t entry = any_capped ? EK_ENTRY_CAPS : EK_ENTRY;
+    const uint64_t table_end = head + 8 * nm + entry * ents.size();
     const uint64_t data_offset = (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN;
     std::vector<uint8_t> h(data_offset, 0);
     std::memcpy(h.data(), compact ? EC_MAGIC : EK_MAGIC, 8);
-    put<uint32_t>(h.data(), 8, compact ? EC_VERSION : EK_VERSION);
+    put<uint32_t>(h.data(), 8, any_capped ? EK_VERSION_CAPS : compact ? EC_VERSION : EK_VERSION);
     put<uint32_t>(h.data(), 12, (uint32_t)ents.size());
     int32_t prm[9];
     from_params(x.prm, prm);
@@ -322,7 +396,8 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
     for (size_t k = 0; k < ents.size(); ++k) {
         ents[k].offset = at;
         at += 8 * ents[k].words;
-        const size_t o = head + 8 * nm + EK_ENTRY * k;
+        const size_t o = head + 8 * nm + entry * k;
+        if (any_capped) put<uint32_t>(h.data(), o + 40, ents[k].max_ell);   // then u32 0 (reserved)
         put<uint32_t>(h.data(), o, ents[k].kind);
         put<uint32_t>(h.data(), o + 4, ents[k].digits);
         put<uint64_t>(h.data(), o + 8, ents[k].galois);
@@ -449,9 +524,8 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
                                                                  ", the context was set to " + std::to_string(x.stride));
         if (x.stride_locked) throw Error(FHELIN_ERR_STATE, "evalkeys_load: the set has another interleave stride than the plaintexts or ciphertexts the context already holds");
     }
-    const int digits = x.digits_at(x.L + 1);
     for (const auto& k : e.keys)
-        if (k.kind != EK_PUBLIC && (int)k.digits != digits)
+        if (k.kind != EK_PUBLIC && (int)k.digits != x.digits_at((int)k.max_ell))
             throw Error(FHELIN_ERR_ARG, "evalkeys_load: switching key digit count does not match the context");
 
     // destinations: nothing is installed until every key has passed (their owners free the blocks on any failure)
@@ -465,8 +539,11 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
             pk = x.scratch<u64>(pk_words);
             segs.push_back({pk, pk_words});
         } else {
-            sw[k] = c->ev.new_key();
-            segs.push_back({sw[k]->d, sw[k]->words()});
+            sw[k] = c->ev.new_key((int)e.keys[k].max_ell);   // a capped key: zero-filled, the payload lands in its present rows
+            if (sw[k]->capped())
+                segs.push_back(Seg{sw[k]->d, (size_t)sw[k]->digits * 2 * (sw[k]->max_ell + x.K) * x.N, sw[k]->max_ell, sw[k]->digits});
+            else
+                segs.push_back({sw[k]->d, sw[k]->words()});
         }
         kinds.push_back(e.keys[k].kind);
     }
@@ -481,18 +558,27 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
             const int ell = pub ? x.L + 1 : x.L + 1 + x.K;
             const size_t half = (size_t)ell * x.N;
             const uint32_t nd = pub ? 1 : e.keys[k].digits;
+            if (segs[k].max_ell > 0) present_runs(in, x, segs[k].d, segs[k].digits, 1, segs[k].max_ell);
             for (uint32_t j = 0; j < nd; ++j) {
-                in.push_back({segs[k].d + (size_t)2 * j * half, half});
+                if (segs[k].max_ell == 0) in.push_back({segs[k].d + (size_t)2 * j * half, half});
                 SeededEntry se;
                 se.key = sk;
                 se.nonce = key_nonce(e.keys[k].kind, j, e.keys[k].galois);
                 se.dst = segs[k].d + (size_t)(2 * j + 1) * half;
                 se.ell = ell;
+                if (segs[k].max_ell > 0) {   // the a half of the present rows only, each at its absolute limb
+                    se.ell = segs[k].max_ell + x.K;
+                    se.split = segs[k].max_ell;
+                    se.skip = x.L + 1 - segs[k].max_ell;
+                }
                 tab.push_back(se);
             }
         }
     } else {
-        in = segs;
+        for (const Seg& s : segs) {
+            if (s.max_ell > 0) present_runs(in, x, s.d, s.digits, 2, s.max_ell);
+            else in.push_back(s);
+        }
     }
     {
         File fh(path, "rb");
@@ -534,7 +620,11 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
     // install
     x.stride = e.stride;
     for (size_t k = 0; k < e.keys.size(); ++k) {
-        if (sw[k]) sw[k]->seeded = e.compact;
+        if (sw[k]) {
+            sw[k]->seeded = e.compact;
+            sw[k]->kind = (int)e.keys[k].kind;   // the file's numbering is EvalKey::kind's
+            sw[k]->galois = e.keys[k].galois;
+        }
         switch (e.keys[k].kind) {
             case EK_RELIN: c->ev.relin_key = sw[k]; break;
             case EK_CONJ:

@@ -407,9 +407,9 @@ Client::~Client() {
 }
 
 // sample a small polynomial on the host, reduce it into `nl` limbs on the GPU and transform to NTT form
-void Client::sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind) {
+void Client::draw_small_host(std::vector<u64>& co, int kind) {
     const size_t N = c_.N;
-    std::vector<u64> co(2 * N);
+    co.resize(2 * N);
     for (size_t i = 0; i < N; ++i) {
         long v;
         if (kind == 0) v = lround(rng_.normal() * 3.19);
@@ -417,6 +417,12 @@ void Client::sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind) 
         co[2 * i] = (u64)v;
         co[2 * i + 1] = v < 0 ? ~0ull : 0;
     }
+}
+
+void Client::sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind) {
+    const size_t N = c_.N;
+    std::vector<u64> co;
+    draw_small_host(co, kind);
     Scratch<u64> dco = c_.scratch<u64>(2 * N);
     c_.upload_async(dco, co.data(), 2 * N);
     launch_reduce_i128(c_.dt, dst, dco, 0, nlimbs_q, c_.stream);
@@ -513,20 +519,45 @@ void Client::install_key_seed(const uint8_t seed[32]) {
     has_key_seed_ = true;
 }
 
+void Client::set_key_caps(const std::vector<KeyCap>& table) {
+    key_caps_.clear();
+    for (const KeyCap& e : table) key_caps_[{e.kind, e.galois}] = e.max_ell;
+}
+
+int Client::key_cap(int kind, u64 galois) const {
+    auto it = key_caps_.find({kind, galois});
+    return it == key_caps_.end() ? c_.L + 1 : it->second;
+}
+
+// Level-capped keys (include/fhelin.h "Level-capped keys"): a key with an entry in the cap table is made with its present rows only - the
+// Q limbs 0 .. cap-1 and the special limbs of the digits_at(cap) digits a switch at <= cap limbs reads - and those are, residue for
+// residue, the rows of the key this call would have made uncapped: the generator and the device sampler are consumed exactly as for the
+// uncapped key (so every later key is unchanged too), and only transforms, products and uploads of absent rows are left out.
 KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois) {
     c_.require_device();
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "key switching keys need special primes (n_p >= 1)");
     const size_t N = c_.N;
     const int L1 = c_.L + 1, nl = L1 + c_.K;
-    KeyPtr key = ev_.new_key();
+    const int cap = key_cap((int)kind, galois), all_digits = c_.digits_at(L1);
+    const bool capped = cap < L1;
+    KeyPtr key = ev_.new_key(cap);
+    key->kind = (int)kind;
+    key->galois = galois;
     if (seeded_keys_) {
         if (!has_key_seed_) throw Error(FHELIN_ERR_STATE, "seeded keys: keygen() draws the key-set seed and has not run");
         if (L1 > KEYGEN_MAX_Q) throw Error(FHELIN_ERR_ARG, "seeded keys: more than 64 Q limbs");
-        // every digit in one launch: e [digits][nl][N] from the device sampler, one forward NTT, then the fused combination
-        const size_t en = (size_t)key->digits * nl * N;
+        // every digit in one launch: e [digits][nl][N] from the device sampler, one forward NTT, then the fused combination.  A capped key
+        // samples the same e (the sampler's stream positions depend on the shape) and transforms the present rows of its digits only
+        const size_t en = (size_t)all_digits * nl * N;
         Scratch<u64> e = c_.scratch<u64>(en);
-        sample_small_device(e, key->digits, nl, 0);
-        c_.ntt(LimbBatch{e, key->digits * nl, nullptr, 0, nl}, false);
+        sample_small_device(e, all_digits, nl, 0);
+        if (!capped) c_.ntt(LimbBatch{e, all_digits * nl, nullptr, 0, nl}, false);
+        else
+            for (int j = 0; j < key->digits; ++j) {
+                u64* ej = e + (size_t)j * nl * N;
+                c_.ntt(LimbBatch{ej, cap, nullptr, 0, cap}, false);
+                c_.ntt(LimbBatch{ej + (size_t)L1 * N, c_.K, nullptr, L1, c_.K}, false);
+            }
         std::vector<u64> pm(L1);
         for (int t = 0; t < L1; ++t) {
             const u64 qt = c_.chain.q[t];
@@ -534,8 +565,12 @@ KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 k
             for (u64 p : c_.chain.p) m = h_mulmod(m, p % qt, qt);
             pm[t] = m;
         }
-        launch_seeded_keygen_combine(c_.dt, key->d, s_to_all, s_from_all, e, nl, key->digits, c_.alpha, L1, pm.data(), key_seed_words(), kind,
-                                     galois, c_.stream);
+        if (!capped)
+            launch_seeded_keygen_combine(c_.dt, key->d, s_to_all, s_from_all, e, nl, key->digits, c_.alpha, L1, pm.data(), key_seed_words(), kind,
+                                         galois, c_.stream);
+        else
+            launch_seeded_keygen_combine_capped(c_.dt, key->d, s_to_all, s_from_all, e, nl, key->digits, c_.alpha, L1, cap, pm.data(),
+                                                key_seed_words(), kind, galois, c_.stream);
         hip_check(hipGetLastError(), "seeded keygen kernels");
         hip_check(hipMemsetAsync(e, 0, en * sizeof(u64), c_.stream), "hipMemsetAsync(key noise)");
         e.reset();
@@ -545,20 +580,41 @@ KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 k
     std::vector<u64> a((size_t)nl * N);
     Scratch<u64> e = c_.scratch<u64>((size_t)nl * N);
     Scratch<u64> tmp = c_.scratch<u64>((size_t)nl * N);
-    for (int j = 0; j < key->digits; ++j) {
-        u64* kb = key->d + (size_t)(2 * j) * nl * N;
-        u64* ka = key->d + (size_t)(2 * j + 1) * nl * N;
+    // the Q rows in use and where the special rows of e / tmp lie: a capped key keeps its noise and products dense, [cap + k][N]
+    const int nq = capped ? cap : L1;
+    for (int j = 0; j < all_digits; ++j) {
         for (int l = 0; l < nl; ++l) {
             const u64 m = c_.moduli[l];
             for (size_t i = 0; i < N; ++i) a[(size_t)l * N + i] = rng_.uniform(m);
         }
-        hip_check(hipMemcpyAsync(ka, a.data(), a.size() * 8, hipMemcpyHostToDevice, c_.stream), "evk upload");
+        if (j >= key->digits) {   // a digit the capped key does not hold: its draws are consumed, nothing is computed
+            std::vector<u64> co;
+            draw_small_host(co, 0);
+            continue;
+        }
+        u64* kb = key->d + (size_t)(2 * j) * nl * N;
+        u64* ka = key->d + (size_t)(2 * j + 1) * nl * N;
+        if (!capped) {
+            hip_check(hipMemcpyAsync(ka, a.data(), a.size() * 8, hipMemcpyHostToDevice, c_.stream), "evk upload");
+        } else {
+            hip_check(hipMemcpyAsync(ka, a.data(), (size_t)nq * N * 8, hipMemcpyHostToDevice, c_.stream), "evk upload");
+            hip_check(hipMemcpyAsync(ka + (size_t)L1 * N, a.data() + (size_t)L1 * N, (size_t)c_.K * N * 8, hipMemcpyHostToDevice, c_.stream),
+                      "evk upload");
+        }
         hip_check(hipStreamSynchronize(c_.stream), "evk sync");
-        sample_small_to_ntt(e, L1, true, 0);
-        launch_ew_mul(c_.dt, tmp, ka, s_to_all, nl, nl, 0, nl, c_.stream);
-        launch_ew_sub(c_.dt, kb, e, tmp, nl, nl, 0, nl, c_.stream);
+        sample_small_to_ntt(e, nq, true, 0);
+        if (!capped) {
+            launch_ew_mul(c_.dt, tmp, ka, s_to_all, nl, nl, 0, nl, c_.stream);
+            launch_ew_sub(c_.dt, kb, e, tmp, nl, nl, 0, nl, c_.stream);
+        } else {
+            const size_t pq = (size_t)nq * N, pl = (size_t)L1 * N;   // special rows: dense in e / tmp, at row L1 in the key and the secrets
+            launch_ew_mul(c_.dt, tmp, ka, s_to_all, nq, nq, 0, nq, c_.stream);
+            launch_ew_sub(c_.dt, kb, e, tmp, nq, nq, 0, nq, c_.stream);
+            launch_ew_mul(c_.dt, tmp + pq, ka + pl, s_to_all + pl, c_.K, c_.K, L1, c_.K, c_.stream);
+            launch_ew_sub(c_.dt, kb + pl, e + pq, tmp + pq, c_.K, c_.K, L1, c_.K, c_.stream);
+        }
         // + P * (Q/Q_j) * [(Q/Q_j)^{-1}]_{Q_j} * s_from  ==  (P mod q_t) * s_from on the limbs of digit j, 0 elsewhere
-        const int lo = j * c_.alpha, hi = std::min((j + 1) * c_.alpha, L1);
+        const int lo = j * c_.alpha, hi = std::min((j + 1) * c_.alpha, nq);
         ScalarSet sc;
         for (int t = lo; t < hi; ++t) {
             const u64 qt = c_.chain.q[t];
@@ -599,7 +655,10 @@ void Client::gen_rotation_key(int index) {
     const u64 ginv = c_.rot_element(-index);
     Scratch<u64> sp = c_.scratch<u64>((size_t)nl * c_.N);
     launch_automorph(c_.dt, sp, s_all, c_.automorph_map(ginv), nl, c_.stream);
-    ev_.rot_keys[g] = make_switch_key(s_all, sp, 2, g);
+    KeyPtr key = make_switch_key(s_all, sp, 2, g);
+    key->has_index = true;
+    key->index = index;
+    ev_.rot_keys[g] = key;
 }
 
 void Client::gen_conj_key() {

@@ -50,6 +50,16 @@ public:
     void gen_conj_key();
     // device [L+1+k][N] NTT form.  kind / galois: the key's nonce fields in seeded-key mode (include/fhelin.h "Seeded evaluation keys")
     KeyPtr make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois);
+    // Level-capped keys (include/fhelin.h "Level-capped keys"): every switching key made from now on whose (kind, Galois element) has an
+    // entry is made capped at the entry's limbs (make_switch_key); an entry of n_q limbs, or none, is an uncapped key.  Replaces the table.
+    // kind 1 relinearisation (galois 0), 2 rotation, 3 conjugation (galois 2N-1).  The caller validates (fhelin_ctx_set_key_caps).
+    struct KeyCap {
+        int kind;
+        u64 galois;
+        int max_ell;
+    };
+    void set_key_caps(const std::vector<KeyCap>& table);
+    int key_cap(int kind, u64 galois) const;   // n_q where the table has no entry
 
     // Seeded-key mode (include/fhelin.h "Seeded evaluation keys"): keygen draws a public key-set seed and every key's a half is
     // its expansion, made on the device by seeded_keygen_combine_kernel.  Off: key generation consumes the generator as before.
@@ -127,6 +137,8 @@ private:
     u64* s_all = nullptr;   // secret, NTT form over Q and P limbs [L+1+k][N]
     u64* pk = nullptr;      // [2][L+1][N]: b = -a s + e, a
     void sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind);  // kind 0 gaussian, 1 ternary (host sampler: key generation)
+    void draw_small_host(std::vector<u64>& co, int kind);   // its draws alone: N coefficients as sign-extended 128-bit pairs
+    std::map<std::pair<int, u64>, int> key_caps_;
     // device sampler (encryption randomness): dst [n_poly][ell][N] coefficient form; a fresh ChaCha20 key per call
     void sample_small_device(u64* dst, int n_poly, int ell, int kind);
     // the wide sampler (launch_sample_flood), keyed as sample_small_device; gauss: e0 + f as one polynomial

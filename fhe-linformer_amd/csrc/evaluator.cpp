@@ -152,14 +152,38 @@ std::vector<CtPtr> Evaluator::make_contiguous(const std::vector<CtPtr>& v, int s
     return o;
 }
 
-KeyPtr Evaluator::new_key() {
+KeyPtr Evaluator::new_key(int max_ell) {
     c_.require_device();
+    if (max_ell < 0 || max_ell > c_.L + 1) throw Error(FHELIN_ERR_ARG, "new_key: max_ell out of range");
     auto k = std::make_shared<EvalKey>();
     k->ctx = &c_;
-    k->digits = c_.digits_at(c_.L + 1);
+    k->max_ell = max_ell ? max_ell : c_.L + 1;
+    k->digits = c_.digits_at(k->max_ell);
     k->d = c_.dalloc<u64>(k->words());
+    if (k->capped()) {   // the absent Q rows of the digits held: zero once, here; the makers write present rows only
+        hip_check(hipMemsetAsync(k->d, 0, k->words() * sizeof(u64), c_.stream), "hipMemsetAsync(capped key)");
+    }
     c_.stride_locked = true;
     return k;
+}
+
+void Evaluator::bind_key(const EvalKey& key, int ell) {
+    if (ell > key.max_ell) {
+        std::string who = key.kind == 1 ? "relinearisation key" : key.kind == 3 ? "conjugation key" : "rotation key";
+        if (key.kind != 1 && key.has_index) who += " for index " + std::to_string(key.index);
+        if (key.kind != 1) who += " (Galois element " + std::to_string((unsigned long long)key.galois) + ")";
+        throw Error(FHELIN_ERR_KEY, who + " is capped at " + std::to_string(key.max_ell) + " limbs: a key switch at " + std::to_string(ell) +
+                                        " limbs was asked for");
+    }
+    if (usage_on) {
+        int& m = usage[{key.kind, key.galois}];
+        m = std::max(m, ell);
+    }
+}
+
+void Evaluator::bind_rotations(const Rotations& rot, const std::vector<CtPtr>& v, bool rescales_first) {
+    for (const CtPtr& x : v)
+        for (int r = 0; r < rot.n; ++r) bind_key(*rot.key[r], rescales_first && x->deg >= 2 ? x->ell - 1 : x->ell);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -188,6 +212,9 @@ void Evaluator::keyswitch_impl(int B, const KsRows* rows, const u64* c_ntt, size
     c_.require_device();
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "hybrid key switching needs at least one special prime");
     if (B < 1) return;
+    if (key) bind_key(*key, ell);
+    else
+        for (int b = 0; b < B; ++b) bind_key(*rows->keys[b], ell);
     KsShape sh = ks_shape(ell, B, {c_stride, out_stride, add_stride, post_stride});
     const bool shared = rows && rows->shared_input;
     if (rows) {
@@ -241,6 +268,7 @@ Evaluator::KsTail Evaluator::moddown_tail(KsOutput o) const {
 
 const u64* Evaluator::set_gather(KsShape& sh, const EvalKey* const* keys, const u32* const* maps, const u64* c0, size_t c0_stride) {
     const u64* evk = nullptr;
+    for (int b = 0; b < (sh.per_row ? (sh.row_mod ? sh.row_mod : sh.batch) : 1); ++b) bind_key(*keys[b], sh.ell);
     sh.gather = 1;
     if (sh.per_row) {
         for (int b = 0; b < (sh.row_mod ? sh.row_mod : sh.batch); ++b) {
@@ -479,6 +507,7 @@ Evaluator::Rotations Evaluator::rotations(const int* indices, int n) {
 // (keys in the layout of EvalKey::d_perm: folded keys), else the rotation key's permuted copy.  shared_digits: the rotations act on ONE
 // input, whose digit tiles are staged in LDS when every automorphism keeps them in place (sh.lds_digits).
 void Evaluator::set_rotations(KsShape& sh, const Rotations& rot, bool shared_digits, const u64* const* keys) {
+    for (int r = 0; r < rot.n; ++r) bind_key(*rot.key[r], sh.ell);   // a folded key is its rotation key's copy: the same cap
     sh.n_rot = rot.n;
     for (int r = 0; r < rot.n; ++r) {
         sh.map_rot[r] = rot.map[r];
@@ -505,6 +534,7 @@ Scratch<u64> Evaluator::debug_ks_accp(const u64* ext, int ell, int batch, const 
     const size_t pn = (size_t)ell * c_.N;
     if (ell < 1 || ell > c_.L + 1 || batch < 1 || n_rot < 0 || n_rot > (int)KsShape::MAX_ROT) throw Error(FHELIN_ERR_ARG, "debug_ks_accp: bad shape");
     if (!n_rot && !relin_key) throw Error(FHELIN_ERR_KEY, "debug_ks_accp: no relinearisation key");
+    if (!n_rot) bind_key(*relin_key, ell);
     KsShape sh = ks_shape(ell, batch, {pn});
     Scratch<u64> own = c_.scratch<u64>((size_t)batch * pn);    // the Q limbs' own-digit operand: the Q half is computed and dropped
     hip_check(hipMemsetAsync(own, 0, (size_t)batch * pn * sizeof(u64), c_.stream), "hipMemsetAsync(debug_ks_accp)");
@@ -519,6 +549,7 @@ void Evaluator::debug_ks_accq(const u64* ext, const u64* own, u64* conv, int ell
     const size_t pn = (size_t)ell * c_.N;
     if (ell < 1 || ell > c_.L + 1 || batch < 1) throw Error(FHELIN_ERR_ARG, "debug_ks_accq: bad shape");
     if (!index && !relin_key) throw Error(FHELIN_ERR_KEY, "debug_ks_accq: no relinearisation key");
+    if (!index) bind_key(*relin_key, ell);
     KsShape sh = ks_shape(ell, batch, {pn, 2 * pn});
     const u64* evk = index ? nullptr : relin_key->d;
     if (index) {
@@ -567,6 +598,7 @@ std::vector<CtPtr> Evaluator::rotate_sum_batch(const std::vector<CtPtr>& vin, co
     if (!have_rotation_keys(indices, vin[0]->slots)) throw Error(FHELIN_ERR_KEY, "rotate_sum_batch: missing rotation key");
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "hybrid key switching needs at least one special prime");
     const Rotations rot = rotations(indices.data(), R);
+    bind_rotations(rot, vin);
     const size_t N = c_.N;
     return for_groups(vin.size(), batch_limit, [&](size_t f, size_t i) { return same_shape(*vin[f], *vin[i]); },
                       [&](const std::vector<size_t>& idx) {
@@ -645,6 +677,7 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
         if (r % ns == 0) throw Error(FHELIN_ERR_ARG, "hoisted_dot_rows: a rotation by 0 is the unrotated term (pts[0])");
     if (rescale_out && c_.K + 1 > 16)   // the merged ModDown + rescale takes at most 16 sources: ModDown, then a separate rescale
         return rescale_batch(hoisted_dot_rows(xin, pts, indices, false));
+    bind_rotations(rotations(indices.data(), R), xin, true);   // before the operands' rescale and the folded keys
     std::vector<CtPtr> x = xin;
     {   // degree-2 operands are rescaled first (as before any product with a plaintext); a ciphertext that occurs twice is rescaled twice
         std::vector<CtPtr> need;
@@ -755,8 +788,14 @@ std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xi
         }
     }
     if (steps.empty()) throw Error(FHELIN_ERR_ARG, "linear_transform_rows: no term");
-    for (int g : giant)
-        if (g % ns != 0) (void)rotation_key(g);
+    // ... and every one of them at the limbs each row will be switched at (a degree-2 row is rescaled first), giant steps included
+    for (const CtPtr& xi : xin) {
+        const int ell = xi->deg >= 2 ? xi->ell - 1 : xi->ell;
+        for (const Step& st : steps)
+            if (st.key) bind_key(*st.key, ell);
+        for (int g : giant)
+            if (g % ns != 0) bind_key(*rotation_key(g).key, ell);
+    }
     std::vector<CtPtr> x = xin;
     rescale_degree2(x, nullptr, "linear_transform_rows: ciphertext must have 2 components");   // as before any product with a plaintext
     const size_t N = c_.N;
@@ -796,6 +835,7 @@ std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xi
                 for (const Step& st : steps) {
                     LtStep e{};
                     if (st.b) {
+                        bind_key(*st.key, ell);
                         e.key = permuted(*st.key, st.map);
                         e.map = st.map;
                     }
@@ -856,6 +896,8 @@ std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xi
 CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vector<int>& indices) {
     if (vin.empty() || vin.size() != indices.size()) throw Error(FHELIN_ERR_ARG, "rotate_each_sum: one index per ciphertext");
     const int ns = slot_count(vin[0]);
+    for (size_t i = 0; i < vin.size(); ++i)   // every key at its term's limbs before the first addition or ModUp runs
+        if (indices[i] % ns != 0) bind_key(*rotation_key(indices[i]).key, vin[i]->ell);
     // unrotated terms are plain additions; the rest go through the merged key switch in groups of <= 7
     std::vector<CtPtr> rot;
     std::vector<int> ridx;
@@ -907,6 +949,9 @@ CtPtr Evaluator::rotate_each_sum(const std::vector<CtPtr>& vin, const std::vecto
 std::vector<CtPtr> Evaluator::rotate_each_sum_rows(const std::vector<std::vector<CtPtr>>& rows, const std::vector<int>& indices) {
     if (rows.empty()) return {};
     const int ns = slot_count(rows[0][0]);
+    for (const auto& row : rows)   // every key at its term's limbs before the first row runs
+        for (size_t r = 0; r < std::min(row.size(), indices.size()); ++r)
+            if (indices[r] % ns != 0) bind_key(*rotation_key(indices[r]).key, row[r]->ell);
     std::vector<int> rot_pos, plain_pos, ridx;
     for (size_t r = 0; r < indices.size(); ++r) {
         if (indices[r] % ns == 0) plain_pos.push_back((int)r);
@@ -1005,6 +1050,7 @@ std::vector<CtPtr> Evaluator::rotate_many(const CtPtr& a, const std::vector<int>
         if (indices[i] % ns == 0) out[i] = a;
         else todo.push_back(i);
     }
+    for (size_t i : todo) bind_key(*rotation_key(indices[i]).key, a->ell);   // all of them before the first chunk runs
     const size_t pn = (size_t)a->ell * c_.N, ctw = 2 * pn;
     for (size_t first = 0; first < todo.size(); first += KsShape::MAX_ROWS) {
         const int B = (int)std::min(todo.size() - first, (size_t)KsShape::MAX_ROWS);
@@ -1030,6 +1076,8 @@ std::vector<CtPtr> Evaluator::rotate_each(const std::vector<CtPtr>& vin, const s
     if (vin.size() != indices.size()) throw Error(FHELIN_ERR_ARG, "rotate_each: one index per ciphertext");
     // an operand that is not rotated is copied and joins no group
     auto rotated = [&](size_t f, size_t i) { return indices[i] % slot_count(vin[f]) != 0; };
+    for (size_t i = 0; i < vin.size(); ++i)   // every key at its operand's limbs before the first group runs
+        if (rotated(i, i)) bind_key(*rotation_key(indices[i]).key, vin[i]->ell);
     return for_groups(vin.size(), std::min(batch_limit, (int)KsShape::MAX_ROWS),
                       [&](size_t f, size_t i) { return rotated(f, f) && rotated(f, i) && same_shape(*vin[f], *vin[i]); },
                       [&](const std::vector<size_t>& idx) {
@@ -1149,6 +1197,7 @@ std::vector<CtPtr> Evaluator::conjugate_batch(const std::vector<CtPtr>& v) {
 }
 
 std::vector<CtPtr> Evaluator::rotate_galois_batch(const std::vector<CtPtr>& vin, u64 g, const EvalKey& key, bool accumulate) {
+    for (const CtPtr& x : vin) bind_key(key, x->ell);   // before the first group runs
     if (vin.size() == 1) return {raw_rotate(vin[0], g, key, accumulate)};
     const u32* map = c_.automorph_map(g);
     // rows that share (level, degree, scale) go through one batched key switch; others form their own groups
@@ -1174,6 +1223,9 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
     for (const CtPtr& x : xs)
         uniform = uniform && x->npoly == 2 && x->ell == xs[0]->ell && x->deg == xs[0]->deg && x->slots == xs[0]->slots;
     if (!uniform) {
+        for (const CtPtr& x : xs)   // every key at every input's limbs before the first input runs
+            for (int r : indices)
+                if (r % slot_count(x) != 0) bind_key(*rotation_key(r).key, x->ell);
         for (size_t i = 0; i < xs.size(); ++i) out[i] = rotate_many(xs[i], indices);
         return out;
     }
@@ -1195,6 +1247,7 @@ std::vector<std::vector<CtPtr>> Evaluator::rotate_many_batch(const std::vector<C
     std::vector<const u32*> maps;
     for (size_t k : todo) {
         const RotKey rk = rotation_key(indices[k]);
+        bind_key(*rk.key, xs[0]->ell);   // the rows' keys go into the shapes below as pointers (row_keys): bound here, before any pass
         keys.push_back(rk.key.get());
         maps.push_back(rk.map);
     }
@@ -1703,6 +1756,7 @@ std::vector<CtPtr> Evaluator::mult_batch(const std::vector<CtPtr>& a, const std:
     if (!relin_key) throw Error(FHELIN_ERR_KEY, "no relinearisation key (EvalMultKeyGen not called)");
     std::vector<CtPtr> x, y;
     product_operands(a, b, x, y);
+    for (const CtPtr& xi : x) bind_key(*relin_key, xi->ell);   // the products' limbs are known only now; before the first tensor product
     std::vector<CtPtr> out = for_groups(a.size(), batch_limit, [&](size_t f, size_t i) { return x[i]->ell == x[f]->ell; },
                                         [&](const std::vector<size_t>& idx) {
         const int B = (int)idx.size(), ell = x[idx[0]]->ell;
@@ -1731,6 +1785,7 @@ std::vector<CtPtr> Evaluator::mult_affine_rescale_batch(const std::vector<CtPtr>
     std::vector<CtPtr> ra = a, rb = b, x(a.size()), y(a.size());
     rescale_degree2(ra, &rb, "mult: operands must have 2 components");
     for (size_t i = 0; i < a.size(); ++i) match(ra[i], rb[i], x[i], y[i]);
+    for (const CtPtr& xi : x) bind_key(*relin_key, xi->ell);   // relin_key->d goes to inner_product below as a pointer
     const size_t N = c_.N;
     const int K = c_.K, L1 = c_.L + 1;
     hipStream_t s = c_.stream;
@@ -1819,6 +1874,7 @@ std::vector<CtPtr> Evaluator::mult_affine_batch(const std::vector<CtPtr>& a, con
     const size_t n = a.size();
     std::vector<CtPtr> x, y;
     product_operands(a, b, x, y);
+    for (const CtPtr& xi : x) bind_key(*relin_key, xi->ell);   // relin_key->d goes to launch_ks_inner below as a pointer
     // where the sequence would adjust the PRODUCT to its addend, or has no limb to drop, it runs itself (on the prepared operands: its own
     // preparation finds nothing left to do)
     for (size_t i = 0; i < n; ++i)

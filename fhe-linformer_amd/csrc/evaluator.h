@@ -105,8 +105,18 @@ struct EvalKey {
     // key streams of ks_inner_multi are contiguous and only the digits are gathered.  A plain rotation gathers at its inner product
     // too and reads the same copy (KsShape::gather).  Built on first use (Evaluator::permuted).
     mutable u64* d_perm = nullptr;
-    int digits = 0;
+    int digits = 0;        // digits held: Context::digits_at(max_ell); d, d_perm and the folded copies all have this many
     bool seeded = false;   // every a half is the expansion of the key-set seed (include/fhelin.h "Seeded evaluation keys")
+    // level-capped keys (include/fhelin.h "Level-capped keys"): the most live limbs a key switch may bind this key at.  Of the digits
+    // held, the Q rows max_ell .. L are zero (never read at ell <= max_ell); max_ell == L+1: uncapped, today's key
+    int max_ell = 0;
+    // what the key is, for the refusal's message and the usage recorder: kind 1 relinearisation / 2 rotation / 3 conjugation as in
+    // the key-set file (0: not known), its Galois element (0 for kind 1), the rotation index it was generated for where known
+    int kind = 0;
+    u64 galois = 0;
+    bool has_index = false;
+    int index = 0;
+    bool capped() const { return max_ell < ctx->L + 1; }
     ~EvalKey();
     size_t words() const { return (size_t)digits * 2 * (ctx->L + 1 + ctx->K) * ctx->N; }
 };
@@ -142,7 +152,15 @@ public:
     bool adjust_items = true;  // the integer products of a batched level adjustment in one launch per 32 ciphertexts (adjust_deg1_batch); FHELIN_ADJUST_ITEMS=0: one launch each
     int batch_limit = 32;   // rows processed per batched key switch (FHELIN_BATCH overrides; 16 / 24 / 32 / 48 / 64 re-measured at the end of round 2: DESIGN.md)
     CtPtr clone(const CtPtr& a);
-    KeyPtr new_key();
+    KeyPtr new_key(int max_ell = 0);   // max_ell in 1 .. L: a level-capped key (zero-filled: its absent rows stay zero); 0 or L+1: uncapped
+
+    // ---- level-capped keys (include/fhelin.h "Level-capped keys")
+    // THE check: every site that hands `key` to a KsShape or an accumulator at `ell` live limbs calls this before it launches or counts
+    // anything.  ell > key.max_ell is FHELIN_ERR_KEY (the rows such a switch would read are not held).  While the usage recorder runs it
+    // also notes max(ell) for the key.  One integer comparison on the default path.
+    void bind_key(const EvalKey& key, int ell);
+    bool usage_on = false;
+    std::map<std::pair<int, u64>, int> usage;   // (kind, galois) -> max ell bound while usage_on
 
     // ---- keys
     std::map<u64, KeyPtr> rot_keys;  // by galois element
@@ -423,6 +441,9 @@ private:
         bool tiles_in_place = true;
     };
     Rotations rotations(const int* indices, int n);
+    // bind_key for every rotation of `rot` at the limbs each operand will be switched at (a degree-2 operand is rescaled first when
+    // rescales_first): the refusal of a batched call comes before its first group runs
+    void bind_rotations(const Rotations& rot, const std::vector<CtPtr>& v, bool rescales_first = false);
     void set_rotations(KsShape& sh, const Rotations& rot, bool shared_digits, const u64* const* keys = nullptr);
     void rotation_sum(KsShape& sh, const u64* ext, const u64* base, size_t c0_stride, const KsOut& o);
     // every degree-2 ciphertext of the list(s) replaced by its rescaled one: one rescale_batch over the distinct ones; FHELIN_ERR_STATE

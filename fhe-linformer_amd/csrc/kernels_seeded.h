@@ -7,14 +7,17 @@
 
 namespace fhelin {
 
-// One ciphertext of a batched expansion: c1 limb l (l < ell) is written to dst + l * N
+// One ciphertext of a batched expansion: c1 limb l (l < ell) is written to dst + l * N.
+// split > 0 (the a half of a level-capped key, include/fhelin.h "Level-capped keys"): ell counts PRESENT rows; row y below split is limb
+// y, row y >= split is limb y + skip (the special limbs: skip = n_q - split), expanded and written at its absolute limb.
 struct SeededEntry {
     SamplerKey key;   // the 32-byte seed as 8 little-endian u32 words
     u64 nonce;
     u64* dst;
     int32_t ell;
-    int32_t pad_ = 0;
-    u64 pad2_ = 0;    // 64 bytes
+    int32_t split = 0;
+    int32_t skip = 0;
+    int32_t pad_ = 0;    // 64 bytes
 };
 static_assert(sizeof(SeededEntry) == 64, "SeededEntry is 64 bytes");
 
@@ -37,5 +40,13 @@ constexpr int KEYGEN_MAX_Q = 64;   // Q limbs of the P mod q_l table passed by v
 // grid (N/4/256, ell, digits)
 void launch_seeded_keygen_combine(const DeviceTables& t, u64* key, const u64* s_to, const u64* s_from, const u64* e, int ell, int digits,
                                   int alpha, int n_q, const u64* p_mod_q, const SamplerKey& seed, u64 kind, u64 galois, hipStream_t st);
+// The same for a switching key capped at max_ell < n_q limbs (include/fhelin.h "Level-capped keys"): only the PRESENT rows - Q limbs
+// 0..max_ell-1 and the ell - n_q special limbs - of the `digits` = digits_at(max_ell) digits held are formed, by the same expansion, and
+// written where the uncapped launch writes them (limb stride ell; the absent rows are not touched).  e: the noise of the UNCAPPED shape,
+// [>= digits][ell][N], of which the present rows are read (the others need not be in NTT form).  ell = the key basis (all n_limbs).
+// grid (N/4/256, max_ell + ell - n_q, digits)
+void launch_seeded_keygen_combine_capped(const DeviceTables& t, u64* key, const u64* s_to, const u64* s_from, const u64* e, int ell, int digits,
+                                         int alpha, int n_q, int max_ell, const u64* p_mod_q, const SamplerKey& seed, u64 kind, u64 galois,
+                                         hipStream_t st);
 
 }  // namespace fhelin

@@ -11,7 +11,7 @@
 //                                grid (N/4/256, ell, n_vec)
 //  * seeded_keygen_combine_kernel : one key of seeded key generation (include/fhelin.h "Seeded evaluation keys"), every digit in
 //                                one launch: b = e - a s_to (+ (P mod q_l) s_from on the digit's limbs), a in registers.
-//                                grid (N/4/256, ell, digits)
+//                                grid (N/4/256, ell, digits); the capped form: grid (N/4/256, max_ell + n_p, digits')
 // Cost: the 20 ChaCha rounds are ~1,000 32-bit VALU operations per 64-byte block against 32 bytes of c1 written per block (plus
 // the 128-bit Barrett reductions): both kernels are bound by the VALU, not by HBM.  No LDS, no MFMA.
 #include <hip/hip_runtime.h>
@@ -52,8 +52,8 @@ __device__ __forceinline__ void seeded_residues4(const SamplerKey& key, u64 nonc
 
 __global__ __launch_bounds__(SE_THREADS) void seeded_expand_kernel(DeviceTables t, const SeededEntry* __restrict__ tab) {
     const SeededEntry& e = tab[blockIdx.z];
-    const int l = blockIdx.y;
-    if (l >= e.ell) return;
+    if ((int)blockIdx.y >= e.ell) return;
+    const int l = e.split > 0 && (int)blockIdx.y >= e.split ? (int)blockIdx.y + e.skip : (int)blockIdx.y;   // block-uniform
     const size_t N = (size_t)1 << t.log_n;
     const u32 b = blockIdx.x * SE_THREADS + threadIdx.x;
     if (b >= N / 4) return;
@@ -93,13 +93,18 @@ __global__ __launch_bounds__(SE_THREADS) void sk_encrypt_combine_kernel(DeviceTa
 
 // The limb index l = blockIdx.y is over Q then P (the key basis); digit j = blockIdx.z.  The s_from term, on limbs
 // [lo, hi) of digit j only, is a wave-uniform branch.
+// CAPPED (include/fhelin.h "Level-capped keys"): blockIdx.y runs over the present_q + n_p PRESENT rows of a key capped at present_q limbs
+// and is mapped to the absolute limb l - Q limb y, or special limb n_q + (y - present_q), a block-uniform select - which the ChaCha counter,
+// the modulus and every address below take: the rows written are, residue for residue, the uncapped key's, at the same full-stride places.
+template <bool CAPPED>
 __global__ __launch_bounds__(SE_THREADS) void seeded_keygen_combine_kernel(DeviceTables t, u64* __restrict__ key, const u64* __restrict__ s_to,
                                                                             const u64* __restrict__ s_from, const u64* __restrict__ e, int ell,
-                                                                            int alpha, int n_q, SamplerKey seed, u64 nonce0, PModSet pm) {
+                                                                            int alpha, int n_q, int present_q, SamplerKey seed, u64 nonce0, PModSet pm) {
     const size_t N = (size_t)1 << t.log_n;
     const u32 b = blockIdx.x * SE_THREADS + threadIdx.x;
     if (b >= N / 4) return;
-    const int j = blockIdx.z, l = blockIdx.y;
+    const int j = blockIdx.z;
+    const int l = CAPPED && (int)blockIdx.y >= present_q ? n_q + ((int)blockIdx.y - present_q) : (int)blockIdx.y;
     const Barrett br = seeded_barrett(t, l);
     u64 a[4];
     seeded_residues4(seed, nonce0 | ((u64)j << 40), l, b, br, a);
@@ -156,8 +161,22 @@ void launch_seeded_keygen_combine(const DeviceTables& t, u64* key, const u64* s_
     if (s_from)
         for (int l = 0; l < n_q; ++l) pm.v[l] = p_mod_q[l];
     const unsigned bx = (unsigned)((((size_t)1 << t.log_n) / 4 + SE_THREADS - 1) / SE_THREADS);
-    hipLaunchKernelGGL(seeded_keygen_combine_kernel, dim3(bx, (unsigned)ell, (unsigned)digits), dim3(SE_THREADS), 0, st, t, key, s_to, s_from,
-                       e, ell, alpha, n_q, seed, key_nonce(kind, 0, galois), pm);
+    hipLaunchKernelGGL(seeded_keygen_combine_kernel<false>, dim3(bx, (unsigned)ell, (unsigned)digits), dim3(SE_THREADS), 0, st, t, key, s_to,
+                       s_from, e, ell, alpha, n_q, n_q, seed, key_nonce(kind, 0, galois), pm);
+}
+
+void launch_seeded_keygen_combine_capped(const DeviceTables& t, u64* key, const u64* s_to, const u64* s_from, const u64* e, int ell, int digits,
+                                         int alpha, int n_q, int max_ell, const u64* p_mod_q, const SamplerKey& seed, u64 kind, u64 galois,
+                                         hipStream_t st) {
+    if (ell != t.n_limbs || ell <= n_q || digits < 1 || digits > 65535 || n_q < 1 || n_q > KEYGEN_MAX_Q || alpha < 1 || max_ell < 1 ||
+        max_ell > n_q || !s_from || (size_t)(digits - 1) * alpha >= (size_t)max_ell)
+        return;   // callers check (client.cpp): a switching key over Q and P, its digits those of a switch at max_ell limbs
+    PModSet pm{};
+    for (int l = 0; l < n_q; ++l) pm.v[l] = p_mod_q[l];
+    const unsigned bx = (unsigned)((((size_t)1 << t.log_n) / 4 + SE_THREADS - 1) / SE_THREADS);
+    const unsigned rows = (unsigned)(max_ell + (ell - n_q));
+    hipLaunchKernelGGL(seeded_keygen_combine_kernel<true>, dim3(bx, rows, (unsigned)digits), dim3(SE_THREADS), 0, st, t, key, s_to, s_from, e,
+                       ell, alpha, n_q, max_ell, seed, key_nonce(kind, 0, galois), pm);
 }
 
 }  // namespace fhelin

@@ -772,3 +772,39 @@ def forward(ctl, w, x_in, X_E, X_F, trace=None, variant="main"):
 
 def logits_from_slots(v):
     return np.asarray(v)[np.arange(20) * 128]
+
+
+def record_key_caps(ctl, w, make_inputs, variant="main", plan=None, margin=0):
+    """One pass of a driver variant under the key-usage recorder (include/fhelin.h "Level-capped keys"): returns (caps, result) - the
+    cap table Engine.set_key_caps takes, every key capped at the most limbs this pass switched it at, and the pass's result handle.
+    make_inputs: a callable that returns the encrypted inputs (ingest_sample / encrypt_inputs); it is called inside the pass so that,
+    with `plan` (Engine.level_plan_end's list), the inputs are the applied plan's first sources as in every planned pass.
+    The table does not depend on the data: it is fixed by the parameters, the plan, the variant and the sample length S, and can be
+    kept next to the model (save_key_caps / load_key_caps).  Caps recorded under one plan are valid for that plan only - without a
+    plan, or under another, values travel at other levels: a pass that goes higher than the caps is refused with FHELIN_ERR_KEY,
+    it does not silently misdecrypt."""
+    from .capi import caps_from_usage
+    e = ctl.e
+    if plan is not None:
+        e.set_level_plan(plan)
+        e.level_plan_begin("apply")
+    try:
+        with e.key_usage() as u:
+            res = forward_encrypted(ctl, w, make_inputs(), variant=variant)
+    finally:
+        if plan is not None:
+            e.level_plan_end()
+    return caps_from_usage(u.table, e.n_q, margin), res
+
+
+def save_key_caps(path, caps, **meta):
+    """the cap table as JSON, with whatever identifies the pass it was recorded from (preset, plan, variant, S)"""
+    import json
+    with open(path, "w") as f:
+        json.dump({"caps": [[int(k), int(g), int(m)] for k, g, m in caps], **meta}, f)
+
+
+def load_key_caps(path):
+    import json
+    with open(path) as f:
+        return [tuple(e) for e in json.load(f)["caps"]]

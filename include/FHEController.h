@@ -279,6 +279,15 @@ public:
      * every key's uniform half the expansion of a public key-set seed; save_evaluation_keys(filename, true) then writes the compact
      * set (b halves and the seed, half the bytes), which load_evaluation_context reads as it reads the full one. */
     void set_seeded_keys(bool on) { seeded_keys = on; }
+    /* Level-capped keys (include/fhelin.h "Level-capped keys"), optional: set_key_caps(kind, galois, max_ell) before generate_context /
+     * load_context hands the table to fhelin_ctx_set_key_caps ahead of the first key, so every key the reference's call sequence then
+     * generates is made only as deep as the table says.  Nothing else changes: the same methods in the same order. */
+    void set_key_caps(const vector<int32_t>& kind, const vector<uint64_t>& galois, const vector<int32_t>& max_ell) {
+        if (kind.size() != galois.size() || kind.size() != max_ell.size()) throw std::runtime_error("set_key_caps: three arrays of one length");
+        cap_kind = kind;
+        cap_galois = galois;
+        cap_max_ell = max_ell;
+    }
     /* Interleaved samples (include/fhelin.h "Interleaved samples"): set_interleave(s) before generate_context / load_context /
      * load_evaluation_context makes every ciphertext carry s samples (s = 2, 4, ... with num_slots * s <= N/2).  The circuit, its
      * rotation indices and num_slots stay as they are (logical); encode / encrypt replicate their values into every sample (model
@@ -905,8 +914,13 @@ private:
     }
     bool seeded_keys = false;   // set_seeded_keys: applied between context creation and keygen
     int interleave_stride = 0;  // set_interleave: applied there too (0: not set, the context's default of 1 or a key set's own)
+    vector<int32_t> cap_kind, cap_max_ell;   // set_key_caps: applied there too
+    vector<uint64_t> cap_galois;
     void apply_seeded_keys() {   // the settings a fresh context takes before its first key: seeded keys, interleaved samples
         if (seeded_keys) fhelin_shim::check(fhelin_ctx_set_seeded_keys(context, 1), "SetSeededKeys");
+        if (!cap_kind.empty())
+            fhelin_shim::check(fhelin_ctx_set_key_caps(context, cap_kind.data(), cap_galois.data(), cap_max_ell.data(), (int32_t)cap_kind.size()),
+                               "SetKeyCaps");
         apply_interleave();
     }
     void apply_interleave() {

@@ -921,6 +921,62 @@ int fhelin_decrypt_batch(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n, 
  * FHELIN_DEVICE_DECODE=1 in the environment when the context is created. */
 int fhelin_ctx_set_device_decode(fhelin_ctx* c, int32_t on);
 
+/* ---- level-capped keys: generate, ship and hold keys only as deep as their use ----------------------------------------------
+ * A hybrid key switch at ell live limbs reads the first digits_at(ell) = ceil(ell / alpha) digits of its key and, within them, the Q rows
+ * 0 .. ell-1 and the n_p special rows.  A key that is only ever used at ell <= max_ell therefore needs nothing else.  A CAPPED key
+ * (relinearisation, rotation or conjugation) carries max_ell, 1 <= max_ell < n_q; max_ell = n_q is an uncapped key, today's in every
+ * respect.  Its digit count is digits' = digits_at(max_ell); its PRESENT ROWS are, for digits 0 .. digits'-1 and both halves, the Q limbs
+ * 0 .. max_ell-1 and all n_p special limbs.
+ *
+ * Sub-block rule: a capped key is, residue for residue, the present rows of the key the same context would have made uncapped at that
+ * point - in default mode and in seeded-key mode (digit j encrypts (P mod q_t) s_from on digit j's own limbs whatever the level of its
+ * later use; the seeded a half's nonce is per digit and its limb index absolute).  Generating it consumes the client generator and the
+ * device sampler exactly as generating the uncapped key does, so every key made afterwards is unchanged too; and every operation at
+ * ell <= max_ell gives bit-identical results with the capped and with the uncapped key.
+ *
+ * Device layout: [digits'][2][n_q + n_p][N] - the limb stride of every key, so no key-switch kernel knows about caps; the absent Q rows
+ * are zero-filled once, when the key is made.  fhelin_key_export writes exactly that (digits' digits, absent rows zero).  The permuted
+ * and the folded copies have the key's own digit count.  What the cap saves in device memory is the digits dropped.  fhelin_key_import
+ * installs uncapped keys only.
+ *
+ * Enforcement: every place that binds a key to a launch at ell limbs checks ell <= max_ell first (rotations of every form, hoisted
+ * dots and their folded keys, linear transforms, relinearisation in every product, the bootstrap's SubSum, linear stages and
+ * conjugations).  A switch above the cap is FHELIN_ERR_KEY; the message names the key (rotation index where the context generated it,
+ * Galois element), its cap and the limbs asked for.  The refused call counts no key switch, returns no handle and leaves the level plan
+ * where it was; in a deferred operation the error surfaces where that operation's errors surface.
+ *
+ * File formats: VERSION 2 of both "FHELINEK" and "FHELINEC".  The header is version 1's; the key table has 48-byte entries - the 40
+ * bytes of version 1, then u32 max_ell, then u32 0 (reserved).  The public key and uncapped keys carry n_q in max_ell.
+ *   full    payload of a switching key [digits'][2][max_ell + n_p][N]; words counts the stored words; digest covers what is stored
+ *   compact payload [digits'][max_ell + n_p][N], the b halves; words counts the stored words; digest is the version 2 FULL form's: b
+ *           and the expanded a, in storage order
+ * Vector j of a payload belongs to limb r = j mod (max_ell + n_p): Q limb r if r < max_ell, else special limb r - max_ell.  Digest
+ * definition and 4096-byte alignment are unchanged.  A context that holds no capped key writes version 1, byte for byte as before;
+ * otherwise version 2; a context loaded from a version 2 set rewrites identical bytes.  fhelin_evalkeys_params, _info and _load read
+ * versions 1 and 2 of both magics and refuse, all or nothing with FHELIN_ERR_ARG, max_ell outside 1 .. n_q, digits other than
+ * digits_at(max_ell), words that do not match, and a non-zero reserved word.  A loaded capped key is enforced like a generated one. */
+/* The cap table of a client context: n entries (kind, galois, max_ell); kind 1 relinearisation (galois 0), 2 rotation (its Galois
+ * element: valid at any interleave stride), 3 conjugation (galois 2N-1), as in the key-set file.  Every key the context generates
+ * AFTERWARDS that matches an entry is generated capped - fhelin_gen_relin_key, fhelin_gen_rotation_keys, fhelin_gen_conj_key, the keys
+ * fhelin_bootstrap_setup generates itself, the keys of wrapped inputs and linear transforms.  Keys without an entry, or with
+ * max_ell = n_q, are uncapped.  A second call replaces the table (n = 0 clears it).  Checked before anything changes, in this order: an
+ * evaluation context FHELIN_ERR_KEY; kind, max_ell or galois out of range, or a duplicate entry FHELIN_ERR_ARG; an entry for a key the
+ * context already holds FHELIN_ERR_STATE.  Works on a host-only context. */
+int fhelin_ctx_set_key_caps(fhelin_ctx* c, const int32_t* kind, const uint64_t* galois, const int32_t* max_ell, int32_t n);
+/* digits held, max_ell and whether the key is seeded; kind / index as fhelin_key_export (0 relinearisation, 1 rotation by index,
+ * 2 conjugation); any out pointer may be NULL.  FHELIN_ERR_KEY: key not present. */
+int fhelin_key_info(fhelin_ctx* c, int32_t kind, int32_t index, int32_t* digits, int32_t* max_ell, int32_t* seeded);
+/* Usage recorder: between _begin and _end every key switch the context issues notes max(ell) for its key - on the host, where the key
+ * is bound to its launch (the same place as the cap check).  _end first evaluates everything deferred on all lanes, then returns the
+ * table sorted by (kind, galois) in the encoding fhelin_ctx_set_key_caps takes: *n = its length, min(cap, *n) entries filled.  A key
+ * that was never used has no entry; the conjugation key is reported once, as kind 3.  Works on evaluation contexts; changes no result
+ * and no level-plan state.  _begin clears the table and (re)starts the recording; _end stops it, and the table stays readable through
+ * further _end calls until the next _begin (a caller sizes its buffers with cap = 0 first).  The table is a property
+ * of the program and its level plan, not of the data: caps recorded under one plan are valid for that plan only - a pass that goes
+ * higher is refused with FHELIN_ERR_KEY, it does not silently misdecrypt. */
+int fhelin_key_usage_begin(fhelin_ctx* c);
+int fhelin_key_usage_end(fhelin_ctx* c, int32_t* kind, uint64_t* galois, int32_t* max_ell, int32_t cap, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif
