@@ -223,6 +223,7 @@ def load_library():
         "fhelin_evalkeys_info": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]),
         "fhelin_evalkeys_load": (i32, [vp, C.c_char_p]),
         "fhelin_evalkeys_save_compact": (i32, [vp, C.c_char_p]),
+        "fhelin_evalkeys_save_packed": (i32, [vp, C.c_char_p, i32]),
         "fhelin_ctx_set_seeded_keys": (i32, [vp, i32]),
         "fhelin_ctx_key_set_seed": (i32, [vp, vp]),
         "fhelin_debug_key_digest": (i32, [vp, vp, i32, i32, C.POINTER(C.c_uint64), C.POINTER(i32)]),
@@ -231,6 +232,13 @@ def load_library():
         "fhelin_ct_export_compact": (i32, [vp, vp, vp, C.c_size_t]),
         "fhelin_compact_info": (i32, [vp, C.c_size_t, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "fhelin_ct_import_compact": (i32, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), i32, C.POINTER(vp)]),
+        "fhelin_ct_packed_bytes": (i32, [vp, vp, i32, C.POINTER(C.c_size_t)]),
+        "fhelin_ct_export_packed": (i32, [vp, vp, i32, vp, C.c_size_t]),
+        "fhelin_packed_info": (i32, [vp, C.c_size_t] + [C.POINTER(i32)] * 6),
+        "fhelin_ct_import_packed": (i32, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), i32, C.POINTER(vp)]),
+        "fhelin_debug_pack": (i32, [vp, vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "fhelin_debug_unpack": (i32, [vp, vp, C.c_size_t, vp, i32, vp]),
+        "fhelin_debug_pack_rate": (i32, [vp, vp, i32, i32, f32p]),
         "fhelin_debug_seeded_expand": (i32, [vp, vp, C.c_uint64, i32, i32, i32, vp, f32p]),
         "fhelin_client_ingest_wrapped": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(vp),
                                                C.POINTER(i32), vp]),
@@ -285,6 +293,18 @@ def compact_info(blob):
     if rc != 0:
         raise FhelinError(rc, lib.fhelin_last_error().decode())
     return dict(zip(("log_n", "ell", "deg", "slots"), (x.value for x in v)))
+
+
+def packed_info(blob):
+    """header of a packed ciphertext blob (include/fhelin.h "Packed formats"), validated against itself and the exact size its own
+    moduli give: dict(log_n, ell, deg, slots, stored, count); host-only"""
+    lib = load_library()
+    b = bytes(blob)
+    v = [C.c_int32() for _ in range(6)]
+    rc = lib.fhelin_packed_info(C.c_char_p(b), len(b), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise FhelinError(rc, lib.fhelin_last_error().decode())
+    return dict(zip(("log_n", "ell", "deg", "slots", "stored", "count"), (x.value for x in v)))
 
 
 def interleave(vectors):
@@ -809,6 +829,50 @@ class Engine:
         outs = self._outs(n)
         self._ck(self.lib.fhelin_ct_import_compact(self.h, ptrs, sizes, n, outs))
         return self._cts(outs, n)
+
+    # ---- packed formats (include/fhelin.h "Packed formats")
+    def save_evalkeys_packed(self, path, compact=False):
+        """save_eval_keys with every residue at its modulus width ("FHELINEP"); from_eval_keys reads it like the other two formats"""
+        self._ck(self.lib.fhelin_evalkeys_save_packed(self.h, str(path).encode(), 1 if compact else 0))
+
+    def import_packed(self, blobs):
+        """packed blobs (Ct.export_packed, seeded or full) -> handles, all in one call; all or nothing"""
+        bs = [bytes(b) for b in blobs]
+        n = len(bs)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.cast(C.c_char_p(b), C.c_void_p) for b in bs])
+        sizes = (C.c_size_t * max(n, 1))(*[len(b) for b in bs])
+        outs = self._outs(n)
+        self._ck(self.lib.fhelin_ct_import_packed(self.h, ptrs, sizes, n, outs))
+        return self._cts(outs, n)
+
+    def debug_pack(self, words, widths):
+        """the pack kernel alone: words [n_vec][N] (each below 2^widths[i]) -> the packed vectors back to back, one u64 array"""
+        w, wp = _np_u64(words)
+        assert w.ndim == 2 and w.shape[1] == self.N
+        wd = np.ascontiguousarray(widths, dtype=np.int32)
+        assert wd.shape == (w.shape[0],)
+        cap = int(self.N // 64 * 64 * w.shape[0])
+        out = np.empty(cap, dtype=np.uint64)
+        n = C.c_size_t()
+        self._ck(self.lib.fhelin_debug_pack(self.h, wp, wd.ctypes.data_as(C.c_void_p), w.shape[0], out.ctypes.data_as(C.c_void_p), cap,
+                                            C.byref(n)))
+        return out[:n.value].copy()
+
+    def debug_unpack(self, packed, widths):
+        """the unpack kernel alone: packed vectors back to back -> [n_vec][N]"""
+        p, pp = _np_u64(packed)
+        wd = np.ascontiguousarray(widths, dtype=np.int32)
+        out = np.empty((wd.size, self.N), dtype=np.uint64)
+        self._ck(self.lib.fhelin_debug_unpack(self.h, pp, p.size, wd.ctypes.data_as(C.c_void_p), wd.size, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def debug_pack_rate(self, widths, reps=5):
+        """device-event times of pack, copy, unpack, copy (the copy: the same unpacked bytes, device to device) in turn: ms [reps][4]"""
+        wd = np.ascontiguousarray(widths, dtype=np.int32)
+        ms = np.zeros((int(reps), 4), dtype=np.float32)
+        self._ck(self.lib.fhelin_debug_pack_rate(self.h, wd.ctypes.data_as(C.c_void_p), wd.size, int(reps),
+                                                 ms.ctypes.data_as(C.POINTER(C.c_float))))
+        return ms
 
     def debug_seeded_expand(self, seed, nonce0, ell, n_ct=1, reps=0, download=True):
         """the expansion kernel alone: (c1 [n_ct][ell][N] or None, mean ms per launch over `reps` timed launches)"""
@@ -1668,6 +1732,19 @@ class Ct:
         n = self.compact_bytes()
         out = C.create_string_buffer(n)
         self.eng._ck(self.eng.lib.fhelin_ct_export_compact(self.eng.h, self.h, out, n))
+        return out.raw
+
+    def packed_bytes(self, seeded=False):
+        n = C.c_size_t()
+        self.eng._ck(self.eng.lib.fhelin_ct_packed_bytes(self.eng.h, self.h, 1 if seeded else 0, C.byref(n)))
+        return n.value
+
+    def export_packed(self, seeded=False):
+        """the packed blob (include/fhelin.h "Packed formats"): every component (seeded=False), or c0 with seed and nonce of an
+        unmodified seeded encryption (seeded=True); bytes"""
+        n = self.packed_bytes(seeded)
+        out = C.create_string_buffer(n)
+        self.eng._ck(self.eng.lib.fhelin_ct_export_packed(self.eng.h, self.h, 1 if seeded else 0, out, n))
         return out.raw
 
     def export_device(self, dptr, cap_words):

@@ -9,6 +9,9 @@
 // and half - plain 1D copies, a few MB each at driver scale), and the digest reads the rows where they lie through the strided digest
 // launch (kernels_keys.h), one launch for the Q rows and one for the special rows of a key.  No scatter kernel: a scatter would need
 // the dense payload in device memory first, which is exactly the copy the cap saves.
+// A packed set ("FHELINEP", include/fhelin.h "Packed formats") holds the same present rows, every limb vector at its modulus width: one
+// key at a time is packed into (or unpacked out of) a scratch block of one key's packed payload, which is what the staging pipeline then
+// streams; digests are those of the unpacked residues, computed by the same launches as for the other two formats.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -17,6 +20,7 @@
 #include <memory>
 #include "capi_internal.h"
 #include "kernels_keys.h"
+#include "kernels_pack.h"
 #include "kernels_seeded.h"
 
 using namespace fhelin;
@@ -25,6 +29,9 @@ namespace {
 
 constexpr char EK_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'K'};
 constexpr char EC_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'C'};   // compact (seeded) set
+constexpr char EP_MAGIC[8] = {'F', 'H', 'E', 'L', 'I', 'N', 'E', 'P'};   // packed set, full or compact (u32 halves at 128)
+constexpr uint32_t EP_VERSION = 1;
+constexpr size_t EP_HEADER = 136;   // EK's 96, the key-set seed (zero for a full set), u32 halves, u32 0
 constexpr uint32_t EK_VERSION = 1, EC_VERSION = 1;
 constexpr uint32_t EK_VERSION_CAPS = 2;   // both magics: 48-byte table entries (the 40 of version 1, u32 max_ell, u32 0), present rows only
 constexpr size_t EK_HEADER = 96, EC_HEADER = 128, EK_ENTRY = 40, EK_ENTRY_CAPS = 48, EK_ALIGN = 4096;
@@ -44,7 +51,8 @@ struct EkFile {
     std::vector<EkEntry> keys;
     uint64_t data_offset = 0;
     int32_t stride = 1;       // interleave stride (header word 88: 0 = 1)
-    bool compact = false;     // "FHELINEC": b halves only, a expanded from `seed`
+    bool compact = false;     // "FHELINEC", or "FHELINEP" with halves = 1: b halves only, a expanded from `seed`
+    bool packed = false;      // "FHELINEP": every limb vector at its modulus width; 48-byte table entries, words = packed words
     uint32_t version = 1;
     uint8_t seed[32] = {};
 };
@@ -94,13 +102,26 @@ EkFile read_header(const char* path) {
     if (fsize < EK_HEADER || std::fread(h, 1, EK_HEADER, fh.f) != EK_HEADER) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
     EkFile e;
     if (std::memcmp(h, EC_MAGIC, 8) == 0) e.compact = true;
+    else if (std::memcmp(h, EP_MAGIC, 8) == 0) e.packed = true;
     else if (std::memcmp(h, EK_MAGIC, 8) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: bad magic");
     e.version = get<uint32_t>(h, 8);
-    if (e.version != (e.compact ? EC_VERSION : EK_VERSION) && e.version != EK_VERSION_CAPS)
+    if (e.packed ? e.version != EP_VERSION : e.version != (e.compact ? EC_VERSION : EK_VERSION) && e.version != EK_VERSION_CAPS)
         throw Error(FHELIN_ERR_ARG, "evaluation-key set: unsupported version");
-    const size_t entry = e.version == EK_VERSION_CAPS ? EK_ENTRY_CAPS : EK_ENTRY;
-    const uint64_t head = e.compact ? EC_HEADER : EK_HEADER;
-    if (e.compact && (fsize < EC_HEADER || std::fread(e.seed, 1, 32, fh.f) != 32)) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
+    const bool caps_table = e.packed || e.version == EK_VERSION_CAPS;   // 48-byte entries that carry max_ell
+    const size_t entry = caps_table ? EK_ENTRY_CAPS : EK_ENTRY;
+    if (e.packed) {   // seed, halves, reserved
+        uint8_t x[EP_HEADER - EK_HEADER];
+        if (fsize < EP_HEADER || std::fread(x, 1, sizeof(x), fh.f) != sizeof(x)) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
+        std::memcpy(e.seed, x, 32);
+        const uint32_t halves = get<uint32_t>(x, 32);
+        if (halves < 1 || halves > 2 || get<uint32_t>(x, 36) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: packed set: halves must be 1 or 2");
+        e.compact = halves == 1;
+        if (!e.compact)
+            for (uint8_t b : e.seed)
+                if (b) throw Error(FHELIN_ERR_ARG, "evaluation-key set: a full packed set carries no key-set seed");
+    }
+    const uint64_t head = e.packed ? EP_HEADER : e.compact ? EC_HEADER : EK_HEADER;
+    if (!e.packed && e.compact && (fsize < EC_HEADER || std::fread(e.seed, 1, 32, fh.f) != 32)) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated header");
     const uint32_t n_keys = get<uint32_t>(h, 12);
     for (int i = 0; i < 9; ++i) e.prm[i] = get<int32_t>(h, 16 + 4 * i);
     for (int i = 0; i < 7; ++i) e.boot[i] = get<int32_t>(h, 52 + 4 * i);
@@ -125,6 +146,13 @@ EkFile read_header(const char* path) {
     if (fsize < table_end) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated key table");
     e.moduli.resize(nm);
     if (std::fread(e.moduli.data(), 8, nm, fh.f) != nm) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated moduli");
+    std::vector<uint64_t> width(nm, 64);   // packed: words of one limb vector = N / 64 * width
+    if (e.packed)
+        for (uint64_t l = 0; l < nm; ++l) {
+            width[l] = (uint64_t)pack_width(e.moduli[l]);
+            if (width[l] < (uint64_t)PACK_MIN_WIDTH || width[l] > (uint64_t)PACK_MAX_WIDTH)
+                throw Error(FHELIN_ERR_ARG, "evaluation-key set: packed set: a modulus outside 20..60 bits");
+        }
     std::vector<uint8_t> t(entry * n_keys);
     if (n_keys && std::fread(t.data(), 1, t.size(), fh.f) != t.size()) throw Error(FHELIN_ERR_ARG, "evaluation-key set: truncated key table");
     if (e.data_offset != (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN)
@@ -142,7 +170,7 @@ EkFile read_header(const char* path) {
         x.words = get<uint64_t>(r, 24);
         x.digest = get<uint64_t>(r, 32);
         x.max_ell = (uint32_t)n_q;
-        if (e.version == EK_VERSION_CAPS) {
+        if (caps_table) {
             x.max_ell = get<uint32_t>(r, 40);
             if (get<uint32_t>(r, 44) != 0) throw Error(FHELIN_ERR_ARG, "evaluation-key set: non-zero reserved word in the key table");
             if (x.max_ell < 1 || x.max_ell > (uint32_t)n_q || (x.kind == EK_PUBLIC && x.max_ell != (uint32_t)n_q))
@@ -154,7 +182,13 @@ EkFile read_header(const char* path) {
         if (x.kind != EK_ROTATION && ++seen[x.kind] > 1) throw Error(FHELIN_ERR_ARG, "evaluation-key set: duplicate key");
         // the compact form stores the b halves only
         const uint64_t halves = e.compact ? 1 : 2;
-        const uint64_t want = x.kind == EK_PUBLIC ? halves * (uint64_t)n_q * N : (uint64_t)x.digits * halves * ((uint64_t)x.max_ell + n_p) * N;
+        uint64_t want = x.kind == EK_PUBLIC ? halves * (uint64_t)n_q * N : (uint64_t)x.digits * halves * ((uint64_t)x.max_ell + n_p) * N;
+        if (e.packed) {   // the same vectors, each N w / 64 words: Q limbs 0 .. max_ell-1, then (switching keys) the special limbs
+            uint64_t bits = 0;
+            for (uint64_t l = 0; l < x.max_ell; ++l) bits += width[l];
+            for (uint64_t l = 0; x.kind != EK_PUBLIC && l < (uint64_t)n_p; ++l) bits += width[(uint64_t)n_q + l];
+            want = (x.kind == EK_PUBLIC ? halves : (uint64_t)x.digits * halves) * bits * (N / 64);
+        }
         if ((x.kind == EK_PUBLIC) != (x.digits == 0) || x.digits > (uint32_t)n_q || x.words != want)
             throw Error(FHELIN_ERR_ARG, "evaluation-key set: key size does not match the parameters");
         const uint64_t g_want = x.kind == EK_CONJ ? 2 * N - 1 : 0;
@@ -209,6 +243,9 @@ struct Seg {
     // > 0: a capped switching key [digits][2][n_q + n_p][N] at d; words counts its PRESENT rows, [digits][2][max_ell + n_p][N]
     int max_ell = 0;
     int digits = 0;
+    // a run of rows that is written or read (the packed formats pack row by row): row r belongs to limb limb0 + r % limbs
+    int limb0 = 0;
+    int limbs = 0;
 };
 
 // the runs of a capped key's present rows in storage order ([digits][halves][max_ell + n_p][N]; halves 1: the b halves): per digit and
@@ -218,8 +255,8 @@ void present_runs(std::vector<Seg>& out, const Context& x, u64* d, int digits, i
     for (int j = 0; j < digits; ++j)
         for (int h = 0; h < halves; ++h) {
             u64* base = d + ((size_t)2 * j + h) * nl * N;
-            out.push_back({base, (size_t)max_ell * N});
-            out.push_back({base + (size_t)(x.L + 1) * N, (size_t)x.K * N});
+            out.push_back(Seg{base, (size_t)max_ell * N, 0, 0, 0, max_ell});
+            out.push_back(Seg{base + (size_t)(x.L + 1) * N, (size_t)x.K * N, 0, 0, x.L + 1, x.K});
         }
 }
 
@@ -282,6 +319,29 @@ void key_digests(Context& x, const std::vector<Seg>& segs, const std::vector<uin
     }
 }
 
+// packed sets: the rows of runs[lo, hi) in order, one table entry each; the packed vectors lie back to back from `packed` on.  unpack:
+// packed -> rows, else rows -> packed.  Returns the packed words.
+size_t pack_table(std::vector<PackEntry>& tab, const Context& x, const std::vector<Seg>& runs, size_t lo, size_t hi, u64* packed, bool unpack) {
+    const size_t N = x.N;
+    size_t at = 0;
+    for (size_t i = lo; i < hi; ++i)
+        for (size_t r = 0; r < runs[i].words / N; ++r) {
+            const int w = pack_width(x.moduli[runs[i].limb0 + (int)(r % (size_t)runs[i].limbs)]);
+            u64* row = runs[i].d + r * N;
+            tab.push_back(unpack ? PackEntry{packed + at, row, (u32)w, 0} : PackEntry{row, packed + at, (u32)w, 0});
+            at += pack_words(N, w);
+        }
+    return at;
+}
+size_t packed_words_of(const Context& x, const std::vector<Seg>& runs, size_t lo, size_t hi) {
+    std::vector<PackEntry> t;
+    return pack_table(t, x, runs, lo, hi, nullptr, false);
+}
+void check_pack_widths(const Context& x) {
+    for (u64 m : x.moduli)
+        if (pack_width(m) < PACK_MIN_WIDTH || pack_width(m) > PACK_MAX_WIDTH) throw Error(FHELIN_ERR_ARG, "packed key set: a modulus outside 20..60 bits");
+}
+
 bool fresh(const fhelin_ctx* c) {
     if (c->cl.keygen_run() || c->cl.eval_only() || c->cl.has_public_key() || c->ev.relin_key || c->ev.conj_key || c->boot.ready())
         return false;
@@ -294,8 +354,9 @@ std::string key_what(uint32_t kind, uint64_t galois) {
     return std::string(kind_name(kind)) + (kind == EK_ROTATION ? " (Galois element " + std::to_string(galois) + ")" : "");
 }
 
-// v1 (full keys) or compact (b halves and the key-set seed): the same table, digests of the full keys in both
-void save_set(fhelin_ctx* c, const char* path, bool compact) {
+// v1 (full keys) or compact (b halves and the key-set seed): the same table, digests of the full keys in both.  packed: "FHELINEP", the
+// same rows in the same order at their modulus widths; the two unpacked forms are written exactly as before
+void save_set(fhelin_ctx* c, const char* path, bool compact, bool packed = false) {
     Context& x = c->ctx;
     x.require_device();
     x.sync();
@@ -335,6 +396,7 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
     if (ents.empty()) throw Error(FHELIN_ERR_KEY, "evalkeys_save: the context holds no keys");
     if (ents.size() > EK_MAX_KEYS) throw Error(FHELIN_ERR_ARG, "evalkeys_save: too many keys");
     if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "evalkeys_save: ring dimension below 2^12");
+    if (packed) check_pack_widths(x);
     if (compact) {
         if (!c->cl.has_key_seed())
             throw Error(FHELIN_ERR_STATE, "evalkeys_save_compact: the keys are not seeded (fhelin_ctx_set_seeded_keys before fhelin_keygen)");
@@ -355,30 +417,52 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
     }
     // what is written: every key whole, or the b half of every digit
     std::vector<Seg> out;
-    if (compact) {
-        for (size_t k = 0; k < ents.size(); ++k) {
-            const size_t half = ents[k].kind == EK_PUBLIC ? (size_t)(x.L + 1) * x.N : (size_t)(x.L + 1 + x.K) * x.N;
+    std::vector<size_t> out_begin;   // first run of key k (and the end, last)
+    for (size_t k = 0; k < ents.size(); ++k) {
+        out_begin.push_back(out.size());
+        const int rows = ents[k].kind == EK_PUBLIC ? x.L + 1 : x.L + 1 + x.K;   // limbs per half of an uncapped key
+        if (compact) {
+            const size_t half = (size_t)rows * x.N;
             const uint32_t nd = ents[k].kind == EK_PUBLIC ? 1 : ents[k].digits;
             if (segs[k].max_ell > 0) present_runs(out, x, segs[k].d, segs[k].digits, 1, segs[k].max_ell);
             else
-                for (uint32_t j = 0; j < nd; ++j) out.push_back({segs[k].d + (size_t)2 * j * half, half});
+                for (uint32_t j = 0; j < nd; ++j) out.push_back(Seg{segs[k].d + (size_t)2 * j * half, half, 0, 0, 0, rows});
             ents[k].words /= 2;
+        } else {
+            if (segs[k].max_ell > 0) present_runs(out, x, segs[k].d, segs[k].digits, 2, segs[k].max_ell);
+            else out.push_back(Seg{segs[k].d, segs[k].words, 0, 0, 0, rows});
         }
-    } else {
-        for (const Seg& s : segs) {
-            if (s.max_ell > 0) present_runs(out, x, s.d, s.digits, 2, s.max_ell);
-            else out.push_back(s);
+    }
+    out_begin.push_back(out.size());
+    // packed: one table for the whole set (key k's rows -> one scratch block, reused key after key in stream order)
+    Scratch<u64> pk_scratch;
+    Scratch<PackEntry> pk_dtab;
+    std::vector<PackEntry> pk_tab;
+    std::vector<size_t> pk_tab_begin;
+    if (packed) {
+        size_t most = 0;
+        for (size_t k = 0; k < ents.size(); ++k) {
+            ents[k].words = packed_words_of(x, out, out_begin[k], out_begin[k + 1]);
+            most = std::max(most, (size_t)ents[k].words);
         }
+        pk_scratch = x.scratch<u64>(most);
+        for (size_t k = 0; k < ents.size(); ++k) {
+            pk_tab_begin.push_back(pk_tab.size());
+            pack_table(pk_tab, x, out, out_begin[k], out_begin[k + 1], pk_scratch, false);
+        }
+        pk_tab_begin.push_back(pk_tab.size());
+        pk_dtab = x.scratch<PackEntry>(pk_tab.size());
+        hip_check(hipMemcpyAsync(pk_dtab, pk_tab.data(), pk_tab.size() * sizeof(PackEntry), hipMemcpyHostToDevice, x.stream), "pack table upload");
     }
 
     const size_t nm = x.moduli.size();
-    const size_t head = compact ? EC_HEADER : EK_HEADER;
-    const size_t entry = any_capped ? EK_ENTRY_CAPS : EK_ENTRY;
+    const size_t head = packed ? EP_HEADER : compact ? EC_HEADER : EK_HEADER;
+    const size_t entry = any_capped || packed ? EK_ENTRY_CAPS : EK_ENTRY;
     const uint64_t table_end = head + 8 * nm + entry * ents.size();
     const uint64_t data_offset = (table_end + EK_ALIGN - 1) / EK_ALIGN * EK_ALIGN;
     std::vector<uint8_t> h(data_offset, 0);
-    std::memcpy(h.data(), compact ? EC_MAGIC : EK_MAGIC, 8);
-    put<uint32_t>(h.data(), 8, any_capped ? EK_VERSION_CAPS : compact ? EC_VERSION : EK_VERSION);
+    std::memcpy(h.data(), packed ? EP_MAGIC : compact ? EC_MAGIC : EK_MAGIC, 8);
+    put<uint32_t>(h.data(), 8, packed ? EP_VERSION : any_capped ? EK_VERSION_CAPS : compact ? EC_VERSION : EK_VERSION);
     put<uint32_t>(h.data(), 12, (uint32_t)ents.size());
     int32_t prm[9];
     from_params(x.prm, prm);
@@ -391,13 +475,14 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
     put<uint64_t>(h.data(), 80, data_offset);
     if (x.stride != 1) put<uint64_t>(h.data(), 88, (uint64_t)x.stride);   // a set written at stride 1 keeps 0 here
     if (compact) std::memcpy(h.data() + EK_HEADER, c->cl.key_seed(), 32);
+    if (packed) put<uint32_t>(h.data(), 128, compact ? 1u : 2u);   // halves; then u32 0
     std::memcpy(h.data() + head, x.moduli.data(), 8 * nm);
     uint64_t at = data_offset;
     for (size_t k = 0; k < ents.size(); ++k) {
         ents[k].offset = at;
         at += 8 * ents[k].words;
         const size_t o = head + 8 * nm + entry * k;
-        if (any_capped) put<uint32_t>(h.data(), o + 40, ents[k].max_ell);   // then u32 0 (reserved)
+        if (any_capped || packed) put<uint32_t>(h.data(), o + 40, ents[k].max_ell);   // then u32 0 (reserved)
         put<uint32_t>(h.data(), o, ents[k].kind);
         put<uint32_t>(h.data(), o + 4, ents[k].digits);
         put<uint64_t>(h.data(), o + 8, ents[k].galois);
@@ -415,7 +500,16 @@ void save_set(fhelin_ctx* c, const char* path, bool compact) {
         Pinned stg(x.stream);
         int cur = 0;
         size_t pend_bytes[2] = {};
-        for (const Seg& s : out) {
+        // packed: key k is packed into the scratch block (in stream order behind the downloads of key k - 1) and that block is streamed
+        std::vector<Seg> packed_runs;
+        for (size_t k = 0; packed && k < ents.size(); ++k) packed_runs.push_back({pk_scratch, (size_t)ents[k].words});
+        const std::vector<Seg>& runs = packed ? packed_runs : out;
+        for (size_t i = 0; i < runs.size(); ++i) {
+            const Seg& s = runs[i];
+            if (packed && io_ok) {
+                launch_pack_residues(pk_dtab + pk_tab_begin[i], (int)(pk_tab_begin[i + 1] - pk_tab_begin[i]), x.N, x.stream);
+                hip_check(hipGetLastError(), "pack kernel");
+            }
             const size_t bytes = s.words * 8;
             for (size_t off = 0; off < bytes && io_ok; off += EK_STAGE_BYTES) {
                 const size_t n = std::min(EK_STAGE_BYTES, bytes - off);
@@ -491,6 +585,13 @@ int fhelin_evalkeys_save_compact(fhelin_ctx* c, const char* path) {
     FHELIN_CATCH
 }
 
+int fhelin_evalkeys_save_packed(fhelin_ctx* c, const char* path, int32_t compact) {
+    if (!c || !path) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    save_set(c, path, compact != 0, true);
+    FHELIN_CATCH
+}
+
 int fhelin_ctx_set_seeded_keys(fhelin_ctx* c, int32_t on) {
     if (!c) return capi_fail(FHELIN_ERR_ARG, "null argument");
     FHELIN_TRY
@@ -549,18 +650,20 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
     }
     // what the file holds: every key whole, or the b half of every digit (the a halves are expanded below)
     std::vector<Seg> in;
+    std::vector<size_t> in_begin;   // first run of key k (and the end, last)
     std::vector<SeededEntry> tab;
     if (e.compact) {
         SamplerKey sk;
         for (int w = 0; w < 8; ++w) sk.w[w] = get<uint32_t>(e.seed, 4 * w);
         for (size_t k = 0; k < e.keys.size(); ++k) {
+            in_begin.push_back(in.size());
             const bool pub = e.keys[k].kind == EK_PUBLIC;
             const int ell = pub ? x.L + 1 : x.L + 1 + x.K;
             const size_t half = (size_t)ell * x.N;
             const uint32_t nd = pub ? 1 : e.keys[k].digits;
             if (segs[k].max_ell > 0) present_runs(in, x, segs[k].d, segs[k].digits, 1, segs[k].max_ell);
             for (uint32_t j = 0; j < nd; ++j) {
-                if (segs[k].max_ell == 0) in.push_back({segs[k].d + (size_t)2 * j * half, half});
+                if (segs[k].max_ell == 0) in.push_back(Seg{segs[k].d + (size_t)2 * j * half, half, 0, 0, 0, ell});
                 SeededEntry se;
                 se.key = sk;
                 se.nonce = key_nonce(e.keys[k].kind, j, e.keys[k].galois);
@@ -575,18 +678,45 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
             }
         }
     } else {
-        for (const Seg& s : segs) {
+        for (size_t k = 0; k < segs.size(); ++k) {
+            const Seg& s = segs[k];
+            in_begin.push_back(in.size());
             if (s.max_ell > 0) present_runs(in, x, s.d, s.digits, 2, s.max_ell);
-            else in.push_back(s);
+            else in.push_back(Seg{s.d, s.words, 0, 0, 0, kinds[k] == EK_PUBLIC ? x.L + 1 : x.L + 1 + x.K});
         }
     }
+    in_begin.push_back(in.size());
+    // packed: what is read is key k's packed payload, into one scratch block (reused key after key in stream order), and unpacked
+    // from there into the rows the unpacked formats are read into
+    Scratch<u64> pk_scratch;
+    Scratch<PackEntry> pk_dtab;
+    std::vector<PackEntry> pk_tab;
+    std::vector<size_t> pk_tab_begin;
+    std::vector<Seg> packed_runs;
+    if (e.packed) {
+        if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "evalkeys_load: ring dimension below 2^12");
+        size_t most = 0;
+        for (const auto& k : e.keys) most = std::max(most, (size_t)k.words);
+        pk_scratch = x.scratch<u64>(most);
+        for (size_t k = 0; k < e.keys.size(); ++k) {
+            pk_tab_begin.push_back(pk_tab.size());
+            if (pack_table(pk_tab, x, in, in_begin[k], in_begin[k + 1], pk_scratch, true) != e.keys[k].words)
+                throw Error(FHELIN_ERR_ARG, "evalkeys_load: packed key size does not match the context");
+            packed_runs.push_back({pk_scratch, (size_t)e.keys[k].words});
+        }
+        pk_tab_begin.push_back(pk_tab.size());
+        pk_dtab = x.scratch<PackEntry>(pk_tab.size());
+        hip_check(hipMemcpyAsync(pk_dtab, pk_tab.data(), pk_tab.size() * sizeof(PackEntry), hipMemcpyHostToDevice, x.stream), "unpack table upload");
+    }
     {
+        const std::vector<Seg>& runs = e.packed ? packed_runs : in;
         File fh(path, "rb");
         if (!fh.f || std::fseek(fh.f, (long)e.data_offset, SEEK_SET) != 0) throw Error(FHELIN_ERR_ARG, "evalkeys_load: cannot read the payloads");
         // file -> pinned buffer b while buffer b^1's previous chunk is on its way to the device
         Pinned stg(x.stream);
         int cur = 0;
-        for (const Seg& s : in) {
+        for (size_t i = 0; i < runs.size(); ++i) {
+            const Seg& s = runs[i];
             const size_t bytes = s.words * 8;
             for (size_t off = 0; off < bytes; off += EK_STAGE_BYTES) {
                 const size_t n = std::min(EK_STAGE_BYTES, bytes - off);
@@ -596,6 +726,10 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
                 hip_check(hipEventRecord(stg.ev[cur], x.stream), "hipEventRecord(key staging)");
                 stg.used[cur] = true;
                 cur ^= 1;
+            }
+            if (e.packed) {
+                launch_unpack_residues(pk_dtab + pk_tab_begin[i], (int)(pk_tab_begin[i + 1] - pk_tab_begin[i]), x.N, x.stream);
+                hip_check(hipGetLastError(), "unpack kernel");
             }
         }
     }

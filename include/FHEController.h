@@ -30,6 +30,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <fcntl.h>
 #include <fstream>
@@ -320,9 +321,11 @@ public:
         for (int i = 0; i < s; i++) out.emplace_back(flat.begin() + (size_t)i * slots, flat.begin() + (size_t)(i + 1) * slots);
         return out;
     }
-    void save_evaluation_keys(const string& filename, bool compact = false) {
+    void save_evaluation_keys(const string& filename, bool compact = false, bool packed = false) {
         const string path = "../" + parameters_folder + "/" + filename;
-        fhelin_shim::check(compact ? fhelin_evalkeys_save_compact(context, path.c_str()) : fhelin_evalkeys_save(context, path.c_str()),
+        fhelin_shim::check(packed    ? fhelin_evalkeys_save_packed(context, path.c_str(), compact ? 1 : 0)
+                           : compact ? fhelin_evalkeys_save_compact(context, path.c_str())
+                                     : fhelin_evalkeys_save(context, path.c_str()),
                            "Serialize(evaluation keys)");
     }
     void load_evaluation_context(const string& filename, bool verbose = true) {
@@ -796,6 +799,37 @@ public:
         }
         if (!f) throw std::runtime_error("save_compact: write to " + filename + " failed");
     }
+    /* Packed ciphertexts (include/fhelin.h "Packed formats"): every residue at its modulus width, the exact 80-bit scale and a digest.
+     * Each blob takes the seeded form when the handle has one (an unmodified seeded encryption, a wrapped input) and the full form
+     * otherwise.  File: a magic of its own, count, then per ciphertext a u64 byte length and the blob; load_vector reads it through
+     * one batched import (all or nothing). */
+    void save_packed(vector<Ctxt> v, string filename) {
+        ofstream f(filename, ios::out | ios::binary);
+        if (!f.is_open()) throw std::runtime_error("save_packed: cannot create " + filename);
+        uint64_t magic = PACKED_FILE_MAGIC, n = v.size();
+        f.write((const char*)&magic, 8);
+        f.write((const char*)&n, 8);
+        vector<uint8_t> blob;
+        try {
+            for (auto& c : v) {
+                // the seeded form where the handle has one: asking for its size is the test (FHELIN_ERR_STATE otherwise, which only
+                // leaves a message in fhelin_last_error that the next failing call overwrites); any other handle takes the full form
+                size_t bytes = 0;
+                const int32_t seeded = fhelin_ct_packed_bytes(context, c->h, 1, &bytes) == FHELIN_OK ? 1 : 0;
+                if (!seeded) fhelin_shim::check(fhelin_ct_packed_bytes(context, c->h, 0, &bytes), "Serialize(packed)");
+                blob.resize(bytes);
+                fhelin_shim::check(fhelin_ct_export_packed(context, c->h, seeded, blob.data(), bytes), "Serialize(packed)");
+                const uint64_t len = bytes;
+                f.write((const char*)&len, 8);
+                f.write((const char*)blob.data(), (streamsize)bytes);
+            }
+            if (!f) throw std::runtime_error("save_packed: write to " + filename + " failed");
+        } catch (...) {   // no partial file stays behind
+            f.close();
+            std::remove(filename.c_str());
+            throw;
+        }
+    }
     vector<Ctxt> load_vector(string filename) {
         vector<Ctxt> result;
         ifstream f(filename, ios::in | ios::binary);
@@ -804,7 +838,8 @@ public:
             f.read((char*)&magic, 8);
             f.read((char*)&n, 8);
         }
-        if (f && magic == COMPACT_FILE_MAGIC) {
+        if (f && (magic == COMPACT_FILE_MAGIC || magic == PACKED_FILE_MAGIC)) {
+            const bool packed = magic == PACKED_FILE_MAGIC;
             vector<vector<uint8_t>> blobs;
             for (uint64_t i = 0; i < n; i++) {
                 uint64_t len = 0;
@@ -821,8 +856,9 @@ public:
                 sizes.push_back(b.size());
             }
             vector<fhelin_ct*> outs(blobs.size(), nullptr);
-            fhelin_shim::check(fhelin_ct_import_compact(context, ptrs.data(), sizes.data(), (int32_t)blobs.size(), outs.data()),
-                               "Deserialize(compact)");
+            fhelin_shim::check(packed ? fhelin_ct_import_packed(context, ptrs.data(), sizes.data(), (int32_t)blobs.size(), outs.data())
+                                      : fhelin_ct_import_compact(context, ptrs.data(), sizes.data(), (int32_t)blobs.size(), outs.data()),
+                               packed ? "Deserialize(packed)" : "Deserialize(compact)");
             for (fhelin_ct* o : outs) result.push_back(wrap(o));
             return result;
         }
@@ -850,6 +886,7 @@ public:
     }
 
     static constexpr uint64_t COMPACT_FILE_MAGIC = 0x46484C4E43433031ull;
+    static constexpr uint64_t PACKED_FILE_MAGIC = 0x46484C4E43503031ull;
 
     int relu_degree = 119;
     string parameters_folder = "keys";

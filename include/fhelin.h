@@ -977,6 +977,71 @@ int fhelin_key_info(fhelin_ctx* c, int32_t kind, int32_t index, int32_t* digits,
 int fhelin_key_usage_begin(fhelin_ctx* c);
 int fhelin_key_usage_end(fhelin_ctx* c, int32_t* kind, uint64_t* galois, int32_t* max_ell, int32_t cap, int32_t* n);
 
+/* ---- packed formats: residues travel at their modulus width -----------------------------------------------------------------
+ * No modulus of an accepted chain has more than 60 bits, and a residue below m carries at most bitlen(m) bits.  The packed formats
+ * store exactly that many; device memory and every kernel that computes keep the u64 layout.
+ *
+ * Packed limb vector.  For a modulus m, w(m) is the number of bits of m, 20 <= w <= 60.  A vector v[0..N) of residues below m becomes
+ * a bit stream of N w bits: residue j occupies stream bits [j w, (j+1) w), least significant bit first; stream bit t is bit t mod 64
+ * of word t / 64; words are little-endian.  N is a multiple of 4096, so a packed vector is exactly N w / 64 words: every vector starts
+ * on a word boundary and there is no padding.  A packed payload is the limb vectors of the unpacked payload in the same storage order,
+ * each packed at the width of its own limb's modulus.
+ *
+ * Digests are unchanged: every digest in a packed object is the existing digest ("Evaluation-key sets") of the UNPACKED residues in
+ * unpacked storage order.  Unpacking can produce any w-bit value; the range check (residue < modulus) and the digest run on the
+ * unpacked data, exactly as the other loaders run them, and decide acceptance, all or nothing.
+ *
+ * Ciphertext blob "FHELINCP", version 1.  Size exactly H + stored * sum_{l < ell} N w_l / 8 bytes.
+ *    0  char[8] "FHELINCP"      8  u32 version = 1      12 u32 header bytes H = 112 + 8 ell + 8 ceil(count / 2)
+ *   16  i32[4]  log_n, ell, deg, slots                  32 f64[2] scale hi, lo (as fhelin_ct_scale)
+ *   48  u64 nonce   56 u8[32] seed                      88 u64 digest over the stored * ell vectors (vector j belongs to limb j mod ell)
+ *   96  u32 stored: 1 = seeded form (c0 stored, c1 = the expansion of seed and nonce, "Compact ciphertexts");
+ *                   2 or 3 = every component stored, fhelin_ct_export order; nonce and seed zero
+ *  100  u32 count (0 = not wrapped; 1..128 needs stored = 1)   104 u32 total (0 when count = 0)   108 u32 0
+ *  112  u64[ell] moduli (first ell of Q; wrapped: of Q then P)  then u32[count] positions, zero padded to 8 bytes
+ *  then the packed payload
+ *
+ * Key set "FHELINEP", version 1: full and compact sets, capped and uncapped keys.  Bytes 8..95 as "FHELINEK" version 1; 96 u8[32]
+ * key-set seed, zero for a full set; 128 u32 halves (2 = full keys, 1 = b halves only); 132 u32 0; 136 u64[n_q + n_p] moduli; then the
+ * key table with the 48-byte entries of format version 2 (max_ell = n_q marks an uncapped key and the public key); data_offset = the
+ * table end rounded up to a multiple of 4096.  An entry's payload is the version 2 dense present-row payload - [digits'][halves]
+ * [max_ell + n_p][N] for a switching key, [halves][n_q][N] for the public key - with every vector packed at its limb's width (present
+ * row r < max_ell is Q limb r, the rows after it are the special limbs).  words counts the packed words stored; digest is the digest
+ * the unpacked set carries, so a packed set's table digests equal those of the unpacked set of the same keys.
+ * fhelin_evalkeys_params, _info, _interleave and _load read it beside the other two magics; _load uploads a key's packed payload,
+ * unpacks it into the at-rest layout, and then expands, digests and installs as for the other formats. */
+/* Writes the packed key set.  compact = 1: the preconditions and errors of fhelin_evalkeys_save_compact; compact = 0: those of
+ * fhelin_evalkeys_save.  Keys are packed on the device into scratch of at most one key's payload at a time and streamed through the
+ * two pinned staging buffers of the other savers.  fhelin_evalkeys_save and _save_compact write what they always wrote. */
+int fhelin_evalkeys_save_packed(fhelin_ctx* c, const char* path, int32_t compact);
+/* Size of the packed blob of `ct`.  seeded = 1: the seeded form; accepts exactly what fhelin_ct_export_compact accepts (wrapped
+ * handles included), anything else FHELIN_ERR_STATE.  seeded = 0: the full form of any ciphertext fhelin_ct_export accepts; a wrapped
+ * handle is FHELIN_ERR_ARG. */
+int fhelin_ct_packed_bytes(fhelin_ctx* c, const fhelin_ct* ct, int32_t seeded, size_t* bytes);
+/* Writes the blob.  Range check, digest and pack run on the device and only the packed bytes are downloaded; one synchronisation.
+ * Level plan: seeded = 1 behaves as fhelin_ct_export_compact, seeded = 0 is a terminal like fhelin_ct_export. */
+int fhelin_ct_export_packed(fhelin_ctx* c, const fhelin_ct* ct, int32_t seeded, uint8_t* out, size_t cap);
+/* Host-only, no context: validates the header against itself and the exact size computed from the header's own moduli; any out
+ * pointer may be NULL.  FHELIN_ERR_ARG on anything inconsistent. */
+int fhelin_packed_info(const uint8_t* blob, size_t bytes, int32_t* log_n, int32_t* ell, int32_t* deg, int32_t* slots, int32_t* stored,
+                       int32_t* count);
+/* n blobs -> n handles, all or nothing.  Every header is checked against the context before anything is allocated; one batch
+ * allocation per limb count; the packed payloads are uploaded and unpacked by one launch, then the strided digest and range check, then
+ * every seeded c1 is expanded in one launch; one synchronisation.  stored = 1 makes exactly the handle fhelin_ct_import_compact makes
+ * from the equivalent version 1 or 2 compact blob; stored >= 2 the handle fhelin_ct_import makes from the same residues, with the exact
+ * 80-bit scale.  Imported values are not level-plan sources.  Works on an evaluation context. */
+int fhelin_ct_import_packed(fhelin_ctx* c, const uint8_t* const* blobs, const size_t* sizes, int32_t n, fhelin_ct** outs);
+/* Test hooks: the two kernels alone.  words[n_vec][N] -> the packed vectors back to back (vector i at width widths[i]); *n_words = the
+ * words written (sum N widths[i] / 64), FHELIN_ERR_ARG if cap_words is smaller.  A width outside 20..60, or (pack) an input at or above
+ * 2^w - checked on the host here; the format paths rely on the range check that precedes every write - is FHELIN_ERR_ARG. */
+int fhelin_debug_pack(fhelin_ctx* c, const uint64_t* words, const int32_t* widths, int32_t n_vec, uint64_t* out, size_t cap_words,
+                      size_t* n_words);
+int fhelin_debug_unpack(fhelin_ctx* c, const uint64_t* packed, size_t n_words, const int32_t* widths, int32_t n_vec, uint64_t* out);
+/* Measurement hook (tools/packed_probe.py): n_vec vectors of the given widths packed, copied device to device (the same unpacked
+ * bytes), unpacked and copied again, in turn, reps times after one untimed round; ms[4 reps] = the device-event times of pack, copy,
+ * unpack, copy of every round. */
+int fhelin_debug_pack_rate(fhelin_ctx* c, const int32_t* widths, int32_t n_vec, int32_t reps, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
