@@ -202,6 +202,8 @@ def load_library():
         "fhelin_bootstrap_pair_partial": (i32, [vp, vp, vp, i32, C.POINTER(vp)]),
         "fhelin_ctx_set_bootstrap_pairing": (i32, [vp, i32]),
         "fhelin_ctx_bootstrap_pairing": (i32, [vp, C.POINTER(i32)]),
+        "fhelin_ctx_set_bootstrap_lt": (i32, [vp, i32, i32]),
+        "fhelin_ctx_bootstrap_lt": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "fhelin_debug_pair_pack": (i32, [vp, C.POINTER(vp), C.POINTER(vp), u64p, u64p, i32, C.POINTER(vp)]),
         "fhelin_debug_pair_split": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
         "fhelin_bootstrap_describe": (i32, [vp, C.POINTER(i32), i32, C.POINTER(i32)]),
@@ -257,6 +259,7 @@ def load_library():
         "fhelin_lt_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "fhelin_lt_rotations": (i32, [vp, C.POINTER(i32), i32, C.POINTER(i32)]),
         "fhelin_lt_apply": (i32, [vp, vp, C.POINTER(vp), i32, i32, C.POINTER(vp)]),
+        "fhelin_lt_encoding_bytes": (i32, [vp, C.POINTER(C.c_uint64)]),
         "fhelin_lt_free": (None, [vp]),
         "fhelin_debug_dot_plain": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp)]),
         "fhelin_debug_dot_groups": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(vp), i32, C.POINTER(vp)]),
@@ -1407,6 +1410,18 @@ class Engine:
         self._ck(self.lib.fhelin_ctx_bootstrap_pairing(self.h, C.byref(on)))
         return bool(on.value)
 
+    def set_bootstrap_lt(self, on, n1=0):
+        """the bootstrap's linear stages on the linear-transform engine (include/fhelin.h "Bootstrap linear stages"; off by default,
+        FHELIN_BOOT_LT=1 / FHELIN_BOOT_LT_N1=k).  n1 = 0: the planner chooses per stage; 1..32 forces the baby-step count.  Binds at
+        bootstrap_setup: FHELIN_ERR_STATE afterwards"""
+        self._ck(self.lib.fhelin_ctx_set_bootstrap_lt(self.h, int(bool(on)), int(n1)))
+
+    def bootstrap_lt(self):
+        """(on, n1) of set_bootstrap_lt"""
+        on, n1 = C.c_int32(), C.c_int32()
+        self._ck(self.lib.fhelin_ctx_bootstrap_lt(self.h, C.byref(on), C.byref(n1)))
+        return bool(on.value), n1.value
+
     def debug_pair_pack(self, a, b, k0_a, k0_b):
         """outs[i] = k0_a[i] a[i] + X^(N/2) k0_b[i] b[i] on the two bottom limbs, every pair in one launch (launch_ew_pair_pack)"""
         n = len(a)
@@ -1426,7 +1441,9 @@ class Engine:
 
     def bootstrap_describe(self):
         """the bootstrapping set-up as the residue-level oracle needs it: parameters + per linear stage the stage's slot count
-        and its (giant, baby, diagonal plaintext) terms in evaluation order"""
+        and its (giant, baby, diagonal plaintext) terms in evaluation order.  "lt": whether the stages run on the linear-transform
+        engine (set_bootstrap_lt); then every stage also has "n1", "n2" of its split, and "lt_n1" (the n1 asked for) and
+        "encoding_bytes" (device bytes of the stages' limb-sliced encodings so far) are set"""
         n = C.c_int32()
         self._ck(self.lib.fhelin_bootstrap_describe(self.h, None, 0, C.byref(n)))
         d = (C.c_int32 * n.value)()
@@ -1447,6 +1464,14 @@ class Engine:
                 terms.append((d[pos], d[pos + 1], Pt(self, h)))
                 pos += 2
             stages.append(dict(slots=st_slots, terms=terms))
+        out["lt"] = pos < len(d) and d[pos] == 1
+        if out["lt"]:
+            out["lt_n1"] = d[pos + 1]
+            pos += 2
+            for st in stages:
+                st["n1"], st["n2"] = d[pos], d[pos + 1]
+                pos += 2
+            out["encoding_bytes"] = (d[pos] & 0xffffffff) | ((d[pos + 1] & 0xffffffff) << 32)
         out["c2s"], out["s2c"] = stages[:n_c2s], stages[n_c2s:]
         cn = C.c_int32()
         self._ck(self.lib.fhelin_bootstrap_cheb(self.h, None, 0, C.byref(cn)))
@@ -1664,6 +1689,12 @@ class LinearTransform:
         i = [C.c_int32() for _ in range(4)]
         self.eng._ck(self.eng.lib.fhelin_lt_info(self.h, *[C.byref(x) for x in i]))
         return dict(n1=i[0].value, n2=i[1].value, n_terms=i[2].value, slots=i[3].value)
+
+    def encoding_bytes(self):
+        """device bytes of the limb-sliced encodings the plan's plaintexts hold: (ell + k) N 8 per (term, distinct (ell, scale) applied at)"""
+        b = C.c_uint64()
+        self.eng._ck(self.eng.lib.fhelin_lt_encoding_bytes(self.h, C.byref(b)))
+        return b.value
 
     def rotations(self):
         """the rotation indices whose keys fhelin_lt_apply needs"""

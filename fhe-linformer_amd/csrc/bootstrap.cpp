@@ -123,6 +123,21 @@ Bootstrapper::~Bootstrapper() {
     }
 }
 
+void Bootstrapper::set_lt(bool on, int n1) {
+    if (n1 < 0 || n1 > LtDot::MAX_STEPS) throw Error(FHELIN_ERR_ARG, "bootstrap_lt: n1 is 0 (the planner chooses) or 1..32");
+    if (ready()) throw Error(FHELIN_ERR_STATE, "bootstrap_lt: the split binds at bootstrap_setup - set the knob before it");
+    lt_ = on;
+    lt_n1_ = n1;
+}
+
+size_t Bootstrapper::lt_encoding_bytes() const {
+    size_t b = 0;
+    for (const auto* v : {&c2s_, &s2c_})
+        for (const auto& st : *v)
+            for (const auto& t : st.terms) b += t.diag->sliced_bytes();
+    return b;
+}
+
 LinStage Bootstrapper::prepare(const DiagMap& m, int n) {
     LinStage st;
     int g = n;
@@ -134,6 +149,18 @@ LinStage Bootstrapper::prepare(const DiagMap& m, int n) {
     int bsz = 1;
     while (bsz * bsz < count) bsz <<= 1;
     st.bsz = std::min(bsz, span);
+    if (lt_) {   // the engine's split: at most LtDot::MAX_STEPS baby steps, forced or by the linear-transform planner's cost
+        const int cap = std::min((int)LtDot::MAX_STEPS, span);
+        std::vector<int> ks;
+        for (const auto& e : m) ks.push_back(e.first / g);
+        int n1 = std::min(lt_n1_, cap);
+        if (lt_n1_ == 0) {
+            n1 = 1;
+            for (int k = 2; k <= cap; ++k)
+                if (Evaluator::lt_split_cost(ks, k) < Evaluator::lt_split_cost(ks, n1)) n1 = k;   // ties go to the smaller n1 (fewer keys)
+        }
+        st.bsz = n1;
+    }
     for (const auto& e : m) {
         const int k = e.first / g;
         const int G = k / st.bsz, B = k % st.bsz;
@@ -150,6 +177,14 @@ LinStage Bootstrapper::prepare(const DiagMap& m, int n) {
             p->imag[j] = v.imag();
         }
         st.terms.push_back({sG, B * g, p});
+    }
+    if (lt_) {
+        for (int b = 0; b < st.bsz; ++b) st.lt_baby.push_back(b * g);
+        for (const auto& t : st.terms)   // the map runs in ascending index order: so do the giant steps
+            if (st.lt_giant.empty() || st.lt_giant.back() != t.giant) st.lt_giant.push_back(t.giant);
+        st.lt_pts.assign(st.lt_giant.size(), std::vector<PtPtr>(st.bsz));
+        for (const auto& t : st.terms)
+            st.lt_pts[std::lower_bound(st.lt_giant.begin(), st.lt_giant.end(), t.giant) - st.lt_giant.begin()][t.baby / g] = t.diag;
     }
     return st;
 }
@@ -273,8 +308,17 @@ CtPtr Bootstrapper::mult_i(const CtPtr& x) {
     return o;
 }
 
+// the scale a stage takes its diagonals at: an input whose scale is not its level's own (the first stage after a ModRaise to fewer limbs
+// than the chain has: run(drop > 0)) takes them at the scale that makes the product land on the next level's scale again; 0: the level's
+static long double stage_pt_scale(const Context& c, const CtPtr& x) {
+    const int lvl = x->level();
+    if (x->ell >= 2 && fabsl(x->scale / c.sf_real[lvl] - 1.0L) > 1e-12L) return c.sf_real[lvl + 1] * (long double)c.chain.q[x->ell - 1] / x->scale;
+    return 0;
+}
+
 CtPtr Bootstrapper::apply(const LinStage& st, const CtPtr& xin) {
     CtPtr x = xin->deg >= 2 ? ev_.rescale(xin) : xin;
+    if (lt_) return ev_.linear_transform_rows({x}, st.lt_pts, st.lt_baby, st.lt_giant, false, stage_pt_scale(ev_.ctx(), x))[0];
     // baby steps: every rotation of x in ONE hoisted key switch (one ModUp of x, per-index inner product + ModDown)
     std::vector<int> bidx;
     for (const auto& t : st.terms)
@@ -289,13 +333,7 @@ CtPtr Bootstrapper::apply(const LinStage& st, const CtPtr& xin) {
         groups[t.giant].first.push_back(babies[t.baby]);
         groups[t.giant].second.push_back(t.diag);
     }
-    // an input whose scale is not its level's own (the first stage after a ModRaise to fewer limbs than the chain has:
-    // run(drop > 0)) takes the diagonals at the scale that makes the product land on the next level's scale again
-    Context& c = ev_.ctx();
-    long double pt_scale = 0;
-    const int lvl = x->level();
-    if (x->ell >= 2 && fabsl(x->scale / c.sf_real[lvl] - 1.0L) > 1e-12L)
-        pt_scale = c.sf_real[lvl + 1] * (long double)c.chain.q[x->ell - 1] / x->scale;
+    const long double pt_scale = stage_pt_scale(ev_.ctx(), x);
     // the inner sums land in ONE block, in giant-step order (the shared-ModDown key switch below takes them as they stand), and
     // all of them come out of ONE pass over the rotated ciphertexts (Evaluator::dot_plain_groups); per-group passes otherwise
     std::map<int, CtPtr> inner;
@@ -434,16 +472,15 @@ std::vector<CtPtr> Bootstrapper::apply_batch(const LinStage& st, const std::vect
     Context& c = ev_.ctx();
     const size_t B = xin.size();
     std::vector<CtPtr> xs = xin[0]->deg >= 2 ? ev_.rescale_batch(xin) : xin;
+    // every ciphertext of the batch in the launches of ONE engine call (they share a shape: one pipeline raised them together)
+    if (lt_) return ev_.linear_transform_rows(xs, st.lt_pts, st.lt_baby, st.lt_giant, false, stage_pt_scale(c, xs[0]));
     std::vector<int> bidx;
     for (const auto& t : st.terms)
         if (std::find(bidx.begin(), bidx.end(), t.baby) == bidx.end()) bidx.push_back(t.baby);
     // baby steps: ONE ModUp over the batch, per ciphertext the inner products of all indices, ONE ModDown over everything
     std::vector<std::vector<CtPtr>> brot = ev_.rotate_many_batch(xs, bidx);
     const CtPtr& x = xs[0];
-    long double pt_scale = 0;
-    const int lvl = x->level();
-    if (x->ell >= 2 && fabsl(x->scale / c.sf_real[lvl] - 1.0L) > 1e-12L)
-        pt_scale = c.sf_real[lvl + 1] * (long double)c.chain.q[x->ell - 1] / x->scale;
+    const long double pt_scale = stage_pt_scale(c, x);
     // giant-step groups: the unrotated one first, then ascending (= rotate_each_sum's order)
     std::vector<int> order;
     {

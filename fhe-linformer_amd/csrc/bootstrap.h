@@ -24,6 +24,11 @@ struct LinStage {
         PtPtr diag;  // diagonal, pre-rotated by -giant
     };
     std::vector<Term> terms;
+    // the engine form of the same terms (Bootstrapper::set_lt on; empty otherwise): the argument lists of
+    // Evaluator::linear_transform_rows - baby[b] = b * g0 for b < bsz, the giant steps that carry a term in ascending order, pts [n2][bsz]
+    // with null where no diagonal falls
+    std::vector<int> lt_baby, lt_giant;
+    std::vector<std::vector<PtPtr>> lt_pts;
 };
 
 class Bootstrapper {
@@ -32,6 +37,16 @@ public:
     ~Bootstrapper();
     void setup(int budget_enc, int budget_dec, int slots);
     bool ready() const { return slots_ > 0; }
+    // Linear stages on the linear-transform engine (include/fhelin.h "Bootstrap linear stages"): every stage is split into
+    // at most 32 baby steps (n1 == 0: the planner's cost 4 (n2 + ceil(R / 7)) + baby keys picks per stage; n1 > 0: forced, capped by the
+    // stage's span) and applied as ONE Evaluator::linear_transform_rows call over the batch - one ModUp, the baby steps' key products
+    // formed once in QP, n2 + ceil(R / 7) pair-ModDowns.  The split decides the diagonals' pre-rotation and the key list, so the knob binds
+    // at setup(): FHELIN_ERR_STATE afterwards.  Off (the default): nothing below changes
+    void set_lt(bool on, int n1);
+    bool lt() const { return lt_; }
+    int lt_n1() const { return lt_n1_; }
+    // device bytes of the limb-sliced encodings the stages' diagonals hold (one per (limbs, scale) a term was applied at)
+    size_t lt_encoding_bytes() const;
     // drop: raise to L+1-drop limbs only, so that the result has `drop` limbs fewer (level plan: the caller knows that the
     // circuit up to the next bootstrap leaves that many unused)
     CtPtr bootstrap(const CtPtr& ct, int drop = 0);
@@ -88,6 +103,8 @@ private:
     int slots_ = 0, logical_slots_ = 0;
     int budget_enc_ = 0, budget_dec_ = 0;
     bool stage_order_legacy_ = false;   // FHELIN_BOOT_STAGES_LEGACY=1: larger stages first (round-1 split 5+5+4)
+    bool lt_ = false;       // set_lt
+    int lt_n1_ = 0;
     bool packed_ = false;   // sparse packing: real and imaginary halves share one ciphertext through EvalMod (bootstrap.cpp)
     int depth_ = 0;
     std::vector<LinStage> c2s_, s2c_;

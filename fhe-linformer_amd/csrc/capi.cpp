@@ -24,6 +24,12 @@ fhelin_ctx::fhelin_ctx(const fhelin::Params& p) : ctx(p), ev(ctx), cl(ev, ctx.pr
     if (const char* e = std::getenv("FHELIN_LAZY_ROWS")) lazy_rows = std::atoi(e) != 0;
     if (const char* e = std::getenv("FHELIN_LAZY_HEAVY")) lazy_heavy = std::atoi(e) != 0;
     if (const char* e = std::getenv("FHELIN_BOOT_PAIRS")) boot_pairs = std::atoi(e) != 0;
+    {   // FHELIN_BOOT_LT=1 / FHELIN_BOOT_LT_N1=k: the bootstrap's linear stages on the linear-transform engine (an n1 outside 0..32 is ignored)
+        const char* on = std::getenv("FHELIN_BOOT_LT");
+        const char* n1 = std::getenv("FHELIN_BOOT_LT_N1");
+        const int k = n1 ? std::atoi(n1) : 0;
+        if (on || n1) boot.set_lt(on && std::atoi(on) != 0, k >= 0 && k <= LtDot::MAX_STEPS ? k : 0);
+    }
 }
 
 #define NEED(x) if (!(x)) return capi_fail(FHELIN_ERR_ARG, "null argument")
@@ -187,6 +193,20 @@ int fhelin_ctx_set_bootstrap_pairing(fhelin_ctx* c, int32_t on) {
 int fhelin_ctx_bootstrap_pairing(fhelin_ctx* c, int32_t* on) {
     if (!c || !on) return capi_fail(FHELIN_ERR_ARG, "null argument");
     *on = c->boot_pairs ? 1 : 0;
+    return FHELIN_OK;
+}
+
+int fhelin_ctx_set_bootstrap_lt(fhelin_ctx* c, int32_t on, int32_t n1) {
+    if (!c) return capi_fail(FHELIN_ERR_ARG, "null context");
+    FHELIN_TRY
+    c->boot.set_lt(on != 0, n1);
+    FHELIN_CATCH
+}
+
+int fhelin_ctx_bootstrap_lt(const fhelin_ctx* c, int32_t* on, int32_t* n1) {
+    if (!c || !on || !n1) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    *on = c->boot.lt() ? 1 : 0;
+    *n1 = c->boot.lt_n1();
     return FHELIN_OK;
 }
 

@@ -624,6 +624,18 @@ int fhelin_bootstrap_describe(fhelin_ctx* c, int32_t* out, int32_t cap, int32_t*
                 d.push_back(t.baby);
             }
         }
+    if (b.lt()) {   // the engine path's trailer (absent with the knob off): 1, the n1 asked for, (n1, n2) per stage, the encodings' bytes
+        d.push_back(1);
+        d.push_back(b.lt_n1());
+        for (int which = 0; which < 2; ++which)
+            for (const LinStage& st : b.stages(which != 0)) {
+                d.push_back(st.bsz);
+                d.push_back((int32_t)st.lt_giant.size());
+            }
+        const uint64_t bytes = b.lt_encoding_bytes();
+        d.push_back((int32_t)(bytes & 0xffffffffu));
+        d.push_back((int32_t)(bytes >> 32));
+    }
     *n = (int32_t)d.size();
     for (int i = 0; i < std::min(cap, *n); ++i) out[i] = d[i];
     FHELIN_CATCH

@@ -22,21 +22,6 @@ struct fhelin_lt {
 namespace {
 int mod_slots(long d, int slots) { return (int)(((d % slots) + slots) % slots); }
 
-// The planner's cost of a split into n1 baby steps, in quarters of a pair-ModDown:  4 * (n2 + ceil(R / 7)) + (baby keys read),
-// n2 = the giant-step groups that carry a diagonal, R = those of them that are rotated (g != 0), baby keys = the distinct nonzero
-// residues d mod n1.  Every group costs one pair-ModDown for its inner sum and the rotated groups share one more per 7 in the giant
-// steps; a baby step costs one pass over its rotation key in the inner product, taken as a quarter of a pair-ModDown (2 beta (ell + k)
-// limb vectors streamed once against the ModDown's 2 k inverse and 2 ell forward transforms and its conversion) - an estimate, not a
-// measurement.  Ties go to the smaller n1 (fewer keys).
-int split_cost(const std::vector<int>& idx, int n1) {
-    std::set<int> groups, babies;
-    for (int d : idx) {
-        groups.insert(d - d % n1);
-        if (d % n1) babies.insert(d % n1);
-    }
-    const int n2 = (int)groups.size(), R = n2 - (int)groups.count(0);
-    return 4 * (n2 + (R + 6) / 7) + (int)babies.size();
-}
 }  // namespace
 
 extern "C" {
@@ -92,7 +77,7 @@ int fhelin_lt_create(fhelin_ctx* c, const double* diags, const int32_t* diag_idx
     if (n1 == 0) {
         n1 = 1;
         for (int k = 2; k <= LtDot::MAX_STEPS; ++k)
-            if (split_cost(idx, k) < split_cost(idx, n1)) n1 = k;
+            if (Evaluator::lt_split_cost(idx, k) < Evaluator::lt_split_cost(idx, n1)) n1 = k;   // the planner's cost; ties go to the smaller n1
     }
     std::vector<int> giant;
     for (int d : seen)
@@ -154,6 +139,16 @@ int fhelin_lt_apply(fhelin_ctx* c, const fhelin_lt* lt, const fhelin_ct* const* 
     std::vector<CtPtr> r = c->ev.linear_transform_rows(in, lt->pts, lt->baby, lt->giant, rescale != 0);
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, r[i]);
     FHELIN_CATCH
+}
+
+int fhelin_lt_encoding_bytes(const fhelin_lt* lt, uint64_t* bytes) {
+    NEED(lt && bytes);
+    uint64_t b = 0;
+    for (const auto& row : lt->pts)
+        for (const PtPtr& p : row)
+            if (p) b += p->sliced_bytes();
+    *bytes = b;
+    return FHELIN_OK;
 }
 
 void fhelin_lt_free(fhelin_lt* lt) { delete lt; }

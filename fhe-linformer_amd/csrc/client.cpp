@@ -231,7 +231,7 @@ void encode_domain_check(double max_abs, long double scale) {
 }
 
 void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale,
-                         int stride, int lanes) {
+                         int stride, int lanes, int ell_q) {
     c.require_device();
     if (slots < 2 || (slots & (slots - 1)) || slots > c.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots must be a power of two in [2, N/2]");
     if (stride < 1 || (stride & (stride - 1)) || (long)slots * stride > c.N / 2 || (lanes != 1 && lanes != stride))
@@ -239,6 +239,7 @@ void encode_batch_device(Context& c, u64* dst, const double* re, const double* i
     // ell = L + 1 + k: the encoding over the FULL key basis (limb ids 0..L+k: Q limbs, then the special limbs), for plaintexts
     // folded into rotation keys (Evaluator::folded_key); the leveled operations only ever ask for ell <= L + 1
     if (ell < 1 || ell > c.L + 1 + c.K) throw Error(FHELIN_ERR_ARG, "encode: level out of range");
+    if (ell_q && (ell_q < 1 || ell_q > c.L + 1 || ell != ell_q + c.K)) throw Error(FHELIN_ERR_ARG, "encode: limb split out of range");
     if (n_vec < 1) return;
     const size_t words = (size_t)2 * slots;                 // one complex vector, in doubles
     const int n_staged = n_vec * lanes;                     // interleaved samples: re / im [n_vec][lanes][n_per], uploads at logical size
@@ -262,28 +263,33 @@ void encode_batch_device(Context& c, u64* dst, const double* re, const double* i
     if (stride > 1) {   // the staged vectors are logical: the physical ones are made on the device, in front of the FFT
         Scratch<double> phys = c.scratch<double>(words * stride * n_vec);
         launch_interleave_slots(phys, dv, slots, stride, lanes, n_vec, c.stream);
-        encode_complex_on_device(c, dst, phys, n_vec, slots * stride, ell, scale);
+        encode_complex_on_device(c, dst, phys, n_vec, slots * stride, ell, scale, ell_q);
         return;
     }
-    encode_complex_on_device(c, dst, dv, n_vec, slots, ell, scale);
+    encode_complex_on_device(c, dst, dv, n_vec, slots, ell, scale, ell_q);
 }
 
 // dv [n_vec][slots][2] complex slot values already on the device (overwritten) -> dst [n_vec][ell][N] encodings, NTT form
-void encode_complex_on_device(Context& c, u64* dst, double* dv, int n_vec, int slots, int ell, long double scale) {
+void encode_complex_on_device(Context& c, u64* dst, double* dv, int n_vec, int slots, int ell, long double scale, int ell_q) {
     const Context::FftDev& tab = fft_dev_tables(c, slots);
     launch_fft_special_inv(dv, tab.rot, tab.ksi, slots, n_vec, c.stream);
     // scale = mant * 2^exp with a 64-bit significand, exactly (the host code multiplies in x87 extended precision)
     int e2 = 0;
     const long double m = frexpl(scale, &e2);               // scale = m * 2^e2, m in [0.5, 1)
     const u64 mant = (u64)ldexpl(m, 64);
-    launch_encode_round_reduce(c.dt, dst, dv, slots, ell, mant, e2 - 64, n_vec, c.stream);
     c.stats.encode += (u64)n_vec;
-    c.ntt(LimbBatch{dst, n_vec * ell, nullptr, 0, ell}, false);
+    if (ell_q) {    // rows = the limbs a key switch at ell_q limbs reads: the forward transform takes their ids from the level's table
+        launch_encode_round_reduce_split(c.dt, dst, dv, slots, ell_q, c.K, c.L + 1, mant, e2 - 64, n_vec, c.stream);
+        c.ntt(LimbBatch{dst, n_vec * ell, c.lvl[ell_q].key_limb_tab, 0, 1, nullptr, ell}, false);
+    } else {
+        launch_encode_round_reduce(c.dt, dst, dv, slots, ell, mant, e2 - 64, n_vec, c.stream);
+        c.ntt(LimbBatch{dst, n_vec * ell, nullptr, 0, ell}, false);
+    }
     hip_check(hipGetLastError(), "encode kernels (device)");
 }
 
 std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>& values, const std::vector<double>& imag, int slots,
-                                           int ell, long double scale, int stride) {
+                                           int ell, long double scale, int stride, int ell_q) {
     c.require_device();
     if (stride > 1 && (c.host_encode || slots < 2)) {   // the host encoder takes the physical vector: every value in all of its lanes
         if ((long)slots * stride > c.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots x stride must be <= N/2");
@@ -292,20 +298,22 @@ std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>
             for (int k = 0; k < stride; ++k) re[(size_t)i * stride + k] = values[i];
         for (int i = 0; i < slots && i < (int)imag.size(); ++i)
             for (int k = 0; k < stride; ++k) im[(size_t)i * stride + k] = imag[i];
-        return encode_to_device(c, re, im, slots * stride, ell, scale, 1);
+        return encode_to_device(c, re, im, slots * stride, ell, scale, 1, ell_q);
     }
     if (slots < 1 || (slots & (slots - 1)) || slots > c.N / 2) throw Error(FHELIN_ERR_ARG, "encode: slots must be a power of two <= N/2");
     if (ell < 1 || ell > c.L + 1 + c.K) throw Error(FHELIN_ERR_ARG, "encode: level out of range");   // L + 1 + k: full key basis (see above)
+    if (ell_q && (ell_q < 1 || ell_q > c.L + 1 || ell != ell_q + c.K)) throw Error(FHELIN_ERR_ARG, "encode: limb split out of range");
     if (!c.host_encode && slots >= 2) {
         auto e = std::make_shared<Encoding>();
         e->ctx = &c;
         e->ell = ell;
+        e->ell_q = ell_q;
         e->scale = scale;
         e->d = c.dalloc<u64>((size_t)ell * c.N);
         std::vector<double> re(slots, 0.0), im(slots, 0.0);
         for (int i = 0; i < slots && i < (int)values.size(); ++i) re[i] = values[i];
         for (int i = 0; i < slots && i < (int)imag.size(); ++i) im[i] = imag[i];
-        encode_batch_device(c, e->d, re.data(), imag.empty() ? nullptr : im.data(), 1, slots, slots, ell, scale, stride, 1);
+        encode_batch_device(c, e->d, re.data(), imag.empty() ? nullptr : im.data(), 1, slots, slots, ell, scale, stride, 1, ell_q);
         return e;
     }
     std::vector<std::pair<double, double>> v(slots, {0.0, 0.0});
@@ -324,16 +332,28 @@ std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>
     auto e = std::make_shared<Encoding>();
     e->ctx = &c;
     e->ell = ell;
+    e->ell_q = ell_q;
     e->scale = scale;
     e->d = c.dalloc<u64>((size_t)ell * N);
-    launch_reduce_i128(c.dt, e->d, dco, 0, ell, c.stream);
     c.stats.encode += 1;
-    c.ntt(LimbBatch{e->d, ell, nullptr, 0, ell}, false);
+    if (ell_q) {
+        launch_reduce_i128(c.dt, e->d, dco, 0, ell_q, c.stream);
+        if (c.K > 0) launch_reduce_i128(c.dt, e->d + (size_t)ell_q * N, dco, c.L + 1, c.K, c.stream);
+        c.ntt(LimbBatch{e->d, ell, c.lvl[ell_q].key_limb_tab, 0, 1, nullptr, ell}, false);
+    } else {
+        launch_reduce_i128(c.dt, e->d, dco, 0, ell, c.stream);
+        c.ntt(LimbBatch{e->d, ell, nullptr, 0, ell}, false);
+    }
     hip_check(hipGetLastError(), "encode kernels");
     return e;
 }
 
-std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
+std::shared_ptr<Encoding> Plaintext::at_sliced(int ell_q, long double scale) {
+    if (ell_q < 1 || ell_q > ctx->L + 1) throw Error(FHELIN_ERR_ARG, "encode: limb split out of range");
+    return at(ell_q + ctx->K, scale, ell_q);
+}
+
+std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale, int ell_q) {
     // an encoding is made on the stream that first asks for it; a DIFFERENT lane that uses it later orders its stream behind the event
     // recorded after the encode (no host wait: with two lanes fed by one host thread a host-side synchronisation of one lane starves the
     // other - 2.9 s of host time per 16 samples before this, tools: FHELIN_HOST_WAITS=1)
@@ -346,9 +366,10 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
     };
     // the encodings over the full key basis (ell = L + 1 + k, fhelin_hoisted_dot's folded keys) are asked for at a level's exact scale:
     // matched exactly, since neighbouring levels' scales can lie within 1e-12 of each other (~60-bit scaling primes)
-    const bool full = ell > ctx->L + 1;
+    // ... and so are the limb-sliced ones (ell_q > 0: the same residues on the rows present), which never match a plain encoding of as many rows
+    const bool full = ell > ctx->L + 1 || ell_q > 0;
     for (size_t i = 0; i < cache.size(); ++i)
-        if (cache[i]->ell == ell && (full ? cache[i]->scale == scale : fabsl(cache[i]->scale / scale - 1.0L) < 1e-12L)) {
+        if (cache[i]->ell == ell && cache[i]->ell_q == ell_q && (full ? cache[i]->scale == scale : fabsl(cache[i]->scale / scale - 1.0L) < 1e-12L)) {
             if (i) std::rotate(cache.begin(), cache.begin() + i, cache.begin() + i + 1);   // most recently used first
             order(cache[0]);
             return cache[0];
@@ -361,14 +382,14 @@ std::shared_ptr<Encoding> Plaintext::at(int ell, long double scale) {
     std::shared_ptr<Encoding> e;
     if (shared)   // an earlier handle of the same values has made exactly this encoding: nothing to launch
         for (size_t i = 0; i < shared->cache.size() && !e; ++i)
-            if (shared->cache[i]->ell == ell && shared->cache[i]->scale == scale) {
+            if (shared->cache[i]->ell == ell && shared->cache[i]->ell_q == ell_q && shared->cache[i]->scale == scale) {
                 if (i) std::rotate(shared->cache.begin(), shared->cache.begin() + i, shared->cache.begin() + i + 1);
                 e = shared->cache[0];
                 order(e);
             }
     if (!e) {
         encode_domain_check(max_abs, scale);   // before anything is launched: a refused encoding leaves the plaintext and its cache as they were
-        e = encode_to_device(*ctx, values, imag, slots, ell, scale, stride);
+        e = encode_to_device(*ctx, values, imag, slots, ell, scale, stride, ell_q);
         e->made_lane = ctx->pool.cur_lane;
         e->lanes_ordered = 1u << e->made_lane;
         if (ctx->n_lanes > 0) {

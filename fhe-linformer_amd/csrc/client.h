@@ -169,14 +169,15 @@ void ckks_fft_special(std::vector<std::pair<double, double>>& v, bool inverse);
 void ckks_fft_tables(int slots, std::vector<u32>& rot, std::vector<std::pair<double, double>>& ksi);
 // stride > 1 (interleaved samples): slots logical values, each replicated into the stride lanes of the slots * stride physical slots
 std::shared_ptr<Encoding> encode_to_device(Context& c, const std::vector<double>& values, const std::vector<double>& imag, int slots,
-                                           int ell, long double scale, int stride = 1);
+                                           int ell, long double scale, int stride = 1, int ell_q = 0);
 // the encoder's domain: throws FHELIN_ERR_ARG for a non-finite max_abs, or when the two exponents allow max_abs * scale >= 2^125
 void encode_domain_check(double max_abs, long double scale);
 // device encoder for n_vec vectors: re / im [n_vec][n_per] (im may be null) -> dst [n_vec][ell][N] NTT form
 // stride > 1: re / im [n_vec][lanes][n_per] with lanes = stride (lane i = sample i) or 1 (the vector replicated); the staged uploads stay at
 // logical size and launch_interleave_slots makes the physical vectors in front of the inverse FFT
 void encode_batch_device(Context& c, u64* dst, const double* re, const double* im, int n_vec, int n_per, int slots, int ell, long double scale,
-                         int stride = 1, int lanes = 1);
-void encode_complex_on_device(Context& c, u64* dst, double* dv, int n_vec, int slots, int ell, long double scale);
+                         int stride = 1, int lanes = 1, int ell_q = 0);
+// ell_q > 0: the limb-sliced form, ell == ell_q + k rows: Q limbs 0..ell_q-1, then the k special limbs (Plaintext::at_sliced)
+void encode_complex_on_device(Context& c, u64* dst, double* dv, int n_vec, int slots, int ell, long double scale, int ell_q = 0);
 
 }  // namespace fhelin

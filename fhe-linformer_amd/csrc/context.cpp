@@ -295,6 +295,9 @@ Context::Context(const Params& p_in) : prm(resolve_params(p_in)) {
         lt.up_hatmod = upload_table(hatmod);
         lt.up_hatmod_r2 = upload_table(hatmod2);
         lt.ext_limb_tab = upload_table(tab);
+        std::vector<int> ktab(nt);
+        for (int t = 0; t < nt; ++t) ktab[t] = t < ell ? limb_id_q(t) : limb_id_p(t - ell);
+        lt.key_limb_tab = upload_table(ktab);
         if (ell >= 2 && K >= 1) {   // ModDown + rescale in one conversion: drop B = (p_0..p_{k-1}, q_{ell-1})
             const u64 ql = chain.q[ell - 1];
             const int e1 = ell - 1;

@@ -47,6 +47,7 @@ struct LevelTables {
     const u64* up_hatmod_r2 = nullptr;   // the same times 2^128: digits that come out times 2^64, for the inner product over the keys as they are
                                          // stored (ks_inner: it ends in redc128 too and has no scaled key copy to read)
     const int* ext_limb_tab = nullptr;  // [beta*(ell+k)] limb id for the NTT after ModUp, -1 on own-digit slots
+    const int* key_limb_tab = nullptr;  // [ell+k] limb ids q_0..q_{ell-1}, p_0..p_{k-1}: the rows of a limb-sliced plaintext encoding
     // ModDown and rescale as ONE basis conversion (kernels_elem.h launch_moddown_rescale_conv; ell >= 2): the dropped basis is
     // B = (p_0..p_{k-1}, q_{ell-1}) with product M = P q_{ell-1}
     const u64* md_hatinv = nullptr;   // [k+1][2]      (M/b)^{-1} mod b, shoup

@@ -1,5 +1,6 @@
 #include "evaluator.h"
 #include <map>
+#include <set>
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
@@ -756,8 +757,19 @@ std::vector<CtPtr> Evaluator::hoisted_dot_rows(const std::vector<CtPtr>& xin, co
     });
 }
 
+int Evaluator::lt_split_cost(const std::vector<int>& idx, int n1) {
+    std::set<int> groups, babies;
+    for (int d : idx) {
+        groups.insert(d - d % n1);
+        if (d % n1) babies.insert(d % n1);
+    }
+    const int n2 = (int)groups.size(), R = n2 - (int)groups.count(0);
+    return 4 * (n2 + (R + 6) / 7) + (int)babies.size();
+}
+
 std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xin, const std::vector<std::vector<PtPtr>>& pts,
-                                                    const std::vector<int>& baby, const std::vector<int>& giant, bool rescale_out) {
+                                                    const std::vector<int>& baby, const std::vector<int>& giant, bool rescale_out,
+                                                    long double pt_scale) {
     const int n1 = (int)baby.size(), n2 = (int)giant.size();
     if (n1 < 1 || n1 > LtDot::MAX_STEPS || n2 < 1 || (int)pts.size() != n2 || baby[0] != 0)
         throw Error(FHELIN_ERR_ARG, "linear_transform_rows: 1..32 baby steps (the first unrotated), >= 1 giant steps, pts [n2][n1]");
@@ -800,19 +812,24 @@ std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xi
     rescale_degree2(x, nullptr, "linear_transform_rows: ciphertext must have 2 components");   // as before any product with a plaintext
     const size_t N = c_.N;
     const int K = c_.K, nl = c_.L + 1 + K;
+    // a plaintext made from residues holds its one encoding over the full key basis: a call that carries one reads every term that way
+    bool dense = true;
+    for (const auto& row : pts)
+        for (const PtPtr& p : row) dense = dense && !(p && p->fixed);
     std::vector<CtPtr> out = for_groups(x.size(), std::max(1, batch_limit / n2), [&](size_t f, size_t i) { return same_shape(*x[f], *x[i]); },
                                         [&](const std::vector<size_t>& idx) {
         const std::vector<CtPtr> chunk = make_contiguous(pick(x, idx), 0);
         const int B = (int)chunk.size(), ell = chunk[0]->ell;
         const size_t pn = (size_t)ell * N, ctw = 2 * pn;
-        const long double sf = c_.sf_real[chunk[0]->level()];
-        // the diagonals over the full key basis at this level's scale: made on first use, kept by the plan's plaintexts
+        const long double sf = pt_scale > 0 ? pt_scale : c_.sf_real[chunk[0]->level()];
+        // the diagonals at this level's scale (or the caller's), over the rows the kernel reads - Q limbs 0..ell-1, then the special limbs
+        // (Plaintext::at_sliced: the residues of the full-basis encoding on those rows): made on first use, kept by the plan's plaintexts
         std::vector<std::shared_ptr<Encoding>> enc((size_t)n2 * n1);
         size_t terms = 0;
         for (int g = 0; g < n2; ++g)
             for (int b = 0; b < n1; ++b)
                 if (pts[g][b]) {
-                    enc[(size_t)g * n1 + b] = pts[g][b]->at(nl, sf);
+                    enc[(size_t)g * n1 + b] = dense ? pts[g][b]->at_sliced(ell, sf) : pts[g][b]->at(nl, sf);
                     ++terms;
                 }
         std::vector<CtPtr> o = new_ct_batch(B * n2, 2, ell, chunk[0]->deg + 1, chunk[0]->scale * sf, chunk[0]->slots);
@@ -831,6 +848,7 @@ std::vector<CtPtr> Evaluator::linear_transform_rows(const std::vector<CtPtr>& xi
                 ld.g0 = g0;
                 ld.groups = n2;
                 ld.pmod = c_.d_pmod;
+                ld.dense_v = dense ? 1 : 0;
                 std::vector<LtStep> tab;
                 for (const Step& st : steps) {
                     LtStep e{};

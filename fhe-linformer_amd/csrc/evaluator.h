@@ -57,6 +57,9 @@ struct Encoding {
     Context* ctx = nullptr;
     u64* d = nullptr;  // [ell][N] NTT form
     int ell = 0;
+    // 0: row l is limb l (ell <= L+1 chain limbs, or the full key basis at ell = L+1+k).  > 0: limb-sliced (Plaintext::at_sliced): ell =
+    // ell_q + k rows, Q limbs 0..ell_q-1 and then the k special limbs - the rows of the full-basis encoding a key switch at ell_q limbs reads
+    int ell_q = 0;
     long double scale = 0;
     // made under lane `made_lane` (stream order covers its later uses there); another lane's stream waits for `ready` before its first
     // use (Plaintext::at) - a device-side wait, the host never blocks
@@ -84,7 +87,17 @@ struct Plaintext {
     double max_abs = 0.0;
     static constexpr size_t MAX_ENCODINGS = 16;
     std::vector<std::shared_ptr<Encoding>> cache;   // most recently used first (Plaintext::at)
-    std::shared_ptr<Encoding> at(int ell, long double scale);
+    std::shared_ptr<Encoding> at(int ell, long double scale, int ell_q = 0);
+    // the limb-sliced encoding over the key basis at ell_q live limbs, [ell_q + k][N], at exactly `scale`: what
+    // Evaluator::linear_transform_rows multiplies in QP.  Cached apart from the plain encodings (Encoding::ell_q is part of the key)
+    std::shared_ptr<Encoding> at_sliced(int ell_q, long double scale);
+    // device bytes of the limb-sliced encodings this handle holds
+    size_t sliced_bytes() const {
+        size_t b = 0;
+        for (const auto& e : cache)
+            if (e->ell_q > 0) b += (size_t)e->ell * ctx->N * 8;
+        return b;
+    }
     // set on a handle of the content-keyed plaintext cache (capi_internal.h PtCache): the cache's own plaintext of the same values.  An
     // encoding this handle has not used yet is taken from there when one exists at EXACTLY this (limb count, scale) - the bytes this
     // handle would have made itself - and every encoding made here is left there for the handles of later passes.  The handle's own
@@ -210,8 +223,18 @@ public:
     // pts [n2][n1], null = term absent; baby[0] == 0; n1 <= 32.  ONE ModUp per row, the inner sums of all groups from the rotation keys
     // as they are (launch_ks_inner_dot: no folded keys, no rotated ciphertext in memory), ONE ModDown over rows x groups, then the
     // giant steps through rotate_each_sum_rows.  The residues of rotate_each_sum([hoisted_dot(x, pts[g], baby[1:]) for g], giant).
+    // The planner's cost of splitting the diagonal indices idx (>= 0) into n1 baby steps, in quarters of a pair-ModDown:
+    // 4 * (n2 + ceil(R / 7)) + (baby keys read); n2 = the giant-step groups that carry a diagonal, R = those of them that are rotated (g != 0),
+    // baby keys = the distinct nonzero residues d mod n1.  Every group costs one pair-ModDown for its inner sum and the rotated groups share one
+    // more per 7 in the giant steps; a baby step costs one pass over its rotation key in the inner product, taken as a quarter of a
+    // pair-ModDown (2 beta (ell + k) limb vectors streamed once against the ModDown's 2 k inverse and 2 ell forward transforms and its
+    // conversion) - an estimate, not a measurement.  Used by fhelin_lt_create and by the bootstrap's stages (Bootstrapper::set_lt)
+    static int lt_split_cost(const std::vector<int>& idx, int n1);
+    // pt_scale > 0: the plaintexts are taken at that scale instead of the level's own (the bootstrap's first stage after a ModRaise to fewer
+    // limbs: Bootstrapper::apply); the result's scale follows
     std::vector<CtPtr> linear_transform_rows(const std::vector<CtPtr>& xs, const std::vector<std::vector<PtPtr>>& pts,
-                                             const std::vector<int>& baby, const std::vector<int>& giant, bool rescale_out = false);
+                                             const std::vector<int>& baby, const std::vector<int>& giant, bool rescale_out = false,
+                                             long double pt_scale = 0);
     // the power steps of a Chebyshev evaluation and EvalMod's double angle through mult_affine_rescale_batch.  OFF by default
     // (FHELIN_MERGED_PRODUCTS=1 turns it on): measured at no gain (282.0 vs 281.2 ms per pass: the launches it saves are replaced by its
     // own) and at 3 x the logit error (0.017 vs 0.006: the merged conversion's rounding has three times the standard deviation of a

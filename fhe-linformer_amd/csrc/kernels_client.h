@@ -17,6 +17,10 @@ void launch_fft_special_inv(double* data, const u32* rot, const double* ksi, int
 // out [n_vec][ell][N] (coefficient form) <- round(v * scale) mod q_l with scale = scale_mant * 2^scale_exp (64-bit significand)
 void launch_encode_round_reduce(const DeviceTables& t, u64* out, const double* fftdata, int slots, int ell, u64 scale_mant, int scale_exp,
                                 int n_vec, hipStream_t s);
+// the limb-sliced form (Plaintext::at_sliced): out [n_vec][ell_q + k][N], the first ell_q rows modulo q_0..q_{ell_q-1}, then k rows modulo
+// the limbs from id L1 on (the special limbs) - the rows of the full-basis encoding that a key switch at ell_q limbs reads, dense
+void launch_encode_round_reduce_split(const DeviceTables& t, u64* out, const double* fftdata, int slots, int ell_q, int k, int L1, u64 scale_mant,
+                                      int scale_exp, int n_vec, hipStream_t s);
 // out [n_poly][ell][N] (coefficient form): kind 0 rounded Gaussian sigma 3.19, kind 1 uniform ternary; polynomial p uses
 // ChaCha20 stream stream_base + p
 void launch_sample_small(const DeviceTables& t, u64* out, const SamplerKey& key, u64 stream_base, int kind, int ell, int n_poly, hipStream_t s);

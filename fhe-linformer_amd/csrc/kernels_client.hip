@@ -149,9 +149,11 @@ __device__ __forceinline__ void x87_mul_round(double v, u64 ms, int es, u64& lo,
 }
 
 // grid (N/256, n_vec): thread = coefficient position n of vector b.  fftdata [n_vec][slots] is the output of the stage
-// kernels (before bit reversal and 1/n scaling); out [n_vec][ell][N] residues (coefficient form)
+// kernels (before bit reversal and 1/n scaling); out [n_vec][ell][N] residues (coefficient form).  Row l is reduced modulo limb
+// l < ell_q ? l : L1 + (l - ell_q): the first ell_q rows are chain limbs, the rest follow from limb id L1 (the special limbs of a
+// limb-sliced encoding, launch_encode_round_reduce_split); ell_q == ell: row l is limb l
 __global__ __launch_bounds__(256) void encode_round_reduce_kernel(DeviceTables t, u64* out, const double2* fftdata, int slots, int log_slots,
-                                                                  int ell, u64 ms, int es, double inv_n) {
+                                                                  int ell, int ell_q, int L1, u64 ms, int es, double inv_n) {
     const size_t N = (size_t)1 << t.log_n;
     const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t gapc = (N / 2) / slots;
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(256) void encode_round_reduce_kernel(DeviceTables t
     bool neg;
     x87_mul_round(val, ms, es, lo, hi, neg);
     for (int l = 0; l < ell; ++l) {
-        const Barrett br = load_barrett(t, l);
+        const Barrett br = load_barrett(t, l < ell_q ? l : L1 + (l - ell_q));
         const u64 h = barrett_reduce128(hi, 0, br);
         u64 r = barrett_reduce128(lo, h, br);
         if (neg) r = neg_mod(r, br.q);
@@ -502,7 +504,14 @@ void launch_encode_round_reduce(const DeviceTables& t, u64* out, const double* f
     int log_slots = 0;
     while ((1 << log_slots) < slots) ++log_slots;
     hipLaunchKernelGGL(encode_round_reduce_kernel, dim3((1u << t.log_n) / 256, (unsigned)n_vec), dim3(256), 0, s, t, out,
-                       reinterpret_cast<const double2*>(fftdata), slots, log_slots, ell, scale_mant, scale_exp, 1.0 / slots);
+                       reinterpret_cast<const double2*>(fftdata), slots, log_slots, ell, ell, 0, scale_mant, scale_exp, 1.0 / slots);
+}
+void launch_encode_round_reduce_split(const DeviceTables& t, u64* out, const double* fftdata, int slots, int ell_q, int k, int L1, u64 scale_mant,
+                                      int scale_exp, int n_vec, hipStream_t s) {
+    int log_slots = 0;
+    while ((1 << log_slots) < slots) ++log_slots;
+    hipLaunchKernelGGL(encode_round_reduce_kernel, dim3((1u << t.log_n) / 256, (unsigned)n_vec), dim3(256), 0, s, t, out,
+                       reinterpret_cast<const double2*>(fftdata), slots, log_slots, ell_q + k, ell_q, L1, scale_mant, scale_exp, 1.0 / slots);
 }
 void launch_sample_small(const DeviceTables& t, u64* out, const SamplerKey& key, u64 stream_base, int kind, int ell, int n_poly, hipStream_t s) {
     const unsigned bx = (unsigned)(((1u << t.log_n) / 8 + 255) / 256);

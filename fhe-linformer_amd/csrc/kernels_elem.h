@@ -321,7 +321,8 @@ struct LtStep {
     static constexpr int MAX_G = 4;
     const u64* key;         // EvalKey::d_perm of the step's rotation key; nullptr: the unrotated term
     const u32* map;         // the rotation's automorphism map
-    const u64* v[MAX_G];    // V_{g,b} over the FULL key basis [L1 + k][N], NTT form, for the launch's groups
+    const u64* v[MAX_G];    // V_{g,b}, NTT form, for the launch's groups: limb-sliced [ell + k][N] (LtDot::dense_v) or over the FULL key
+                            // basis [L1 + k][N]
     u32 mask;               // bit g: the term (g, b) is present
     u32 pad;
 };
@@ -332,6 +333,10 @@ struct LtDot {
     int n_groups = 0;                      // groups of this launch (<= LtStep::MAX_G)
     int g0 = 0, groups = 0;                // first group of the launch, groups per batch row in accQ / accP
     const u64* pmod = nullptr;             // [L+1][2] P mod q_t, shoup
+    // 1: every V of the launch is a limb-sliced encoding (Plaintext::at_sliced) - the rows the launch reads, dense: Q limbs 0..ell-1, then
+    // the k special limbs - and is indexed by the block's own row; 0: encodings over the full key basis, indexed by limb id (what a
+    // plaintext made from residues holds)
+    int dense_v = 0;
 };
 // c0 / c1: the two components of batch row b at + b * sh.c_stride; ext: the digits of c1 from modup (not times 2^64)
 void launch_ks_inner_dot(const DeviceTables& t, const KsShape& sh, const LtDot& ld, u64* accQ, u64* accP, const u64* ext, const u64* c0,

@@ -445,6 +445,7 @@ __global__ __launch_bounds__(256) void ks_inner_dot_kernel(DeviceTables t, KsSha
     const int bi = kb_.bi, tt = kb_.tt;
     const bool isq = tt < sh.ell;
     const int limb = isq ? tt : sh.L1 + (tt - sh.ell);
+    const int vrow = ld.dense_v ? tt : limb;   // the plaintexts' row of this limb: limb-sliced encodings hold only the rows read here (LtDot)
     const size_t N = (size_t)1 << t.log_n, row = N >> 1;
     const int own = isq ? tt / sh.alpha : -1;
     const Barrett br = load_barrett(t, limb);
@@ -517,7 +518,7 @@ __global__ __launch_bounds__(256) void ks_inner_dot_kernel(DeviceTables t, KsSha
         for (int g = 0; g < G; ++g)
             if ((st.mask >> g) & 1) {
                 // canonical residues: plaintext encodings come from the plain forward NTT (never LimbBatch::lazy_out), which the 2^125 bound needs
-                const u64x2 v = reinterpret_cast<const u64x2*>(st.v[g])[(size_t)limb * row + n2];
+                const u64x2 v = reinterpret_cast<const u64x2*>(st.v[g])[(size_t)vrow * row + n2];
                 acc_mac(sum[g][0], w[0], v.x);
                 acc_mac(sum[g][1], w[1], v.y);
                 acc_mac(sum[g][2], w[2], v.x);

@@ -59,7 +59,7 @@ def _keep_mask(keep_slots):
 class GpuController:
     """The reference's FHEController surface on top of fhe_linformer_amd.Engine."""
 
-    def __init__(self, eng, verbose=False, pair_bootstraps=False):
+    def __init__(self, eng, verbose=False, pair_bootstraps=False, bootstrap_lt=False):
         self.e, self.verbose = eng, verbose
         self.num_slots = SLOTS
         self.n_boot = 0
@@ -68,6 +68,10 @@ class GpuController:
         self.pair_bootstraps = bool(pair_bootstraps)
         if self.pair_bootstraps:
             eng.set_bootstrap_pairing(True)
+        # the bootstrap's linear stages on the linear-transform engine (Engine.set_bootstrap_lt; off: the engine's setting, FHELIN_BOOT_LT,
+        # stays as it is).  The split binds at bootstrap_setup: an engine that was set up without it refuses (FHELIN_ERR_STATE)
+        if bootstrap_lt and not eng.bootstrap_lt()[0]:
+            eng.set_bootstrap_lt(True)
 
     # handles
     def level(self, c):
@@ -320,13 +324,15 @@ class BatchedController:
     of a sample run in batches of 2B, 5B and B.  Sample x ends in EXACTLY the residues its own single pass gives
     (tests/test_batched_forward_gpu.py).  All samples of a batch have one token count."""
 
-    def __init__(self, eng, B, verbose=False, pair_bootstraps=False):
+    def __init__(self, eng, B, verbose=False, pair_bootstraps=False, bootstrap_lt=False):
         self.e, self.B, self.verbose = eng, int(B), verbose
         self.num_slots = SLOTS
         self.n_boot = 0
         self.pair_bootstraps = bool(pair_bootstraps)   # as GpuController's
         if self.pair_bootstraps:
             eng.set_bootstrap_pairing(True)
+        if bootstrap_lt and not eng.bootstrap_lt()[0]:   # as GpuController's
+            eng.set_bootstrap_lt(True)
 
     # ---- layout helpers: a list of n Batches <-> the flat sample-major handle list the C ABI takes
     def _flat(self, rows):
@@ -509,10 +515,10 @@ class LanedBatchedController:
 
     _ONCE = ("level", "encode", "read_plain_input", "read_plain_repeated_input", "read_plain_expanded_input")
 
-    def __init__(self, eng, B, lanes=2, pair_bootstraps=False):
+    def __init__(self, eng, B, lanes=2, pair_bootstraps=False, bootstrap_lt=False):
         assert B % lanes == 0 and lanes >= 1
         self.e, self.B, self.lanes, self.h = eng, B, lanes, B // lanes
-        self.sub = [BatchedController(eng, self.h, pair_bootstraps=pair_bootstraps) for _ in range(lanes)]
+        self.sub = [BatchedController(eng, self.h, pair_bootstraps=pair_bootstraps, bootstrap_lt=bootstrap_lt) for _ in range(lanes)]
         self.num_slots = SLOTS
 
     @property

@@ -311,7 +311,10 @@ int fhelin_level_reduce(fhelin_ctx* c, const fhelin_ct* a, int32_t new_ell, fhel
  * rotated ciphertext and no plaintext-folded key is ever stored, and a call costs one ModDown per group plus one per <= 7 rotated groups.
  *
  * A plan (fhelin_lt) is host data: the split, the two index lists and one plaintext per term.  Creating one needs no device; the
- * encodings over the full key basis are made on first use per (limb count, scale) and stay with the plan's plaintexts.
+ * encodings are made on first use per (limb count, scale) and stay with the plan's plaintexts.  An encoding is LIMB-SLICED: a term
+ * applied at ell limbs holds the rows the inner product reads - Q limbs 0..ell-1, then the k special limbs, (ell + k) N words - with the
+ * residues of the encoding over the full key basis on those rows.  fhelin_lt_encoding_bytes: the device bytes the plan's plaintexts hold
+ * that way, sum over (term, distinct (ell, scale) applied at) of (ell + k) N 8.
  *
  * fhelin_lt_create: diags [n_diag][slots], diag_idx [n_diag] (reduced mod slots; duplicates, n_diag < 1, a slots that is not the
  * context's packing, n1 outside 0..32 and non-finite values are FHELIN_ERR_ARG); n1 = 0 lets the planner choose n1 <= 32.  It builds
@@ -336,6 +339,7 @@ int fhelin_lt_create_pts(fhelin_ctx* c, const fhelin_pt* const* pts /* [n2][n1],
 int fhelin_lt_info(const fhelin_lt* lt, int32_t* n1, int32_t* n2, int32_t* n_terms, int32_t* slots);
 int fhelin_lt_rotations(const fhelin_lt* lt, int32_t* out, int32_t cap, int32_t* n);
 int fhelin_lt_apply(fhelin_ctx* c, const fhelin_lt* lt, const fhelin_ct* const* v, int32_t n, int32_t rescale, fhelin_ct** outs);
+int fhelin_lt_encoding_bytes(const fhelin_lt* lt, uint64_t* bytes);
 void fhelin_lt_free(fhelin_lt* lt);
 
 /* ---- the same residue functions without scale/level bookkeeping (bit-exact parity vs oracle/) -- */
@@ -545,10 +549,26 @@ int fhelin_bootstrap_pair_partial(fhelin_ctx* c, const fhelin_ct* a, const fheli
  * fhelin_bootstrap_paired_batch would.  The results are bootstraps of the same values with different residues; off, nothing changes. */
 int fhelin_ctx_set_bootstrap_pairing(fhelin_ctx* c, int32_t on);
 int fhelin_ctx_bootstrap_pairing(fhelin_ctx* c, int32_t* on);
+/* ---- Bootstrap linear stages on the linear-transform engine (runtime knob, OFF by default; FHELIN_BOOT_LT=1 and FHELIN_BOOT_LT_N1=k are
+ * read at context creation).  On: every CoeffsToSlots / SlotsToCoeffs stage is split as a linear transform above - d = g + b with at most
+ * 32 baby steps, all indices multiples of the stage's stride, V_{g,b} = rot(diag_{g+b}, -g) - and applied as ONE fhelin_lt_apply-shaped
+ * call over all ciphertexts of the batch (single, batched, dropped, level-planned, paired and iterative bootstraps alike): one ModUp per
+ * stage, the baby steps' key products formed once in QP, n2 + ceil(R / 7) pair-ModDowns.  Bit for bit the composition stated for
+ * fhelin_lt_apply, with the diagonals at sf[level + 1] q_{ell-1} / scale where a stage's input is not at its level's own scale (the first
+ * stage after a ModRaise to fewer limbs).  The plaintext products are taken in QP before the ModDown, so the residues (not the values)
+ * differ from the default path's.  n1 = 0: the linear-transform planner's cost, 4 (n2 + ceil(R / 7)) + baby keys, chooses per stage;
+ * 1 <= n1 <= 32 forces the baby-step count (capped by the number of indices a stage can hold); anything else is FHELIN_ERR_ARG.
+ * The knob chooses the split, and with it the diagonals' pre-rotation and the rotation-key list: it binds at fhelin_bootstrap_setup and
+ * changing it afterwards is FHELIN_ERR_STATE.  An evaluation-key set holds the keys of the setting its client had; loading it under the
+ * other setting names the missing key at fhelin_bootstrap_setup (FHELIN_ERR_KEY).  Off: describe, key list and every residue are unchanged. */
+int fhelin_ctx_set_bootstrap_lt(fhelin_ctx* c, int32_t on, int32_t n1);
+int fhelin_ctx_bootstrap_lt(const fhelin_ctx* c, int32_t* on, int32_t* n1);
 /* ---- read-only views of the bootstrapping set-up: the residue-level oracle (oracle/residue_boot.py, tests only) composes
  * EvalBootstrap (:445) from the same linear stages, Chebyshev coefficients and keys and must reach the same residues.
  * describe: out = {packed, slots, K, R, cheb_degree, correction, depth, n_c2s, n_s2c, then per stage (CoeffsToSlots stages
- * first): stage_slots, n_terms, n_terms x (giant, baby)}; *n = words needed (fills min(cap, *n)).
+ * first): stage_slots, n_terms, n_terms x (giant, baby)}; *n = words needed (fills min(cap, *n)).  With the linear-transform knob on
+ * a trailer follows: 1, the n1 asked for, per stage (same order) n1, n2 of the split in use, and the device bytes of the stages'
+ * limb-sliced encodings as two words (low, high) - sum over (term, distinct (ell, scale) applied at) of (ell + k) N 8.
  * diag: the plaintext diagonal of term `term` of stage `stage` (which: 0 CoeffsToSlots, 1 SlotsToCoeffs) as a handle for
  * fhelin_pt_export.  cheb: the cosine-fit coefficients EvalMod evaluates.  Key kind 2 of fhelin_key_export = conjugation key. */
 int fhelin_bootstrap_describe(fhelin_ctx* c, int32_t* out, int32_t cap, int32_t* n);
