@@ -242,6 +242,11 @@ def load_library():
         "fhelin_debug_unpack": (i32, [vp, vp, C.c_size_t, vp, i32, vp]),
         "fhelin_debug_pack_rate": (i32, [vp, vp, i32, i32, f32p]),
         "fhelin_debug_seeded_expand": (i32, [vp, vp, C.c_uint64, i32, i32, i32, vp, f32p]),
+        "fhelin_ct_frame_bytes": (i32, [vp, C.POINTER(vp), i32, i32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "fhelin_ct_export_device_many": (i32, [vp, C.POINTER(vp), i32, i32, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), vp]),
+        "fhelin_ct_import_device_many": (i32, [vp, vp, C.c_size_t, C.POINTER(C.c_double), i32, i32, vp, C.POINTER(vp)]),
+        "fhelin_debug_sync_count": (i32, [vp, u64p]),
+        "fhelin_debug_ct_addr": (i32, [vp, u64p, u64p]),
         "fhelin_client_ingest_wrapped": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(vp),
                                                C.POINTER(i32), vp]),
         "fhelin_client_ingest_wrapped_interleaved": (i32, [vp, i32, C.POINTER(vp), C.POINTER(vp), vp, i32, i32, vp, vp, vp, vp, vp, vp, i32,
@@ -1594,6 +1599,50 @@ class Engine:
         self._ck(self.lib.fhelin_ct_import_device(self.h, C.c_void_p(dptr), npoly, ell, deg, scale_hi, scale_lo, slots, C.byref(h)))
         return Ct(self, h)
 
+    # ---- device transport (include/fhelin.h "Device transport")
+    FRAME_RAW, FRAME_PACKED = 0, 1
+    STREAM_LEGACY = 1     # hipStreamLegacy: names the legacy default stream, whose own handle is 0 (0 / None mean "no stream")
+
+    def frame_bytes(self, cts, format=1):
+        """payload bytes of every ciphertext's frame (raw: the words of export(); packed: every limb vector at its modulus width):
+        (list of sizes, the largest)"""
+        cts = list(cts)
+        n = len(cts)
+        each = (C.c_size_t * max(n, 1))()
+        most = C.c_size_t()
+        self._ck(self.lib.fhelin_ct_frame_bytes(self.h, self._harr(cts) if n else None, n, int(format), each, C.byref(most)))
+        return list(each[:n]), most.value
+
+    def export_device_many(self, cts, dptr, stride, cap, format=1, stream=None):
+        """cts -> the frames dptr + i * stride of one device buffer of `cap` bytes, in one step; returns meta [n, 8] (float64: npoly,
+        ell, deg, slots, scale hi, scale lo, payload bytes, format).  stream: a HIP stream handle (torch: stream.cuda_stream) that is
+        ordered behind the writes without a host synchronisation (torch's default stream has the handle 0: pass STREAM_LEGACY for
+        it); None: one host synchronisation for the whole set"""
+        cts = list(cts)
+        n = len(cts)
+        meta = np.zeros((n, 8), dtype=np.float64)
+        self._ck(self.lib.fhelin_ct_export_device_many(self.h, self._harr(cts) if n else None, n, int(format), C.c_void_p(dptr), int(stride),
+                                                       int(cap), meta.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       C.c_void_p(stream) if stream else None))
+        return meta
+
+    def import_device_many(self, dptr, stride, meta, check=False, stream=None):
+        """the frames export_device_many wrote (meta [n, 8]) -> n handles, all or nothing; one allocation per (npoly, ell).  check: also
+        the range check residue < modulus (one host synchronisation).  stream: the stream whose work produced the frames; the import is
+        ordered behind it, and it behind the import, without a host synchronisation"""
+        m = np.ascontiguousarray(meta, dtype=np.float64).reshape(-1, 8)
+        n = m.shape[0]
+        outs = self._outs(n)
+        self._ck(self.lib.fhelin_ct_import_device_many(self.h, C.c_void_p(dptr), int(stride), m.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                                       1 if check else 0, C.c_void_p(stream) if stream else None, outs))
+        return self._cts(outs, n)
+
+    def sync_count(self):
+        """host synchronisations of this context so far (test hook)"""
+        n = C.c_uint64()
+        self._ck(self.lib.fhelin_debug_sync_count(self.h, C.byref(n)))
+        return n.value
+
     def generate_containers(self, inputs, bias=None):
         cap = (len(inputs) + 31) // 32
         outs = self._outs(cap)
@@ -1780,6 +1829,12 @@ class Ct:
 
     def export_device(self, dptr, cap_words):
         self.eng._ck(self.eng.lib.fhelin_ct_export_device(self.eng.h, self.h, C.c_void_p(dptr), cap_words))
+
+    def debug_addr(self):
+        """test hook: (device address of the residues, of the batch allocation they are a view of or 0)"""
+        d, b = C.c_uint64(), C.c_uint64()
+        self.eng._ck(self.eng.lib.fhelin_debug_ct_addr(self.h, C.byref(d), C.byref(b)))
+        return d.value, b.value
 
     def clone(self):
         return self.eng._un(self.eng.lib.fhelin_ct_clone, self)

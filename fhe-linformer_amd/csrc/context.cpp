@@ -398,6 +398,7 @@ Context::~Context() {
             if (lane_stream[k]) (void)hipStreamDestroy(lane_stream[k]);
         }
         if (fork_event) (void)hipEventDestroy(fork_event);
+        if (transport_ev) (void)hipEventDestroy(transport_ev);
         for (int i = 0; i < STAGE_SLOTS; ++i) {
             if (stage_ev[i]) (void)hipEventDestroy(stage_ev[i]);
             if (stage_buf[i]) (void)hipHostFree(stage_buf[i]);
@@ -418,6 +419,7 @@ void Context::require_device() const {
 
 void Context::sync() {
     require_device();
+    ++sync_count;
     hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
     if (stream == main_stream) {  // asynchronous lane work counts as issued work of the context
         for (int k = 1; k <= n_lanes; ++k) {

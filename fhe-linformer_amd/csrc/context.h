@@ -230,6 +230,8 @@ struct Context {
     };
     std::map<int, FftDev> fft_dev;    // by slot count
     void sync();
+    u64 sync_count = 0;             // host synchronisations so far: counted in sync() and nowhere else (fhelin_debug_sync_count)
+    hipEvent_t transport_ev = nullptr;   // stream hand-off of the device transport (capi_transport.cpp); made on first use
     // K1 launch + accounting (active = vectors actually transformed, for tables with skipped entries)
     void ntt(const LimbBatch& b, bool inverse, int active = -1) {
         stats.limb_ntt += (u64)(active >= 0 ? active : b.nvec);

@@ -35,6 +35,13 @@ def gather_results(dist, local, max_rows):
     return [o.cpu().numpy()[: int(m[0])] for o, m in zip(out, metas)]
 
 
+def _current_stream(eng):
+    """torch's current stream as the engine's transport calls take it: the default stream's handle is 0, which there means "no stream"
+    (a host synchronisation), so it goes by the name HIP has for it"""
+    import torch
+    return torch.cuda.current_stream().cuda_stream or eng.STREAM_LEGACY
+
+
 def _payload_ready(dev):
     """the engine imports gathered residues on ITS OWN HIP stream: the collective's output must be complete on torch's
     stream first (fhelin_ct_import_device / _export_device are host-synchronous on the library stream only)"""
@@ -64,11 +71,18 @@ class SlotTransport:
 
 class EngineTransport:
     """ciphertexts of fhe_linformer_amd.Engine: residues + (npoly, ell, deg, slots, scale hi/lo).  With the nccl backend the
-    residues go GPU -> GPU through device buffers (fhelin_ct_export_device / fhelin_ct_import_device, RCCL over xGMI);
-    with gloo (rehearsal, tests) through host arrays."""
+    residues go GPU -> GPU through device buffers (RCCL over xGMI); with gloo (rehearsal, tests) through host arrays.
 
-    def __init__(self, eng, device=False):
-        self.eng, self.device = eng, device
+    device=True: pack_many / unpack_many move a whole set of rows through the frames of ONE device buffer
+    (fhelin_ct_export_device_many / fhelin_ct_import_device_many): no host synchronisation per row, ordered against
+    torch's current stream by events.  pack / unpack (one ciphertext per call, fhelin_ct_export_device / _import_device) stay.
+    packed=True (default): frames carry every residue at its modulus width, about 0.83 of the raw 64-bit words on the bench chain (55- and 52-bit moduli).
+    The default rests on an argument, not on a measurement: pack and unpack run at HBM-class rates and an xGMI link
+    does not, so fewer bytes on the link should win - but no link has been measured here (no multi-GPU node).  packed=False
+    selects the raw words."""
+
+    def __init__(self, eng, device=False, packed=True):
+        self.eng, self.device, self.packed = eng, device, packed
 
     def force(self, cts):
         """the rows this rank owns are evaluated in ONE batched call, and only they (deferred rows of the engine)"""
@@ -94,6 +108,37 @@ class EngineTransport:
         limbs = np.ascontiguousarray(payload[: words * 8]).view(np.uint64).reshape(npoly, ell, self.eng.N)
         return self.eng.ct_import(limbs, deg=deg, scale=float(meta[4]), slots=slots)
 
+    @property
+    def format(self):
+        return self.eng.FRAME_PACKED if self.packed else self.eng.FRAME_RAW
+
+    def frame_stride(self, cts):
+        """bytes between the frames of `cts`: the largest payload, rounded up to the 16 bytes the frames are aligned to"""
+        return max(16, -(-self.eng.frame_bytes(cts, self.format)[1] // 16) * 16)
+
+    def pack_many(self, cts, out=None):
+        """cts -> (uint8 tensor [n, stride] on the device, meta [n, 8]); out: a [>= n, stride] tensor to write the frames into (the
+        send buffer of a collective).  The frames are ordered before whatever torch's current stream does next; padding bytes between
+        a payload and the stride are left as they are"""
+        import torch
+        cts = list(cts)
+        if out is None:
+            out = torch.empty((len(cts), self.frame_stride(cts)), dtype=torch.uint8, device="cuda")
+        assert out.dtype == torch.uint8 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= len(cts)
+        stride = out.stride(0) if out.shape[0] > 1 else out.shape[1]
+        meta = self.eng.export_device_many(cts, out.data_ptr(), stride, stride * out.shape[0], self.format,
+                                           stream=_current_stream(self.eng))
+        return out, meta
+
+    def unpack_many(self, buf, meta):
+        """the frames of buf [>= n, stride] described by meta [n, 8] -> n ciphertexts, one allocation per shape; ordered behind
+        whatever torch's current stream did to buf (the collective), and that stream behind the read"""
+        import torch
+        meta = np.asarray(meta, dtype=np.float64).reshape(-1, 8)
+        assert buf.dtype == torch.uint8 and buf.dim() == 2 and buf.stride(1) == 1 and buf.shape[0] >= len(meta)
+        stride = buf.stride(0) if buf.shape[0] > 1 else buf.shape[1]
+        return self.eng.import_device_many(buf.data_ptr(), stride, meta, check=False, stream=_current_stream(self.eng))
+
 
 def _all_gather_indexed(dist, transport, local, owned):
     """owned[r] = the indices rank r holds (local[i] on that rank) -> {index: ciphertext} of all of them on every rank (the owner
@@ -105,6 +150,8 @@ def _all_gather_indexed(dist, transport, local, owned):
     per = max(1, max(len(o) for o in owned))
     if hasattr(transport, "force"):
         transport.force([local[i] for i in mine])
+    if getattr(transport, "device", False) and hasattr(transport, "pack_many"):
+        return _all_gather_frames(dist, transport, [local[i] for i in mine], owned, per)
     packed = [transport.pack(local[i]) for i in mine]
     dev = _device(dist)
     size = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -127,6 +174,33 @@ def _all_gather_indexed(dist, transport, local, owned):
         for k, i in enumerate(owned[r]):
             payload = bufs[r][k] if getattr(transport, "device", False) else bufs[r][k].cpu().numpy()
             out[i] = transport.unpack(payload, metas[r][k].cpu().numpy())
+    return out
+
+
+def _all_gather_frames(dist, transport, mine, owned, per):
+    """the device path of _all_gather_indexed: the owned rows are exported straight into the (per, stride) send buffer
+    (transport.pack_many) and every rank's slice of the gathered buffer is imported in one step (transport.unpack_many).  No payload
+    is zero-filled or copied row by row, and the host does not wait for the collective: the engine orders its stream against torch's
+    by events.  Rows past a rank's count and bytes past a payload are never read (the metadata says what is there)."""
+    import torch
+    world = dist.get_world_size()
+    dev = _device(dist)
+    size = torch.tensor([transport.frame_stride(mine) if mine else 16], dtype=torch.int64, device=dev)
+    dist.all_reduce(size, op=dist.ReduceOp.MAX)
+    meta = torch.zeros((per, 8), dtype=torch.float64, device=dev)
+    buf = torch.empty((per, int(size[0])), dtype=torch.uint8, device=dev)
+    if mine:
+        _, m = transport.pack_many(mine, out=buf)
+        meta[: len(mine)] = torch.as_tensor(m, dtype=torch.float64)
+    metas = [torch.zeros_like(meta) for _ in range(world)]
+    bufs = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(metas, meta)
+    dist.all_gather(bufs, buf)
+    out = {}
+    for r in range(world):
+        if owned[r]:
+            got = transport.unpack_many(bufs[r], metas[r][: len(owned[r])].cpu().numpy())
+            out.update(zip(owned[r], got))
     return out
 
 

@@ -1062,6 +1062,56 @@ int fhelin_debug_unpack(fhelin_ctx* c, const uint64_t* packed, size_t n_words, c
  * unpack, copy of every round. */
 int fhelin_debug_pack_rate(fhelin_ctx* c, const int32_t* widths, int32_t n_vec, int32_t reps, float* ms);
 
+/* ---- device transport: many ciphertexts through one device buffer, no host synchronisation per ciphertext ---------------------
+ * The row gather of several GPUs moves a set of ciphertexts at once.  fhelin_ct_export_device / _import_device above move one per
+ * call and synchronise the host every time; the calls here write (read) n FRAMES of one device buffer - a collective's send (receive)
+ * buffer - in one step and hand the ordering over to the caller's stream.
+ *
+ * Frames.  Frame i starts at d_buf + i * stride_bytes.  format 0 (raw): the words of fhelin_ct_export, npoly * ell * N * 8 bytes.
+ * format 1 (packed): the same limb vectors in the same order, each a "Packed limb vector" (see "Packed formats") at the width of its
+ * own limb's modulus: npoly * sum_{l < ell} N w_l / 8 bytes.  No header: the shape travels in `meta`.  d_buf is 16-byte aligned,
+ * stride_bytes is a multiple of 16 and at least the largest frame, and n * stride_bytes <= cap_bytes.  The bytes of a frame's stride
+ * beyond its payload are neither written nor read.
+ *
+ * Metadata (host memory).  meta[i] = {npoly, ell, deg, slots, scale_hi, scale_lo, payload_bytes, format} as doubles: the 8-double row
+ * the row-sharded driver exchanges next to the payload; the scale is the 80-bit value as fhelin_ct_scale gives it.
+ *
+ * Stream hand-off (hip_stream, a hipStream_t of the caller's, e.g. the framework's current stream).  NULL means "no stream" here, so
+ * the legacy default stream - whose own handle is NULL - is named by hipStreamLegacy ((hipStream_t)1).
+ *   NULL      one host synchronisation at the end of the call (one per batch, not one per ciphertext).  The caller makes sure that
+ *             whatever produced (import) or still reads (export) the buffer has finished.
+ *   non-NULL  no host synchronisation.  At call time the library's stream is ordered behind everything already issued on the caller's
+ *             stream (an event recorded there): the producer of the frames of an import, the last reader of the buffer of an export.
+ *             After the library's last launch the caller's stream waits for an event of the library's, so work issued on that stream
+ *             afterwards - a collective that sends the frames, a framework that reuses the buffer - is ordered behind the call.
+ * fhelin_debug_sync_count: the host synchronisations of the context so far (the counter is incremented in the one place the library
+ * synchronises a context's streams, and nowhere else); the tests prove the contract above with it. */
+/* Payload bytes of every handle's frame (bytes_each[n], may be NULL) and the largest of them (max_bytes, may be NULL).  Deferred
+ * handles are evaluated (one batched force).  A wrapped handle, a handle with other than 2 or 3 components, format other than 0 or 1:
+ * FHELIN_ERR_ARG.  n = 0: *max_bytes = 0. */
+int fhelin_ct_frame_bytes(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n, int32_t format, size_t* bytes_each, size_t* max_bytes);
+/* Writes frame i from cts[i] and fills meta[i].  Deferred handles among cts are evaluated in one batched force; every handle is a
+ * level-plan terminal exactly as in fhelin_ct_export_device; a wrapped handle is FHELIN_ERR_ARG.  Packed: one pack table for all
+ * n * npoly * ell vectors through pinned staging and one launch of the pack kernel; raw: one device copy per frame.  Arguments are
+ * checked before anything is launched (format, stride, capacity and alignment before the handles are looked at); on an error nothing
+ * has been written.  n = 0 succeeds and does nothing. */
+int fhelin_ct_export_device_many(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n, int32_t format, uint8_t* d_buf,
+                                 size_t stride_bytes, size_t cap_bytes, double* meta, void* hip_stream);
+/* n frames -> n handles, all or nothing (on any error outs is untouched).  Every meta row is validated on the host before anything is
+ * allocated or launched: npoly 2 or 3, 1 <= ell <= n_q, deg 1 or 2, slots 0 (unset, as fhelin_ct_import leaves it) or a power of two up to N / 2, a finite positive scale,
+ * format 0 or 1, payload_bytes equal to the size the context's own moduli give and not above the stride.  One batch allocation per
+ * (npoly, ell), rows in frame order, so batched kernels downstream find the rows of a shape contiguous; one unpack launch (raw: one
+ * device copy per frame).  check = 1 also runs the range check residue < modulus of the other loaders on the imported residues: it
+ * costs the call's one host synchronisation (with a stream: the only one) and gives FHELIN_ERR_ARG and no handles on a violation.
+ * check = 0 imports whatever the frames hold: meant for frames this library wrote in the same trust domain (the GPUs of one node).
+ * Imported values are not level-plan sources, are never lowered and are never `seeded`.  n = 0 succeeds and does nothing. */
+int fhelin_ct_import_device_many(fhelin_ctx* c, const uint8_t* d_buf, size_t stride_bytes, const double* meta, int32_t n, int32_t check,
+                                 void* hip_stream, fhelin_ct** outs);
+int fhelin_debug_sync_count(fhelin_ctx* c, uint64_t* out);
+/* test hook: the device address of an evaluated handle's residues and of the batch allocation they are a view of (0: an allocation
+ * of its own).  The rows an import makes for one shape are views of one block, frame order, back to back. */
+int fhelin_debug_ct_addr(const fhelin_ct* ct, uint64_t* data, uint64_t* block);
+
 #ifdef __cplusplus
 }
 #endif
