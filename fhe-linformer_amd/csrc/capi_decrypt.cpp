@@ -36,10 +36,7 @@ int fhelin_decrypt_batch(fhelin_ctx* c, const fhelin_ct* const* cts, int32_t n, 
             in.push_back(ct->p);
             continue;
         }
-        if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
-        const CtPtr& p = ct_in(c, ct);
-        c->plan.check_terminal(*p, 2);
-        in.push_back(p);
+        in.push_back(terminal_in(c, ct));
     }
     c->cl.decrypt_batch(in, slots, flood_bits, all_lanes != 0, idx, n_idx, out);
     FHELIN_CATCH

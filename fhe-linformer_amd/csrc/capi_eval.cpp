@@ -311,9 +311,7 @@ int fhelin_decrypt(fhelin_ctx* c, const fhelin_ct* ct, double* out, int32_t slot
         std::memcpy(out, v.data(), v.size() * sizeof(double));
         return FHELIN_OK;
     }
-    if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
-    c->plan.check_terminal(*ct_in(c, ct), 2);
-    auto v = c->cl.decrypt(ct_in(c, ct), slots);
+    auto v = c->cl.decrypt(terminal_in(c, ct), slots);
     std::memcpy(out, v.data(), v.size() * sizeof(double));
     FHELIN_CATCH
 }
@@ -330,9 +328,7 @@ int fhelin_ct_import(fhelin_ctx* c, const uint64_t* limbs, int32_t npoly, int32_
 int fhelin_ct_export(fhelin_ctx* c, const fhelin_ct* ct, uint64_t* out, size_t cap) {
     NEED(c && ct && out);
     FHELIN_TRY
-    if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
-    const CtPtr& p = ct_in(c, ct);
-    c->plan.check_terminal(*p, 2);
+    const CtPtr& p = terminal_in(c, ct);
     if (cap < p->words()) throw Error(FHELIN_ERR_ARG, "buffer too small");
     hip_check(hipMemcpyAsync(out, p->d, p->words() * 8, hipMemcpyDeviceToHost, c->ctx.stream), "ct export");
     c->ctx.sync();
@@ -341,9 +337,7 @@ int fhelin_ct_export(fhelin_ctx* c, const fhelin_ct* ct, uint64_t* out, size_t c
 int fhelin_ct_export_device(fhelin_ctx* c, const fhelin_ct* ct, uint64_t* d_out, size_t cap) {
     NEED(c && ct && d_out);
     FHELIN_TRY
-    if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
-    const CtPtr& p = ct_in(c, ct);
-    c->plan.check_terminal(*p, 2);
+    const CtPtr& p = terminal_in(c, ct);
     if (cap < p->words()) throw Error(FHELIN_ERR_ARG, "buffer too small");
     hip_check(hipMemcpyAsync(d_out, p->d, p->words() * 8, hipMemcpyDeviceToDevice, c->ctx.stream), "ct export (device)");
     c->ctx.sync();   // the caller's framework reads the buffer on its own stream next

@@ -45,9 +45,7 @@ int fhelin_decrypt_interleaved(fhelin_ctx* c, const fhelin_ct* ct, int32_t flood
         std::memcpy(out, v.data(), v.size() * sizeof(double));
         return FHELIN_OK;
     }
-    if (c->plan.live(ct->node, ct->node_epoch)) c->plan.terminal(ct->node, 2);
-    c->plan.check_terminal(*ct_in(c, ct), 2);
-    auto v = c->cl.decrypt_interleaved(ct_in(c, ct), slots, flood_bits);
+    auto v = c->cl.decrypt_interleaved(terminal_in(c, ct), slots, flood_bits);
     std::memcpy(out, v.data(), v.size() * sizeof(double));
     FHELIN_CATCH
 }

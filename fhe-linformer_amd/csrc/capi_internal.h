@@ -11,6 +11,7 @@
 #include "composite.h"
 #include "bootstrap.h"
 #include "kernels_keys.h"
+#include "wire_header.h"   // get / put: fields of the file and blob formats, at any alignment
 #include "deferred.h"   // LazyRows, LazyHeavy and the forcing rules that ct_in and vec_of go through
 
 namespace fhelin {
@@ -143,13 +144,6 @@ struct fhelin_pt {
 
 namespace fhelin {
 int capi_fail(int code, const std::string& msg);
-// fields of the file and blob formats (capi_keys.cpp, capi_compact.cpp), at any alignment
-template <class T> T get(const uint8_t* b, size_t off) {
-    T v;
-    std::memcpy(&v, b + off, sizeof(T));
-    return v;
-}
-template <class T> void put(uint8_t* b, size_t off, T v) { std::memcpy(b + off, &v, sizeof(T)); }
 // the per-vector device digests h[n_vec][2] (launch_key_digest: digest, range flag) of one key or one c0 folded into its digest;
 // in_range: every residue below its limb's modulus
 inline u64 fold_key_digest(const u64* h, size_t n_vec, bool& in_range) {
@@ -192,6 +186,14 @@ inline const CtPtr& ct_in(fhelin_ctx* c, const fhelin_ct* h) {
         x.release_holds(ct.async_lane, ct.async_seq);
     }
     return h->p;
+}
+// `h` is read by a terminal of the level plan (a decryption, an export: `need` effective limbs are all it reads): marked while
+// recording, checked while applying, and the value itself as ct_in gives it
+inline const CtPtr& terminal_in(fhelin_ctx* c, const fhelin_ct* h, int need = 2) {
+    if (c->plan.live(h->node, h->node_epoch)) c->plan.terminal(h->node, need);
+    const CtPtr& p = ct_in(c, h);
+    c->plan.check_terminal(*p, need);
+    return p;
 }
 // the ciphertexts behind v[0..n): no null handle, everything deferred among them evaluated together (force_many), then ct_in in index order
 inline CtVec vec_of(fhelin_ctx* c, const fhelin_ct* const* v, int n) {

@@ -12,6 +12,9 @@
 // A packed set ("FHELINEP", include/fhelin.h "Packed formats") holds the same present rows, every limb vector at its modulus width: one
 // key at a time is packed into (or unpacked out of) a scratch block of one key's packed payload, which is what the staging pipeline then
 // streams; digests are those of the unpacked residues, computed by the same launches as for the other two formats.
+// Shared with the ciphertext formats (wire.h): the limb widths with the one 20..60 check, the pack-table row builder and the digest
+// run of fhelin_debug_key_digest.  The key-set headers and tables, key_digests (whose capped keys reorder the per-vector pairs) and the
+// table's upload beside the staged file stream stay here.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -22,6 +25,7 @@
 #include "kernels_keys.h"
 #include "kernels_pack.h"
 #include "kernels_seeded.h"
+#include "wire.h"   // limb widths, the pack-table builder and the digest run, shared with the ciphertext formats
 
 using namespace fhelin;
 
@@ -322,25 +326,19 @@ void key_digests(Context& x, const std::vector<Seg>& segs, const std::vector<uin
 // packed sets: the rows of runs[lo, hi) in order, one table entry each; the packed vectors lie back to back from `packed` on.  unpack:
 // packed -> rows, else rows -> packed.  Returns the packed words.
 size_t pack_table(std::vector<PackEntry>& tab, const Context& x, const std::vector<Seg>& runs, size_t lo, size_t hi, u64* packed, bool unpack) {
-    const size_t N = x.N;
     size_t at = 0;
-    for (size_t i = lo; i < hi; ++i)
-        for (size_t r = 0; r < runs[i].words / N; ++r) {
-            const int w = pack_width(x.moduli[runs[i].limb0 + (int)(r % (size_t)runs[i].limbs)]);
-            u64* row = runs[i].d + r * N;
-            tab.push_back(unpack ? PackEntry{packed + at, row, (u32)w, 0} : PackEntry{row, packed + at, (u32)w, 0});
-            at += pack_words(N, w);
-        }
+    for (size_t i = lo; i < hi; ++i) {
+        std::vector<int> width;
+        limb_widths(x, runs[i].limb0, runs[i].limbs, "packed key set", &width);
+        at += pack_rows(tab, x.N, runs[i].d, runs[i].words / x.N, width.data(), runs[i].limbs, packed + at, unpack);
+    }
     return at;
 }
 size_t packed_words_of(const Context& x, const std::vector<Seg>& runs, size_t lo, size_t hi) {
     std::vector<PackEntry> t;
     return pack_table(t, x, runs, lo, hi, nullptr, false);
 }
-void check_pack_widths(const Context& x) {
-    for (u64 m : x.moduli)
-        if (pack_width(m) < PACK_MIN_WIDTH || pack_width(m) > PACK_MAX_WIDTH) throw Error(FHELIN_ERR_ARG, "packed key set: a modulus outside 20..60 bits");
-}
+void check_pack_widths(const Context& x) { limb_widths(x, 0, (int)x.moduli.size(), "packed key set"); }
 
 bool fresh(const fhelin_ctx* c) {
     if (c->cl.keygen_run() || c->cl.eval_only() || c->cl.has_public_key() || c->ev.relin_key || c->ev.conj_key || c->boot.ready())
@@ -790,17 +788,10 @@ int fhelin_debug_key_digest(fhelin_ctx* c, const uint64_t* words, int32_t n_limb
     if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "debug_key_digest: ring dimension below 2^12");
     const size_t n = (size_t)n_limbs * x.N;
     Scratch<u64> d = x.scratch<u64>(n);
-    Scratch<u64> part = x.scratch<u64>(key_digest_scratch_words(x.N, n_limbs));
-    Scratch<u64> out = x.scratch<u64>(2 * (size_t)n_limbs);
     hip_check(hipMemcpyAsync(d, words, n * 8, hipMemcpyHostToDevice, x.stream), "debug digest upload");
-    launch_key_digest(x.dt, d, n_limbs, limb_first, n_limbs, part, out, x.stream);
-    hip_check(hipGetLastError(), "key digest kernels");
-    std::vector<u64> h(2 * (size_t)n_limbs);
-    hip_check(hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "debug digest download");
+    DigestRun run(x, {DigestItem{d, (size_t)n_limbs, limb_first, n_limbs, n_limbs}});
     hip_check(hipStreamSynchronize(x.stream), "debug digest sync");
-    d.reset();
-    part.reset();
-    out.reset();
+    const u64* h = run.pairs(0);
     for (int i = 0; i < n_limbs; ++i) {
         out_digests[i] = h[2 * i];
         out_ok[i] = (int32_t)h[2 * i + 1];

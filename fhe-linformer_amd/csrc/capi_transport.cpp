@@ -1,15 +1,15 @@
 // extern "C" boundary, part 13: device transport (include/fhelin.h "Device transport": frames, metadata and the stream contract are
 // documented there).  A set of ciphertexts goes into (comes out of) the frames of ONE device buffer: one pack table for every limb
 // vector of the set through pinned staging and one launch of the packing kernels (kernels_pack.hip) - or one device copy per raw
-// frame - and the ordering against the caller's stream is a pair of events, not a host synchronisation per ciphertext.
+// frame - and the ordering against the caller's stream is a pair of events, not a host synchronisation per ciphertext.  Widths, the
+// pack table and its upload, allocation by shape and the range run are wire.h's, shared with the blob formats; the metadata rows and
+// the stream hand-off are this file's own.
 #include "../../include/fhelin.h"
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include <map>
 #include <vector>
 #include "capi_internal.h"
-#include "kernels_keys.h"
-#include "kernels_pack.h"
+#include "wire.h"
 
 using namespace fhelin;
 
@@ -19,14 +19,7 @@ constexpr int META = 8;   // doubles per metadata row: npoly, ell, deg, slots, s
 
 // payload bytes of one component's first `ell` limb vectors
 size_t limb_bytes(const Context& x, int ell, int format) {
-    if (format == 0) return (size_t)ell * x.N * 8;
-    size_t words = 0;
-    for (int l = 0; l < ell; ++l) {
-        const int w = pack_width(x.moduli[l]);
-        if (w < PACK_MIN_WIDTH || w > PACK_MAX_WIDTH) throw Error(FHELIN_ERR_ARG, "device transport: a modulus outside 20..60 bits");
-        words += pack_words(x.N, w);
-    }
-    return words * 8;
+    return 8 * (format == 0 ? (size_t)ell * x.N : limb_widths(x, 0, ell, "device transport"));
 }
 
 void check_format(int32_t format) {
@@ -54,16 +47,6 @@ size_t frame_bytes_of(const Context& x, const Ciphertext& ct, int format, const 
     if (ct.wrapped()) throw Error(FHELIN_ERR_ARG, std::string(who) + ": handle " + std::to_string(i) + " is a wrapped input ciphertext");
     if (ct.npoly < 2 || ct.npoly > 3) throw Error(FHELIN_ERR_ARG, std::string(who) + ": handle " + std::to_string(i) + " has other than 2 or 3 components");
     return (size_t)ct.npoly * limb_bytes(x, ct.ell, format);
-}
-
-// the table of a pack / unpack launch, through the pinned staging ring (no stream drain), in pieces of at most one staging slot
-void upload_table(Context& x, PackEntry* d_tab, const std::vector<PackEntry>& tab) {
-    static_assert(sizeof(PackEntry) == 24, "a table entry is three words");
-    const size_t per = x.stage_words / 3;   // entries per piece
-    for (size_t lo = 0; lo < tab.size(); lo += per) {
-        const size_t cnt = std::min(per, tab.size() - lo);
-        x.upload_async(reinterpret_cast<u64*>(d_tab + lo), reinterpret_cast<const u64*>(tab.data() + lo), 3 * cnt);
-    }
 }
 
 hipEvent_t transport_event(Context& x) {
@@ -157,42 +140,32 @@ int fhelin_ct_export_device_many(fhelin_ctx* c, const fhelin_ct* const* cts, int
     if (format == 1 && x.N % 4096) throw Error(FHELIN_ERR_ARG, "export_device_many: packed frames need a ring dimension of at least 2^12");
     std::vector<size_t> bytes(n);
     size_t n_vec = 0;
+    int max_ell = 0;
     for (int i = 0; i < n; ++i) {
         bytes[i] = frame_bytes_of(x, *cts[i]->p, format, "export_device_many", i);
         if (bytes[i] > stride_bytes)
             throw Error(FHELIN_ERR_ARG, "export_device_many: frame " + std::to_string(i) + " needs " + std::to_string(bytes[i]) +
                                             " bytes, above stride_bytes");
         n_vec += (size_t)cts[i]->p->npoly * cts[i]->p->ell;
+        max_ell = std::max(max_ell, cts[i]->p->ell);
     }
     // 3. every handle is a terminal of the level plan, as in fhelin_ct_export_device
     CtVec ps(n);
-    for (int i = 0; i < n; ++i) {
-        if (c->plan.live(cts[i]->node, cts[i]->node_epoch)) c->plan.terminal(cts[i]->node, 2);
-        ps[i] = ct_in(c, cts[i]);
-        c->plan.check_terminal(*ps[i], 2);
-    }
+    for (int i = 0; i < n; ++i) ps[i] = terminal_in(c, cts[i]);
     const Caller caller(hip_stream);
     wait_for_caller(x, caller);   // whatever still reads the buffer on the caller's stream comes first
-    const size_t N = x.N;
     if (format == 0) {
         for (int i = 0; i < n; ++i)
             hip_check(hipMemcpyAsync(d_buf + (size_t)i * stride_bytes, ps[i]->d, bytes[i], hipMemcpyDeviceToDevice, x.stream), "export_device_many copy");
     } else {
-        std::vector<int> width(x.L + 1);
-        for (int l = 0; l <= x.L; ++l) width[l] = pack_width(x.moduli[l]);
+        std::vector<int> width;
+        limb_widths(x, 0, max_ell, "device transport", &width);
         std::vector<PackEntry> tab;
         tab.reserve(n_vec);
-        for (int i = 0; i < n; ++i) {
-            const Ciphertext& ct = *ps[i];
-            u64* at = reinterpret_cast<u64*>(d_buf + (size_t)i * stride_bytes);
-            for (int v = 0; v < ct.npoly * ct.ell; ++v) {
-                const int w = width[v % ct.ell];
-                tab.push_back(PackEntry{ct.d + (size_t)v * N, at, (u32)w, 0});
-                at += pack_words(N, w);
-            }
-        }
-        Scratch<PackEntry> d_tab = x.scratch<PackEntry>(tab.size());
-        upload_table(x, d_tab, tab);
+        for (int i = 0; i < n; ++i)
+            pack_rows(tab, x.N, ps[i]->d, (size_t)ps[i]->npoly * ps[i]->ell, width.data(), ps[i]->ell,
+                      reinterpret_cast<u64*>(d_buf + (size_t)i * stride_bytes), false);
+        Scratch<PackEntry> d_tab = upload_pack_table(x, tab);
         launch_pack_residues(d_tab, (int)tab.size(), x.N, x.stream);
         hip_check(hipGetLastError(), "export_device_many pack");
     }
@@ -222,7 +195,7 @@ int fhelin_ct_import_device_many(fhelin_ctx* c, const uint8_t* d_buf, size_t str
     // 1. every row of the metadata, on the host, before anything is allocated or launched
     check_buffer(d_buf, stride_bytes);
     std::vector<Frame> fr(n);
-    bool any_packed = false;
+    int packed_ell = 0;   // most limbs of a packed frame
     for (int i = 0; i < n; ++i) {
         const double* m = meta + (size_t)META * i;
         const std::string at = "import_device_many: frame " + std::to_string(i) + ": ";
@@ -240,89 +213,54 @@ int fhelin_ct_import_device_many(fhelin_ctx* c, const uint8_t* d_buf, size_t str
         if (m[6] != (double)want)
             throw Error(FHELIN_ERR_ARG, at + "payload_bytes does not match the context's moduli (" + std::to_string(want) + " expected)");
         if (want > stride_bytes) throw Error(FHELIN_ERR_ARG, at + "payload_bytes is above stride_bytes");
-        any_packed |= f.format == 1;
+        if (f.format == 1) packed_ell = std::max(packed_ell, f.ell);
     }
     x.require_device();
-    if (any_packed && x.N % 4096) throw Error(FHELIN_ERR_ARG, "import_device_many: packed frames need a ring dimension of at least 2^12");
+    if (packed_ell && x.N % 4096) throw Error(FHELIN_ERR_ARG, "import_device_many: packed frames need a ring dimension of at least 2^12");
     // 2. one batch allocation per (components, limbs), rows in frame order
-    std::map<std::pair<int, int>, std::vector<int>> groups;
-    for (int i = 0; i < n; ++i) groups[{fr[i].npoly, fr[i].ell}].push_back(i);
-    std::vector<CtPtr> cts(n);
-    size_t n_vec = 0;
-    for (auto& g : groups) {
-        std::vector<CtPtr> b = c->ev.new_ct_batch((int)g.second.size(), g.first.first, g.first.second, 1, 1.0L, 1);
-        for (size_t k = 0; k < g.second.size(); ++k) {
-            const Frame& f = fr[g.second[k]];
-            b[k]->deg = f.deg;
-            b[k]->slots = f.slots;
-            b[k]->scale = f.scale;
-            cts[g.second[k]] = b[k];
-            if (f.format == 1) n_vec += (size_t)f.npoly * f.ell;
-        }
+    std::vector<std::pair<int, int>> shape(n);
+    for (int i = 0; i < n; ++i) shape[i] = {fr[i].npoly, fr[i].ell};
+    ShapeBatch sb(c, shape);
+    const std::vector<CtPtr>& cts = sb.cts;
+    for (int i = 0; i < n; ++i) {
+        cts[i]->deg = fr[i].deg;
+        cts[i]->slots = fr[i].slots;
+        cts[i]->scale = fr[i].scale;
     }
     // 3. behind the producer of the frames; raw frames are copies, every packed vector goes through one unpack launch
     const Caller caller(hip_stream);
     wait_for_caller(x, caller);
-    const size_t N = x.N;
     std::vector<PackEntry> tab;
-    tab.reserve(n_vec);
-    std::vector<int> width(x.L + 1);
-    for (int l = 0; l <= x.L; ++l) width[l] = pack_width(x.moduli[l]);
+    std::vector<int> width;
+    limb_widths(x, 0, packed_ell, "device transport", &width);
     for (int i = 0; i < n; ++i) {
         const Frame& f = fr[i];
-        const uint8_t* src = d_buf + (size_t)i * stride_bytes;
-        if (f.format == 0) {
+        uint8_t* src = const_cast<uint8_t*>(d_buf) + (size_t)i * stride_bytes;   // read only: the source side of an unpack entry
+        if (f.format == 0)
             hip_check(hipMemcpyAsync(cts[i]->d, src, cts[i]->words() * 8, hipMemcpyDeviceToDevice, x.stream), "import_device_many copy");
-            continue;
-        }
-        const u64* at = reinterpret_cast<const u64*>(src);
-        for (int v = 0; v < f.npoly * f.ell; ++v) {
-            const int w = width[v % f.ell];
-            tab.push_back(PackEntry{at, cts[i]->d + (size_t)v * N, (u32)w, 0});
-            at += pack_words(N, w);
-        }
+        else
+            pack_rows(tab, x.N, cts[i]->d, (size_t)f.npoly * f.ell, width.data(), f.ell, reinterpret_cast<u64*>(src), true);
     }
     Scratch<PackEntry> d_tab;
     if (!tab.empty()) {
-        d_tab = x.scratch<PackEntry>(tab.size());
-        upload_table(x, d_tab, tab);
+        d_tab = upload_pack_table(x, tab);
         launch_unpack_residues(d_tab, (int)tab.size(), x.N, x.stream);
         hip_check(hipGetLastError(), "import_device_many unpack");
     }
-    // 4. the range check of the other loaders over each shape's block (its vectors are contiguous), at most 65535 vectors a launch;
-    // its download needs the host: the call's one synchronisation
+    // 4. the range check of the other loaders over each shape's block (its vectors are contiguous); its download needs the host: the
+    // call's one synchronisation
     bool synced = false;
     if (check) {
         if (x.N % 4096) throw Error(FHELIN_ERR_ARG, "import_device_many: the range check needs a ring dimension of at least 2^12");
-        size_t total = 0, most = 0;
-        for (auto& g : groups) {
-            const size_t per = (size_t)g.first.first * g.first.second, rows = std::max<size_t>(1, 65535 / per);
-            total += g.second.size() * per;
-            most = std::max(most, std::min(rows, g.second.size()) * per);
-        }
-        Scratch<u64> part = x.scratch<u64>(key_digest_scratch_words(x.N, (int)most));
-        Scratch<u64> dg = x.scratch<u64>(2 * total);
-        std::vector<size_t> dg_at(n);
-        size_t v0 = 0;
-        for (auto& g : groups) {
-            const int ell = g.first.second;
-            const size_t per = (size_t)g.first.first * ell, rows = std::max<size_t>(1, 65535 / per);
-            for (size_t lo = 0; lo < g.second.size(); lo += rows) {
-                const size_t cnt = std::min(rows, g.second.size() - lo);
-                launch_key_digest(x.dt, cts[g.second[lo]]->d, (int)(cnt * per), 0, ell, part, dg + 2 * v0, x.stream);
-                for (size_t k = 0; k < cnt; ++k) dg_at[g.second[lo + k]] = v0 + k * per;
-                v0 += cnt * per;
-            }
-        }
-        hip_check(hipGetLastError(), "import_device_many range check");
-        std::vector<u64> h(2 * total);
-        hip_check(hipMemcpyAsync(h.data(), dg, h.size() * 8, hipMemcpyDeviceToHost, x.stream), "range flags download");
+        DigestRun run(x, sb.items);
         x.sync();
         synced = true;
-        for (int i = 0; i < n; ++i)
-            for (size_t v = 0; v < (size_t)fr[i].npoly * fr[i].ell; ++v)
-                if (!h[2 * (dg_at[i] + v) + 1])
-                    throw Error(FHELIN_ERR_ARG, "import_device_many: frame " + std::to_string(i) + " holds a residue not below its modulus (range check)");
+        for (int i = 0; i < n; ++i) {
+            bool in_range;
+            run.fold(sb.at[i].first, sb.at[i].second, (size_t)fr[i].npoly * fr[i].ell, in_range);
+            if (!in_range)
+                throw Error(FHELIN_ERR_ARG, "import_device_many: frame " + std::to_string(i) + " holds a residue not below its modulus (range check)");
+        }
     }
     hand_over(x, caller, synced);
     for (int i = 0; i < n; ++i) outs[i] = wrap(c, cts[i]);   // imported: not a level-plan source, never lowered
