@@ -144,7 +144,7 @@ struct fhelin_pt {
 
 namespace fhelin {
 int capi_fail(int code, const std::string& msg);
-// the per-vector device digests h[n_vec][2] (launch_key_digest: digest, range flag) of one key or one c0 folded into its digest;
+// the per-vector device digests h[n_vec][2] (launch_key_digest_strided: digest, range flag) of one key or one c0 folded into its digest;
 // in_range: every residue below its limb's modulus
 inline u64 fold_key_digest(const u64* h, size_t n_vec, bool& in_range) {
     u128 acc = 0;

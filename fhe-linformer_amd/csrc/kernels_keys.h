@@ -23,14 +23,12 @@ FHE_HD u64 key_red61(u64 a) {
     return a >= KEY_DIGEST_P ? a - KEY_DIGEST_P : a;
 }
 
-// Per limb vector v of data[n_vec][N] (modulus of limb limb_first + v % limb_count): d_out[2 v] = sum_i (x_i mod P) k_i mod P,
+// Per limb vector v (modulus of limb limb_first + v % limb_count): d_out[2 v] = sum_i (x_i mod P) k_i mod P,
 // d_out[2 v + 1] = 1 if every x_i < q, else 0.  d_part: key_digest_scratch_words(N, n_vec) words of device scratch.
 size_t key_digest_scratch_words(int N, int n_vec);
-void launch_key_digest(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, u64* d_part, u64* d_out,
-                       hipStream_t s);
-// the same over vectors that come in groups of limb_count, group_stride vectors apart: vector v is read from
+// The vectors come in groups of limb_count, group_stride vectors apart: vector v is read from
 // data + ((v / limb_count) * group_stride + v % limb_count) * N (the c0 limbs of a batch of ciphertexts [n][2][ell][N]:
-// limb_count = ell, group_stride = 2 ell)
+// limb_count = ell, group_stride = 2 ell; data[n_vec][N] back to back: group_stride = limb_count)
 void launch_key_digest_strided(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, int group_stride,
                                u64* d_part, u64* d_out, hipStream_t s);
 

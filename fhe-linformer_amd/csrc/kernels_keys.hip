@@ -81,11 +81,6 @@ __global__ void key_digest_final_kernel(const u64* __restrict__ part, int nb, in
 
 size_t key_digest_scratch_words(int N, int n_vec) { return (size_t)n_vec * (size_t)(N / DG_CHUNK); }
 
-void launch_key_digest(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, u64* d_part, u64* d_out,
-                       hipStream_t s) {
-    launch_key_digest_strided(dt, data, n_vec, limb_first, limb_count, limb_count, d_part, d_out, s);
-}
-
 void launch_key_digest_strided(const DeviceTables& dt, const u64* data, int n_vec, int limb_first, int limb_count, int group_stride,
                                u64* d_part, u64* d_out, hipStream_t s) {
     const int N = 1 << dt.log_n;

@@ -1,6 +1,6 @@
 // Wire formats, device part: what every way of a ciphertext (or key) into or out of the device shares - limb widths, the table of a
 // pack / unpack launch and its upload, the range-check-and-digest run, allocation by shape, and the import of ciphertext blobs.  The
-// callers are capi_compact.cpp, capi_packed.cpp, capi_transport.cpp and capi_keys.cpp; the blob header is wire_header.h.
+// callers are capi_compact.cpp, capi_packed.cpp, capi_transport.cpp and capi_keys.cpp; the blob header is wire_header.h, the key-set header keyset_header.h.
 #pragma once
 #include <utility>
 #include <vector>

@@ -121,9 +121,10 @@ def test_header_word_88_is_the_stride(fa, tmp_path, toy10, magic, word88, stride
     assert got["log_slots"] == 10 and boot["slots"] == 1024      # both stay logical
 
 
-@pytest.mark.parametrize("word88", [1, 3, 4, 6, 1 << 40])
+@pytest.mark.parametrize("word88", [1, 3, 4, 6, 1 << 40, 1 << 54, 1 << 63])
 def test_header_word_88_refusals(fa, tmp_path, toy10, word88):
-    """1 is written as 0; no power of two; 4 x 1024 slots exceed N/2 = 2048"""
+    """1 is written as 0; no power of two; 4 x 1024 slots exceed N/2 = 2048; 2^54 and 2^63 shifted left by log_slots = 10 wrap to 0
+    in 64 bits, and so does their low half as a stride"""
     cfg, moduli = toy10
     p = tmp_path / "bad.evk"
     p.write_bytes(_build_header(cfg, moduli, word88))
