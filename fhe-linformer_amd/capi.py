@@ -204,6 +204,10 @@ def load_library():
         "fhelin_ctx_bootstrap_pairing": (i32, [vp, C.POINTER(i32)]),
         "fhelin_ctx_set_bootstrap_lt": (i32, [vp, i32, i32]),
         "fhelin_ctx_bootstrap_lt": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "fhelin_ctx_set_bootstrap_sparse_secret": (i32, [vp, i32]),
+        "fhelin_ctx_bootstrap_sparse_secret": (i32, [vp, C.POINTER(i32)]),
+        "fhelin_debug_boot_sparse_secret": (i32, [vp, C.c_void_p, C.c_size_t]),
+        "fhelin_debug_cheb_depth": (i32, [i32, C.POINTER(i32)]),
         "fhelin_debug_pair_pack": (i32, [vp, C.POINTER(vp), C.POINTER(vp), u64p, u64p, i32, C.POINTER(vp)]),
         "fhelin_debug_pair_split": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp)]),
         "fhelin_bootstrap_describe": (i32, [vp, C.POINTER(i32), i32, C.POINTER(i32)]),
@@ -301,6 +305,16 @@ def compact_info(blob):
     if rc != 0:
         raise FhelinError(rc, lib.fhelin_last_error().decode())
     return dict(zip(("log_n", "ell", "deg", "slots"), (x.value for x in v)))
+
+
+def cheb_depth(degree):
+    """the levels the bootstrap's depth counts for a cosine fit of this degree (fhelin_debug_cheb_depth; host only)"""
+    lib = load_library()
+    out = C.c_int32()
+    rc = lib.fhelin_debug_cheb_depth(int(degree), C.byref(out))
+    if rc != 0:
+        raise FhelinError(rc, lib.fhelin_last_error().decode())
+    return out.value
 
 
 def packed_info(blob):
@@ -724,7 +738,8 @@ class Engine:
         self._ck(self.lib.fhelin_secret_import(self.h, arr.ctypes.data_as(C.c_void_p), arr.size))
 
     def key_export(self, kind, index=0):
-        """[digits][2][n_q + n_p][N]; a level-capped key has digits_at(max_ell) digits and its absent rows zero"""
+        """[digits][2][n_q + n_p][N]; a level-capped key has digits_at(max_ell) digits and its absent rows zero.  kind 0 relinearisation,
+        1 rotation by index, 2 conjugation, 3 / 4 the to-sparse and from-sparse keys of sparse-secret bootstrapping"""
         out = np.empty((self.key_info(kind, index)["digits"], 2, self.n_limbs, self.N), dtype=np.uint64)
         self._ck(self.lib.fhelin_key_export(self.h, kind, index, out.ctypes.data_as(C.c_void_p), out.size))
         return out
@@ -1355,6 +1370,8 @@ class Engine:
         self._ck(self.lib.fhelin_bootstrap_setup(self.h, budget_enc, budget_dec, slots))
 
     def bootstrap_config(self, K=28, R=3, cheb_degree=47, correction=10):
+        """all four parameters are written, the defaults included: under set_bootstrap_sparse_secret a call that names only `correction`
+        puts K and the degree back to 28 and 47 (still a correct bootstrap - the depth follows the degree - but at 15 levels again)"""
         self._ck(self.lib.fhelin_bootstrap_config(self.h, K, R, cheb_degree, correction))
 
     def bootstrap_batch(self, v):
@@ -1427,6 +1444,25 @@ class Engine:
         self._ck(self.lib.fhelin_ctx_bootstrap_lt(self.h, C.byref(on), C.byref(n1)))
         return bool(on.value), n1.value
 
+    def set_bootstrap_sparse_secret(self, hamming):
+        """sparse-secret bootstrapping (include/fhelin.h "Sparse-secret bootstrapping"; off = 0 by default, FHELIN_BOOT_SPARSE_H=h): key
+        switches to an ephemeral secret of this Hamming weight around the ModRaise - at 32, K = 12, a degree-28 cosine fit and 14 levels
+        per bootstrap instead of 15, for two more key switches.  8 <= hamming <= N; binds at bootstrap_setup: FHELIN_ERR_STATE afterwards.
+        Writes K, R and cheb_degree; a later bootstrap_config overrides them - ALL of them, its defaults included"""
+        self._ck(self.lib.fhelin_ctx_set_bootstrap_sparse_secret(self.h, int(hamming)))
+
+    def bootstrap_sparse_secret(self):
+        """the Hamming weight of set_bootstrap_sparse_secret (0: off)"""
+        h = C.c_int32()
+        self._ck(self.lib.fhelin_ctx_bootstrap_sparse_secret(self.h, C.byref(h)))
+        return h.value
+
+    def boot_sparse_secret(self):
+        """test hook: the coefficients (-1, 0, 1) of the ephemeral secret, int8 [N]; client contexts only, after bootstrap_setup"""
+        out = np.empty(self.N, dtype=np.int8)
+        self._ck(self.lib.fhelin_debug_boot_sparse_secret(self.h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
     def debug_pair_pack(self, a, b, k0_a, k0_b):
         """outs[i] = k0_a[i] a[i] + X^(N/2) k0_b[i] b[i] on the two bottom limbs, every pair in one launch (launch_ew_pair_pack)"""
         n = len(a)
@@ -1448,7 +1484,8 @@ class Engine:
         """the bootstrapping set-up as the residue-level oracle needs it: parameters + per linear stage the stage's slot count
         and its (giant, baby, diagonal plaintext) terms in evaluation order.  "lt": whether the stages run on the linear-transform
         engine (set_bootstrap_lt); then every stage also has "n1", "n2" of its split, and "lt_n1" (the n1 asked for) and
-        "encoding_bytes" (device bytes of the stages' limb-sliced encodings so far) are set"""
+        "encoding_bytes" (device bytes of the stages' limb-sliced encodings so far) are set.  "sparse_h": the Hamming weight of
+        sparse-secret bootstrapping's ephemeral secret (set_bootstrap_sparse_secret), 0 with the knob off"""
         n = C.c_int32()
         self._ck(self.lib.fhelin_bootstrap_describe(self.h, None, 0, C.byref(n)))
         d = (C.c_int32 * n.value)()
@@ -1477,6 +1514,8 @@ class Engine:
                 st["n1"], st["n2"] = d[pos], d[pos + 1]
                 pos += 2
             out["encoding_bytes"] = (d[pos] & 0xffffffff) | ((d[pos + 1] & 0xffffffff) << 32)
+            pos += 2
+        out["sparse_h"] = d[pos + 1] if pos + 1 < len(d) and d[pos] == 2 else 0   # sparse-secret bootstrapping's trailer (2, h~)
         out["c2s"], out["s2c"] = stages[:n_c2s], stages[n_c2s:]
         cn = C.c_int32()
         self._ck(self.lib.fhelin_bootstrap_cheb(self.h, None, 0, C.byref(cn)))

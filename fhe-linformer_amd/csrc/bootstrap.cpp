@@ -130,6 +130,25 @@ void Bootstrapper::set_lt(bool on, int n1) {
     lt_n1_ = n1;
 }
 
+void Bootstrapper::set_sparse(int hamming) {
+    if (hamming != 0 && (hamming < 8 || hamming > ev_.ctx().N)) throw Error(FHELIN_ERR_ARG, "bootstrap_sparse_secret: the Hamming weight is 0 (off) or 8 .. N");
+    if (ready()) throw Error(FHELIN_ERR_STATE, "bootstrap_sparse_secret: the ephemeral secret and its keys are made by bootstrap_setup - set the knob before it");
+    if (hamming == 0) {
+        if (sparse_h_) {   // back to the default approximation
+            K = 28;
+            R = 3;
+            cheb_degree = 47;
+        }
+        sparse_h_ = 0;
+        return;
+    }
+    sparse_h_ = hamming;
+    // |I| has standard deviation sqrt((h + 1) / 12): the default's K = 28 at h = 192 is 7.0 sigma, and K keeps that ratio
+    K = (int)std::ceil(28.0 * std::sqrt((hamming + 1) / 193.0) - 1e-12);
+    R = 3;
+    cheb_degree = K <= SPARSE_MAX_K ? SPARSE_CHEB_DEGREE : 47;
+}
+
 size_t Bootstrapper::lt_encoding_bytes() const {
     size_t b = 0;
     for (const auto* v : {&c2s_, &s2c_})
@@ -208,6 +227,8 @@ void Bootstrapper::setup(int budget_enc, int budget_dec, int slots) {
     if (slots <= 0) slots = 1 << c.prm.log_slots;
     if (slots & (slots - 1) || slots > c.N / 2 || slots < 4) throw Error(FHELIN_ERR_ARG, "bootstrap: slots must be a power of two in [4, N/2]");
     if (budget_enc < 1 || budget_dec < 1) throw Error(FHELIN_ERR_ARG, "bootstrap: level budget must be >= 1");
+    // sparse-secret encapsulation: s~, the to-sparse and the from-sparse key, in front of every other draw of this call
+    if (sparse_h_) cl_.gen_sparse_keys(sparse_h_);
     slots_ = slots;
     logical_slots_ = logical;
     budget_enc_ = budget_enc;
@@ -266,20 +287,22 @@ void Bootstrapper::setup(int budget_enc, int budget_dec, int slots) {
     for (int j = 1; j < gapN; j <<= 1) cl_.gen_rotation_key(n * j);
     if (!ev_.conj_key) cl_.gen_conj_key();
 
-    // cosine fit: f(y) = cos((2 pi K y - pi/2) / 2^R) on [-1,1]; R double-angle steps give sin(2 pi K y)
-    const int d = cheb_degree, nn = d + 1;
-    cheb_.assign(nn, 0.0);
+    // cosine fit: f(y) = cos((2 pi K y - pi/2) / 2^R) on [-1,1]; R double-angle steps give sin(2 pi K y).  The interpolant at the
+    // d + 1 Chebyshev nodes; under a sparse ephemeral secret the series itself, truncated at d, from twice the nodes: the degree that
+    // fits five levels is 28, where aliasing costs the interpolant a third of its accuracy (1.8e-12 against 1.2e-12)
+    const int d = cheb_degree, nn = sparse_h_ ? 2 * (d + 1) : d + 1;
+    cheb_.assign(d + 1, 0.0);
     std::vector<double> fx(nn);
     const double sc = 1.0 / (double)(1 << R);
     for (int j = 0; j < nn; ++j) fx[j] = std::cos((2.0 * PI * K * std::cos(PI * (j + 0.5) / nn) - PI / 2) * sc);
-    for (int k = 0; k < nn; ++k) {
+    for (int k = 0; k <= d; ++k) {
         double s = 0;
         for (int j = 0; j < nn; ++j) s += fx[j] * std::cos(PI * k * (j + 0.5) / nn);
         cheb_[k] = 2.0 * s / nn;
     }
 
     ensure_mono_i();
-    depth_ = budget_enc + budget_dec + R + 6;
+    depth_ = budget_enc + budget_dec + R + Evaluator::cheb_depth(cheb_degree);
 }
 
 // multiplication by i == multiplication by the monomial X^{N/2}.  Depends on the ring alone: made once, by setup() or by the first use of
@@ -386,6 +409,7 @@ CtPtr Bootstrapper::mod_raise(const CtPtr& ct, long double& rho, int top_ell) {
     const u64 k0 = (u64)llroundl(target * q1 / x->scale);
     if (k0 < 2) throw Error(FHELIN_ERR_STATE, "bootstrap: ciphertext scale too large for the correction factor");
     x = ev_.mult_int(x, k0, true, x->scale * (long double)k0);
+    if (sparse_h_) x = ev_.switch_key(x, *ev_.to_sparse_key);   // to s~ at two limbs: the rescale divides the switch's noise
     x = ev_.rescale(x);  // one limb (q0), scale ~ q0 / 2^correction
     rho = x->scale * (long double)(1ull << correction) / q0;
 
@@ -394,6 +418,7 @@ CtPtr Bootstrapper::mod_raise(const CtPtr& ct, long double& rho, int top_ell) {
     up->deg = 1;
     up->scale = c.sf_real[0];   // the scale the CoeffsToSlots constants were built for (setup), whatever the start level
     up->slots = slots_;
+    if (sparse_h_) up = ev_.switch_key(up, *ev_.from_sparse_key);   // I is now that of s~: back to s before anything reads a key of s
     // SubSum: project onto the subring of X^{N/(2 slots)} (sparse packing)
     const int gapN = (c.N / 2) / slots_;
     for (int j = 1; j < gapN; j <<= 1) {
@@ -700,6 +725,7 @@ std::vector<CtPtr> Bootstrapper::run_items(const std::vector<Item>& items, int d
         if (x->ell > 2) x = ev_.level_reduce(x, 2);
         xs[i] = ev_.mult_int(x, k0[2 * i], true, x->scale * (long double)k0[2 * i]);
     }
+    if (sparse_h_) xs = ev_.switch_key_batch(xs, *ev_.to_sparse_key);   // mod_raise's switch to s~, one batched key switch over the items
     xs = ev_.rescale_batch(xs);
     for (size_t i = 0; i < B; ++i) rho[i] = xs[i]->scale * two_corr / q0;
     // ---- the shared core: ModRaise, SubSum, CoeffsToSlots, conjugation, EvalMod, SlotsToCoeffs
@@ -710,6 +736,7 @@ std::vector<CtPtr> Bootstrapper::run_items(const std::vector<Item>& items, int d
         u->scale = c.sf_real[0];
         u->slots = slots_;
     }
+    if (sparse_h_) w = ev_.switch_key_batch(w, *ev_.from_sparse_key);   // ... and its switch back to s
     const int gapN = (c.N / 2) / slots_;
     for (int j = 1; j < gapN; j <<= 1) {
         const u64 g = c.galois_element(slots_ * j);

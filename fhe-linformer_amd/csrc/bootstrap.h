@@ -47,6 +47,15 @@ public:
     int lt_n1() const { return lt_n1_; }
     // device bytes of the limb-sliced encodings the stages' diagonals hold (one per (limbs, scale) a term was applied at)
     size_t lt_encoding_bytes() const;
+    // Sparse-secret encapsulation (include/fhelin.h "Sparse-secret bootstrapping"): hamming = h~ > 0 switches to an
+    // ephemeral secret of that weight around the ModRaise - the two-limb ciphertext in front of the rescale to q0 goes to s~, the raised
+    // one comes back to s - so that |I| is bounded by the smaller K this call writes together with R and cheb_degree (a later
+    // fhelin_bootstrap_config overrides them).  0: off, nothing below changes.  8 <= h~ <= N (FHELIN_ERR_ARG otherwise); the secret and
+    // the two keys are made by setup(): FHELIN_ERR_STATE afterwards
+    void set_sparse(int hamming);
+    int sparse_h() const { return sparse_h_; }
+    // the degree the knob writes for a K: the largest one Evaluator::cheb_depth evaluates in five levels where the range allows it
+    static constexpr int SPARSE_MAX_K = 12, SPARSE_CHEB_DEGREE = 28;
     // drop: raise to L+1-drop limbs only, so that the result has `drop` limbs fewer (level plan: the caller knows that the
     // circuit up to the next bootstrap leaves that many unused)
     CtPtr bootstrap(const CtPtr& ct, int drop = 0);
@@ -94,7 +103,7 @@ public:
     // parameters (DESIGN.md "Bootstrapping")
     int K = 28;            // bound on |I|: t = Delta m + q0 I
     int R = 3;             // double-angle iterations
-    int cheb_degree = 47;  // degree of the cosine fit (depth 6)
+    int cheb_degree = 47;  // degree of the cosine fit (depth 6: Evaluator::cheb_depth)
     int correction = 10;   // message is scaled to q0 / 2^correction before ModRaise
 
 private:
@@ -105,6 +114,7 @@ private:
     bool stage_order_legacy_ = false;   // FHELIN_BOOT_STAGES_LEGACY=1: larger stages first (round-1 split 5+5+4)
     bool lt_ = false;       // set_lt
     int lt_n1_ = 0;
+    int sparse_h_ = 0;      // set_sparse
     bool packed_ = false;   // sparse packing: real and imaginary halves share one ciphertext through EvalMod (bootstrap.cpp)
     int depth_ = 0;
     std::vector<LinStage> c2s_, s2c_;

@@ -30,6 +30,10 @@ fhelin_ctx::fhelin_ctx(const fhelin::Params& p) : ctx(p), ev(ctx), cl(ev, ctx.pr
         const int k = n1 ? std::atoi(n1) : 0;
         if (on || n1) boot.set_lt(on && std::atoi(on) != 0, k >= 0 && k <= LtDot::MAX_STEPS ? k : 0);
     }
+    if (const char* e = std::getenv("FHELIN_BOOT_SPARSE_H")) {   // sparse-secret bootstrapping at this Hamming weight (a value outside 8..N is ignored)
+        const int h = std::atoi(e);
+        if (h >= 8 && h <= ctx.N) boot.set_sparse(h);
+    }
 }
 
 #define NEED(x) if (!(x)) return capi_fail(FHELIN_ERR_ARG, "null argument")
@@ -208,6 +212,37 @@ int fhelin_ctx_bootstrap_lt(const fhelin_ctx* c, int32_t* on, int32_t* n1) {
     *on = c->boot.lt() ? 1 : 0;
     *n1 = c->boot.lt_n1();
     return FHELIN_OK;
+}
+
+int fhelin_ctx_set_bootstrap_sparse_secret(fhelin_ctx* c, int32_t hamming) {
+    if (!c) return capi_fail(FHELIN_ERR_ARG, "null context");
+    FHELIN_TRY
+    c->boot.set_sparse(hamming);
+    FHELIN_CATCH
+}
+
+int fhelin_ctx_bootstrap_sparse_secret(const fhelin_ctx* c, int32_t* hamming) {
+    if (!c || !hamming) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    *hamming = c->boot.sparse_h();
+    return FHELIN_OK;
+}
+
+int fhelin_debug_boot_sparse_secret(fhelin_ctx* c, int8_t* out, size_t cap) {
+    if (!c || !out) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    if (c->cl.eval_only()) throw Error(FHELIN_ERR_KEY, "boot_sparse_secret: an evaluation context holds no secret");
+    if (!c->cl.has_sparse_secret()) throw Error(FHELIN_ERR_STATE, "boot_sparse_secret: the ephemeral secret is made by bootstrap_setup with the knob on");
+    const std::vector<int8_t>& s = c->cl.sparse_secret();
+    if (cap < s.size()) throw Error(FHELIN_ERR_ARG, "buffer too small");
+    std::memcpy(out, s.data(), s.size());
+    FHELIN_CATCH
+}
+
+int fhelin_debug_cheb_depth(int32_t degree, int32_t* levels) {
+    if (!levels) return capi_fail(FHELIN_ERR_ARG, "null argument");
+    FHELIN_TRY
+    *levels = Evaluator::cheb_depth(degree);
+    FHELIN_CATCH
 }
 
 int fhelin_level_plan_begin(fhelin_ctx* c, int32_t mode) {

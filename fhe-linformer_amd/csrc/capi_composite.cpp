@@ -636,6 +636,10 @@ int fhelin_bootstrap_describe(fhelin_ctx* c, int32_t* out, int32_t cap, int32_t*
         d.push_back((int32_t)(bytes & 0xffffffffu));
         d.push_back((int32_t)(bytes >> 32));
     }
+    if (b.sparse_h()) {   // sparse-secret bootstrapping's trailer (absent with the knob off): 2, the Hamming weight of s~
+        d.push_back(2);
+        d.push_back(b.sparse_h());
+    }
     *n = (int32_t)d.size();
     for (int i = 0; i < std::min(cap, *n); ++i) out[i] = d[i];
     FHELIN_CATCH

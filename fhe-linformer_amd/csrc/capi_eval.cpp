@@ -30,6 +30,8 @@ static KeyPtr& key_slot(fhelin_ctx* c, int kind, int index) {
     if (kind == 0) return c->ev.relin_key;
     if (kind == 1) return c->ev.rot_keys[c->ctx.rot_element(index)];
     if (kind == 2) return c->ev.conj_key;
+    if (kind == 3) return c->ev.to_sparse_key;     // sparse-secret bootstrapping: s -> s~ ...
+    if (kind == 4) return c->ev.from_sparse_key;   // ... and s~ -> s
     throw Error(FHELIN_ERR_ARG, "unknown key kind");
 }
 
@@ -178,7 +180,7 @@ int fhelin_key_import(fhelin_ctx* c, int32_t kind, int32_t index, const uint64_t
     c->ctx.sync();
     KeyPtr& slot = key_slot(c, kind, index);   // throws for an unknown kind
     k->kind = kind + 1;                        // the key-set file's numbering (EvalKey::kind): what the usage recorder reports
-    k->galois = kind == 0 ? 0 : kind == 1 ? c->ctx.rot_element(index) : 2ull * c->ctx.N - 1;
+    k->galois = kind == 0 || kind >= 3 ? 0 : kind == 1 ? c->ctx.rot_element(index) : 2ull * c->ctx.N - 1;
     k->has_index = kind == 1;
     k->index = index;
     slot = k;

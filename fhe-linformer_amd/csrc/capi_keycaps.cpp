@@ -21,10 +21,14 @@ int fhelin_ctx_set_key_caps(fhelin_ctx* c, const int32_t* kind, const uint64_t* 
     std::vector<Client::KeyCap> table;
     for (int i = 0; i < n; ++i) {
         const std::string at = "set_key_caps: entry " + std::to_string(i) + ": ";
-        if (kind[i] < 1 || kind[i] > 3) throw Error(FHELIN_ERR_ARG, at + "kind is 1 (relinearisation), 2 (rotation) or 3 (conjugation)");
+        // kinds 4 and 5, the keys of sparse-secret bootstrapping, are known to a context with that knob on (as to fhelin_key_info): a
+        // recorded table names both.  The to-sparse key is held at two limbs whatever its entry says (Client::gen_sparse_keys)
+        if (kind[i] < 1 || kind[i] > (c->boot.sparse_h() ? 5 : 3))
+            throw Error(FHELIN_ERR_ARG, at + "kind is 1 (relinearisation), 2 (rotation) or 3 (conjugation); with sparse-secret bootstrapping on "
+                                             "also 4 (to-sparse) or 5 (from-sparse)");
         if (max_ell[i] < 1 || max_ell[i] > n_q) throw Error(FHELIN_ERR_ARG, at + "max_ell outside 1 .. n_q");
-        const bool g_ok = kind[i] == 1 ? galois[i] == 0 : kind[i] == 3 ? galois[i] == g_conj : (galois[i] & 1) && galois[i] > 1 && galois[i] < g_conj;
-        if (!g_ok) throw Error(FHELIN_ERR_ARG, at + "the Galois element is 0 for kind 1, 2N-1 for kind 3, an odd number in (1, 2N-1) for kind 2");
+        const bool g_ok = kind[i] == 1 || kind[i] >= 4 ? galois[i] == 0 : kind[i] == 3 ? galois[i] == g_conj : (galois[i] & 1) && galois[i] > 1 && galois[i] < g_conj;
+        if (!g_ok) throw Error(FHELIN_ERR_ARG, at + "the Galois element is 0 for kinds 1, 4 and 5, 2N-1 for kind 3, an odd number in (1, 2N-1) for kind 2");
         if (!seen.insert({kind[i], galois[i]}).second) throw Error(FHELIN_ERR_ARG, at + "a second entry for the same key");
         table.push_back(Client::KeyCap{kind[i], galois[i], max_ell[i]});
     }
@@ -32,12 +36,14 @@ int fhelin_ctx_set_key_caps(fhelin_ctx* c, const int32_t* kind, const uint64_t* 
         bool held = false;
         if (e.kind == 1) held = (bool)c->ev.relin_key;
         else if (e.kind == 3) held = (bool)c->ev.conj_key;
+        else if (e.kind == 4) held = (bool)c->ev.to_sparse_key;
+        else if (e.kind == 5) held = (bool)c->ev.from_sparse_key;
         else {
             auto it = c->ev.rot_keys.find(e.galois);
             held = it != c->ev.rot_keys.end() && it->second;
         }
         if (held)
-            throw Error(FHELIN_ERR_STATE, "set_key_caps: the context already holds the " + std::string(e.kind == 1 ? "relinearisation key" : e.kind == 3 ? "conjugation key" : "rotation key of Galois element " + std::to_string((unsigned long long)e.galois)) +
+            throw Error(FHELIN_ERR_STATE, "set_key_caps: the context already holds the " + std::string(e.kind == 1 ? "relinearisation key" : e.kind == 3 ? "conjugation key" : e.kind == 4 ? "to-sparse key" : e.kind == 5 ? "from-sparse key" : "rotation key of Galois element " + std::to_string((unsigned long long)e.galois)) +
                                               " - caps apply to keys generated afterwards");
     }
     c->cl.set_key_caps(table);
@@ -53,7 +59,8 @@ int fhelin_key_info(fhelin_ctx* c, int32_t kind, int32_t index, int32_t* digits,
     else if (kind == 1) {
         auto it = c->ev.rot_keys.find(c->ctx.rot_element(index));
         if (it != c->ev.rot_keys.end()) k = it->second;
-    } else throw Error(FHELIN_ERR_ARG, "unknown key kind");
+    } else if ((kind == 3 || kind == 4) && c->boot.sparse_h()) k = kind == 3 ? c->ev.to_sparse_key : c->ev.from_sparse_key;   // known with the knob on
+    else throw Error(FHELIN_ERR_ARG, "unknown key kind");
     if (!k) throw Error(FHELIN_ERR_KEY, "key not present");
     if (digits) *digits = k->digits;
     if (max_ell) *max_ell = k->max_ell;

@@ -44,8 +44,8 @@ struct File {
 };
 
 const char* kind_name(uint32_t k) {
-    static const char* n[] = {"public key", "relinearisation key", "rotation key", "conjugation key"};
-    return k < 4 ? n[k] : "?";
+    static const char* n[] = {"public key", "relinearisation key", "rotation key", "conjugation key", "to-sparse key", "from-sparse key"};
+    return k < EK_KINDS ? n[k] : "?";
 }
 
 Params to_params(const int32_t* p, int device, uint64_t seed) {
@@ -282,6 +282,16 @@ void save_set(fhelin_ctx* c, const char* path, bool compact, bool packed = false
     if (c->cl.has_public_key()) add(EK_PUBLIC, 0, nullptr);
     if (c->ev.relin_key) add(EK_RELIN, 0, c->ev.relin_key.get());
     if (c->ev.conj_key) add(EK_CONJ, g_conj, c->ev.conj_key.get());
+    if (c->ev.to_sparse_key && c->ev.from_sparse_key) {   // sparse-secret bootstrapping: both or neither; their entries carry h~ (48-byte entries)
+        if (c->boot.sparse_h() < 8)   // keys put in by fhelin_key_import under a knob that is off: no reader would take the set
+            throw Error(FHELIN_ERR_STATE, "evalkeys_save: the context holds the to-sparse and from-sparse keys but sparse-secret bootstrapping is off - "
+                                          "set fhelin_ctx_set_bootstrap_sparse_secret to the weight they were made for");
+        add(EK_TO_SPARSE, 0, c->ev.to_sparse_key.get());
+        e.keys.back().reserved = (uint32_t)c->boot.sparse_h();
+        add(EK_FROM_SPARSE, 0, c->ev.from_sparse_key.get());
+        e.keys.back().reserved = (uint32_t)c->boot.sparse_h();
+        any_capped = true;
+    }
     for (const auto& kv : c->ev.rot_keys)   // ordered by Galois element; the conjugation key is stored once, above
         if (kv.second && kv.first != g_conj) add(EK_ROTATION, kv.first, kv.second.get());
     if (e.keys.empty()) throw Error(FHELIN_ERR_KEY, "evalkeys_save: the context holds no keys");
@@ -536,12 +546,16 @@ int fhelin_evalkeys_load(fhelin_ctx* c, const char* path) {
                 c->ev.rot_keys[2ull * x.N - 1] = sw[k];
                 break;
             case EK_ROTATION: c->ev.rot_keys[e.keys[k].galois] = sw[k]; break;
+            case EK_TO_SPARSE: c->ev.to_sparse_key = sw[k]; break;
+            case EK_FROM_SPARSE: c->ev.from_sparse_key = sw[k]; break;
             default: break;
         }
     }
     c->cl.install_public_key(pk.release(), e.compact());
     if (e.compact()) c->cl.install_key_seed(e.seed);
-    if (e.boot[2] > 0) {   // the client's approximation parameters; fhelin_bootstrap_setup is the caller's (fhelin_evalkeys_info)
+    // the client's sparse-secret knob (its keys' entries carry it), then its approximation parameters over what the knob writes
+    if (e.sparse_h && e.sparse_h != c->boot.sparse_h()) c->boot.set_sparse(e.sparse_h);
+    if (e.boot[2] > 0) {   // fhelin_bootstrap_setup is the caller's (fhelin_evalkeys_info)
         c->boot.K = e.boot[3];
         c->boot.R = e.boot[4];
         c->boot.cheb_degree = e.boot[5];

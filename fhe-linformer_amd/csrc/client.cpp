@@ -422,6 +422,7 @@ Client::Client(Evaluator& ev, const uint8_t seed[32]) : ev_(ev), c_(ev.ctx()), r
 Client::~Client() {
     try {
         if (s_all) c_.pool.free(s_all);
+        if (s_sparse) c_.pool.free(s_sparse);
         if (pk) c_.pool.free(pk);
     } catch (...) {
     }
@@ -463,16 +464,8 @@ void Client::install_public_key(u64* d_pk, bool seeded) {
     c_.stride_locked = true;
 }
 
-void Client::keygen() {
-    if (eval_only_) throw Error(FHELIN_ERR_KEY, "keygen: an evaluation context holds no secret and cannot make one");
-    c_.require_device();
-    keygen_run_ = true;
-    c_.stride_locked = true;
+void Client::place_sparse_ternary(std::vector<u64>& co, int h) {
     const size_t N = c_.N;
-    const int L1 = c_.L + 1, nl = L1 + c_.K;
-    // sparse ternary secret of Hamming weight h (reference SetSecretKeyDist(SPARSE_TERNARY), :8)
-    std::vector<u64> co(2 * N, 0);
-    int h = std::min<int>(c_.prm.hamming, (int)N);
     int placed = 0;
     while (placed < h) {
         size_t pos = rng_.uniform(N);
@@ -485,6 +478,18 @@ void Client::keygen() {
         }
         ++placed;
     }
+}
+
+void Client::keygen() {
+    if (eval_only_) throw Error(FHELIN_ERR_KEY, "keygen: an evaluation context holds no secret and cannot make one");
+    c_.require_device();
+    keygen_run_ = true;
+    c_.stride_locked = true;
+    const size_t N = c_.N;
+    const int L1 = c_.L + 1, nl = L1 + c_.K;
+    // sparse ternary secret of Hamming weight h (reference SetSecretKeyDist(SPARSE_TERNARY), :8)
+    std::vector<u64> co(2 * N, 0);
+    place_sparse_ternary(co, std::min<int>(c_.prm.hamming, (int)N));
     if (seeded_keys_ && L1 > KEYGEN_MAX_Q) throw Error(FHELIN_ERR_ARG, "seeded keys: more than 64 Q limbs");
     if (seeded_keys_) {   // the public key-set seed: the next four words of the stream, bytes as begin_call
         for (int i = 0; i < 4; ++i) {
@@ -554,12 +559,12 @@ int Client::key_cap(int kind, u64 galois) const {
 // Q limbs 0 .. cap-1 and the special limbs of the digits_at(cap) digits a switch at <= cap limbs reads - and those are, residue for
 // residue, the rows of the key this call would have made uncapped: the generator and the device sampler are consumed exactly as for the
 // uncapped key (so every later key is unchanged too), and only transforms, products and uploads of absent rows are left out.
-KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois) {
+KeyPtr Client::make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois, int force_cap) {
     c_.require_device();
     if (c_.K < 1) throw Error(FHELIN_ERR_STATE, "key switching keys need special primes (n_p >= 1)");
     const size_t N = c_.N;
     const int L1 = c_.L + 1, nl = L1 + c_.K;
-    const int cap = key_cap((int)kind, galois), all_digits = c_.digits_at(L1);
+    const int cap = force_cap > 0 ? std::min(force_cap, L1) : key_cap((int)kind, galois), all_digits = c_.digits_at(L1);
     const bool capped = cap < L1;
     KeyPtr key = ev_.new_key(cap);
     key->kind = (int)kind;
@@ -693,6 +698,34 @@ void Client::gen_conj_key() {
     launch_automorph(c_.dt, sp, s_all, c_.automorph_map(g), nl, c_.stream);
     ev_.conj_key = make_switch_key(s_all, sp, 3, g);
     ev_.rot_keys[g] = ev_.conj_key;
+}
+
+void Client::gen_sparse_keys(int hamming) {
+    if (!s_all) {
+        const char* missing = !ev_.to_sparse_key ? "to-sparse key" : !ev_.from_sparse_key ? "from-sparse key" : nullptr;
+        if (!missing) return;
+        throw Error(FHELIN_ERR_KEY, eval_only_ ? std::string(missing) + " not in the evaluation-key set (it was saved without sparse-secret bootstrapping)"
+                                              : "keygen() has not been called");
+    }
+    if (s_sparse && ev_.to_sparse_key && ev_.from_sparse_key) return;   // once per context, as the conjugation key
+    const size_t N = c_.N;
+    const int nl = c_.L + 1 + c_.K;
+    if (hamming < 1 || hamming > (int)N) throw Error(FHELIN_ERR_ARG, "sparse-secret bootstrapping: Hamming weight outside 1 .. N");
+    std::vector<u64> co(2 * N, 0);
+    place_sparse_ternary(co, hamming);
+    sparse_coeffs_.assign(N, 0);
+    for (size_t i = 0; i < N; ++i) sparse_coeffs_[i] = co[2 * i + 1] ? -1 : (int8_t)co[2 * i];
+    if (!s_sparse) s_sparse = c_.dalloc<u64>((size_t)nl * N);
+    Scratch<u64> dco = c_.scratch<u64>(2 * N);
+    hip_check(hipMemcpyAsync(dco, co.data(), 2 * N * 8, hipMemcpyHostToDevice, c_.stream), "sparse secret upload");
+    hip_check(hipStreamSynchronize(c_.stream), "sparse secret sync");
+    launch_reduce_i128(c_.dt, s_sparse, dco, 0, nl, c_.stream);
+    launch_ntt(c_.dt, LimbBatch{s_sparse, nl, nullptr, 0, nl}, false, c_.stream);
+    hip_check(hipMemsetAsync(dco, 0, 2 * N * sizeof(u64), c_.stream), "hipMemsetAsync(sparse secret staging)");
+    dco.reset();
+    // a switch from s to s~ encrypts s under s~ (s_from = s, s_to = s~), and back
+    ev_.to_sparse_key = make_switch_key(s_all, s_sparse, 4, 0, 2);
+    ev_.from_sparse_key = make_switch_key(s_sparse, s_all, 5, 0);
 }
 
 PtPtr Client::encode(const double* vals, int n, int level, int slots) {

@@ -48,11 +48,20 @@ public:
     void gen_relin_key();                // EvalMultKeyGen
     void gen_rotation_key(int index);    // EvalRotateKeyGen for one index
     void gen_conj_key();
+    // Sparse-secret bootstrapping (include/fhelin.h "Sparse-secret bootstrapping"), once per context: the ephemeral secret s~ (ternary,
+    // exactly `hamming` non-zero coefficients, keygen's placement loop on the context's generator), then the to-sparse key s -> s~
+    // (kind 4, always capped at two limbs) and the from-sparse key s~ -> s (kind 5, capped by a table entry of its kind), in this
+    // order.  Without the secret: confirms that both keys are present (FHELIN_ERR_KEY names the missing one)
+    void gen_sparse_keys(int hamming);
+    bool has_sparse_secret() const { return s_sparse != nullptr; }
+    const std::vector<int8_t>& sparse_secret() const { return sparse_coeffs_; }   // the coefficients of s~ (test hook)
     // device [L+1+k][N] NTT form.  kind / galois: the key's nonce fields in seeded-key mode (include/fhelin.h "Seeded evaluation keys")
-    KeyPtr make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois);
+    // force_cap > 0: the key is capped at that many limbs whatever the cap table says
+    KeyPtr make_switch_key(const u64* s_from_all, const u64* s_to_all, u64 kind, u64 galois, int force_cap = 0);
     // Level-capped keys (include/fhelin.h "Level-capped keys"): every switching key made from now on whose (kind, Galois element) has an
     // entry is made capped at the entry's limbs (make_switch_key); an entry of n_q limbs, or none, is an uncapped key.  Replaces the table.
-    // kind 1 relinearisation (galois 0), 2 rotation, 3 conjugation (galois 2N-1).  The caller validates (fhelin_ctx_set_key_caps).
+    // kind 1 relinearisation (galois 0), 2 rotation, 3 conjugation (galois 2N-1), 4 to-sparse and 5 from-sparse (galois 0; the to-sparse
+    // key is held at two limbs whatever its entry says).  The caller validates (fhelin_ctx_set_key_caps).
     struct KeyCap {
         int kind;
         u64 galois;
@@ -136,6 +145,10 @@ private:
     Prng rng_;
     u64* s_all = nullptr;   // secret, NTT form over Q and P limbs [L+1+k][N]
     u64* pk = nullptr;      // [2][L+1][N]: b = -a s + e, a
+    u64* s_sparse = nullptr;             // the ephemeral secret s~ of sparse-secret bootstrapping, as s_all; never on an evaluation context
+    std::vector<int8_t> sparse_coeffs_;  // its N coefficients
+    // the placement loop of a sparse ternary secret: h distinct positions, a sign each; co [2N] sign-extended 128-bit pairs, zero on entry
+    void place_sparse_ternary(std::vector<u64>& co, int h);
     void sample_small_to_ntt(u64* dst, int nlimbs_q, bool with_p, int kind);  // kind 0 gaussian, 1 ternary (host sampler: key generation)
     void draw_small_host(std::vector<u64>& co, int kind);   // its draws alone: N coefficients as sign-extended 128-bit pairs
     std::map<std::pair<int, u64>, int> key_caps_;

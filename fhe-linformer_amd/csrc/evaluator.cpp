@@ -170,9 +170,10 @@ KeyPtr Evaluator::new_key(int max_ell) {
 
 void Evaluator::bind_key(const EvalKey& key, int ell) {
     if (ell > key.max_ell) {
-        std::string who = key.kind == 1 ? "relinearisation key" : key.kind == 3 ? "conjugation key" : "rotation key";
+        std::string who = key.kind == 1 ? "relinearisation key" : key.kind == 3 ? "conjugation key" : key.kind == 4 ? "to-sparse key" :
+                          key.kind == 5 ? "from-sparse key" : "rotation key";
         if (key.kind != 1 && key.has_index) who += " for index " + std::to_string(key.index);
-        if (key.kind != 1) who += " (Galois element " + std::to_string((unsigned long long)key.galois) + ")";
+        if (key.kind == 2 || key.kind == 3) who += " (Galois element " + std::to_string((unsigned long long)key.galois) + ")";
         throw Error(FHELIN_ERR_KEY, who + " is capped at " + std::to_string(key.max_ell) + " limbs: a key switch at " + std::to_string(ell) +
                                         " limbs was asked for");
     }
@@ -1217,11 +1218,34 @@ std::vector<CtPtr> Evaluator::conjugate_batch(const std::vector<CtPtr>& v) {
 std::vector<CtPtr> Evaluator::rotate_galois_batch(const std::vector<CtPtr>& vin, u64 g, const EvalKey& key, bool accumulate) {
     for (const CtPtr& x : vin) bind_key(key, x->ell);   // before the first group runs
     if (vin.size() == 1) return {raw_rotate(vin[0], g, key, accumulate)};
-    const u32* map = c_.automorph_map(g);
     // rows that share (level, degree, scale) go through one batched key switch; others form their own groups
-    return for_groups(vin.size(), batch_limit, [&](size_t f, size_t i) { return same_shape(*vin[f], *vin[i]); },
+    return keyswitch_groups(vin, key, c_.automorph_map(g), accumulate, false, "rotate: ciphertext must have 2 components");
+}
+
+CtPtr Evaluator::switch_key(const CtPtr& a, const EvalKey& key) {
+    if (a->npoly != 2) throw Error(FHELIN_ERR_STATE, "switch_key: ciphertext must have 2 components");
+    const size_t pn = (size_t)a->ell * c_.N;
+    CtPtr o = new_ct(2, a->ell, a->deg, a->scale, a->slots);
+    keyswitch(a->d + pn, a->ell, key, o->d, a->d, nullptr, nullptr);
+    return o;
+}
+
+std::vector<CtPtr> Evaluator::switch_key_batch(const std::vector<CtPtr>& vin, const EvalKey& key) {
+    for (const CtPtr& x : vin) bind_key(key, x->ell);   // before the first group runs
+    if (vin.size() == 1) return {switch_key(vin[0], key)};
+    // the switch reads neither degree nor scale: rows of one limb count share the launches (the items of a bootstrap batch in front of
+    // their rescale to q0 carry a scale each), and every output keeps its input's bookkeeping
+    return keyswitch_groups(vin, key, nullptr, false, true, "switch_key: ciphertext must have 2 components");
+}
+
+// (c0 + KS(c1)[0], KS(c1)[1]) of every row, written through `map` (null: the identity), one batched key switch per group of rows.  A group
+// is the rows of one shape (same_shape), or with by_limbs those of one limb count, each output then keeping its own degree and slots too
+std::vector<CtPtr> Evaluator::keyswitch_groups(const std::vector<CtPtr>& vin, const EvalKey& key, const u32* map, bool accumulate, bool by_limbs,
+                                               const char* two_components) {
+    return for_groups(vin.size(), batch_limit,
+                      [&](size_t f, size_t i) { return by_limbs ? vin[f]->npoly == vin[i]->npoly && vin[f]->ell == vin[i]->ell : same_shape(*vin[f], *vin[i]); },
                       [&](const std::vector<size_t>& idx) {
-        if (vin[idx[0]]->npoly != 2) throw Error(FHELIN_ERR_STATE, "rotate: ciphertext must have 2 components");
+        if (vin[idx[0]]->npoly != 2) throw Error(FHELIN_ERR_STATE, two_components);
         const std::vector<CtPtr> chunk = make_contiguous(pick(vin, idx), 4);
         const int B = (int)chunk.size();
         const int ell = chunk[0]->ell;
@@ -1229,7 +1253,13 @@ std::vector<CtPtr> Evaluator::rotate_galois_batch(const std::vector<CtPtr>& vin,
         std::vector<CtPtr> o = new_ct_batch(B, 2, ell, chunk[0]->deg, chunk[0]->scale, chunk[0]->slots);
         const u64* base = chunk[0]->d;  // contiguous by construction (or a single ciphertext)
         keyswitch_batch(B, base + pn, ctw, ell, key, o[0]->d, ctw, base, nullptr, ctw, map, accumulate ? base : nullptr, ctw);
-        for (int b = 0; b < B; ++b) o[b]->scale = vin[idx[b]]->scale;
+        for (int b = 0; b < B; ++b) {
+            o[b]->scale = vin[idx[b]]->scale;
+            if (by_limbs) {
+                o[b]->deg = vin[idx[b]]->deg;
+                o[b]->slots = vin[idx[b]]->slots;
+            }
+        }
         return o;
     });
 }

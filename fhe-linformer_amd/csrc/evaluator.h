@@ -179,6 +179,9 @@ public:
     std::map<u64, KeyPtr> rot_keys;  // by galois element
     KeyPtr relin_key;
     KeyPtr conj_key;
+    // sparse-secret bootstrapping (include/fhelin.h "Sparse-secret bootstrapping"): s -> s~ (kind 4, always capped at two limbs) and
+    // s~ -> s (kind 5); null with the knob off
+    KeyPtr to_sparse_key, from_sparse_key;
 
     // ---- K6-K8 composite: out[2][ell][N] = KeySwitch(c) (+ add0/add1, gathered through map if given)
     void keyswitch(const u64* c_ntt, int ell, const EvalKey& key, u64* out, const u64* add0, const u64* add1, const u32* map,
@@ -274,6 +277,11 @@ public:
     // rotations by multiples of the slot count); accumulate: v_i + sigma_g(v_i)
     std::vector<CtPtr> rotate_galois_batch(const std::vector<CtPtr>& v, u64 galois, const EvalKey& key, bool accumulate);
     std::vector<CtPtr> conjugate_batch(const std::vector<CtPtr>& v);
+    // the identity-automorphism switch to the secret `key` targets: (c0 + KS(c1)[0], KS(c1)[1]) - the relinearisation's key switch with
+    // c1 where that has c2 and no second addend.  Limbs, degree, scale and slots pass through.  The batch: rows of one shape through
+    // one batched key switch, out[i] the residues of switch_key(v[i], key)
+    CtPtr switch_key(const CtPtr& a, const EvalKey& key);
+    std::vector<CtPtr> switch_key_batch(const std::vector<CtPtr>& v, const EvalKey& key);
     std::vector<CtPtr> raw_modraise_batch(const std::vector<CtPtr>& v, int new_ell);   // raw_modraise over many one-limb ciphertexts
     // rot(v[i], indices[i]) for ciphertexts of identical shape, one batched key switch per chunk of rows
     std::vector<CtPtr> rotate_each(const std::vector<CtPtr>& v, const std::vector<int>& indices);
@@ -342,6 +350,9 @@ public:
     // the same Chebyshev series on several ciphertexts at once: every product of the evaluation runs as mult_batch over
     // all ciphertexts AND all independent nodes of the same depth (baby powers of one doubling round)
     std::vector<CtPtr> eval_chebyshev_many(const std::vector<CtPtr>& xs, const std::vector<double>& coeffs, double a, double b);
+    // levels eval_chebyshev_many spends on a series of this degree (>= 1) with every knob at its default, the result's pending rescale
+    // counted: the depth of the tree it builds (polyeval.cpp), worked out on the host.  4 for 14, 5 for 28, 6 for 29..59, 7 for 119
+    static int cheb_depth(int degree);
     std::vector<CtPtr> rescale_batch(const std::vector<CtPtr>& v);
 
     // ---- leveled ops (functional: inputs are never modified)
@@ -398,6 +409,9 @@ public:
 
 private:
     Context& c_;
+    // the one body of rotate_galois_batch and switch_key_batch (evaluator.cpp)
+    std::vector<CtPtr> keyswitch_groups(const std::vector<CtPtr>& vin, const EvalKey& key, const u32* map, bool accumulate, bool by_limbs,
+                                        const char* two_components);
     void keyswitch_impl(int batch, const KsRows* rows, const u64* c_ntt, size_t c_stride, int ell, const EvalKey* key, u64* out,
                         size_t out_stride, const u64* add0, const u64* add1, size_t add_stride, const u32* map, const u64* post,
                         size_t post_stride);

@@ -10,7 +10,10 @@
 
 namespace fhelin {
 
-enum : uint32_t { EK_PUBLIC = 0, EK_RELIN = 1, EK_ROTATION = 2, EK_CONJ = 3 };
+// EK_TO_SPARSE / EK_FROM_SPARSE: the two keys of sparse-secret bootstrapping (include/fhelin.h), in formats with 48-byte entries only;
+// Galois element 0, and the entry's last word - zero on every other entry - is the Hamming weight of the ephemeral secret
+enum : uint32_t { EK_PUBLIC = 0, EK_RELIN = 1, EK_ROTATION = 2, EK_CONJ = 3, EK_TO_SPARSE = 4, EK_FROM_SPARSE = 5 };
+constexpr uint32_t EK_KINDS = 6;
 constexpr size_t EK_ALIGN = 4096;   // the payloads start at a multiple of it
 constexpr uint32_t EK_MAX_KEYS = 1u << 16;
 
@@ -39,6 +42,7 @@ struct EkEntry {
     uint32_t kind = 0, digits = 0;
     uint64_t galois = 0, offset = 0, words = 0, digest = 0;
     uint32_t max_ell = 0, reserved = 0;   // max_ell: n_q for the public key, for an uncapped key and for every key of a format without caps
+                                          // reserved: 0, or on EK_TO_SPARSE / EK_FROM_SPARSE the Hamming weight of the ephemeral secret
 };
 struct EkFile {
     const KeysetFormat* fmt = nullptr;
@@ -48,6 +52,7 @@ struct EkFile {
     uint64_t data_offset = 0, stride_word = 0;  // stride_word: 0, or the interleave stride when it is not 1
     uint8_t seed[32] = {};                      // zero unless compact()
     uint32_t halves = 2, reserved = 0;
+    int32_t sparse_h = 0;                       // a reader's: the Hamming weight the two sparse-secret entries carry (0: the set has none)
     std::vector<uint64_t> moduli;
     std::vector<EkEntry> keys;
     int32_t stride() const { return stride_word ? (int32_t)stride_word : 1; }
@@ -169,18 +174,22 @@ inline EkFile read_keyset_header(const uint8_t* b, size_t have, uint64_t file_si
     if (have < table_end) throw refuse("truncated key table");
     if (e.data_offset != keyset_data_offset(table_end)) throw refuse("bad payload offset");
     uint64_t at = e.data_offset, last_g = 0;
-    int seen[4] = {};
+    int seen[EK_KINDS] = {};
     for (uint32_t k = 0; k < e.n_keys; ++k) {
         EkEntry x;
         x.max_ell = (uint32_t)n_q;
         keyset_entry_fields(KeysetIo{b + table + f.entry * k, nullptr}, f, x);
         if (f.caps) {
-            if (x.reserved != 0) throw refuse("non-zero reserved word in the key table");
+            const bool sparse = x.kind == EK_TO_SPARSE || x.kind == EK_FROM_SPARSE;
+            if (sparse ? x.reserved < 8 || x.reserved > N || (e.sparse_h && (uint32_t)e.sparse_h != x.reserved) : x.reserved != 0)
+                throw refuse(sparse ? "bad Hamming weight on a sparse-secret key" : "non-zero reserved word in the key table");
+            if (sparse) e.sparse_h = (int32_t)x.reserved;
             if (x.max_ell < 1 || x.max_ell > (uint32_t)n_q || (x.kind == EK_PUBLIC && x.max_ell != (uint32_t)n_q)) throw refuse("max_ell outside 1 .. n_q");
-            if (x.kind != EK_PUBLIC && x.kind <= EK_CONJ && x.digits != (x.max_ell + alpha - 1) / alpha)
+            if (x.kind == EK_TO_SPARSE && x.max_ell != std::min<uint32_t>(2, (uint32_t)n_q)) throw refuse("the to-sparse key is held at two limbs");
+            if (x.kind != EK_PUBLIC && x.kind < EK_KINDS && x.digits != (x.max_ell + alpha - 1) / alpha)
                 throw refuse("digit count is not that of a key switch at max_ell limbs");
         }
-        if (x.kind > EK_CONJ) throw refuse("unknown key kind");
+        if (x.kind >= (f.caps ? EK_KINDS : EK_TO_SPARSE)) throw refuse("unknown key kind");
         if (x.kind != EK_ROTATION && ++seen[x.kind] > 1) throw refuse("duplicate key");
         if ((x.kind == EK_PUBLIC) != (x.digits == 0) || x.digits > (uint32_t)n_q ||
             x.words != keyset_key_words(f, e.prm, x.kind, x.digits, x.max_ell, e.halves, width.data()))
@@ -195,6 +204,7 @@ inline EkFile read_keyset_header(const uint8_t* b, size_t have, uint64_t file_si
         at += 8 * x.words;
         e.keys.push_back(x);
     }
+    if (seen[EK_TO_SPARSE] != seen[EK_FROM_SPARSE]) throw refuse("one sparse-secret key without the other");
     if (file_size != at) throw refuse("file size does not match the key table (truncated?)");
     return e;
 }

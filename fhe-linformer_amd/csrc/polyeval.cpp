@@ -2,7 +2,9 @@
 // Chebyshev-series evaluation (baby-step/giant-step with the identity T_i = 2 T_m T_{i-m} - T_{2m-i}).
 // Mirrors what the reference obtains from OpenFHE's EvalPoly / EvalMultMany / EvalChebyshevFunction
 // (reference src/FHEController.cpp:1289-1336).  All arithmetic runs through the GPU evaluator ops.
+#include <algorithm>
 #include <cmath>
+#include <functional>
 #include <map>
 #include "evaluator.h"
 
@@ -525,6 +527,37 @@ std::vector<CtPtr> Evaluator::eval_chebyshev_many(const std::vector<CtPtr>& xs, 
     // the baby powers as they are: cheb_recurse brings the ones a leaf needs to that leaf's level
     std::vector<CtRow> babies(T.begin(), T.begin() + baby);   // index 0 unused
     return cheb_recurse(c, babies, G, baby);
+}
+
+// The level bookkeeping of eval_chebyshev_many + cheb_recurse on a series with no vanishing coefficient, every knob at its default
+// (leaf classes, leaves born at their product): `at` counts the limbs a value has left behind.  A power T_k = rescale(2 T_j T_(k-j) - ..)
+// lies one below the deeper of its factors; a leaf is a degree-2 sum at the deepest baby power of its class; a product q T_m rescales q
+// first and meets T_m at the deeper of the two; a remainder leaf is born at its product.  The result is at degree 2: its rescale counts.
+int Evaluator::cheb_depth(int n) {
+    if (n < 1) throw Error(FHELIN_ERR_ARG, "cheb_depth: need degree >= 1");
+    int l = 0;
+    while ((1 << (2 * l)) < n + 1) ++l;
+    const int baby = std::max(2, 1 << l);
+    std::vector<int> T(baby + 1, 0);
+    for (int h = 1; h < baby; h *= 2)
+        for (int k = h + 1; k <= std::min(2 * h, baby); ++k) T[k] = std::max(T[k / 2], T[k - k / 2]) + 1;
+    std::map<int, int> G;
+    G[baby] = T[baby];
+    for (int m = baby; m * 2 <= n; m *= 2) G[2 * m] = G[m] + 1;
+    auto leaf = [&](int d) {
+        int j = 0;
+        while ((1 << j) < std::max(d, 1)) ++j;
+        const int prefix = std::min(1 << j, baby - 1);
+        return *std::max_element(T.begin() + 1, T.begin() + prefix + 1);
+    };
+    std::function<int(int, int)> node = [&](int d, int product_at) {
+        if (d < baby) return std::max(product_at, leaf(d));   // product_at < 0: a leaf at the bottom of a quotient chain
+        int m = baby;
+        while (m * 2 <= d) m *= 2;
+        const int p = std::max(node(d - m, -1) + 1, G[m]);
+        return std::max(p, node(m - 1, p));
+    };
+    return node(n, -1) + 1;
 }
 
 }  // namespace fhelin

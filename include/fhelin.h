@@ -563,6 +563,43 @@ int fhelin_ctx_bootstrap_pairing(fhelin_ctx* c, int32_t* on);
  * other setting names the missing key at fhelin_bootstrap_setup (FHELIN_ERR_KEY).  Off: describe, key list and every residue are unchanged. */
 int fhelin_ctx_set_bootstrap_lt(fhelin_ctx* c, int32_t on, int32_t n1);
 int fhelin_ctx_bootstrap_lt(const fhelin_ctx* c, int32_t* on, int32_t* n1);
+/* ---- Sparse-secret bootstrapping (runtime knob, OFF by default = 0; FHELIN_BOOT_SPARSE_H=h is read at context creation).  Sparse-secret
+ * encapsulation (Bossuat, Troncoso-Pastoriza, Hubaux 2022): the ciphertext is key-switched to a much sparser EPHEMERAL secret s~ only
+ * around the ModRaise and back to s right after it, so that I in t = Delta m + q0 I has the spread of s~: with Hamming weight h~ = 32 a
+ * bound K = 12 keeps the default's K / sigma, the cosine fit needs five levels instead of six, and a bootstrap spends 3 + 5 + 3 + 3 = 14.
+ * The price is two key switches per bootstrap.  No security claim is made or changed; what is structural: the key that targets s~
+ * exists on two Q limbs and the special limbs only.
+ * Definition (residue-exact).  On a client context with the knob on, fhelin_bootstrap_setup draws and generates, in this order, before
+ * anything else it draws: (1) s~, ternary with exactly h~ non-zero coefficients, by fhelin_keygen's placement loop on the context's
+ * generator; (2) the to-sparse key, a switching key from s to s~, ALWAYS capped at max_ell = 2 whatever the cap table says; (3) the
+ * from-sparse key from s~ to s, uncapped or capped by a fhelin_ctx_set_key_caps entry of kind 5 (set the knob first).  Once per context, as the conjugation
+ * key; seeded-key mode gives them the nonce kinds 4 and 5 (Galois field 0).  switch(ct, key) = (c0 + KS(c1)[0], KS(c1)[1]) with KS the
+ * hybrid key switch, no automorphism (oracle: orc.keyswitch).  The ModRaise step of every pipeline (single, batched, paired, iterative,
+ * dropped, level-planned, linear-transform knob, interleaved) is then: y = switch(x2, to-sparse) at two limbs, x2 the two-limb ciphertext
+ * the step is about to rescale to q0 (k0 x for a single, the packed k0_a a + i k0_b b for a pair); x1 = rescale(y); up = modraise(x1,
+ * top_ell); up = switch(up, from-sparse) at top_ell; SubSum and everything after it unchanged.  Degree, scale and slots pass through the
+ * switches; a batch runs each switch as one batched key switch and keeps the residues of the single calls.
+ * The setter writes what fhelin_bootstrap_config holds: K = ceil(28 sqrt((h~ + 1) / 193)), R = 3, cheb_degree = 28 when K <= 12 (the
+ * largest degree the Chebyshev evaluator takes in five levels; degree 31 takes six) else 47, correction unchanged; a later
+ * fhelin_bootstrap_config overrides them.  With the knob on the fit is the Chebyshev series truncated at the degree (from twice the
+ * nodes) instead of the interpolant.  depth = budget_enc + budget_dec + R + (levels the evaluator spends on cheb_degree; 6 at 47).
+ * 8 <= h~ <= N, anything else FHELIN_ERR_ARG; after fhelin_bootstrap_setup FHELIN_ERR_STATE.  fhelin_key_export / fhelin_key_info kinds
+ * 3 (to-sparse, max_ell 2) and 4 (from-sparse); usage recorder and cap table kinds 4 and 5 (Galois element 0; a kind-4 entry is accepted
+ * and the to-sparse key still held at two limbs, so a recorded table goes back in as it is).  fhelin_key_info and the cap table know
+ * these kinds on a context with the knob on, and refuse them as unknown (FHELIN_ERR_ARG) otherwise.  fhelin_bootstrap_describe
+ * appends the pair (2, h~).  Key sets (all formats, always with 48-byte entries): entry kinds 4 and 5 after the conjugation key, Galois
+ * field 0, the entry's last word = h~; a context that loads the set adopts h~ and the approximation parameters.  A set written with the
+ * knob off is byte for byte what it was; loading one into a context with the knob on names the missing key at fhelin_bootstrap_setup
+ * (FHELIN_ERR_KEY).  An evaluation context never holds s~.  Off: no residue, key, file byte or generator draw changes. */
+int fhelin_ctx_set_bootstrap_sparse_secret(fhelin_ctx* c, int32_t hamming);
+int fhelin_ctx_bootstrap_sparse_secret(const fhelin_ctx* c, int32_t* hamming);
+/* test hook: the N coefficients (-1, 0, 1) of s~; client contexts only (FHELIN_ERR_KEY on an evaluation context, FHELIN_ERR_STATE
+ * before the set-up made it) */
+int fhelin_debug_boot_sparse_secret(fhelin_ctx* c, int8_t* out, size_t cap);
+/* test hook, host only: the levels the bootstrap's depth counts for a cosine fit of this degree (>= 1, else FHELIN_ERR_ARG) - the host's
+ * restatement of the level bookkeeping of fhelin_eval_chebyshev with every knob at its default and no vanishing coefficient, the
+ * result's pending rescale counted.  The tests hold it to the limbs the evaluation really spends. */
+int fhelin_debug_cheb_depth(int32_t degree, int32_t* levels);
 /* ---- read-only views of the bootstrapping set-up: the residue-level oracle (oracle/residue_boot.py, tests only) composes
  * EvalBootstrap (:445) from the same linear stages, Chebyshev coefficients and keys and must reach the same residues.
  * describe: out = {packed, slots, K, R, cheb_degree, correction, depth, n_c2s, n_s2c, then per stage (CoeffsToSlots stages
